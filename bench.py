@@ -6,19 +6,27 @@ frontier expansion + n_layer fused message-passing layers + GRU/readout + filter
 synthetic KG 10k entities / 50 relations / 200k triples (seed 1234), n_layer=3, hidden_dim=64,
 attn_dim=5, batch of B queries per GPU.  Queries are sharded over ranks by estimated cost (weak scaling:
 B per GPU fixed); for N>1 scores are all-gathered over RCCL and the 4 metric sums all-reduced.
-After the timed region (never inside it) rank 0 also runs: the second half of the metric's name —
-BaseModel.evaluate on the real family graph (configs[0] shape, n_tbatch=50) — and the CPU baseline,
-whose oracle scores double as an end-to-end parity check at bench size.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-cpu-baseline] [--no-family-eval]
+A plain run sets up, warms up, times --steps steps and prints the result line (`value`, `ms_per_step`, ...); nothing else.
+With --full, after the timed region (never inside it) rank 0 also runs: the second half of the metric's name —
+BaseModel.evaluate on the real family graph (configs[0] shape, n_tbatch=50) — the same step with the dense products on
+the f32 MFMA forms, and the CPU baseline, whose oracle scores double as an end-to-end parity check at bench size; the
+timed steps then also carry per-kernel HIP events for the roofline objects.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
+    python bench.py --full [--no-cpu-baseline] [--no-family-eval] [--no-dense-f32] [--no-kernel-events]
 
     python bench.py --train [--config C2] [--batch 256]        one training step (forward + loss + HIP backward + Adam) per step
     python bench.py --global-batch G --gpus N                  strong scaling: G queries dealt over the N ranks (BASELINE's C4 256 / 4)
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with `roofline` for the dominant
+--dump-outputs DIR writes what the last timed step computed (rank 0's share) as DIR/<name>.npy in float32 / float64, at
+most MAX_DUMP_BYTES in all (beyond that, a fixed seeded sample of rows of each array); the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
+
+Prints ONE JSON line on rank 0 (contract in the task statement); with --full it also holds `roofline` for the dominant
 kernel (the layer_fwd kernels, HIP events on their stream: the L2-gather roof that binds them, SURVEY 8d's
-algorithmic-HBM figure beside it as `hbm_algorithmic`), `per_hop`, `roofline_dense`, `cpu_baseline` (the oracle on
-host cores) and `family_eval` (configs[0]: real family graph, queries/s, edges/s and its own CPU leg).
+algorithmic-HBM figure beside it as `hbm_algorithmic`), `per_hop`, `roofline_dense`, `dense_f32`, `cpu_baseline` (the
+oracle on host cores) and `family_eval` (configs[0]: real family graph, queries/s, edges/s and its own CPU leg).
 """
 import argparse
 import json
@@ -38,6 +46,7 @@ L2_GATHER_PEAK = 18.8e12   # B/s, same guide, "Indexed rows": rows shared by eve
 MFMA_F32_PEAK = 157.3e12   # FLOP/s, same guide: f32-input MFMA = the FP32 vector rate
 MFMA_F16_PEAK = 2.5e15     # FLOP/s, same guide: dense f16 / bf16 MFMA
 TRAFFIC_FILE = os.path.join(ROOT, "profiles", "traffic_layer_fwd.json")
+MAX_DUMP_BYTES = 64 * 10 ** 6   # --dump-outputs: all arrays of one run together
 
 # `dtype` of the line = the arithmetic the path computes in (storage, sums and - for f32 / f16x3 - operands and products are fp32)
 DTYPE_OF = {"f32": "f32", "f16x3": "f32", "f16x2": "f32 storage and accumulation, dense products on 22-bit operands (f16x2 splits)"}
@@ -399,6 +408,7 @@ def bench_temporal(args, dist, world, rank, engine, scaling="weak"):
         dt, edges = float(tmax[0]), float(tsum[1])
     if rank != 0:
         return
+    dumped = dump_outputs(args.dump_outputs, {"scores": scores}) if args.dump_outputs else None
     roof = None
     ev_ms = [(e0.elapsed_time(e1), ne, nn) for (e0, e1, ne, nn) in kernel_events]
     if ev_ms:
@@ -443,6 +453,8 @@ def bench_temporal(args, dist, world, rank, engine, scaling="weak"):
         "eval_queries_per_s": B * world * args.steps / dt, "edges_per_step": edges / args.steps,
         "roofline": roof, "cpu_baseline": cpu, "parity": parity, "rg_version": int(_lib_version()),
     }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     print(json.dumps(out))
 
 
@@ -516,6 +528,12 @@ def bench_extrapolation(args, dist, world, rank, engine, scaling="weak"):
     engine.KERNEL_EVENTS = None
     if rank != 0:
         return
+    dumped = None
+    if args.dump_outputs:            # a training step's caller also receives the updated parameters
+        outs = {"scores": scores}
+        if args.train:
+            outs.update(("param." + k, v) for k, v in model.named_parameters())
+        dumped = dump_outputs(args.dump_outputs, outs)
     roof = None
     ev_ms = [(e0.elapsed_time(e1), ne, nn) for (e0, e1, ne, nn) in kernel_events]
     if ev_ms:
@@ -566,6 +584,8 @@ def bench_extrapolation(args, dist, world, rank, engine, scaling="weak"):
         "eval_queries_per_s": B * world * args.steps / dt, "edges_per_step": edges / args.steps,
         "roofline": roof, "cpu_baseline": cpu, "parity": parity, "rg_version": int(_lib_version()),
     }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     print(json.dumps(out))
 
 
@@ -618,6 +638,7 @@ def bench_train(args, dist, world, rank, engine):
     if not args.no_kernel_events:
         engine.KERNEL_EVENTS, engine.BWD_EVENTS = fwd_ev, bwd_ev
     marks = []
+    last = {}
 
     def step(timed=False):
         opt.zero_grad(set_to_none=True)
@@ -635,6 +656,7 @@ def bench_train(args, dist, world, rank, engine):
         if dist is not None:
             allreduce_gradients(list(model.parameters()), dist)
         opt.step()
+        last["scores"], last["loss"] = scores.detach(), loss.detach()
         return model.last_stats
 
     for _ in range(max(args.warmup, 2)):
@@ -660,6 +682,10 @@ def bench_train(args, dist, world, rank, engine):
     engine.KERNEL_EVENTS = engine.BWD_EVENTS = None
     if rank != 0:
         return
+    dumped = None
+    if args.dump_outputs:            # a training step's caller receives the loss and the updated parameters
+        dumped = dump_outputs(args.dump_outputs, dict([("scores", last["scores"]), ("loss", last["loss"])] +
+                                                      [("param." + k, v) for k, v in model.named_parameters()]))
     e_lvl = st["n_edges"]
     fwd_ms = [(a.elapsed_time(b), ne, nn) for (a, b, ne, nn) in fwd_ev]
     bwd_ms = [(a.elapsed_time(b), lvl, n_old) for (a, b, lvl, n_old) in bwd_ev]
@@ -690,7 +716,36 @@ def bench_train(args, dist, world, rank, engine):
         "edges_per_step": edges / args.steps, "roofline": roof_b, "roofline_forward": roof_f, "per_hop_forward": per_hop,
         "cpu_baseline": None, "rg_version": int(_lib_version()),
     }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     print(json.dumps(out))
+
+
+def dump_outputs(out_dir, arrays, max_bytes=MAX_DUMP_BYTES):
+    """--dump-outputs: every array (torch tensor or numpy) as out_dir/<name>.npy, float64 kept, everything else as float32
+    (integers in float64).  Over max_bytes in all, each array keeps the same fraction of its rows, picked by a fixed seed
+    (so two runs of the same arguments keep the same rows).  Returns {name: shape written}."""
+    host = {}
+    for name, a in arrays.items():
+        if hasattr(a, "detach"):
+            a = a.detach().cpu().numpy()
+        a = np.asarray(a)
+        host[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64 if a.dtype.kind in "iub" else np.float32)
+    total = sum(a.nbytes for a in host.values())
+    if total > max_bytes:
+        fixed = sum(a.nbytes for a in host.values() if a.size <= 1)
+        frac = (max_bytes - fixed) / (total - fixed)
+        for name, a in host.items():
+            if a.size <= 1:
+                continue
+            if a.shape[0] == 1:
+                a = a.reshape(-1)
+            keep = max(1, int(a.shape[0] * frac))
+            host[name] = a[np.sort(np.random.default_rng(1234).choice(a.shape[0], keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in host.items()}
 
 
 def _lib_version():
@@ -725,7 +780,15 @@ def main():
     ap.add_argument("--backend", default="nccl", help="process-group backend: nccl (= RCCL; one GPU per rank) or gloo (rehearsal of the "
                     "N > 1 path with several ranks sharing one GPU)")
     ap.add_argument("--force-dist", action="store_true", help="initialise the process group even at world size 1 (exercises the RCCL path on one GPU)")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need: per-kernel HIP events "
+                    "and roofline objects, the f32-MFMA dense step, the family-graph evaluation and the CPU baseline with its parity check "
+                    "(each can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if not args.full:                # a plain run: set up, warm up, the timed steps, the result line
+        args.no_cpu_baseline = args.no_family_eval = args.no_dense_f32 = args.no_kernel_events = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -861,6 +924,11 @@ def main():
     ev_ms = [(e0.elapsed_time(e1), ne, nn) for (e0, e1, ne, nn) in kernel_events]
     dense_ms = [(e0.elapsed_time(e1), n) for (e0, e1, n) in dense_events]
     last_default = dict(last)          # the timed region's last scores (default precision)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        s = sums.double().cpu()
+        dumped = dump_outputs(args.dump_outputs, {"scores": last["scores"], "ranks": last["ranks"],
+                                                  "metrics": torch.stack([s[0] / s[3], s[1] / s[3], s[2] / s[3]])})
     gpu_scores = last["scores"].cpu().numpy() if (rank == 0 and world == 1 and not args.no_cpu_baseline) else None
     gpu_ranks = last["ranks"].double().cpu().numpy() if gpu_scores is not None else None
 
@@ -937,6 +1005,8 @@ def main():
             "roofline": roof, "per_hop": per_hop, "roofline_dense": roof_dense, "cpu_baseline": cpu,
             "parity": parity, "family_eval": family, "rg_version": version,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()

@@ -1664,3 +1664,30 @@ def test_fused_training_dense_step_with_dropout_mask(act, d, n):
         for a_, b_, name in zip(g3, g4, ["agg", "hidden_prev", "W_h", "w_ih", "w_hh", "b_ih", "b_hh", "Ws_next"]):
             r = b_.cpu().numpy()
             np.testing.assert_allclose(a_.cpu().numpy(), r, rtol=2e-3, atol=2e-5 * max(1.0, float(np.abs(r).max())), err_msg="%s attn=%d" % (name, attn))
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_its_outputs(tmp_path):
+    """A plain bench.py run: exactly --steps timed steps, the headline fields only (no roofline, CPU baseline or family evaluation),
+    and --dump-outputs writes the last step's scores, ranks and metrics, the metrics being those of the dumped ranks."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "16",
+           "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=root)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "edges/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert abs(line["eval_queries_per_s"] * line["ms_per_step"] * 1e-3 - 16) < 1e-6 * 16
+    for k in ("roofline", "per_hop", "roofline_dense", "dense_f32", "cpu_baseline", "parity", "family_eval"):
+        assert line[k] is None, k
+    scores, ranks, metrics = (np.load(str(out / (k + ".npy"))) for k in ("scores", "ranks", "metrics"))
+    assert line["dumped_outputs"] == {"scores": list(scores.shape), "ranks": list(ranks.shape), "metrics": [3]}
+    from red_gnn_amd.synthetic import SHAPES
+    assert scores.dtype == np.float32 and scores.shape == (16, SHAPES["C2"]["n_ent"]) and np.isfinite(scores).all()
+    assert ranks.dtype == np.float32 and len(ranks) >= 16 and (ranks >= 1).all() and (ranks <= scores.shape[1]).all()
+    assert np.allclose(metrics, [np.mean(1.0 / ranks), np.mean(ranks <= 1), np.mean(ranks <= 10)], rtol=1e-5)
+    assert abs(line["mrr_of_random_init"] - metrics[0]) < 1e-9

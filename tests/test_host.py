@@ -364,6 +364,31 @@ def test_bench_dense_roofline_per_precision():
     assert bench.DTYPE_OF["f16x3"] == "f32" and bench.DTYPE_OF["f16x2"] != "f32"
 
 
+def test_bench_dump_outputs():
+    """bench.dump_outputs (--dump-outputs): float arrays as they are, integers as float64; over the byte budget every array keeps
+    the same fraction of its rows, the same rows from run to run."""
+    import bench
+    scores = np.random.default_rng(0).standard_normal((100, 50)).astype(np.float32)
+    arrays = {"scores": torch.from_numpy(scores), "ranks": np.arange(1, 101, dtype=np.int32), "metrics": np.array([0.5, 0.25, 0.75]),
+              "loss": torch.tensor(1.5)}
+    with tempfile.TemporaryDirectory() as td:
+        shapes = bench.dump_outputs(os.path.join(td, "a"), arrays)
+        assert shapes == {"scores": [100, 50], "ranks": [100], "metrics": [3], "loss": []}
+        got = {k: np.load(os.path.join(td, "a", k + ".npy")) for k in shapes}
+        assert got["scores"].dtype == np.float32 and np.array_equal(got["scores"], scores)
+        assert got["ranks"].dtype == np.float64 and np.array_equal(got["ranks"], np.arange(1, 101))
+        assert got["metrics"].dtype == np.float64 and got["loss"].shape == () and float(got["loss"]) == 1.5
+        budget = 5000
+        small = [bench.dump_outputs(os.path.join(td, d), arrays, max_bytes=budget) for d in ("b", "c")]
+        assert small[0] == small[1] and small[0]["scores"][0] < 100 and small[0]["scores"][1] == 50
+        files = [os.path.join(td, "b", k + ".npy") for k in shapes]
+        assert sum(np.load(f).nbytes for f in files) <= budget
+        for k in shapes:
+            assert np.array_equal(np.load(os.path.join(td, "b", k + ".npy")), np.load(os.path.join(td, "c", k + ".npy")))
+        kept = np.load(os.path.join(td, "b", "scores.npy"))
+        assert all(any(np.array_equal(r, s) for s in scores) for r in kept)      # whole rows of the output
+
+
 def test_loader_id_cache_roundtrip():
     """Binary id cache of the parsed text: second construction reads the cache, same loader state."""
     from red_gnn_amd.load_data import DataLoader
