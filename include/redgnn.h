@@ -344,6 +344,35 @@ int rg_dense_train_bwd2(int64_t n, int32_t d, const float* grad_hidden, const fl
                         float keep, int32_t act, const float* W_h, const float* w_ih, const float* w_hh, const int32_t* prev_idx,
                         float* grad_gates_i, float* grad_gates_hn, float* grad_pre, float* grad_agg, float* grad_prev, void* stream);
 
+/* ---- relational digraph of an answer (the r-digraph RED-GNN is named for; the reference draws it per setting with
+ * the temporal model_cuda*_vis.py scripts): for row b = (s, r, o) of a batch, the union of the length-L paths s -> o through the frontier's
+ * levels (identity edges count as steps), each edge with the attention alpha of its layer (rg_layer_fwd's formula and arithmetic).
+ * Needs a frontier that still holds levels 0..L (n_levels >= L + 1) and, per hop l, the arguments rg_layer_fwd had: a_s of level
+ * l-1 [N_{l-1}, ap], a_r [2R+1, ap], a_q [B, ap], w_alpha, b_alpha.  Marks are batch-major bitmaps uint32 [batch][ceil(n_ent/32)].
+ * rg_explain_seed: marks_out = {(b, objs[b])} where objs[b] is in level `level` (= L); reached_out uint8 [batch] says which.
+ * Then for l = L..1:
+ * rg_explain_count: the hop-l edges (h, rel, t) with t marked, h in level l-1 and alpha >= min_alpha; marks_prev_out = their heads
+ *   (written, every word); word_ptr_out int32 [batch*ceil(n_ent/32) + 1] = exclusive scan of the kept edges per mark word, total
+ *   last.  Returns the hop's total in *n_edges_host (synchronises `stream`; < 2^31 per hop).  scratch: rg_explain_scratch_bytes(),
+ *   256-B aligned.
+ * rg_explain_emit: the same edges, edges_out int32 [E_l, 4] = (row, head, rel, tail) (16-B aligned) and alpha_out [E_l], in
+ *   (row, tail, CSR-by-tail position) order, i.e. fact-row order inside a tail; deterministic.
+ * rg_explain_gather: puts one hop's list (n edges, `hop` = l) into a (row, hop, ...) layout: edge i of row b goes to
+ *   row_base[b] + i - row_first[b] (int64 [batch] each), as (row, hop, head, rel, tail) into edges_out int32 [n_out, 5] and alpha_out.
+ * Reads no buffer of the subgraph's edge count: per hop the marked tails' CSR rows, the level bitmap and the attention tables. */
+size_t rg_explain_scratch_bytes(const rg_frontier* f);
+int rg_explain_seed(const rg_frontier* f, int32_t batch, int32_t n_ent, int32_t level, const int32_t* objs, uint32_t* marks_out,
+                    uint8_t* reached_out, void* stream);
+int rg_explain_count(const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level, const uint32_t* marks,
+                     const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha,
+                     int32_t attn_dim, float min_alpha, uint32_t* marks_prev_out, int32_t* word_ptr_out, void* scratch,
+                     size_t scratch_bytes, int64_t* n_edges_host, void* stream);
+int rg_explain_emit(const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level, const uint32_t* marks,
+                    const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha,
+                    int32_t attn_dim, float min_alpha, const int32_t* word_ptr, int32_t* edges_out, float* alpha_out, void* stream);
+int rg_explain_gather(int64_t n, int32_t hop, int32_t batch, const int32_t* edges, const float* alpha, const int64_t* row_first,
+                      const int64_t* row_base, int64_t n_out, int32_t* edges_out, float* alpha_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,7 @@ SYMBOLS = [
     "rg_frontier_reset_nodes", "rg_frontier_expand", "rg_frontier_nodes", "rg_frontier_edges_scratch_bytes", "rg_frontier_edges",
     "rg_layer_fwd_scratch_bytes", "rg_layer_fwd", "rg_layer_fwd_plan", "rg_tlayer_fwd", "rg_xlayer_fwd", "rg_frontier_set_window", "rg_layer_bwd_scratch_bytes", "rg_layer_bwd", "rg_tlayer_bwd_scratch_bytes", "rg_tlayer_bwd", "rg_xlayer_bwd", "rg_dense_fwd_supported", "rg_dense_scratch_bytes", "rg_dense_fwd", "rg_dense_fwd_dev", "rg_dense_train_fwd", "rg_dense_train_fwd_as", "rg_rows_addmm", "rg_dense_train_bwd", "rg_dense_train_bwd2", "rg_split3_roundtrip", "rg_split3_product_check", "rg_gram_tn_scratch_bytes", "rg_gram_tn", "rg_rank",
     "rg_frontier_expand_async", "rg_frontier_expand_nodes_async", "rg_frontier_set_edge_hint", "rg_frontier_count_ptr", "rg_frontier_level_counts", "rg_attn_tables",
+    "rg_explain_scratch_bytes", "rg_explain_seed", "rg_explain_count", "rg_explain_emit", "rg_explain_gather",
 ]
 
 _lib = None
@@ -103,6 +104,13 @@ def lib():
     L.rg_gram_tn_scratch_bytes.restype = sz
     L.rg_gram_tn.argtypes = [vp, i64, i32, vp, i64, i32, i64, vp, vp, vp, sz, vp]
     L.rg_split3_product_check.argtypes = [i32, i64, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.rg_explain_scratch_bytes.argtypes = [vp]
+    L.rg_explain_scratch_bytes.restype = sz
+    L.rg_explain_seed.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
+    L.rg_explain_count.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, i32, C.c_float, vp, vp, vp, sz,
+                                   C.POINTER(i64), vp]
+    L.rg_explain_emit.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, i32, C.c_float, vp, vp, vp, vp]
+    L.rg_explain_gather.argtypes = [i64, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp]
     _lib = L
     return L
 

@@ -21,6 +21,8 @@ KERNEL_EVENTS = None
 DENSE_EVENTS = None
 # ... and (start_event, end_event, n_edges, n_old) per rg_layer_bwd call (its kernels: layer_bwd_kernel, bwd_combine_kernel, drel_kernel)
 BWD_EVENTS = None
+# tools/probe_explain.py sets this to a list to collect (start_event, end_event, level, n_edges) per hop of explain_hop
+EXPLAIN_EVENTS = None
 
 
 def _require_gpu(device):
@@ -340,6 +342,60 @@ def layer_fwd(frontier, graph, level, nodes_new, hidden, rela, d, a_s, a_r, a_q,
         ev[1].record()
         KERNEL_EVENTS.append((ev[0], ev[1], frontier.n_edges, n_new))
     return agg
+
+
+def explain_seed(frontier, level, objs):
+    """rg_explain_seed: (marks int32 [B, W] words = {(b, objs[b])} where objs[b] is in level `level`, reached bool [B])."""
+    assert objs.dtype == torch.int32 and objs.is_cuda and objs.numel() == frontier.batch
+    W = (frontier.n_ent + 31) // 32
+    marks = torch.empty((frontier.batch, W), dtype=torch.int32, device=frontier.device)
+    reached = torch.empty(frontier.batch, dtype=torch.bool, device=frontier.device)
+    _lib.check(_lib.lib().rg_explain_seed(frontier.handle, frontier.batch, frontier.n_ent, level, _lib.ptr(objs.contiguous()),
+                                          _lib.ptr(marks), _lib.ptr(reached), _lib.stream_ptr()))
+    return marks, reached
+
+
+def explain_hop(frontier, graph, level, marks, a_s, a_r, a_q, w_alpha, b_alpha, attn_dim, min_alpha):
+    """One hop of the r-digraph extraction (rg_explain_count + rg_explain_emit): the hop-`level` edges into the marked tails whose head
+    is in level-1 and whose attention is >= min_alpha.  Returns (marks of their heads [B, W], edges int32 [E, 4] = (row, head, rel, tail)
+    in (row, tail, CSR position) order, alpha [E])."""
+    for t in (a_s, a_r, a_q, w_alpha, b_alpha):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+    ap = a_s.shape[1]
+    assert a_r.shape[1] == ap and a_q.shape[1] == ap
+    L, dev = _lib.lib(), frontier.device
+    marks_prev = torch.empty_like(marks)
+    word_ptr = torch.empty(marks.numel() + 1, dtype=torch.int32, device=dev)
+    scratch = frontier.scratch(L.rg_explain_scratch_bytes(frontier.handle) + 256)
+    base = scratch.data_ptr()
+    aligned = (base + 255) // 256 * 256
+    n_e = C.c_int64()
+    args = (frontier.handle, graph.handle, frontier.batch, frontier.n_ent, level, _lib.ptr(marks), _lib.ptr(a_s), _lib.ptr(a_r),
+            _lib.ptr(a_q), ap, _lib.ptr(w_alpha), _lib.ptr(b_alpha), attn_dim, float(min_alpha))
+    ev = None
+    if EXPLAIN_EVENTS is not None:
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        ev[0].record()
+    _lib.check(L.rg_explain_count(*args, _lib.ptr(marks_prev), _lib.ptr(word_ptr), C.c_void_p(aligned),
+                                  scratch.numel() - (aligned - base), C.byref(n_e), _lib.stream_ptr()))
+    edges = torch.empty((n_e.value, 4), dtype=torch.int32, device=dev)
+    alpha = torch.empty(n_e.value, dtype=torch.float32, device=dev)
+    if n_e.value:
+        _lib.check(L.rg_explain_emit(*args, _lib.ptr(word_ptr), _lib.ptr(edges), _lib.ptr(alpha), _lib.stream_ptr()))
+    if ev is not None:
+        ev[1].record()
+        EXPLAIN_EVENTS.append((ev[0], ev[1], level, n_e.value))
+    return marks_prev, edges, alpha
+
+
+def explain_gather(hop, batch, edges, alpha, row_first, row_base, edges_out, alpha_out):
+    """rg_explain_gather: one hop's (row, head, rel, tail) list into the (row, hop, head, rel, tail) layout of edges_out [n_out, 5]:
+    edge i of row b goes to row_base[b] + i - row_first[b] (int64 [batch] each)."""
+    assert edges.dtype == torch.int32 and edges.is_contiguous() and edges_out.is_contiguous() and alpha_out.is_contiguous()
+    assert row_first.dtype == torch.int64 and row_base.dtype == torch.int64
+    _lib.check(_lib.lib().rg_explain_gather(edges.shape[0], hop, batch, _lib.ptr(edges), _lib.ptr(alpha.contiguous()),
+                                            _lib.ptr(row_first.contiguous()), _lib.ptr(row_base.contiguous()), edges_out.shape[0],
+                                            _lib.ptr(edges_out), _lib.ptr(alpha_out), _lib.stream_ptr()))
 
 
 def layer_fwd_plan(frontier, graph, level, n_old, n_new, n_edges, ld):

@@ -387,6 +387,20 @@ class RED_GNN_trans(nn.Module):
         return self._frontiers.get(n_ent, batch, n_levels, device)
 
     def forward(self, subs, rels, mode="train", trace=None):
+        return self._run(subs, rels, mode, trace)
+
+    def explain(self, subs, rels, objs=None, mode="test", min_alpha=0.0):
+        """The relational digraph behind the score of o for each row (s, r, o): every edge of the query subgraph on a length-L path
+        s -> o (identity edges count as steps) whose edges all have attention >= min_alpha, with that attention.  ``objs=None``: the
+        model's own top answer per row (smallest entity id on a tie).  Eval semantics (dropout = identity) under no_grad; parameters
+        and ``training`` are left as they are.  Returns an explain.RDigraph (device tensors)."""
+        from . import explain as _explain
+        return _explain.explain(self, subs, rels, objs, mode, min_alpha)
+
+    def _run(self, subs, rels, mode, trace=None, kept=None):
+        """forward(); with ``kept`` (a list) the frontier keeps all n_layer + 1 levels, nothing is graph-replayed, and per layer
+        dict(a_s = the attention projection of the layer's input level [n_old, ap], tables = (a_r, a_q, rela_p) or None) is appended
+        for rg_explain_*."""
         device = self.W_final.weight.device
         engine._require_gpu(device)
         n = len(subs)
@@ -402,16 +416,19 @@ class RED_GNN_trans(nn.Module):
         need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
         n_ent = graph.n_ent                     # the inductive setting switches graphs (and n_ent) with the mode
         # the fused kernels implement dropout as the identity: they serve eval mode (and training mode with p = 0) only
-        no_dropout = not self.training or self.dropout.p == 0.0
+        training = self.training and kept is None          # (explain: eval semantics whatever the module's mode)
+        no_dropout = not training or self.dropout.p == 0.0
         fused = not need_grad and no_dropout and self.fused_dense and engine.dense_supported(self.hidden_dim, self.attn_dim)
-        if fused and self.use_graphs and trace is None and engine.KERNEL_EVENTS is None and engine.DENSE_EVENTS is None:
+        if fused and self.use_graphs and trace is None and kept is None and engine.KERNEL_EVENTS is None and engine.DENSE_EVENTS is None:
             out = self._forward_graphed(graph, q_sub, q_rel, n, device)
             if out is not None:
                 return out
-        fr = self._frontier(n_ent, n, self.n_layer + 1 if need_grad else 2, device)
+        fr = self._frontier(n_ent, n, self.n_layer + 1 if (need_grad or kept is not None) else 2, device)
         fr.reset(q_sub)
+        if kept is not None:
+            kept.append(dict(frontier=fr, graph=graph, q_rel=q_rel))
         if fused:
-            return self._forward_inference(fr, graph, q_sub, q_rel, n, device, trace)
+            return self._forward_inference(fr, graph, q_sub, q_rel, n, device, trace, kept)
         lease = engine.FrontierLease(fr)      # lives as long as the autograd contexts of this forward
 
         d = self.hidden_dim
@@ -428,11 +445,20 @@ class RED_GNN_trans(nn.Module):
             n_edges.append(n_e)
             engine.prefer_blas(n_new)
             layer = self.gnn_layers[i]
+            if kept is not None:
+                # the attention projection aggregate() forms of the layer's input, formed here to be kept (same op, same result)
+                a_s_keep = a_s_next
+                if a_s_keep is None:
+                    a, ap = self.attn_dim, pad_attn(self.attn_dim)
+                    w_s = F.pad(layer.Ws_attn.weight, (0, 0, 0, ap - a)) if ap != a else layer.Ws_attn.weight
+                    a_s_keep = tall_linear(hidden, w_s)
+                kept.append(dict(a_s=a_s_keep, tables=None))
             if fused_train:
                 # models.py:80-83 with the dense part in one kernel: W_h + act, h0 carry (gather by prev_idx), dropout, GRU step
-                agg = layer.aggregate(q_rel, hidden, lease, graph, fr.level, nodes, nodes_old, a_s=a_s_next)
+                agg = layer.aggregate(q_rel, hidden, lease, graph, fr.level, nodes, nodes_old,
+                                      a_s=a_s_next if kept is None else kept[-1]["a_s"])
                 mask = None
-                if self.training and self.dropout.p > 0.0:
+                if training and self.dropout.p > 0.0:
                     keep = 1.0 - self.dropout.p
                     mask = torch.empty((n_new, d), device=device).bernoulli_(keep).div_(keep)
                 # the next layer's attention projection of the new state comes out of the same kernel (attn <= 16) - and after the last
@@ -444,6 +470,11 @@ class RED_GNN_trans(nn.Module):
                 out = _DenseStep.apply(agg, h0, layer.W_h.weight, g.weight_ih_l0, g.weight_hh_l0, g.bias_ih_l0, g.bias_hh_l0, Ws_next,
                                        prev_idx, old_new, mask, self.act_name, g, 1.0 - self.dropout.p)
                 hidden, a_s_next = out if Ws_next is not None else (out, None)
+            elif kept is not None:
+                agg = layer.aggregate(q_rel, hidden, lease, graph, fr.level, nodes, nodes_old, a_s=kept[-1]["a_s"])
+                hidden = layer.act(tall_linear(agg, layer.W_h.weight))                 # GNNLayer.forward with the kept a_s
+                h0 = torch.zeros((n_new, d), device=device).index_copy(0, old_new.long(), h0)
+                hidden = gru_step(hidden, h0, g)                                     # (dropout: identity in eval)
             else:
                 hidden = layer(q_sub, q_rel, hidden, lease, graph, fr.level, nodes, nodes_old)             # models.py:80
                 h0 = torch.zeros((n_new, d), device=device).index_copy(0, old_new.long(), h0)           # models.py:81
@@ -522,7 +553,7 @@ class RED_GNN_trans(nn.Module):
         self._graph_failed.clear()
         self._pending_key = None
 
-    def _forward_inference(self, fr, graph, q_sub, q_rel, n, device, trace):
+    def _forward_inference(self, fr, graph, q_sub, q_rel, n, device, trace, kept=None):
         """The same forward with no autograd graph: per layer one expansion, one fused message-passing
         kernel and one fused dense kernel; hidden / a_s never leave their padded device layout."""
         d, a = self.hidden_dim, self.attn_dim
@@ -540,6 +571,8 @@ class RED_GNN_trans(nn.Module):
             n_edges.append(n_e)
             sizes.append((n_new, engine.layer_fwd_plan(fr, graph, fr.level, n_old, n_new, n_e, ld), n_e))
             layer = self.gnn_layers[i]
+            if kept is not None:
+                kept.append(dict(a_s=a_s, tables=tables[i]))
             agg = layer.aggregate_nograd(tables[i], hidden, a_s, fr, graph, fr.level, nodes)
             last = i + 1 == self.n_layer
             hidden, a_s = engine.dense_fwd(
@@ -564,3 +597,6 @@ class RED_GNN_induc(RED_GNN_trans):
 
     def forward(self, subs, rels, mode="transductive", trace=None):
         return super().forward(subs, rels, mode=mode, trace=trace)
+
+    def explain(self, subs, rels, objs=None, mode="transductive", min_alpha=0.0):
+        return super().explain(subs, rels, objs=objs, mode=mode, min_alpha=min_alpha)
