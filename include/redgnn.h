@@ -296,6 +296,21 @@ int rg_rank(const float* scores, int32_t batch, int32_t n_ent,
             const int32_t* filt_ptr, const int32_t* filt_idx,
             float* ranks_out, void* stream);
 
+/* ---- filtered top-k prediction: the k best new answers of each query row (models.py RED_GNN_trans.predict)
+ * scores device fp32 [batch, n_ent] (contiguous, the readout's output).  q_key int64 [batch]: key = s * (2*n_rel + 1) + r of the row.
+ * Known-answer index (device): known_keys int64 [n_keys] sorted ascending and unique, known_ptr int64 [n_keys + 1], known_idx int32:
+ * the tails of key i are known_idx[known_ptr[i]:known_ptr[i+1]], ascending and unique.  n_keys = 0 (arrays may be NULL): exclude
+ * nothing.  Each row drops the tails its key lists (binary search of known_keys on the device) and returns in idx_out int32
+ * [batch, k] / score_out fp32 [batch, k] the remaining entities ordered by score descending, then entity id ascending; -0.0 ranks
+ * equal to +0.0, NaN below -inf (returned only when nothing else is left).  Fewer than k remaining: the row's tail is idx -1,
+ * score -inf.  score_out holds scores[row, idx] bit for bit.  1 <= k <= 1024, n_ent any positive int32.  Each row depends only on
+ * its own inputs; results are deterministic (integer atomics only).  Known tails outside 0..n_ent-1 are ignored; a known list that
+ * is not ascending and unique breaks the contract: the row's result is then unspecified (it may differ from the top-k and from run
+ * to run), though nothing is read or written out of bounds. */
+int rg_topk(const float* scores, int32_t batch, int32_t n_ent, int32_t k, const int64_t* q_key,
+            const int64_t* known_keys, const int64_t* known_ptr, const int32_t* known_idx, int64_t n_keys,
+            int32_t* idx_out, float* score_out, void* stream);
+
 /* rg_dense_fwd with the node count read on the device (after rg_frontier_expand_async): n_cap = capacity of the row buffers,
  * n_dev = rg_frontier_count_ptr() of the frontier whose newest level the rows belong to, n_hint = the row count the caller expects
  * (0 = unknown): it only sizes the grid, every row count up to n_cap is processed correctly. */

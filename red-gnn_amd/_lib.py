@@ -18,6 +18,7 @@ SYMBOLS = [
     "rg_layer_fwd_scratch_bytes", "rg_layer_fwd", "rg_layer_fwd_plan", "rg_tlayer_fwd", "rg_xlayer_fwd", "rg_frontier_set_window", "rg_layer_bwd_scratch_bytes", "rg_layer_bwd", "rg_tlayer_bwd_scratch_bytes", "rg_tlayer_bwd", "rg_xlayer_bwd", "rg_dense_fwd_supported", "rg_dense_scratch_bytes", "rg_dense_fwd", "rg_dense_fwd_dev", "rg_dense_train_fwd", "rg_dense_train_fwd_as", "rg_rows_addmm", "rg_dense_train_bwd", "rg_dense_train_bwd2", "rg_split3_roundtrip", "rg_split3_product_check", "rg_gram_tn_scratch_bytes", "rg_gram_tn", "rg_rank",
     "rg_frontier_expand_async", "rg_frontier_expand_nodes_async", "rg_frontier_set_edge_hint", "rg_frontier_count_ptr", "rg_frontier_level_counts", "rg_attn_tables",
     "rg_explain_scratch_bytes", "rg_explain_seed", "rg_explain_count", "rg_explain_emit", "rg_explain_gather",
+    "rg_topk",
 ]
 
 _lib = None
@@ -99,6 +100,7 @@ def lib():
     L.rg_dense_train_bwd.argtypes = [i64, i32, vp, vp, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.rg_dense_train_bwd2.argtypes = [i64, i32, vp, vp, vp, vp, C.c_float, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.rg_rank.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.rg_topk.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp]
     L.rg_split3_roundtrip.argtypes = [vp, i64, i32, vp, vp, vp]
     L.rg_gram_tn_scratch_bytes.argtypes = [i32, i32]
     L.rg_gram_tn_scratch_bytes.restype = sz

@@ -755,3 +755,25 @@ def rank(scores, ans_ptr, ans_idx, filt_ptr, filt_idx):
     _lib.check(_lib.lib().rg_rank(_lib.ptr(scores), B, n_ent, _lib.ptr(ans_ptr), _lib.ptr(ans_idx),
                                   _lib.ptr(filt_ptr), _lib.ptr(filt_idx), _lib.ptr(out), _lib.stream_ptr()))
     return out
+
+
+def topk(scores, k, q_key=None, known=None):
+    """Filtered top-k (rg_topk) of every row of scores fp32 [B, n_ent]: (ids int32 [B, k], scores fp32 [B, k]), score descending then
+    id ascending, -1 / -inf past the row's remaining entities.  ``known`` = (keys int64, ptr int64, idx int32) device tensors of a
+    known-answer index (load_data.DataLoader.known_index) and ``q_key`` int64 [B] the rows' keys; None excludes nothing."""
+    assert scores.is_cuda and scores.dtype == torch.float32 and scores.is_contiguous() and scores.dim() == 2
+    B, n_ent = scores.shape
+    idx = torch.empty((B, k), dtype=torch.int32, device=scores.device)
+    val = torch.empty((B, k), dtype=torch.float32, device=scores.device)
+    if known is None or known[0].numel() == 0:
+        keys = ptr = tails = q_key = None
+        n_keys = 0
+    else:
+        keys, ptr, tails = known
+        assert q_key is not None and q_key.dtype == torch.int64 and q_key.is_contiguous() and q_key.numel() == B
+        assert keys.dtype == torch.int64 and ptr.dtype == torch.int64 and tails.dtype == torch.int32
+        assert all(t.is_cuda and t.is_contiguous() for t in (q_key, keys, ptr, tails)) and ptr.numel() == keys.numel() + 1
+        n_keys = keys.numel()
+    _lib.check(_lib.lib().rg_topk(_lib.ptr(scores), B, n_ent, int(k), _lib.ptr(q_key), _lib.ptr(keys), _lib.ptr(ptr), _lib.ptr(tails),
+                                  n_keys, _lib.ptr(idx), _lib.ptr(val), _lib.stream_ptr()))
+    return idx, val

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from .engine import Frontier, Graph, _require_gpu
+from .load_data import known_index_of
 
 
 class DataLoader:
@@ -76,6 +77,17 @@ class DataLoader:
             for h, r, t in part.tolist():
                 filters[(h, r)].add(t)
         return {k: sorted(v) for k, v in filters.items()}
+
+    def known_index(self, mode="transductive"):
+        """The filter sets of ``mode``'s evaluation as a sorted CSR over query keys s * (2*n_rel + 1) + r, numpy (keys, ptr, idx): those
+        behind ``val_filters`` for 'transductive' / 'train', those behind ``tst_filters`` otherwise (the graph_for mapping).  Built
+        once per mode from the (already doubled) triple arrays."""
+        mode = "transductive" if mode in ("transductive", "train") else "inductive"
+        cache = self.__dict__.setdefault("_known_index", {})
+        if mode not in cache:
+            parts = (self.tra_train_all, self.tra_valid, self.tra_test) if mode == "transductive" else (self.ind_train, self.ind_valid, self.ind_test)
+            cache[mode] = known_index_of(np.concatenate(parts, 0), self.n_rel)
+        return cache[mode]
 
     def load_query(self, triples):
         by_hr = defaultdict(list)

@@ -17,6 +17,22 @@ import torch
 from .engine import Frontier, Graph, _require_gpu
 
 
+def known_index_of(triples, n_rel):
+    """(keys, ptr, idx) of the (h, r) -> {t} sets of int64 triples [n, 3] (already doubled): keys = h * (2*n_rel + 1) + r sorted and
+    unique, ptr int64 [len(keys) + 1], idx int32 with each key's tails ascending and unique (lexsort + unique, no Python loop)."""
+    triples = np.asarray(triples, dtype=np.int64).reshape(-1, 3)
+    key = triples[:, 0] * (2 * n_rel + 1) + triples[:, 1]
+    tail = triples[:, 2]
+    o = np.lexsort((tail, key))
+    key, tail = key[o], tail[o]
+    keep = np.ones(len(key), dtype=bool)
+    keep[1:] = (key[1:] != key[:-1]) | (tail[1:] != tail[:-1])
+    key, tail = key[keep], tail[keep]
+    keys, first = np.unique(key, return_index=True)
+    ptr = np.append(first, len(key)).astype(np.int64)
+    return keys.astype(np.int64), ptr, tail.astype(np.int32)
+
+
 class DataLoader:
     def __init__(self, task_dir=None, ids=None, device="cuda", verbose=True, cache_dir=None):
         self.task_dir = task_dir
@@ -83,6 +99,16 @@ class DataLoader:
     @filters.setter
     def filters(self, value):
         self._filters = value
+
+    def known_index(self, mode="test"):
+        """The filter sets as a sorted CSR over query keys, numpy (keys int64 [K], ptr int64 [K+1], idx int32): the tails of key
+        s * (2*n_rel + 1) + r are idx[ptr[i]:ptr[i+1]] (ascending, unique) where keys[i] is that key.  Same content as ``filters``
+        (every split with its inverses, whatever the mode); built once from the triple arrays, vectorised (rg_topk's exclusion)."""
+        cache = self.__dict__.setdefault("_known_index", {})
+        if "all" not in cache:
+            trip = np.concatenate([self.fact_triple, self.train_triple, self.valid_triple, self.test_triple], 0)
+            cache["all"] = known_index_of(self.double_triple(trip), self.n_rel)
+        return cache["all"]
 
     def _cached_ids(self, task_dir, cache_dir):
         """Parse the text files once; later runs load `<cache_dir>/<name>_ids.npz` while it is newer than every text file.

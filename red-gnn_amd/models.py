@@ -397,10 +397,20 @@ class RED_GNN_trans(nn.Module):
         from . import explain as _explain
         return _explain.explain(self, subs, rels, objs, mode, min_alpha)
 
-    def _run(self, subs, rels, mode, trace=None, kept=None):
+    def predict(self, subs, rels, k=10, exclude_known=True, mode="test"):
+        """The k best answers of each query (s, r, ?): prediction.Prediction(ids int64 [B, k], scores fp32 [B, k]) on the device,
+        ordered by score descending, then entity id ascending (-0.0 == +0.0, NaN last).  ``exclude_known``: the tails the loader's
+        filter sets already hold for (s, r) (loader.known_index(mode)) are left out, so the answers are new facts; where fewer than k
+        entities remain the row ends in id -1, score -inf.  The scores are forward()'s, bit for bit; the selection is one HIP launch
+        (rg_topk).  Eval semantics (dropout = identity) under no_grad; parameters and ``training`` are left as they are.
+        To explain the j-th answer: ``model.explain(subs, rels, pred.ids[:, j])`` (rows whose id is -1 have no answer to explain)."""
+        from . import prediction as _prediction
+        return _prediction.predict(self, subs, rels, k, exclude_known, mode)
+
+    def _run(self, subs, rels, mode, trace=None, kept=None, eval_mode=False):
         """forward(); with ``kept`` (a list) the frontier keeps all n_layer + 1 levels, nothing is graph-replayed, and per layer
         dict(a_s = the attention projection of the layer's input level [n_old, ap], tables = (a_r, a_q, rela_p) or None) is appended
-        for rg_explain_*."""
+        for rg_explain_*.  ``eval_mode``: dropout is the identity whatever the module's mode (predict)."""
         device = self.W_final.weight.device
         engine._require_gpu(device)
         n = len(subs)
@@ -416,7 +426,7 @@ class RED_GNN_trans(nn.Module):
         need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
         n_ent = graph.n_ent                     # the inductive setting switches graphs (and n_ent) with the mode
         # the fused kernels implement dropout as the identity: they serve eval mode (and training mode with p = 0) only
-        training = self.training and kept is None          # (explain: eval semantics whatever the module's mode)
+        training = self.training and kept is None and not eval_mode   # (explain, predict: eval semantics whatever the module's mode)
         no_dropout = not training or self.dropout.p == 0.0
         fused = not need_grad and no_dropout and self.fused_dense and engine.dense_supported(self.hidden_dim, self.attn_dim)
         if fused and self.use_graphs and trace is None and kept is None and engine.KERNEL_EVENTS is None and engine.DENSE_EVENTS is None:
@@ -478,7 +488,8 @@ class RED_GNN_trans(nn.Module):
             else:
                 hidden = layer(q_sub, q_rel, hidden, lease, graph, fr.level, nodes, nodes_old)             # models.py:80
                 h0 = torch.zeros((n_new, d), device=device).index_copy(0, old_new.long(), h0)           # models.py:81
-                hidden = self.dropout(hidden)                                        # models.py:82
+                if not eval_mode:                                                    # (predict: identity whatever the module's mode)
+                    hidden = self.dropout(hidden)                                    # models.py:82
                 hidden = gru_step(hidden, h0, g)                                     # models.py:83
             h0 = hidden
             if trace is not None:
@@ -600,3 +611,6 @@ class RED_GNN_induc(RED_GNN_trans):
 
     def explain(self, subs, rels, objs=None, mode="transductive", min_alpha=0.0):
         return super().explain(subs, rels, objs=objs, mode=mode, min_alpha=min_alpha)
+
+    def predict(self, subs, rels, k=10, exclude_known=True, mode="transductive"):
+        return super().predict(subs, rels, k=k, exclude_known=exclude_known, mode=mode)

@@ -29,6 +29,18 @@ class Options(object):
     pass
 
 
+def save_checkpoint(path, net, opts, dataset, epoch, mrr):
+    """{"state_dict": CPU tensors, "opts": what predict.py needs to rebuild the network}, written aside and renamed into place."""
+    ckpt = {"state_dict": {k: v.detach().cpu() for k, v in net.state_dict().items()},
+            "opts": dict(hidden_dim=opts.hidden_dim, attn_dim=opts.attn_dim, n_layer=opts.n_layer, act=opts.act, dropout=opts.dropout,
+                         n_ent=opts.n_ent, n_rel=opts.n_rel, dataset=dataset, epoch=epoch, mrr=float(mrr))}
+    d = os.path.dirname(os.path.abspath(path))
+    os.makedirs(d, exist_ok=True)
+    tmp = "%s.%d.tmp" % (path, os.getpid())
+    torch.save(ckpt, tmp)
+    os.replace(tmp, path)
+
+
 def main():
     parser = argparse.ArgumentParser(description="RED-GNN on MI355X")
     parser.add_argument("--data_path", type=str, default="data/family/")
@@ -37,6 +49,7 @@ def main():
     parser.add_argument("--epochs", type=int, default=50)
     parser.add_argument("--ids", type=str, default=None, help="npz of pre-parsed id triples (n_ent, n_rel, facts, train, valid, test) instead of text files")
     parser.add_argument("--preset", type=str, default=None, help="hyper-parameter preset name (default: the dataset directory name)")
+    parser.add_argument("--save", type=str, default=None, help="checkpoint path: rank 0 writes the model on each new best MRR (predict.py reads it)")
     args = parser.parse_args()
 
     np.random.seed(args.seed)
@@ -74,6 +87,8 @@ def main():
             best_mrr, best_str = mrr, out_str
             if rank0:
                 print(str(epoch) + "\t" + best_str)
+                if args.save:
+                    save_checkpoint(args.save, model.model, opts, dataset, epoch, mrr)
     if rank0:
         print(best_str)
     if world > 1:
