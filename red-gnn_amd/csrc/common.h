@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
+#include <type_traits>
 
 #include "redgnn.h"
 
@@ -48,6 +49,55 @@ static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; 
 size_t scan_scratch_elems(int64_t n);
 int scan_exclusive(const uint32_t* in, int32_t* out, int64_t n, bool popc, int32_t* total_dev,
                    int32_t* scratch, hipStream_t s);
+
+// ---- compile-time widths of the layer kernels --------------------------------------------
+// f(std::integral_constant<int, AP4>()) for the padded attention width ap4 = ap / 4
+template <typename F>
+inline int with_ap4(int ap4, const char* who, F&& f) {
+  switch (ap4) {
+    case 1: return f(std::integral_constant<int, 1>());
+    case 2: return f(std::integral_constant<int, 2>());
+    case 3: return f(std::integral_constant<int, 3>());
+    case 4: return f(std::integral_constant<int, 4>());
+    case 8: return f(std::integral_constant<int, 8>());
+    default: set_error("%s: padded attention dim %d not in {4,8,12,16,32}", who, ap4 * 4); return 1;
+  }
+}
+
+// f(std::integral_constant<int, G>()) for the lanes that own a row of ld4 float4: the power of two G >= ld4, at least 4
+template <typename F>
+inline int with_g(int ld4, F&& f) {
+  if (ld4 <= 4) return f(std::integral_constant<int, 4>());
+  if (ld4 <= 8) return f(std::integral_constant<int, 8>());
+  if (ld4 <= 16) return f(std::integral_constant<int, 16>());
+  if (ld4 <= 32) return f(std::integral_constant<int, 32>());
+  return f(std::integral_constant<int, 64>());
+}
+
+// ---- device helpers of the layer kernels ----------------------------------------------------
+__device__ __forceinline__ float4 f4zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+
+template <int CTRL>
+__device__ __forceinline__ float dpp_add(float v) {
+  const int t = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false);
+  return v + __int_as_float(t);
+}
+
+// sum over the G lanes of a group; every lane gets the total
+template <int G>
+__device__ __forceinline__ float group_sum(float v) {
+  if constexpr (G >= 16) {
+    v = dpp_add<0x128>(v);  // row_ror:8
+    v = dpp_add<0x124>(v);  // row_ror:4
+    v = dpp_add<0x122>(v);  // row_ror:2
+    v = dpp_add<0x121>(v);  // row_ror:1
+    if constexpr (G >= 32) v += __shfl_xor(v, 16, 64);
+    if constexpr (G >= 64) v += __shfl_xor(v, 32, 64);
+  } else {
+    for (int o = G / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  }
+  return v;
+}
 
 }  // namespace rg
 

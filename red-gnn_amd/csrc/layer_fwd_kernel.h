@@ -70,8 +70,6 @@ struct FwdArgs {
   int n_data;
 };
 
-__device__ __forceinline__ float4 f4zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-
 constexpr int FWD_BLOCK = 512;   // 3 workgroups per CU = 24 waves at <= 80 VGPRs (no spills)
 
 template <int G, int AP4, bool PACKED, bool DENSE, int KPG, bool RELA_LDS, bool TEMPORAL>
@@ -96,7 +94,7 @@ __global__ __launch_bounds__(FWD_BLOCK, TEMPORAL ? 4 : (G >= 32 ? 4 : 6)) void l
   if constexpr (RELA_LDS) {
     for (int i = threadIdx.x; i < A.n_rela_rows * G; i += BLOCK) {
       const int r = i / G, c = i - r * G;
-      rela_l[i] = c < A.ld4 ? A.rela[(int64_t)r * A.ld4 + c] : f4zero();
+      rela_l[i] = c < A.ld4 ? A.rela[(int64_t)r * A.ld4 + c] : rg::f4zero();
     }
   }
   __syncthreads();
@@ -124,7 +122,7 @@ __global__ __launch_bounds__(FWD_BLOCK, TEMPORAL ? 4 : (G >= 32 ? 4 : 6)) void l
       qt = A.q_time[b];
       if (A.win_lo) { wlo = A.win_lo[b]; whi = A.win_hi[b]; }
     }
-    float4 acc = f4zero();
+    float4 acc = rg::f4zero();
     for (int c0 = beg; c0 < end; c0 += G) {
       // ---- phase 1: one candidate in-edge per lane ---------------------------------------------
       const int c = c0 + lane_g;
@@ -184,7 +182,7 @@ __global__ __launch_bounds__(FWD_BLOCK, TEMPORAL ? 4 : (G >= 32 ? 4 : 6)) void l
       const int pos = __popcll(m & ((1ull << lane_g) - 1ull));
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // previous round's reads are done
       __builtin_amdgcn_wave_barrier();
-      if (lane_g >= cnt) my_stage[lane_g] = f4zero();          // pad tuples: alpha = 0, row 0
+      if (lane_g >= cnt) my_stage[lane_g] = rg::f4zero();      // pad tuples: alpha = 0, row 0
       if (valid) my_stage[pos] = make_float4(__int_as_float(s), __int_as_float(r), alpha, __int_as_float(trow));
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       __builtin_amdgcn_wave_barrier();
@@ -316,19 +314,6 @@ int launch(const FwdArgs& A, int B, const rg_vrows& vr, bool dense, int kpg, hip
   return dense ? launch2<G, AP4, false, true, TEMPORAL>(A, B, vr, kpg, s) : launch2<G, AP4, false, false, TEMPORAL>(A, B, vr, kpg, s);
 }
 
-template <int G, bool TEMPORAL>
-int launch_ap(const FwdArgs& A, int ap4, int B, const rg_vrows& vr, bool dense, int kpg, hipStream_t s) {
-  switch (ap4) {
-    case 1: return launch<G, 1, TEMPORAL>(A, B, vr, dense, kpg, s);
-    case 2: return launch<G, 2, TEMPORAL>(A, B, vr, dense, kpg, s);
-    case 3: return launch<G, 3, TEMPORAL>(A, B, vr, dense, kpg, s);
-    case 4: return launch<G, 4, TEMPORAL>(A, B, vr, dense, kpg, s);
-    case 8: return launch<G, 8, TEMPORAL>(A, B, vr, dense, kpg, s);
-    default: rg::set_error("rg_layer_fwd: padded attention dim %d not in {4,8,12,16,32}", ap4 * 4); return 1;
-  }
-}
-
-
 // checks shared by the static and the temporal entry points; fills the common part of FwdArgs
 inline int fill_common(const char* who, const rg_frontier* f, const rg_graph* g, int32_t level, int64_t n_new, int32_t d,
                        int32_t ld, int32_t ap, int32_t attn_dim, const void* scratch, size_t scratch_bytes, size_t need, FwdArgs* A) {
@@ -360,11 +345,11 @@ inline int fill_common(const char* who, const rg_frontier* f, const rg_graph* g,
 
 template <bool TEMPORAL>
 int dispatch(const FwdArgs& A, int ld4, int ap4, int B, const rg_vrows& vr, bool dense, int kpg, hipStream_t s) {
-  if (ld4 <= 4) return launch_ap<4, TEMPORAL>(A, ap4, B, vr, dense, kpg, s);
-  if (ld4 <= 8) return launch_ap<8, TEMPORAL>(A, ap4, B, vr, dense, kpg, s);
-  if (ld4 <= 16) return launch_ap<16, TEMPORAL>(A, ap4, B, vr, dense, kpg, s);
-  if (ld4 <= 32) return launch_ap<32, TEMPORAL>(A, ap4, B, vr, dense, kpg, s);
-  return launch_ap<64, TEMPORAL>(A, ap4, B, vr, dense, kpg, s);
+  return rg::with_g(ld4, [&](auto g) {
+    return rg::with_ap4(ap4, "rg_layer_fwd", [&](auto ap) {
+      return launch<decltype(g)::value, decltype(ap)::value, TEMPORAL>(A, B, vr, dense, kpg, s);
+    });
+  });
 }
 
 }  // namespace

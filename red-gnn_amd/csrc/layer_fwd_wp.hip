@@ -36,8 +36,6 @@ constexpr int QCAP = 256;   // queued edges per wave between flushes; >= RG_PACK
 constexpr int WAVE_LDS = QCAP * 16 + 64;     // bytes: tuples [QCAP] (the 8-B fill queue aliases their upper half) + 4 head masks
 static_assert(QCAP == 256 && RG_PACK == 128, "a lane holds two entries of a pack; phase 1 takes four queued edges per lane");
 
-__device__ __forceinline__ float4 f4zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-
 __device__ __forceinline__ uint32_t wave_or(uint32_t v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v |= (uint32_t)__shfl_xor((int)v, o, 64);
@@ -72,7 +70,7 @@ __global__ __launch_bounds__(WP_BLOCK, 4) void layer_fwd_wp_kernel(WpArgs A) {
   if constexpr (RELA_LDS) {
     for (int i = threadIdx.x; i < A.n_rela_rows * RW; i += WP_BLOCK) {
       const int r = i / RW, c = i - r * RW;
-      rela_l[i] = c < A.ld4 ? A.rela[(int64_t)r * A.ld4 + c] : f4zero();
+      rela_l[i] = c < A.ld4 ? A.rela[(int64_t)r * A.ld4 + c] : rg::f4zero();
     }
   }
   __syncthreads();
@@ -247,7 +245,7 @@ __global__ __launch_bounds__(WP_BLOCK, 4) void layer_fwd_wp_kernel(WpArgs A) {
       if (e < end) {
         float4 acc[F], hvA[F], hvB[F];
 #pragma unroll
-        for (int f = 0; f < F; ++f) acc[f] = f4zero();
+        for (int f = 0; f < F; ++f) acc[f] = rg::f4zero();
         float4 tA = st[e], tB;
         int cur = __float_as_int(tA.w);
         gather(tA, hvA);
@@ -259,7 +257,7 @@ __global__ __launch_bounds__(WP_BLOCK, 4) void layer_fwd_wp_kernel(WpArgs A) {
           if (e + 1 >= end || __float_as_int(tB.w) != cur) {
             store_row(cur, acc);
 #pragma unroll
-            for (int f = 0; f < F; ++f) acc[f] = f4zero();
+            for (int f = 0; f < F; ++f) acc[f] = rg::f4zero();
             cur = __float_as_int(tB.w);
           }
           if (e + 1 >= end) break;
@@ -269,7 +267,7 @@ __global__ __launch_bounds__(WP_BLOCK, 4) void layer_fwd_wp_kernel(WpArgs A) {
           if (e + 2 >= end || __float_as_int(tA.w) != cur) {
             store_row(cur, acc);
 #pragma unroll
-            for (int f = 0; f < F; ++f) acc[f] = f4zero();
+            for (int f = 0; f < F; ++f) acc[f] = rg::f4zero();
             cur = __float_as_int(tA.w);
           }
           if (e + 2 >= end) break;
@@ -347,18 +345,6 @@ int launch2(const WpArgs& A, hipStream_t s) {
   return launch3<G, F, AP4, false>(A, lds, s);
 }
 
-template <int G, int F>
-int launch_ap(const WpArgs& A, int ap4, hipStream_t s) {
-  switch (ap4) {
-    case 1: return launch2<G, F, 1>(A, s);
-    case 2: return launch2<G, F, 2>(A, s);
-    case 3: return launch2<G, F, 3>(A, s);
-    case 4: return launch2<G, F, 4>(A, s);
-    case 8: return launch2<G, F, 8>(A, s);
-    default: rg::set_error("rg_layer_fwd: padded attention dim %d not in {4,8,12,16,32}", ap4 * 4); return 1;
-  }
-}
-
 }  // namespace
 
 bool offsets_fit(int64_t n_old, int32_t ld) { return n_old >= 0 && (uint64_t)n_old * ld * sizeof(float) < ((uint64_t)1 << 32); }
@@ -368,11 +354,9 @@ bool offsets_fit(int64_t n_old, int32_t ld) { return n_old >= 0 && (uint64_t)n_o
 // the tuple reads) - profiles/r02/per_hop_wp_lane_grouping_variants.txt
 int launch(const WpArgs& A, int ap4, hipStream_t s) {
   RG_CHECK(A.n_items / 8 + ((int64_t)1 << 26) < ((int64_t)1 << 31), "rg_layer_fwd: work space too large for 32-bit queue tickets");
-  if (A.ld4 <= 4) return launch_ap<2, 2>(A, ap4, s);
-  if (A.ld4 <= 8) return launch_ap<4, 2>(A, ap4, s);
-  if (A.ld4 <= 16) return launch_ap<8, 2>(A, ap4, s);
-  if (A.ld4 <= 32) return launch_ap<16, 2>(A, ap4, s);
-  return launch_ap<32, 2>(A, ap4, s);
+  return rg::with_g(A.ld4, [&](auto g) {      // G / 2 lanes, two float4 each, per row
+    return rg::with_ap4(ap4, "rg_layer_fwd", [&](auto ap) { return launch2<decltype(g)::value / 2, 2, decltype(ap)::value>(A, s); });
+  });
 }
 
 }  // namespace rgwp
