@@ -388,6 +388,26 @@ int rg_explain_emit(const rg_frontier* f, const rg_graph* g, int32_t batch, int3
 int rg_explain_gather(int64_t n, int32_t hop, int32_t batch, const int32_t* edges, const float* alpha, const int64_t* row_first,
                       const int64_t* row_base, int64_t n_out, int32_t* edges_out, float* alpha_out, void* stream);
 
+/* ---- attention profile of a hop: which edge relations a query listens to (the reference's attention_vis table,
+ * Temporal/interpolation/model_cuda.py:117-119,163-166: per relation the sum of alpha and the number of edges, there a python loop with
+ * two .item() read-backs per relation and layer).  Over the hop-`level` edges e = (b, h, rel, t) the forward aggregates (t in level
+ * `level` of query b, h in level-1 of the same query; identity edges included, duplicated facts counted once each):
+ *   count_out[b][rel] += number of such edges,   sum_out[b][rel] += sum of llrintf(alpha_e * 2^32)
+ * with alpha_e of rg_layer_fwd, its arithmetic bit for bit (arguments as rg_explain_count: a_s of level-1 [n_old, ap], a_r
+ * [n_rela_rows, ap], a_q [batch, ap], w_alpha, b_alpha).  sum_out / count_out: device int64 [batch][n_rela_rows], caller-owned and
+ * caller-zeroed (or carrying earlier hops: the call adds).  alpha is summed as 64-bit fixed point with 32 fraction bits: the per-edge
+ * rounding is q = 2^-33, the sum of a cell is exact in integers and therefore bit-identical across runs, across any split of the batch
+ * and any order of its queries; alpha_sum = sum_out * 2^-32.  Needs a frontier that still holds levels level-1 and level with their
+ * node counts known on the host (rg_frontier_expand); n_old is checked against it.  The relation bins live in LDS per workgroup (one
+ * query per workgroup) and are flushed with non-returning 64-bit integer atomics.  The edges are enumerated from the heads (level
+ * `level` is the set of tails of the out-edges of level-1, so these are all out-edges of the level-1 nodes: CSR by head, no candidate
+ * read in vain); where n_rela_rows * (4 * ap + 12) bytes exceed 48 KB
+ * the kernel adds per edge into sum_out / count_out directly (same result, slower).  attn_dim <= 32, batch <= 65535.  Allocates
+ * nothing, asynchronous on `stream`. */
+int rg_attn_profile(const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level, int64_t n_old,
+                    const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha,
+                    int32_t attn_dim, int64_t* sum_out, int64_t* count_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,7 @@ SYMBOLS = [
     "rg_frontier_expand_async", "rg_frontier_expand_nodes_async", "rg_frontier_set_edge_hint", "rg_frontier_count_ptr", "rg_frontier_level_counts", "rg_attn_tables",
     "rg_explain_scratch_bytes", "rg_explain_seed", "rg_explain_count", "rg_explain_emit", "rg_explain_gather",
     "rg_topk",
+    "rg_attn_profile",
 ]
 
 _lib = None
@@ -113,6 +114,7 @@ def lib():
                                    C.POINTER(i64), vp]
     L.rg_explain_emit.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, i32, C.c_float, vp, vp, vp, vp]
     L.rg_explain_gather.argtypes = [i64, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp]
+    L.rg_attn_profile.argtypes = [vp, vp, i32, i32, i32, i64, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp]
     _lib = L
     return L
 

@@ -205,3 +205,11 @@ class BaseModel(object):
         test = self._performance(self._rank_split("test", self.n_test))
         i_time = time.time() - started
         return valid[0], _OUT_FMT % (*valid, *test, self.t_time, i_time)
+
+    # ---- attention profile of a whole split ------------------------------------------------------------------------
+    def attention_profile(self, data="test", max_queries=None):
+        """model.attention_profile(group="relation") over the queries of the valid or test split, walked in n_tbatch batches as
+        ``evaluate`` walks them; the per-batch integer tables are added, so the result does not depend on n_tbatch.  ``max_queries``:
+        only the first so many queries of the split.  Not sharded: under a process group every rank computes the whole table."""
+        from .profile import split_profile
+        return split_profile(self.model, self.loader, data, self.n_tbatch, max_queries)

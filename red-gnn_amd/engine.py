@@ -23,6 +23,8 @@ DENSE_EVENTS = None
 BWD_EVENTS = None
 # tools/probe_explain.py sets this to a list to collect (start_event, end_event, level, n_edges) per hop of explain_hop
 EXPLAIN_EVENTS = None
+# tools/probe_profile.py sets this to a list to collect (start_event, end_event, level) per attn_profile call
+PROFILE_EVENTS = None
 
 
 def _require_gpu(device):
@@ -396,6 +398,28 @@ def explain_gather(hop, batch, edges, alpha, row_first, row_base, edges_out, alp
     _lib.check(_lib.lib().rg_explain_gather(edges.shape[0], hop, batch, _lib.ptr(edges), _lib.ptr(alpha.contiguous()),
                                             _lib.ptr(row_first.contiguous()), _lib.ptr(row_base.contiguous()), edges_out.shape[0],
                                             _lib.ptr(edges_out), _lib.ptr(alpha_out), _lib.stream_ptr()))
+
+
+def attn_profile(frontier, graph, level, a_s, a_r, a_q, w_alpha, b_alpha, attn_dim, sum_out, count_out):
+    """rg_attn_profile: adds the hop-`level` edges of every query into sum_out / count_out (int64 [B, n_rela_rows], zeroed by the
+    caller): per edge relation the number of edges and the sum of llrintf(alpha * 2^32).  Integer sums: bit-identical whatever the
+    schedule, the split of the batch or the order of its queries."""
+    for t in (a_s, a_r, a_q, w_alpha, b_alpha):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+    ap = a_s.shape[1]
+    assert a_r.shape == (2 * graph.n_rel + 1, ap) and a_q.shape == (frontier.batch, ap)      # (the kernel's bins: the graph's rows)
+    for t in (sum_out, count_out):
+        assert t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.shape == (frontier.batch, a_r.shape[0])
+    ev = None
+    if PROFILE_EVENTS is not None:
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        ev[0].record()
+    _lib.check(_lib.lib().rg_attn_profile(frontier.handle, graph.handle, frontier.batch, frontier.n_ent, level, a_s.shape[0],
+                                          _lib.ptr(a_s), _lib.ptr(a_r), _lib.ptr(a_q), ap, _lib.ptr(w_alpha), _lib.ptr(b_alpha),
+                                          attn_dim, _lib.ptr(sum_out), _lib.ptr(count_out), _lib.stream_ptr()))
+    if ev is not None:
+        ev[1].record()
+        PROFILE_EVENTS.append((ev[0], ev[1], level))
 
 
 def layer_fwd_plan(frontier, graph, level, n_old, n_new, n_edges, ld):

@@ -407,6 +407,15 @@ class RED_GNN_trans(nn.Module):
         from . import prediction as _prediction
         return _prediction.predict(self, subs, rels, k, exclude_known, mode)
 
+    def attention_profile(self, subs, rels, mode="test", group="relation"):
+        """Which edge relations the queries listen to, and at which hop: profile.AttentionProfile with count int64 and alpha_sum
+        float64 [G, L, 2R+1] over the hop-l edges the forward aggregates (identity edges included), per query relation id
+        (group="relation", G = 2R+1) or per query in the order given (group="query", G = B).  One HIP launch per hop (rg_attn_profile)
+        with the forward's alpha bit for bit, summed as 64-bit fixed point: bit-identical across runs, splits of the batch and orders
+        of its queries.  Eval semantics (dropout = identity) under no_grad; parameters and ``training`` are left as they are."""
+        from . import profile as _profile
+        return _profile.attention_profile(self, subs, rels, mode, group)
+
     def _run(self, subs, rels, mode, trace=None, kept=None, eval_mode=False):
         """forward(); with ``kept`` (a list) the frontier keeps all n_layer + 1 levels, nothing is graph-replayed, and per layer
         dict(a_s = the attention projection of the layer's input level [n_old, ap], tables = (a_r, a_q, rela_p) or None) is appended
@@ -614,3 +623,6 @@ class RED_GNN_induc(RED_GNN_trans):
 
     def predict(self, subs, rels, k=10, exclude_known=True, mode="transductive"):
         return super().predict(subs, rels, k=k, exclude_known=exclude_known, mode=mode)
+
+    def attention_profile(self, subs, rels, mode="transductive", group="relation"):
+        return super().attention_profile(subs, rels, mode=mode, group=group)

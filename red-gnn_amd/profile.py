@@ -1,0 +1,148 @@
+"""Attention profile: when the model answers relation q, which edge relations does it listen to, and at which hop?
+
+    prof = model.attention_profile(subs, rels)            # group="relation": one row per query relation id
+    prof.alpha_sum[q, l - 1, rel], prof.count[q, l - 1, rel]
+    prof.mean()                                           # mean alpha per cell, NaN where there is no edge
+    rel_ids, mean = prof.top(q, k=5)                      # per hop the k edge relations with the largest mean alpha
+
+Over the hop-l edges (b, h, rel, t) of the query subgraphs - exactly the edges the forward aggregates, identity edges included -
+count is the number of edges and alpha_sum the sum of their attention, per query (group="query") or per query relation
+(group="relation").  Summed over the hops this is the reference's attention_vis table (Temporal/interpolation/model_cuda.py:117-119,
+163-166).  The reduction runs in HIP (csrc/profile.hip, rg_attn_profile): one launch per hop re-evaluates alpha with the forward
+kernel's arithmetic and adds it as 64-bit fixed point (2^-32 units, per-edge rounding Q = 2^-33), so every cell is an exact integer
+sum: bit-identical across runs, across any split of a batch and any order of its queries.  Grouping by relation is an integer
+index_add on the device; the conversion to float64 is the last step.
+"""
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import engine
+
+FRACTION_BITS = 32
+Q = 2.0 ** -(FRACTION_BITS + 1)          # rounding of one edge's alpha in alpha_sum
+
+
+@dataclass
+class AttentionProfile:
+    """count int64 [G, L, 2R+1] and fixed int64 [G, L, 2R+1] (the sums of alpha in units of 2^-32), on the device that computed them.
+    G = 2R+1 query relation ids (group == "relation"; rows of relations not queried are zero) or the B queries in the order given
+    (group == "query").  ``axes`` names the dimensions: code that indexes through it keeps working when a setting adds one (the
+    temporal models' edge direction).  Profiles of the same grouping add (``+``): integer sums, exact."""
+    fixed: torch.Tensor
+    count: torch.Tensor
+    group: str = "relation"
+    axes: tuple = ("group", "hop", "relation")
+
+    @property
+    def alpha_sum(self):
+        """float64 [G, L, 2R+1]: the sum of alpha per cell."""
+        return self.fixed.double() * 2.0 ** -FRACTION_BITS
+
+    @property
+    def n_hops(self):
+        return self.count.shape[self.axes.index("hop")]
+
+    def mean(self):
+        """float64 [G, L, 2R+1]: mean alpha per cell, NaN where count == 0."""
+        c = self.count.double()
+        return torch.where(self.count > 0, self.alpha_sum / c.clamp(min=1.0), torch.full_like(c, float("nan")))
+
+    def total(self):
+        """The profile summed over the hops, [G, 1, 2R+1]: the reference's attention_vis table."""
+        h = self.axes.index("hop")
+        return AttentionProfile(self.fixed.sum(h, keepdim=True), self.count.sum(h, keepdim=True), self.group, self.axes)
+
+    def top(self, row, k=5):
+        """Per hop the k edge relations with the largest mean alpha in row ``row`` (a query relation id, or a query's position with
+        group == "query"), ties to the smaller relation id.  Returns (relation ids int64 [L, k], mean alpha float64 [L, k]); where
+        fewer than k relations have edges the row ends in id -1, mean NaN."""
+        n_rows, n_rel_rows = self.count.shape[0], self.count.shape[-1]
+        if not 0 <= int(row) < n_rows:
+            raise ValueError("top: row %d not in 0..%d" % (int(row), n_rows - 1))
+        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or k < 1:
+            raise ValueError("top: k must be a positive integer (got %r)" % (k,))
+        k = min(int(k), n_rel_rows)
+        mean = self.mean()[int(row)]                                              # [L, 2R+1]
+        key = torch.where(torch.isnan(mean), torch.full_like(mean, -1.0), mean)   # alpha >= 0: cells without edges sort last
+        order = torch.argsort(key, dim=-1, descending=True, stable=True)[:, :k]
+        best = torch.gather(mean, 1, order)
+        ids = torch.where(torch.isnan(best), torch.full_like(order, -1), order)
+        return ids, best
+
+    def __add__(self, other):
+        if not isinstance(other, AttentionProfile):
+            return NotImplemented
+        if other.group != self.group or other.axes != self.axes or other.count.shape != self.count.shape:
+            raise ValueError("profiles of different grouping or shape do not add (%s %s, %s %s)"
+                             % (self.group, tuple(self.count.shape), other.group, tuple(other.count.shape)))
+        return AttentionProfile(self.fixed + other.fixed, self.count + other.count, self.group, self.axes)
+
+    def cpu(self):
+        return AttentionProfile(self.fixed.cpu(), self.count.cpu(), self.group, self.axes)
+
+
+def _ids(x):
+    a = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+    return a.astype(np.int64).reshape(-1)
+
+
+def attention_profile(model, subs, rels, mode="test", group="relation"):
+    """RED_GNN_trans.attention_profile (see there)."""
+    from .models import _pad4, pad_attn
+    device = model.W_final.weight.device
+    engine._require_gpu(device)
+    if group not in ("relation", "query"):
+        raise ValueError("attention_profile: group must be 'relation' or 'query' (got %r)" % (group,))
+    subs_h, rels_h = _ids(subs), _ids(rels)
+    n = len(subs_h)
+    if n == 0 or len(rels_h) != n:
+        raise ValueError("attention_profile: need one relation per subject and at least one row (got %d subjects, %d relations)"
+                         % (n, len(rels_h)))
+    graph = model.loader.graph_for(mode)
+    n_ent, n_rows = graph.n_ent, 2 * model.n_rel + 1
+    if subs_h.min() < 0 or subs_h.max() >= n_ent or rels_h.min() < 0 or rels_h.max() >= n_rows:
+        raise ValueError("query subject / relation id out of range (n_ent=%d, 2*n_rel+1=%d)" % (n_ent, n_rows))
+    L = model.n_layer
+    d, a = model.hidden_dim, model.attn_dim
+    ld, ap = max(16, _pad4(d)), pad_attn(a)
+    with torch.no_grad():
+        kept = []
+        model._run(subs_h, rels_h, mode, kept=kept)
+        fr, q_rel = kept[0]["frontier"], kept[0]["q_rel"]
+        layers = kept[1:]
+        tables = [k["tables"] for k in layers]
+        if any(t is None for t in tables):
+            tables = model.inference_tables(q_rel, ld, ap)
+        fixed = torch.zeros((L, n, n_rows), dtype=torch.int64, device=device)
+        count = torch.zeros((L, n, n_rows), dtype=torch.int64, device=device)
+        for l in range(1, L + 1):
+            layer = model.gnn_layers[l - 1]
+            a_r, a_q, _ = tables[l - 1]
+            engine.attn_profile(fr, graph, l, layers[l - 1]["a_s"].detach().contiguous(), a_r.contiguous(), a_q.contiguous(),
+                                layer.w_alpha.weight.detach().reshape(-1).contiguous(), layer.w_alpha.bias.detach().contiguous(), a,
+                                fixed[l - 1], count[l - 1])
+        fixed, count = fixed.transpose(0, 1), count.transpose(0, 1)               # [B, L, 2R+1]
+        if group == "relation":                                                  # integer adds: exact whatever their order
+            fixed = torch.zeros((n_rows, L, n_rows), dtype=torch.int64, device=device).index_add_(0, q_rel, fixed)
+            count = torch.zeros((n_rows, L, n_rows), dtype=torch.int64, device=device).index_add_(0, q_rel, count)
+    return AttentionProfile(fixed=fixed.contiguous(), count=count.contiguous(), group=group)
+
+
+def split_profile(model, loader, data="test", batch=50, max_queries=None):
+    """The group="relation" profile of the queries of the valid or test split (BaseModel.attention_profile): batches of ``batch``
+    queries, their integer tables added."""
+    if data not in ("valid", "test"):
+        raise ValueError("attention_profile: data must be 'valid' or 'test' (got %r)" % (data,))
+    query = loader.valid_q if data == "valid" else loader.test_q
+    n = len(query) if max_queries is None else min(len(query), int(max_queries))
+    if n <= 0 or batch <= 0:
+        raise ValueError("attention_profile: no queries to profile in the %s split (n=%d, batch=%d)" % (data, n, batch))
+    mode = loader.eval_mode(data) if hasattr(loader, "eval_mode") else data
+    subs, rels = np.array([q[0] for q in query[:n]]), np.array([q[1] for q in query[:n]])
+    prof = None
+    for lo in range(0, n, batch):
+        part = model.attention_profile(subs[lo:lo + batch], rels[lo:lo + batch], mode=mode, group="relation")
+        prof = part if prof is None else prof + part
+    return prof

@@ -10,7 +10,8 @@ parameter layout of Temporal/interpolation/model.py (one rela_embed / attention_
 What is different inside: the per-call scipy coo build, the dense [B, n_ent] index maps and the python
 attention_vis loop with .item() syncs (model_cuda.py:121-135,163-166,178-184) do not exist; frontier expansion is the
 device bitmap walk, and the per-edge work of a layer is one fused kernel (rg_tlayer_fwd) with the three direction linears
-hoisted per node / relation / |dt| (W(h + r + tau) = Wh + Wr + Wtau).
+hoisted per node / relation / |dt| (W(h + r + tau) = Wh + Wr + Wtau).  (The attention_vis table itself - alpha sum and edge count per
+relation - exists for the static models: RED_GNN_trans.attention_profile, red-gnn_amd/profile.py.)
 Training: ``mode='train'`` drops the batch's own quadruples (``batch['example_idx']`` rows of ``params.graph``,
 model_cuda.py:103-104) by building a device graph for the batch, applies ``nn.Dropout(params.dropout)`` before the
 activation (:196) and is differentiable: the per-edge work of the backward pass is rg_tlayer_bwd, the hoisted linears are
