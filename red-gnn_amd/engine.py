@@ -90,7 +90,7 @@ class Graph:
         vr = np.empty((n_vrows.value, 4), np.int32)
         ent = np.empty((n_packs.value * 128, 2), np.int32)
         pack = np.empty((n_packs.value, 4), np.int32)
-        rows = np.empty((n_vrows.value, 2), np.int32)
+        rows = np.empty((n_vrows.value if n_packs.value else 0, 2), np.int32)      # (a graph without packs has no pack rows: nothing is copied)
         _lib.check(L.rg_graph_export_packs(self.handle, None, None, _lib.ptr(ent), _lib.ptr(pack), _lib.ptr(rows), _lib.ptr(vr)))
         return vr, ent, pack, rows
 

@@ -892,7 +892,7 @@ def _ids(n_ent, n_rel, facts, train=None, test=None):
                 test=z if test is None else np.asarray(test, np.int64).reshape(-1, 3))
 
 
-@pytest.mark.parametrize("case", ["tiny", "hubs", "C2", "C3", "no_triples"])
+@pytest.mark.parametrize("case", ["tiny", "hubs", "C2", "C3", "no_triples", "wide_ent", "wide_rel"])
 def test_device_graph_build_equals_host_build(case):
     """rg_graph_create_device (the graph of shuffle_train's re-split, built where it is used) against rg_graph_create on the same
     triples: both CSRs, the length-sorted virtual rows and the word-parallel walk's packs are equal array for array; the model
@@ -905,6 +905,15 @@ def test_device_graph_build_equals_host_build(case):
         n_ent, n_rel, trip = kg.n_ent, kg.n_rel, np.concatenate([kg.facts, kg.train], 0)
     elif case == "no_triples":
         n_ent, n_rel, trip = 37, 2, np.zeros((0, 3), np.int64)
+    elif case in ("wide_ent", "wide_rel"):
+        # ids too wide for the packed (rel << 20 | entity) entries (graph.hip: n_ent <= 2^20 && n_rela_rows <= 2^12): int2 entries only,
+        # no word-parallel packs; the highest entity ids and relation ids are in use
+        n_ent, n_rel, m = ((1 << 20) + 37, 5, 5000) if case == "wide_ent" else (700, 2050, 5000)
+        h, t = rng.integers(0, n_ent, m), rng.integers(0, n_ent, m)
+        h[:40], t[40:80] = n_ent - 1 - np.arange(40), n_ent - 1 - np.arange(40)
+        r = rng.integers(0, n_rel, m)
+        r[:3] = n_rel - 1
+        trip = np.stack([h, r, t], 1)
     else:
         n_ent, n_rel, m = (50, 4, 300) if case == "tiny" else (400, 7, 9000)
         h, t = rng.integers(0, n_ent, m), rng.integers(0, n_ent, m)
@@ -921,6 +930,7 @@ def test_device_graph_build_equals_host_build(case):
         assert np.array_equal(a, b), name
     for a, b, name in zip(g_h.export_packs(), g_d.export_packs(), ("in_vrows", "pack_entries", "packs", "pack_rows")):
         assert a.shape == b.shape and np.array_equal(a, b), name
+    assert (len(g_h.export_packs()[2]) == 0) == case.startswith("wide_")      # int2 entries only: no word-parallel packs
 
 
 def test_shuffle_train_builds_its_graph_on_the_device():
