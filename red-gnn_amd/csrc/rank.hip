@@ -20,7 +20,7 @@ __device__ __forceinline__ T wave_sum(T v) {
 }
 
 // STAGED: the query's score row is copied to LDS on the pass that finds its minimum and every answer's counting pass reads it from
-// there (a row is read from memory once instead of once per answer + 1; rows up to 16 k entities)
+// there (a row is read from memory once instead of once per answer + 1; rows of up to 16368 entities, see rg_rank)
 template <bool STAGED>
 __global__ __launch_bounds__(RT) void rank_kernel(const float* __restrict__ scores, int n_ent,
                                                   const int32_t* __restrict__ ans_ptr, const int32_t* __restrict__ ans_idx,
@@ -74,8 +74,13 @@ extern "C" int rg_rank(const float* scores, int32_t batch, int32_t n_ent, const 
                        const int32_t* filt_ptr, const int32_t* filt_idx, float* ranks_out, void* stream) {
   RG_CHECK(scores && ans_ptr && ans_idx && filt_ptr && filt_idx && ranks_out, "rg_rank: NULL argument");
   RG_CHECK(batch > 0 && n_ent > 0, "rg_rank: batch=%d n_ent=%d", batch, n_ent);
-  if (n_ent <= 16384)
-    hipLaunchKernelGGL(rank_kernel<true>, dim3(batch), dim3(RT), (size_t)n_ent * sizeof(float), (hipStream_t)stream, scores, n_ent, ans_ptr,
+  // staged only while the row (dynamic LDS) plus the kernel's static LDS (s_min, s_cnt) fits the 64 KiB a launch may request without
+  // raising hipFuncAttributeMaxDynamicSharedMemorySize: n_ent <= 16368.  Longer rows are read from memory once per answer.
+  constexpr size_t STATIC_LDS = (RT / 64) * sizeof(float) + 3 * (RT / 64) * sizeof(int);
+  constexpr size_t LDS_LIMIT = 64 * 1024;
+  const size_t row_bytes = (size_t)n_ent * sizeof(float);
+  if (row_bytes + STATIC_LDS <= LDS_LIMIT)
+    hipLaunchKernelGGL(rank_kernel<true>, dim3(batch), dim3(RT), row_bytes, (hipStream_t)stream, scores, n_ent, ans_ptr,
                        ans_idx, filt_ptr, filt_idx, ranks_out);
   else
     hipLaunchKernelGGL(rank_kernel<false>, dim3(batch), dim3(RT), 0, (hipStream_t)stream, scores, n_ent, ans_ptr, ans_idx, filt_ptr,

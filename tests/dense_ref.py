@@ -1,0 +1,368 @@
+"""Plain-numpy reference of the DENSE half of a training step (what include/redgnn.h promises for rg_dense_train_fwd / _fwd_as,
+rg_dense_train_bwd / _bwd2, rg_rows_addmm and rg_attn_tables), plus the case table the dense-kernel tests share.  TEST INFRASTRUCTURE.
+
+    forward    h0 = hidden_prev[prev_idx] (0 where prev_idx = -1 or NULL)
+               pre = agg W_h^T;  x = act(pre) * mask                                      (act: 0 identity, 1 relu, 2 tanh)
+               r = sigmoid(W_ir x + b_ir + W_hr h0 + b_hr);  z = sigmoid(W_iz x + b_iz + W_hz h0 + b_hz)
+               hn = W_hn h0 + b_hn;  n = tanh(W_in x + b_in + r hn);  hidden = (1 - z) n + z h0;  a_s = hidden Ws_next^T
+               workspace ws [rows, 5, d] = {r, z, n, h0, hn}
+    backward   from g = grad_hidden and the SAVED ws / x (inputs, exactly as the kernels take them):
+               dn = g (1 - z) (1 - n^2);  dr = dn hn r (1 - r);  dz = g (h0 - n) z (1 - z)
+               dgi = (dr, dz, dn);  dgh = (dr, dz, dn r);  dgh_n = dn r
+               dx = dgi W_ih;  dh0 = g z + dgh W_hh;  dpre = dx * mask * act'(.);  dagg = dpre W_h
+                   act' : 1 | 1[x > 0] | 1 - y^2 with y = x * keep under a mask (x = tanh(pre) / keep where kept), y = x without
+               grad_prev[prev_idx[m]] = dh0[m] for prev_idx[m] >= 0  (prev_idx NULL: grad_prev = dh0)
+    rows_addmm out = base + g[:, :k] W          attn_tables a_r = rela Wr^T, a_q = rela[q_rel] Wqr^T + bqr, rela padded to ld columns
+
+Every function takes ``dtype``: np.float64 is the reference; np.float32 (the same code, the same order) is the yardstick of what a
+correct fp32 evaluation costs.  Besides each output the functions return, in fp64, ``n`` = the number of terms summed into the
+element along its longest chain of dot products (a product over inputs that are themselves sums adds their count), and ``S`` = the
+same expression with every term replaced by its absolute value: |agg| |W_h|^T for pre, |1| + |z| for 1 - z, 1 + n^2 for 1 - n^2,
+|h0| + |n| for h0 - n.  Through a function the pre-activation's S is carried to first order, plus the function's own rounding:
+
+    relu, identity   S        (1-Lipschitz: a sign flip of a pre-activation within its error moves x by no more than that error,
+                               so no element at the kink needs exempting)
+    f = sigmoid      |f'| (S + 1) + |f|     f' = f (1 - f)      the + 1: the exp's own 1-ulp relative error moves f by |f'| u
+    f = tanh         |f'| (S + 1) + |f|     f' = 1 - f^2
+    a product        S_a |b| + |a| S_b      (r hn, (1 - z) n, z h0 with h0 exact: S_z |h0|)
+
+The error of an fp32 evaluation scales with u * S:
+
+    |fp32 - fp64| <= c * (n + n0) * u * S + tiny         u = 2^-24, tiny = 1e-30 (S = 0: the value must be exactly 0)
+
+n0 (``N0_STEP`` = 12) is the elementwise work between the sums of the step that n does not count: activation (exp, reciprocal, the
+1 - e and the product: 4), mask, the bias adds (2), the product and the add of r hn (2), the three operations of the state update:
+12.  The two row-wise products have n0 = 1 (the final add).  ``C_BOUND`` / ``C_BOUND_ROWS`` below are 4 x the worst ratio
+|ref32 - ref64| / ((n + n0) u S) measured over every element of every output of every case of the table (test_dense_ref.py keeps
+that measurement honest: it fails if a case exceeds REF32_WORST_RATIO / REF32_WORST_RATIO_ROWS).
+"""
+import types
+
+import numpy as np
+
+U = 2.0 ** -24
+TINY = 1e-30
+# measured: max over all cases, outputs and elements of |ref32 - ref64| / ((n + n0) * u * S), rounded up
+# (test_fp32_reference_within_its_bound prints the per-case figures).  Two constants because the two accountings differ in kind: the
+# step's n counts whole dot-product chains (its worst element, a dgi entry - five products in a row, n = 0 - reaches 0.274), the
+# row-wise products count every single rounding (k = 1: two roundings against n + n0 = 3, 0.561)
+REF32_WORST_RATIO = 0.3
+REF32_WORST_RATIO_ROWS = 0.6
+# the GPU's allowance: 4 x the fp32 reference's own cost (another summation order in the MFMA chains, fused multiply-adds, the 1-ulp
+# hardware exp / reciprocal); the factor tests/_util.assert_close_fp32 and layer_ref.C_BOUND grant the GPU over the CPU fp32 path
+C_BOUND = 4.0 * REF32_WORST_RATIO
+C_BOUND_ROWS = 4.0 * REF32_WORST_RATIO_ROWS
+N0_STEP = 12
+N0_ROWS = 1
+
+ACT = {"idd": 0, "relu": 1, "tanh": 2}
+FWD_OUTPUTS = ("hidden", "x", "ws", "a_s")
+BWD_OUTPUTS = ("dgi", "dgh", "dgh_n", "dpre", "dagg", "dh0", "grad_prev")
+
+
+def bound(S, n, n0, c):
+    return c * (np.asarray(n, np.float64) + n0) * U * np.asarray(S, np.float64) + TINY
+
+
+def worst_ratio(val, ref, S, n, n0):
+    """max (|val - ref| - tiny) / ((n + n0) u S) over the elements: the c that ``bound`` would need (inf where S = 0 and the values
+    differ by more than tiny)."""
+    err = np.maximum(np.abs(np.asarray(val, np.float64) - np.asarray(ref, np.float64)) - TINY, 0.0)
+    den = (np.asarray(n, np.float64) + n0) * U * np.asarray(S, np.float64)
+    if err.size == 0:
+        return 0.0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        q = np.where(den > 0, err / den, np.where(err > 0, np.inf, 0.0))
+    return float(q.max())
+
+
+def _c(dt, x):
+    return None if x is None else np.asarray(x).astype(dt)
+
+
+def _sigmoid(x):
+    one = x.dtype.type(1)
+    with np.errstate(over="ignore"):
+        return one / (one + np.exp(-x))
+
+
+# ---- forward ------------------------------------------------------------------------------------------------------------------------
+def _gather(hidden_prev, prev_idx, n, d, dt):
+    h0 = np.zeros((n, d), dt)
+    if prev_idx is not None:
+        old = np.asarray(prev_idx) >= 0
+        h0[old] = hidden_prev[np.asarray(prev_idx, np.int64)[old]]
+    return h0
+
+
+def _fwd_values(dt, agg, hidden_prev, prev_idx, W_h, act, w_ih, w_hh, b_ih, b_hh, mask, Ws_next, fault=None):
+    agg, hidden_prev, W_h, w_ih, w_hh, b_ih, b_hh, mask, Ws_next = (_c(dt, t) for t in (agg, hidden_prev, W_h, w_ih, w_hh, b_ih, b_hh, mask,
+                                                                                       Ws_next))
+    n, d = agg.shape
+    one = dt.type(1)
+    h0 = _gather(hidden_prev, prev_idx, n, d, dt)
+    pre = agg @ W_h.T
+    a = pre if act == 0 else np.maximum(pre, dt.type(0)) if act == 1 else np.tanh(pre)
+    x = a if mask is None else a * mask
+    gi = x @ w_ih.T + b_ih
+    hh = h0 @ w_hh.T
+    b_hn = b_hh[2 * d:] if fault != "no_b_hn" else np.zeros(d, dt)      # fault: one gate bias dropped (negative tests only)
+    r = _sigmoid(gi[:, :d] + hh[:, :d] + b_hh[:d])
+    z = _sigmoid(gi[:, d:2 * d] + hh[:, d:2 * d] + b_hh[d:2 * d])
+    hn = hh[:, 2 * d:] + b_hn
+    npre = gi[:, 2 * d:] + r * hn
+    ng = np.tanh(npre)
+    hidden = (one - z) * ng + z * h0
+    a_s = None if Ws_next is None else hidden @ Ws_next.T
+    return dict(h0=h0, pre=pre, a=a, x=x, r=r, z=z, hn=hn, ng=ng, hidden=hidden, a_s=a_s)
+
+
+def forward(agg, hidden_prev, prev_idx, W_h, act, w_ih, w_hh, b_ih, b_hh, mask=None, Ws_next=None, ap=None, dtype=np.float64, fault=None):
+    """hidden [n, d], x [n, d], ws [n, 5, d] = {r, z, n, h0, hn}, a_s [n, ap] (None without Ws_next; columns attn_dim .. ap - 1 zero) in
+    ``dtype``; .S / .n per output name in fp64 (include/redgnn.h, rg_dense_train_fwd / rg_dense_train_fwd_as)."""
+    act = ACT.get(act, act)
+    args = (agg, hidden_prev, prev_idx, W_h, act, w_ih, w_hh, b_ih, b_hh, mask, Ws_next)
+    v = _fwd_values(np.dtype(dtype), *args, fault=fault)
+    w = _fwd_values(np.dtype(np.float64), *args)
+    A = lambda t: np.abs(np.asarray(t, np.float64))
+    n_rows, d = np.shape(agg)
+    S_pre = A(agg) @ A(W_h).T
+    S_a = S_pre if act != 2 else (1 - w["a"] ** 2) * (S_pre + 1) + np.abs(w["a"])
+    S_x = S_a if mask is None else S_a * A(mask)
+    Wi, Wh, bi, bh, h0 = A(w_ih), A(w_hh), A(b_ih), A(b_hh), np.abs(w["h0"])
+    gate = lambda g: S_x @ Wi[g * d:(g + 1) * d].T + bi[g * d:(g + 1) * d]
+    hside = lambda g: h0 @ Wh[g * d:(g + 1) * d].T + bh[g * d:(g + 1) * d]
+    sig = lambda f, S: f * (1 - f) * (S + 1) + f
+    S_r, S_z = sig(w["r"], gate(0) + hside(0)), sig(w["z"], gate(1) + hside(1))
+    S_hn = hside(2)
+    S_npre = gate(2) + S_r * np.abs(w["hn"]) + w["r"] * S_hn
+    S_n = (1 - w["ng"] ** 2) * (S_npre + 1) + np.abs(w["ng"])
+    S_h = S_z * (np.abs(w["ng"]) + h0) + (1 - w["z"]) * S_n
+    n_x, n_rz, n_hn, n_n = d, 2 * d + 2, d + 1, 2 * d + 3
+    S = dict(x=S_x, hidden=S_h, ws=np.stack([S_r, S_z, S_n, h0, S_hn], 1))
+    n = dict(x=n_x, hidden=n_n, ws=np.array([n_rz, n_rz, n_n, 0, n_hn], np.float64).reshape(1, 5, 1))
+    a_s = None
+    if Ws_next is not None:
+        attn = np.shape(Ws_next)[0]
+        ap = (attn + 3) // 4 * 4 if ap is None else ap
+        a_s = np.zeros((n_rows, ap), v["a_s"].dtype)
+        a_s[:, :attn] = v["a_s"]
+        S["a_s"] = np.zeros((n_rows, ap))
+        S["a_s"][:, :attn] = S_h @ A(Ws_next).T
+        n["a_s"] = n_n + d
+    ws = np.stack([v["r"], v["z"], v["ng"], v["h0"], v["hn"]], 1)
+    return types.SimpleNamespace(hidden=v["hidden"], x=v["x"], ws=ws, a_s=a_s, S=S, n=n)
+
+
+# ---- backward -----------------------------------------------------------------------------------------------------------------------
+def _bwd_values(dt, g, ws, x, mask, keep, act, W_h, w_ih, w_hh, absolute, fault=None):
+    """dgi, dgh, dpre, dagg, dh0; absolute = the S form (every term replaced by its absolute value, 1 - t by 1 + |t|)."""
+    g, ws, x, mask, W_h, w_ih, w_hh = (_c(dt, t) for t in (g, ws, x, mask, W_h, w_ih, w_hh))
+    n, d = x.shape
+    ws = ws.reshape(n, 5, d)
+    r, z, ng, h0, hn = (ws[:, i] for i in range(5))
+    if fault == "col_shift":      # fault: the last, partly filled 16-column block reads z one column to the right (negative tests only)
+        flat = ws.reshape(n, 5 * d)
+        z = np.concatenate([z[:, :32], flat[:, d + 33:2 * d + 1]], 1)
+    one = dt.type(1)
+    if absolute:
+        g, r, z, ng, h0, hn, W_h, w_ih, w_hh = (np.abs(t) for t in (g, r, z, ng, h0, hn, W_h, w_ih, w_hh))
+        mask = None if mask is None else np.abs(mask)
+        om = lambda t: one + t
+        diff = h0 + ng
+    else:
+        om = lambda t: one - t
+        diff = h0 - ng
+    dn = g * om(z) * om(ng * ng)
+    dr = dn * hn * r * om(r)
+    dz = g * diff * z * om(z)
+    dnr = dn * r if fault != "dgh_n_no_r" else dn      # fault: dgh's n block missing its * r (negative tests only)
+    dgi, dgh = np.concatenate([dr, dz, dn], 1), np.concatenate([dr, dz, dnr], 1)
+    dx = dgi @ w_ih
+    dh0 = g * z + dgh @ w_hh
+    v = dx if mask is None else dx * mask
+    if act == 1:
+        v = np.where(x > 0, v, dt.type(0))
+    elif act == 2:
+        y = x if mask is None else x * dt.type(keep)
+        v = v * om(y * y)
+    dagg = v @ W_h
+    return dict(dgi=dgi, dgh=dgh, dgh_n=dnr, dpre=v, dagg=dagg, dh0=dh0)
+
+
+def _scatter_prev(dh0, prev_idx, n_old):
+    if prev_idx is None:
+        return dh0
+    out = np.zeros((n_old, dh0.shape[1]), dh0.dtype)
+    p = np.asarray(prev_idx, np.int64)
+    out[p[p >= 0]] = dh0[p >= 0]
+    return out
+
+
+def backward(grad_hidden, ws, x, mask, keep, act, W_h, w_ih, w_hh, prev_idx=None, n_old=0, dtype=np.float64, fault=None):
+    """dgi, dgh [n, 3d], dgh_n, dpre, dagg, dh0 [n, d], grad_prev [n_old, d] (prev_idx NULL: = dh0) in ``dtype``; .S / .n per output name
+    (include/redgnn.h, rg_dense_train_bwd / rg_dense_train_bwd2).  ws / x are the SAVED forward outputs, taken as given."""
+    act = ACT.get(act, act)
+    keep = float(np.float32(keep))      # the kernels take keep as a C float
+    args = (grad_hidden, ws, x, mask, keep, act, W_h, w_ih, w_hh)
+    v = _bwd_values(np.dtype(dtype), *args, absolute=False, fault=fault)
+    S = _bwd_values(np.dtype(np.float64), *args, absolute=True)
+    d = np.shape(x)[1]
+    n = dict(dgi=0, dgh=0, dgh_n=0, dpre=3 * d, dagg=4 * d, dh0=3 * d + 1, grad_prev=3 * d + 1)
+    v["grad_prev"], S["grad_prev"] = _scatter_prev(v["dh0"], prev_idx, n_old), _scatter_prev(S["dh0"], prev_idx, n_old)
+    return types.SimpleNamespace(S=S, n=n, **v)
+
+
+# ---- the two row-wise products --------------------------------------------------------------------------------------------------------
+def rows_addmm(base, g, W, dtype=np.float64):
+    """out = base + g[:, :k] W for W [k, n] (include/redgnn.h, rg_rows_addmm); the sum runs j = 0 .. k - 1 onto base, as a row's thread
+    does."""
+    dt = np.dtype(dtype)
+    k = np.shape(W)[0]
+    b, gg, w = _c(dt, base), _c(dt, g)[:, :k], _c(dt, W)
+    out = b.copy()
+    for j in range(k):
+        out = out + gg[:, j:j + 1] * w[j:j + 1]
+    S = np.abs(np.asarray(base, np.float64)) + np.abs(np.asarray(g, np.float64)[:, :k]) @ np.abs(np.asarray(W, np.float64))
+    return types.SimpleNamespace(out=out, S=dict(out=S), n=dict(out=k + 1))
+
+
+def attn_tables(rela, Wr, Wqr, bqr, q_rel, ap, ld, dtype=np.float64):
+    """One layer of rg_attn_tables: a_r [rows, ap], a_q [B, ap] (columns attn_dim .. ap - 1 zero), rela_pad [rows, ld] (the table with
+    zero columns d .. ld - 1; a bit copy)."""
+    dt = np.dtype(dtype)
+    r, wr, wq, b = _c(dt, rela), _c(dt, Wr), _c(dt, Wqr), _c(dt, bqr)
+    rows, d = r.shape
+    attn = wr.shape[0]
+    q = np.asarray(q_rel, np.int64)
+    a_r, a_q = np.zeros((rows, ap), dt), np.zeros((len(q), ap), dt)
+    a_r[:, :attn] = r @ wr.T
+    a_q[:, :attn] = r[q] @ wq.T + b
+    pad = np.zeros((rows, ld), dt)
+    pad[:, :d] = r
+    A = lambda t: np.abs(np.asarray(t, np.float64))
+    S_r, S_q = np.zeros((rows, ap)), np.zeros((len(q), ap))
+    S_r[:, :attn] = A(rela) @ A(Wr).T
+    S_q[:, :attn] = A(rela)[q] @ A(Wqr).T + A(bqr)
+    return types.SimpleNamespace(a_r=a_r, a_q=a_q, rela_pad=pad, S=dict(a_r=S_r, a_q=S_q), n=dict(a_r=d, a_q=d + 1))
+
+
+# ---- the case table -----------------------------------------------------------------------------------------------------------------
+# One entry per dispatch condition; ``why`` cites the line the case flips.  A step case runs the training forward (rg_dense_train_fwd,
+# or _fwd_as when attn_dim > 0) and, for d <= 64, both backward entries on the saved outputs of the fp64 forward, rounded once.
+# These are direct calls: every kernel gets every row count, not only the ones models._DenseStep would route to it.
+def _step(name, d, n, act="relu", masked=False, prev="third", attn_dim=0, seed=0, why=""):
+    return types.SimpleNamespace(name=name, kind="step", d=d, n=n, act=ACT[act], masked=masked, keep=0.7, prev=prev, attn_dim=attn_dim,
+                                 ap=(attn_dim + 3) // 4 * 4, seed=seed, why=why, fwd_only=d == 128)
+
+
+def _addmm(name, cols, k, n_rows, g_width=None, base_width=None, alias=False, seed=0, why=""):
+    return types.SimpleNamespace(name=name, kind="addmm", cols=cols, k=k, n_rows=n_rows, g_width=k if g_width is None else g_width,
+                                 base_width=cols if base_width is None else base_width, alias=alias, seed=seed, why=why)
+
+
+def _tables(name, n_layer, d, ld, attn_dim, ap, n_rows=11, B=9, seed=0, why=""):
+    return types.SimpleNamespace(name=name, kind="tables", n_layer=n_layer, d=d, ld=ld, attn_dim=attn_dim, ap=ap, n_rows=n_rows, B=B,
+                                 seed=seed, why=why)
+
+
+_CASE_LIST = [
+    # ---- width: dense.hip launch<2> / dense_bwd.hip launch_bwd<2> for d <= 32, <4> above; `col < d` leaves the last 16-column block
+    # partly empty at d = 20, 36, 60 (dense_bwd.hip fetch / stores, dense.hip TRAIN stores)
+    _step("d16_relu", 16, 1000, "relu", False, "third", seed=1, why="dense_bwd.hip:240 d <= 32 -> NB = 2, full blocks"),
+    _step("d20_tanh_mask", 20, 1000, "tanh", True, "all", seed=2, why="NB = 2, block 1 holds 4 of 16 columns (col < d)"),
+    _step("d32_idd", 32, 1000, "idd", False, "none", seed=3, why="NB = 2 at its upper edge"),
+    _step("d36_relu_mask", 36, 1000, "relu", True, "third", seed=4, why="dense_bwd.hip:240 d > 32 -> NB = 4, block 2 holds 4 columns, block 3 none"),
+    _step("d48_tanh", 48, 1000, "tanh", False, "null", seed=5, why="NB = 4, block 3 empty"),
+    _step("d60_idd_mask", 60, 1000, "idd", True, "third", seed=6, why="NB = 4, block 3 holds 12 columns"),
+    _step("d64_relu_mask", 64, 1000, "relu", True, "all", seed=7, why="NB = 4, full blocks"),
+    _step("d64_tanh_mask", 64, 1000, "tanh", True, "third", seed=8, why="dense_bwd.hip:179 y = x * keep under a mask"),
+    _step("d128_relu", 128, 300, "relu", False, "third", seed=9, why="dense.hip:418 d == 128 -> dense128_launch (forward only)"),
+    _step("d128_tanh_mask", 128, 2049, "tanh", True, "all", seed=10, why="dense128.hip TRAIN with a mask"),
+    # ---- rows around the 16-row tile (n_tiles = ceil(n / 16); in_n guards)
+    _step("n1", 64, 1, "relu", True, "all", seed=11, why="one row of one tile"),
+    _step("n15", 32, 15, "tanh", False, "third", seed=12, why="tile short of one row"),
+    _step("n16", 64, 16, "idd", True, "third", seed=13, why="exactly one tile"),
+    _step("n17", 36, 17, "relu", False, "all", seed=14, why="one row into the second tile"),
+    # ---- rows around models.py _FUSED_BWD_ROWS = 8192 and _TALL_ROWS = 32768 (what _DenseStep routes by)
+    _step("n8191", 48, 8191, "relu", True, "third", seed=15, why="models.py:176 below _FUSED_BWD_ROWS"),
+    _step("n8193", 16, 8193, "tanh", True, "all", seed=16, why="models.py:176 above _FUSED_BWD_ROWS"),
+    _step("n32767", 64, 32767, "tanh", False, "third", seed=17, why="models.py:166 below _TALL_ROWS; one full pass of the persistent grid less a row"),
+    _step("n32769", 64, 32769, "relu", True, "third", attn_dim=5, seed=18, why="models.py:166 above _TALL_ROWS; the grid-stride loop's second pass: one row"),
+    # ---- the persistent grid's second pass full and a third begun: 256 workgroups x 8 waves x 16 rows = 32768 rows per pass
+    _step("n70001_d64", 64, 70001, "relu", True, "third", seed=19, why="dense_bwd.hip:89 / dense.hip:183 t += gridDim.x * NW, two full passes"),
+    _step("n70001_d20", 20, 70001, "idd", False, "all", attn_dim=8, seed=20, why="the same with NB = 2 and a partly filled block"),
+    _step("n70001_d128", 128, 70001, "idd", False, "none", seed=21, why="dense128.hip persistent grid"),
+    # ---- rg_dense_train_fwd_as: attn_dim 1, 5, 8, 16 (ap 4, 8, 8, 16; `4 * hq < A.ap` store guard, pad columns zero)
+    _step("as1", 64, 1000, "relu", False, "third", attn_dim=1, seed=22, why="dense.hip:289 ap = 4: one lane quarter stores"),
+    _step("as5", 48, 1000, "tanh", True, "third", attn_dim=5, seed=23, why="ap = 8, three pad columns"),
+    _step("as8", 32, 1000, "idd", False, "all", attn_dim=8, seed=24, why="ap = 8, no pad"),
+    _step("as16", 20, 1000, "relu", True, "null", attn_dim=16, seed=25, why="ap = 16: all four lane quarters store"),
+    _step("as16_d128", 128, 1000, "tanh", False, "third", attn_dim=16, seed=26, why="dense128.hip:276 a_s store"),
+    # ---- rg_rows_addmm: columns 16 .. 128 (per_block = 256 / (n / 4): 64, 32, 21 with 4 idle threads, 16, 8), k 1, 5, 16, 32
+    _addmm("am16_k1", 16, 1, 1000, seed=30, why="gram.hip:198 per_block = 64"),
+    _addmm("am32_k5", 32, 5, 1000, g_width=8, seed=31, why="per_block = 32; g = a column block of a wider buffer (ldg > k)"),
+    _addmm("am48_k16", 48, 16, 70001, seed=32, why="gram.hip:200 per_block = 21: threads 252 .. 255 idle; 2048 workgroups' grid-stride loop"),
+    _addmm("am64_k32", 64, 32, 33000, g_width=40, base_width=192, seed=33, why="k at its limit; spaced base rows (ldb = 192) and ldg = 40"),
+    _addmm("am128_k5", 128, 5, 1000, g_width=8, alias=True, seed=34, why="n at its limit (per_block = 8); out aliases base"),
+    _addmm("am48_k5_alias", 48, 5, 17, g_width=8, alias=True, seed=35, why="fewer rows than one workgroup pass; out aliases base"),
+    # ---- rg_attn_tables (rank.hip attn_tables_kernel): layers, ld != d copy, pad columns, repeated query relations, 475 rows
+    _tables("t1_ld_eq", 1, 64, 64, 5, 8, seed=40, why="rank.hip:143 ld == d: no rela_pad"),
+    _tables("t3_d30_ld32", 3, 30, 32, 3, 4, seed=41, why="rank.hip:121 the ld != d copy, d % 4 != 0"),
+    _tables("t5_d48_ld64", 5, 48, 64, 16, 32, seed=42, why="five layers; attn_dim 16 in ap 32: half the columns are pad"),
+    _tables("t3_475rows", 3, 128, 128, 5, 8, n_rows=475, B=64, seed=43, why="475 relation rows (n_rel = 237), a batch of repeated relations"),
+]
+CASES = {c.name: c for c in _CASE_LIST}
+
+
+def _prev(rng, mode, n):
+    """(prev_idx int32 [n] or None, n_old): NULL; all -1; a third of the rows old; every row old (a permutation)."""
+    if mode == "null":
+        return None, 0
+    if mode == "none":
+        return np.full(n, -1, np.int32), 0
+    n_old = n if mode == "all" else (n + 2) // 3
+    p = np.full(n, -1, np.int32)
+    p[rng.choice(n, n_old, replace=False)] = rng.permutation(n_old).astype(np.int32)
+    return p, n_old
+
+
+def inputs(case):
+    """Seeded random inputs of a case: dict of float32 arrays (prev_idx int32, q_rel int64) in the kernels' layouts."""
+    rng = np.random.default_rng(500 + case.seed)
+    f = lambda *shape, scale=1.0: (rng.standard_normal(shape) * scale).astype(np.float32)
+    if case.kind == "step":
+        d, n = case.d, case.n
+        prev_idx, n_old = _prev(rng, case.prev, n)
+        x = dict(agg=f(n, d), prev_idx=prev_idx, n_old=n_old,
+                 hidden_prev=None if prev_idx is None else np.clip(f(max(n_old, 1), d, scale=0.5), -1, 1),
+                 W_h=f(d, d, scale=d ** -0.5), w_ih=f(3 * d, d, scale=d ** -0.5), w_hh=f(3 * d, d, scale=d ** -0.5),
+                 b_ih=f(3 * d, scale=0.3), b_hh=f(3 * d, scale=0.3),
+                 mask=((rng.random((n, d)) < case.keep) / np.float32(case.keep)).astype(np.float32) if case.masked else None,
+                 Ws_next=f(case.attn_dim, d, scale=d ** -0.5) if case.attn_dim else None, grad_hidden=f(n, d))
+        return x
+    if case.kind == "addmm":
+        return dict(base=f(case.n_rows, case.base_width), g=f(case.n_rows, case.g_width), W=f(case.k, case.cols, scale=case.k ** -0.5))
+    q_rel = rng.integers(0, case.n_rows, case.B).astype(np.int64)
+    q_rel[1::2] = q_rel[0]      # every other query repeats the first one's relation
+    q_rel[-1] = case.n_rows - 1
+    return dict(q_rel=q_rel, rela=[f(case.n_rows, case.d) for _ in range(case.n_layer)],
+                Wr=[f(case.attn_dim, case.d, scale=case.d ** -0.5) for _ in range(case.n_layer)],
+                Wqr=[f(case.attn_dim, case.d, scale=case.d ** -0.5) for _ in range(case.n_layer)],
+                bqr=[f(case.attn_dim, scale=0.3) for _ in range(case.n_layer)])
+
+
+def step_forward(case, x, dtype=np.float64, fault=None):
+    return forward(x["agg"], x["hidden_prev"], x["prev_idx"], x["W_h"], case.act, x["w_ih"], x["w_hh"], x["b_ih"], x["b_hh"], x["mask"],
+                   x["Ws_next"], case.ap if case.attn_dim else None, dtype=dtype, fault=fault)
+
+
+def saved(case, x):
+    """What the backward kernels are fed: x and ws of the fp64 forward, rounded once to fp32 (ws as [n, 5 d])."""
+    f = step_forward(case, x)
+    return f.x.astype(np.float32), f.ws.astype(np.float32).reshape(case.n, 5 * case.d)
+
+
+def step_backward(case, x, x_saved, ws_saved, dtype=np.float64, fault=None):
+    return backward(x["grad_hidden"], ws_saved, x_saved, x["mask"], case.keep, case.act, x["W_h"], x["w_ih"], x["w_hh"], x["prev_idx"],
+                    x["n_old"], dtype=dtype, fault=fault)
