@@ -28,9 +28,8 @@ namespace {
 template <int DP>
 __device__ __forceinline__ int sw(int row, int slot) { return row * (DP / 4) + (slot ^ (row & (DP / 4 - 1))); }
 
-// 8 waves per workgroup (2 per SIMD, <= 256 VGPRs).  NB = DP / 16 in {2, 4}: d <= 64, where the 7 weight images fit LDS
+// DENSE_T threads = 8 waves per workgroup.  NB = DP / 16 in {2, 4}: d <= 64, where the 7 weight images fit LDS
 // (d = 128 streams them: dense128.hip).
-constexpr int DENSE_T = 512;
 
 // TRAIN: the same kernel also applies the dropout mask to the GRU input and writes what the backward pass needs - the GRU input
 // and the gate workspace in the layout of aten's fused GRU cell, so that its fused backward kernel can be reused - straight
@@ -82,6 +81,8 @@ __global__ __launch_bounds__(DENSE_T, 2) void dense_kernel(DenseArgs A) {
   }
   load_w(E_l, A.Ws, A.Ws ? A.attn : 0, 0, 16);
   load_w(E_l, A.W_final, A.W_final ? 1 : 0, 16, 16);
+  // (fill_gru_bias<DENSE_T, DP, false, true> of dense_common.h, written out: with the call in its place this kernel's registers are
+  // allocated differently all the way through the tile loop)
   for (int i = threadIdx.x; i < 4 * DP; i += DENSE_T) {
     const int g = i / DP, c = i - g * DP;
     float v = 0.f;
@@ -318,12 +319,7 @@ int launch(const DenseArgs& A, hipStream_t s) {
   constexpr int DP = 16 * NB, S = DP / 4, NW = DENSE_T / 64;
   const size_t lds = (size_t)(7 * DP * S + 32 * S) * sizeof(float4) + 4 * DP * sizeof(float) + (size_t)NW * 16 * S * sizeof(float4);
   RG_HIP(hipFuncSetAttribute((const void*)dense_kernel<NB, TRAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  // one persistent workgroup per CU at most; with a device-side row count the grid follows the caller's expectation (+25 %) instead of
-  // the capacity: a 50-query batch has a few hundred tiles, and 256 workgroups staging 123 KB of weights each kept every CU busy for
-  // 30 us per launch while other streams' batches waited
-  const int64_t tiles = A.n_dev && A.n_hint > 0 ? std::min<int64_t>(A.n_tiles, rg::ceil_div(A.n_hint + A.n_hint / 4, 16)) : A.n_tiles;
-  const int grid = (int)std::max<int64_t>(std::min<int64_t>(rg::ceil_div(tiles, NW), 256), 1);
-  hipLaunchKernelGGL((dense_kernel<NB, TRAIN>), dim3(grid), dim3(DENSE_T), lds, s, A);
+  hipLaunchKernelGGL((dense_kernel<NB, TRAIN>), dim3(dense_grid(A, NW)), dim3(DENSE_T), lds, s, A);
   RG_LAUNCH_CHECK();
   return 0;
 }
@@ -355,14 +351,10 @@ static int dense_fwd_impl(int64_t n, const int32_t* n_dev, int64_t n_hint, int32
   RG_CHECK((((uintptr_t)agg | (uintptr_t)hidden_prev | (uintptr_t)hidden_out | (uintptr_t)a_s_out) & 15) == 0,
            "rg_dense_fwd: float buffers must be 16-B aligned");
   if (n == 0) return 0;
-  DenseArgs A;
-  A.n = n; A.n_dev = n_dev; A.n_hint = n_hint; A.d = d; A.ld4 = ld / 4;
-  A.agg = (const float4*)agg; A.hprev = (const float4*)hidden_prev; A.prev_idx = prev_idx;
-  A.W_h = W_h; A.w_ih = w_ih; A.w_hh = w_hh; A.b_ih = b_ih; A.b_hh = b_hh;
+  DenseArgs A = dense_args(n, d, ld, agg, hidden_prev, prev_idx, W_h, act, w_ih, w_hh, b_ih, b_hh, hidden_out);
+  A.n_dev = n_dev; A.n_hint = n_hint;
   A.Ws = Ws_next; A.attn = attn_dim; A.ap = ap; A.a_s_out = a_s_out;
   A.W_final = W_final; A.nodes = nodes; A.n_ent = n_ent; A.scores = scores_all;
-  A.hidden_out = (float4*)hidden_out; A.act = act;
-  A.n_tiles = (int)rg::ceil_div(n, 16);
   hipStream_t s = (hipStream_t)stream;
   if (d == 128)
     return precision == 1 ? rg::dense128_split_launch(A, scratch, scratch_bytes, s)
@@ -405,14 +397,8 @@ static int dense_train_fwd_impl(const char* who, int64_t n, int32_t d, const flo
   RG_CHECK((((uintptr_t)agg | (uintptr_t)hidden_prev | (uintptr_t)hidden_out | (uintptr_t)x_out | (uintptr_t)gates_ws_out |
              (uintptr_t)mask | (uintptr_t)a_s_out) & 15) == 0, "%s: float buffers must be 16-B aligned", who);
   if (n == 0) return 0;
-  DenseArgs A;
-  A.n = n; A.n_dev = nullptr; A.d = d; A.ld4 = d / 4;
-  A.agg = (const float4*)agg; A.hprev = (const float4*)hidden_prev; A.prev_idx = prev_idx;
-  A.W_h = W_h; A.w_ih = w_ih; A.w_hh = w_hh; A.b_ih = b_ih; A.b_hh = b_hh;
-  A.Ws = Ws_next; A.attn = Ws_next ? attn_dim : 0; A.ap = Ws_next ? ap : 0; A.a_s_out = Ws_next ? a_s_out : nullptr;
-  A.W_final = nullptr; A.nodes = nullptr; A.n_ent = 0; A.scores = nullptr;
-  A.hidden_out = (float4*)hidden_out; A.act = act;
-  A.n_tiles = (int)rg::ceil_div(n, 16);
+  DenseArgs A = dense_args(n, d, d, agg, hidden_prev, prev_idx, W_h, act, w_ih, w_hh, b_ih, b_hh, hidden_out);
+  if (Ws_next) { A.Ws = Ws_next; A.attn = attn_dim; A.ap = ap; A.a_s_out = a_s_out; }
   A.mask = mask; A.x_out = x_out; A.ws_out = gates_ws_out;
   hipStream_t s = (hipStream_t)stream;
   if (d == 128) return rg::dense128_launch(A, s);

@@ -16,8 +16,6 @@
 namespace rg {
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int DP = 128, S = 32, KS = 32, NB = 8, NW = 8, T = 512;
 constexpr int BLK = 16 * S;       // float4 per 16-row weight block
 constexpr int CHUNK = 3 * BLK;    // float4 per chunk (24 KB)
@@ -40,10 +38,7 @@ __global__ __launch_bounds__(T, 2) void dense128_kernel(DenseArgs A) {
     const float* src = r < 16 ? (A.Ws && r < A.attn ? A.Ws + (int64_t)r * DP : nullptr) : (r == 16 ? A.W_final : nullptr);
     E_l[swz(r, sl)] = src ? *reinterpret_cast<const float4*>(src + 4 * sl) : make_float4(0.f, 0.f, 0.f, 0.f);
   }
-  for (int i = threadIdx.x; i < 4 * DP; i += T) {
-    const int g = i / DP, c = i - g * DP;
-    bias_l[i] = g == 0 ? A.b_ih[c] + A.b_hh[c] : g == 1 ? A.b_ih[DP + c] + A.b_hh[DP + c] : g == 2 ? A.b_ih[2 * DP + c] : A.b_hh[2 * DP + c];
-  }
+  fill_gru_bias<T, DP, false, false>(bias_l, A, DP);
   __syncthreads();
 
   const int lane0 = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -304,9 +299,7 @@ int dense128_launch(const DenseArgs& A, hipStream_t s) {
   const size_t lds = (size_t)(2 * CHUNK + 32 * S + NW * 16 * S) * sizeof(float4) + 4 * DP * sizeof(float);
   auto kern = A.ws_out ? dense128_kernel<true> : dense128_kernel<false>;
   RG_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int64_t tiles = A.n_dev && A.n_hint > 0 ? std::min<int64_t>(A.n_tiles, ceil_div(A.n_hint + A.n_hint / 4, 16)) : A.n_tiles;
-  const int grid = (int)std::max<int64_t>(std::min<int64_t>(ceil_div(tiles, NW), 256), 1);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(T), lds, s, A);
+  hipLaunchKernelGGL(kern, dim3(dense_grid(A, NW)), dim3(T), lds, s, A);
   RG_LAUNCH_CHECK();
   return 0;
 }

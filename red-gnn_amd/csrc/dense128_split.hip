@@ -7,19 +7,14 @@
 // would cost as many vector instructions as the rest of the kernel, so a small kernel writes the split image (already in the swizzled
 // LDS layout: a chunk is a linear 24 KB copy) and the weight scale into a scratch buffer of the caller first; both run on the stream.
 //   image: 256-byte header (1 / weight scale of the layer, of the projections), then 58 blocks of 8 KB = [hi: 16 rows x 16 slots x 16 B][lo: the same]; slot (4 s + hq) ^ (row & 15)
-//   of a row holds its weights for k = 16 (2 s + j / 4) + 4 hq + j % 4, j = 0..7 (the lane's accumulator rows, as in dense_split.hip).
+//   of a row holds its weights for k = 16 (2 s + j / 4) + 4 hq + j % 4, j = 0..7 (the lane's accumulator rows, as in Geo of dense_common.h).
 //   blocks 0..7 W_h, 8 + 8 g + ob weight_ih, 32 + 8 g + ob weight_hh (gate g, output block ob), 56 Ws (rows < attn), 57 W_final (row 0).
-#include <type_traits>
-#include "dense_common.h"
+#include "split3.h"
 
 namespace rg {
 namespace {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef float f2v __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+using namespace rg::sp3;
 
 constexpr int DP = 128, NB = 8, KST = 4, KS = 32, NW = 8, T = 512;
 constexpr int S = 32;                       // float4 per row of the node buffers
@@ -27,78 +22,16 @@ constexpr int BLK_B = 8192;                 // bytes of a 16-row block image
 constexpr int CHUNK_B = 3 * BLK_B;
 constexpr int N_BLOCKS = 58;
 constexpr int HDR_B = 256;
-constexpr float LOG2E = 1.44269504088896340736f;
-
-__device__ __forceinline__ float resid_lo(h2 hi, float x) {
-  float r;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(hi), "v"(x));
-  return r;
-}
-__device__ __forceinline__ float resid_hi(h2 hi, float x) {
-  float r;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(hi), "v"(x));
-  return r;
-}
-__device__ __forceinline__ void split4(float a, float b, float c, float d, h4& hi, h4& lo) {
-  const f2v x0 = {a, b}, x1 = {c, d};
-  const h2 h0 = __builtin_convertvector(x0, h2), h1 = __builtin_convertvector(x1, h2);
-  const f2v r0 = {resid_lo(h0, a), resid_hi(h0, b)}, r1 = {resid_lo(h1, c), resid_hi(h1, d)};
-  const h2 l0 = __builtin_convertvector(r0, h2), l1 = __builtin_convertvector(r1, h2);
-  hi = __builtin_shufflevector(h0, h1, 0, 1, 2, 3);
-  lo = __builtin_shufflevector(l0, l1, 0, 1, 2, 3);
-}
-__device__ __forceinline__ void row_scale(float m, float& sc, float& inv) {
-  uint32_t eb = (__float_as_uint(m) >> 23) & 0xffu;
-  eb = eb < 15u ? 15u : (eb > 254u ? 254u : eb);
-  sc = __uint_as_float((268u - eb) << 23);
-  inv = __uint_as_float((eb - 14u) << 23);
-}
 
 // ---- the split image ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(T) void prepare128_kernel(const float* __restrict__ W_h, const float* __restrict__ w_ih,
                                                         const float* __restrict__ w_hh, const float* __restrict__ Ws, int attn,
                                                         const float* __restrict__ W_final, char* __restrict__ image) {
-  __shared__ uint32_t wmax_bits[2];
-  if (threadIdx.x < 2) wmax_bits[threadIdx.x] = 0u;
-  __syncthreads();
-  // every block finds the largest magnitudes itself (117 k weights out of L2: cheaper than a second launch).  The projections (Ws,
-  // W_final) get a scale of their own: the state they read does not depend on which of them a launch carries.
-  float wm = 0.0f;
-  auto scan = [&](const float* p, int n4) {
-    for (int i = threadIdx.x; i < n4; i += T) {
-      const float4 q = reinterpret_cast<const float4*>(p)[i];
-      wm = fmaxf(fmaxf(wm, fmaxf(fabsf(q.x), fabsf(q.y))), fmaxf(fabsf(q.z), fabsf(q.w)));
-    }
-  };
-  scan(W_h, DP * DP / 4); scan(w_ih, 3 * DP * DP / 4); scan(w_hh, 3 * DP * DP / 4);
-  atomicMax(&wmax_bits[0], __float_as_uint(wm));
-  wm = 0.0f;
-  if (Ws) scan(Ws, attn * DP / 4);
-  if (W_final) scan(W_final, DP / 4);
-  atomicMax(&wmax_bits[1], __float_as_uint(wm));
-  __syncthreads();
-  auto fit = [](float wmax) -> float {          // largest magnitude to [2^13, 2^14)
-    if (!(wmax > 0.0f)) return 4096.0f;
-    uint32_t eb = (__float_as_uint(wmax) >> 23) & 0xffu;
-    eb = eb < 15u ? 15u : (eb > 254u ? 254u : eb);
-    return __uint_as_float((267u - eb) << 23);
-  };
-  const float sw_g = fit(__uint_as_float(wmax_bits[0])), sw_e = fit(__uint_as_float(wmax_bits[1]));
-  const int b = blockIdx.x;
-  if (b == 0 && threadIdx.x == 0) { reinterpret_cast<float*>(image)[0] = 1.0f / sw_g; reinterpret_cast<float*>(image)[1] = 1.0f / sw_e; }
-  const float sw = b < 56 ? sw_g : sw_e;
   const int r = threadIdx.x >> 5, ch = threadIdx.x & 31;          // row of the block, 4-float chunk of the row
-  const float* src = nullptr;
-  if (b < 8) src = W_h + (int64_t)(16 * b + r) * DP;
-  else if (b < 32) src = w_ih + (int64_t)(16 * (b - 8) + r) * DP;
-  else if (b < 56) src = w_hh + (int64_t)(16 * (b - 32) + r) * DP;
-  else if (b == 56) src = (Ws && r < attn) ? Ws + (int64_t)r * DP : nullptr;
-  else src = (W_final && r == 0) ? W_final : nullptr;
-  float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (src) q = reinterpret_cast<const float4*>(src)[ch];
+  const float4 q = prepare128_scaled_chunk<T>(W_h, w_ih, w_hh, Ws, attn, W_final, image, r, ch);
   h4 hi, lo;
-  split4(q.x * sw, q.y * sw, q.z * sw, q.w * sw, hi, lo);
-  const int kb = ch >> 2, hq = ch & 3;              // k block of 16, lane quarter
+  split4(q.x, q.y, q.z, q.w, hi, lo);
+  const int b = blockIdx.x, kb = ch >> 2, hq = ch & 3;              // k block of 16, lane quarter
   const int slot = (4 * (kb >> 1) + hq) ^ (r & 15);
   char* blk = image + HDR_B + (int64_t)b * BLK_B;
   reinterpret_cast<h4*>(blk + (r * 16 + slot) * 16)[kb & 1] = hi;
@@ -118,11 +51,7 @@ __global__ __launch_bounds__(T, 2) void dense128_split_kernel(DenseArgs A, const
   const float inv_w = reinterpret_cast<const float*>(image)[0], inv_e = reinterpret_cast<const float*>(image)[1];
   for (int i = threadIdx.x; i < 2 * BLK_B / 16; i += T)
     reinterpret_cast<float4*>(E_l)[i] = reinterpret_cast<const float4*>(image + HDR_B + 56 * BLK_B)[i];
-  for (int i = threadIdx.x; i < 4 * DP; i += T) {
-    const int g = i / DP, c = i - g * DP;
-    bias_l[i] = g == 0 ? -LOG2E * (A.b_ih[c] + A.b_hh[c]) : g == 1 ? -LOG2E * (A.b_ih[DP + c] + A.b_hh[DP + c])
-              : g == 2 ? -2.0f * LOG2E * A.b_ih[2 * DP + c] : -2.0f * LOG2E * A.b_hh[2 * DP + c];
-  }
+  fill_gru_bias<T, DP, true, false>(bias_l, A, DP);
   __syncthreads();
 
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -179,13 +108,6 @@ __global__ __launch_bounds__(T, 2) void dense128_split_kernel(DenseArgs A, const
     }
     return acc;
   };
-  auto row_max = [&](const float (&f)[KS], float m) -> float {
-#pragma unroll
-    for (int i = 0; i < KS; ++i) m = fmaxf(m, fabsf(f[i]));
-    m = fmaxf(m, __shfl_xor(m, 16));
-    m = fmaxf(m, __shfl_xor(m, 32));
-    return m;
-  };
   auto split_frag = [&](const float (&f)[KS], float sc, h8 (&fh)[KST], h8 (&fl)[KST]) {
 #pragma unroll
     for (int s = 0; s < KST; ++s) {
@@ -237,7 +159,7 @@ __global__ __launch_bounds__(T, 2) void dense128_split_kernel(DenseArgs A, const
       float fx[KS];
 #pragma unroll
       for (int ob = 0; ob < NB; ++ob) { fx[4 * ob] = va[ob].x; fx[4 * ob + 1] = va[ob].y; fx[4 * ob + 2] = va[ob].z; fx[4 * ob + 3] = va[ob].w; }
-      row_scale(row_max(fx, 0.f), sc1, inv1);
+      row_scale(row_abs_max(fx, 0.f), sc1, inv1);
       split_frag(fx, sc1, xh, xl);
     }
     float4 vh[NB];
@@ -302,10 +224,10 @@ __global__ __launch_bounds__(T, 2) void dense128_split_kernel(DenseArgs A, const
         my_stash[ob * 64] = vh[ob];        // lane-private: read back per block for z * h
         hf[4 * ob] = vh[ob].x; hf[4 * ob + 1] = vh[ob].y; hf[4 * ob + 2] = vh[ob].z; hf[4 * ob + 3] = vh[ob].w;
       }
-      row_scale(row_max(hf, row_max(xf, 0.f)), sc, inv);
+      row_scale(row_abs_max(hf, row_abs_max(xf, 0.f)), sc, inv);
       split_frag(hf, sc, gh, gl);
     } else {
-      row_scale(row_max(xf, 0.f), sc, inv);
+      row_scale(row_abs_max(xf, 0.f), sc, inv);
     }
     split_frag(xf, sc, xh, xl);
     const float inv_s = inv * inv_w * -LOG2E, inv_t = inv * inv_w * (-2.0f * LOG2E);
@@ -373,9 +295,7 @@ template <int ACT>
 int launch(const DenseArgs& A, const char* image, hipStream_t s) {
   const size_t lds = 2 * CHUNK_B + 2 * BLK_B + 4 * DP * sizeof(float) + (size_t)NW * NB * 64 * sizeof(float4);
   RG_HIP(hipFuncSetAttribute((const void*)dense128_split_kernel<ACT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int64_t tiles = A.n_dev && A.n_hint > 0 ? std::min<int64_t>(A.n_tiles, ceil_div(A.n_hint + A.n_hint / 4, 16)) : A.n_tiles;
-  const int grid = (int)std::max<int64_t>(std::min<int64_t>(ceil_div(tiles, NW), 256), 1);
-  hipLaunchKernelGGL((dense128_split_kernel<ACT>), dim3(grid), dim3(T), lds, s, A, image);
+  hipLaunchKernelGGL((dense128_split_kernel<ACT>), dim3(dense_grid(A, NW)), dim3(T), lds, s, A, image);
   RG_LAUNCH_CHECK();
   return 0;
 }
@@ -392,7 +312,7 @@ int dense128_split_launch(const DenseArgs& A, void* scratch, int64_t scratch_byt
   char* image = (char*)scratch;
   hipLaunchKernelGGL(prepare128_kernel, dim3(N_BLOCKS), dim3(T), 0, s, A.W_h, A.w_ih, A.w_hh, A.Ws, A.attn, A.W_final, image);
   RG_LAUNCH_CHECK();
-  return A.act == 0 ? launch<0>(A, image, s) : A.act == 1 ? launch<1>(A, image, s) : launch<2>(A, image, s);
+  return with_act(A.act, [&](auto ACT) { return launch<decltype(ACT)::value>(A, image, s); });
 }
 
 }  // namespace rg

@@ -10,29 +10,17 @@
 //   image: 256-byte header (1 / weight scale of the layer, of the projections), then 58 blocks of 10 KB =
 //          [hi: 16 rows x 16 slots x 16 B][mid: the same][lo8: 16 rows x 128 B]
 //   f16 parts: slot (4 s + hq) ^ (row & 15) of a row holds its weights for k = 16 (2 s + j / 4) + 4 hq + j % 4, j = 0..7 (k-step s,
-//          lane quarter hq: the lane's accumulator rows, as in dense_split.hip)
+//          lane quarter hq: the lane's accumulator rows, as in Geo of dense_common.h)
 //   lo8 part: the 16-B quad ((hq & 1) + 2 half + 4 (hq >> 1)) ^ (2 ((row >> 1) & 3)) of a row holds k-steps 2 half, 2 half + 1 of
 //          quarter hq (8 bytes each): a ds_read_b128 per half, whose lane groups cover the 64 banks
 //   blocks 0..7 W_h, 8 + 8 g + ob weight_ih, 32 + 8 g + ob weight_hh (gate g, output block ob), 56 Ws (rows < attn), 57 W_final (row 0).
-#include <type_traits>
-#include <utility>
-#include "dense_common.h"
 #include "split3.h"
 
 namespace rg {
 namespace {
 
 using namespace rg::sp3;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef long l2v __attribute__((ext_vector_type(2)));
-
-#define RG_PIN(x) asm volatile("" : "+v"(x))      // see dense_split3.hip: pins the order of the instruction that produced x
-#define RG_PIN_ACC(x) asm volatile("" : "+a"(x))  // the same for an MFMA accumulator, which lives in the accumulation registers here
-
-template <class Fn, int... I>
-__device__ __forceinline__ void static_for_impl(Fn&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class Fn>
-__device__ __forceinline__ void static_for(Fn&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
 
 constexpr int DP = 128, NB = 8, KST = 4, KS = 32, NW = 4, T = 256;
 constexpr int S = 32;                       // float4 per row of the node buffers
@@ -43,7 +31,6 @@ constexpr int CHUNK_B = 3 * BLK_B;
 constexpr int N_BLOCKS = 58;
 constexpr int HDR_B = 256;
 constexpr int PREP_T = 512;
-constexpr float LOG2E = 1.44269504088896340736f;
 
 __device__ __forceinline__ int lo_quad(int row, int hq, int half) { return (((hq & 1) + 2 * half + 4 * (hq >> 1)) ^ (2 * ((row >> 1) & 3))); }
 
@@ -51,42 +38,12 @@ __device__ __forceinline__ int lo_quad(int row, int hq, int half) { return (((hq
 __global__ __launch_bounds__(PREP_T) void prepare128x3_kernel(const float* __restrict__ W_h, const float* __restrict__ w_ih,
                                                                const float* __restrict__ w_hh, const float* __restrict__ Ws, int attn,
                                                                const float* __restrict__ W_final, char* __restrict__ image) {
-  __shared__ uint32_t wmax_bits[2];
-  if (threadIdx.x < 2) wmax_bits[threadIdx.x] = 0u;
-  __syncthreads();
-  // every block finds the largest magnitudes itself (117 k weights out of L2: cheaper than a second launch).  The projections (Ws,
-  // W_final) get a scale of their own: the state they read does not depend on which of them a launch carries.
-  float wm = 0.0f;
-  auto scan = [&](const float* p, int n4) {
-    for (int i = threadIdx.x; i < n4; i += PREP_T) {
-      const float4 q = reinterpret_cast<const float4*>(p)[i];
-      wm = fmaxf(fmaxf(wm, fmaxf(fabsf(q.x), fabsf(q.y))), fmaxf(fabsf(q.z), fabsf(q.w)));
-    }
-  };
-  scan(W_h, DP * DP / 4); scan(w_ih, 3 * DP * DP / 4); scan(w_hh, 3 * DP * DP / 4);
-  atomicMax(&wmax_bits[0], __float_as_uint(wm));
-  wm = 0.0f;
-  if (Ws) scan(Ws, attn * DP / 4);
-  if (W_final) scan(W_final, DP / 4);
-  atomicMax(&wmax_bits[1], __float_as_uint(wm));
-  __syncthreads();
-  const float sw_g = fit_weight_scale(__uint_as_float(wmax_bits[0])), sw_e = fit_weight_scale(__uint_as_float(wmax_bits[1]));
-  const int b = blockIdx.x;
-  if (b == 0 && threadIdx.x == 0) { reinterpret_cast<float*>(image)[0] = 1.0f / sw_g; reinterpret_cast<float*>(image)[1] = 1.0f / sw_e; }
-  const float sw = b < 56 ? sw_g : sw_e;
   const int r = threadIdx.x >> 5, ch = threadIdx.x & 31;          // row of the block, 4-float chunk of the row
-  const float* src = nullptr;
-  if (b < 8) src = W_h + (int64_t)(16 * b + r) * DP;
-  else if (b < 32) src = w_ih + (int64_t)(16 * (b - 8) + r) * DP;
-  else if (b < 56) src = w_hh + (int64_t)(16 * (b - 32) + r) * DP;
-  else if (b == 56) src = (Ws && r < attn) ? Ws + (int64_t)r * DP : nullptr;
-  else src = (W_final && r == 0) ? W_final : nullptr;
-  float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (src) q = reinterpret_cast<const float4*>(src)[ch];
+  const float4 q = prepare128_scaled_chunk<PREP_T>(W_h, w_ih, w_hh, Ws, attn, W_final, image, r, ch);
   h4 hi, mid;
   uint32_t lo8;
-  split3_4_lo8(q.x * sw, q.y * sw, q.z * sw, q.w * sw, hi, mid, lo8);
-  const int kb = ch >> 2, hq = ch & 3;              // k block of 16 (= 2 s + j / 4), lane quarter
+  split3_4_lo8(q.x, q.y, q.z, q.w, hi, mid, lo8);
+  const int b = blockIdx.x, kb = ch >> 2, hq = ch & 3;              // k block of 16 (= 2 s + j / 4), lane quarter
   const int s = kb >> 1;
   const int slot = (4 * s + hq) ^ (r & 15);
   char* blk = image + HDR_B + (int64_t)b * BLK_B;
@@ -113,11 +70,7 @@ __global__ __launch_bounds__(T, 1) void dense128_split3_kernel(DenseArgs A, cons
   const float inv_w = reinterpret_cast<const float*>(image)[0], inv_e = reinterpret_cast<const float*>(image)[1];
   for (int i = threadIdx.x; i < 2 * BLK_B / 16; i += T)
     reinterpret_cast<float4*>(E_l)[i] = reinterpret_cast<const float4*>(image + HDR_B + 56 * BLK_B)[i];
-  for (int i = threadIdx.x; i < 4 * DP; i += T) {
-    const int g = i / DP, c = i - g * DP;
-    bias_l[i] = g == 0 ? -LOG2E * (A.b_ih[c] + A.b_hh[c]) : g == 1 ? -LOG2E * (A.b_ih[DP + c] + A.b_hh[DP + c])
-              : g == 2 ? -2.0f * LOG2E * A.b_ih[2 * DP + c] : -2.0f * LOG2E * A.b_hh[2 * DP + c];
-  }
+  fill_gru_bias<T, DP, true, false>(bias_l, A, DP);
   __syncthreads();
 
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -242,13 +195,6 @@ __global__ __launch_bounds__(T, 1) void dense128_split3_kernel(DenseArgs A, cons
     join(acc, acc8);
     return acc;
   };
-  auto row_max = [&](const float (&f)[KS], float m) -> float {
-#pragma unroll
-    for (int i = 0; i < KS; ++i) m = fmaxf(m, fabsf(f[i]));
-    m = fmaxf(m, __shfl_xor(m, 16));
-    m = fmaxf(m, __shfl_xor(m, 32));
-    return m;
-  };
   auto split_frag = [&](const float (&f)[KS], float sc, Frag4& X) {
 #pragma unroll
     for (int s = 0; s < KST; ++s) {
@@ -307,7 +253,7 @@ __global__ __launch_bounds__(T, 1) void dense128_split3_kernel(DenseArgs A, cons
       float fx[KS];
 #pragma unroll
       for (int ob = 0; ob < NB; ++ob) { fx[4 * ob] = va[ob].x; fx[4 * ob + 1] = va[ob].y; fx[4 * ob + 2] = va[ob].z; fx[4 * ob + 3] = va[ob].w; }
-      row_scale(row_max(fx, 0.f), sc1, inv1);
+      row_scale(row_abs_max(fx, 0.f), sc1, inv1);
       split_frag(fx, sc1, X);
     }
     float4 vh[NB];
@@ -370,10 +316,10 @@ __global__ __launch_bounds__(T, 1) void dense128_split3_kernel(DenseArgs A, cons
 #pragma unroll
     for (int ob = 0; ob < NB; ++ob) { hf[4 * ob] = vh[ob].x; hf[4 * ob + 1] = vh[ob].y; hf[4 * ob + 2] = vh[ob].z; hf[4 * ob + 3] = vh[ob].w; }
     if (hh) {
-      row_scale(row_max(hf, row_max(xf, 0.f)), sc, inv);
+      row_scale(row_abs_max(hf, row_abs_max(xf, 0.f)), sc, inv);
       split_frag(hf, sc, H);
     } else {
-      row_scale(row_max(xf, 0.f), sc, inv);
+      row_scale(row_abs_max(xf, 0.f), sc, inv);
     }
     split_frag(xf, sc, X);
     const float inv_s = inv * inv_w * -LOG2E, inv_t = inv * inv_w * (-2.0f * LOG2E);
@@ -484,9 +430,7 @@ template <int ACT>
 int launch(const DenseArgs& A, const char* image, hipStream_t s) {
   const size_t lds = 2 * CHUNK_B + 2 * BLK_B + 4 * DP * sizeof(float);
   RG_HIP(hipFuncSetAttribute((const void*)dense128_split3_kernel<ACT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int64_t tiles = A.n_dev && A.n_hint > 0 ? std::min<int64_t>(A.n_tiles, ceil_div(A.n_hint + A.n_hint / 4, 16)) : A.n_tiles;
-  const int grid = (int)std::max<int64_t>(std::min<int64_t>(ceil_div(tiles, NW), 256), 1);
-  hipLaunchKernelGGL((dense128_split3_kernel<ACT>), dim3(grid), dim3(T), lds, s, A, image);
+  hipLaunchKernelGGL((dense128_split3_kernel<ACT>), dim3(dense_grid(A, NW)), dim3(T), lds, s, A, image);
   RG_LAUNCH_CHECK();
   return 0;
 }
@@ -503,7 +447,7 @@ int dense128_split3_launch(const DenseArgs& A, void* scratch, int64_t scratch_by
   char* image = (char*)scratch;
   hipLaunchKernelGGL(prepare128x3_kernel, dim3(N_BLOCKS), dim3(PREP_T), 0, s, A.W_h, A.w_ih, A.w_hh, A.Ws, A.attn, A.W_final, image);
   RG_LAUNCH_CHECK();
-  return A.act == 0 ? launch<0>(A, image, s) : A.act == 1 ? launch<1>(A, image, s) : launch<2>(A, image, s);
+  return with_act(A.act, [&](auto ACT) { return launch<decltype(ACT)::value>(A, image, s); });
 }
 
 }  // namespace rg

@@ -15,67 +15,17 @@
 // scales, and one wave keeps the next tile's rows and the prev_idx word of the tile after in flight.
 // rg_dense_fwd(..., precision = 1) selects it; precision = 0 keeps the exact-fp32 kernel of dense.hip.
 #include <type_traits>
-#include "dense_common.h"
+#include "split3.h"
 
 using namespace rg;
+using namespace rg::sp3;
 
 namespace {
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef float f4v __attribute__((ext_vector_type(4)));
-
-constexpr int DENSE_T = 512;
-constexpr float LOG2E = 1.44269504088896340736f;
-
-// hi / lo halves of four (already scaled) floats
-// (the residual x - float(hi) as one v_fma_mix_f32 per value - hi read as f16 in place - instead of a conversion and a subtraction:
-// the compiler does not form it, and the splits are a third of the kernel's vector instructions)
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float resid_lo(h2 hi, float x) {
-  float r;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(hi), "v"(x));
-  return r;
-}
-__device__ __forceinline__ float resid_hi(h2 hi, float x) {
-  float r;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(hi), "v"(x));
-  return r;
-}
-typedef float f2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void split4(float a, float b, float c, float d, h4& hi, h4& lo) {
-  const f2v x0 = {a, b}, x1 = {c, d};
-  const h2 h0 = __builtin_convertvector(x0, h2), h1 = __builtin_convertvector(x1, h2);
-  const f2v r0 = {resid_lo(h0, a), resid_hi(h0, b)}, r1 = {resid_lo(h1, c), resid_hi(h1, d)};
-  const h2 l0 = __builtin_convertvector(r0, h2), l1 = __builtin_convertvector(r1, h2);
-  hi = __builtin_shufflevector(h0, h1, 0, 1, 2, 3);
-  lo = __builtin_shufflevector(l0, l1, 0, 1, 2, 3);
-}
-
-// power-of-two scale that puts m (>= 0) into [2^14, 2^15), and its inverse; rows of (near) zeros keep a finite scale
-__device__ __forceinline__ void row_scale(float m, float& sc, float& inv) {
-  uint32_t eb = (__float_as_uint(m) >> 23) & 0xffu;
-  eb = eb < 15u ? 15u : (eb > 254u ? 254u : eb);
-  sc = __uint_as_float((268u - eb) << 23);
-  inv = __uint_as_float((eb - 14u) << 23);
-}
-
-// DP in {32, 64}: padded width.  Weight images in LDS: per row DP f16 of hi and, in a second image, of lo; the 16-B slot (k-step s,
-// lane quarter hq) holds the row's weights for k = 16 * (2s + j / 4) + 4 * hq + j % 4, j = 0..7 - the k order in which a lane holds
-// its accumulator rows, so that accumulators convert in place into the next B fragment.  Slots are XOR-swizzled with the row so that
-// the 16 rows read by a quarter wave cover the 16 bank groups.
-template <int DP>
-struct Geo {
-  static constexpr int SR = DP / 8;                  // 16-B slots per image row
-  static constexpr int SH = DP == 64 ? 1 : 2;        // rows per 256 B of LDS
-  static constexpr int KST = DP / 32;                // k-steps of 32 per product
-  __device__ static __forceinline__ int at(int row, int slot) { return row * SR + (slot ^ ((row >> SH) & (SR - 1))); }
-};
 
 template <int NB, int ACT>
 __global__ __launch_bounds__(DENSE_T, 2) void dense_split_kernel(DenseArgs A) {
   constexpr int DP = 16 * NB;
-  using G = Geo<DP>;
+  using G = Geo<DP>;               // the images' slot order and swizzle (dense_common.h)
   constexpr int SR = G::SR, KST = G::KST;
   constexpr int S = DP / 4;        // float4 chunks per padded row
   constexpr int KS = DP / 4;       // values per lane of a fragment
@@ -143,37 +93,21 @@ __global__ __launch_bounds__(DENSE_T, 2) void dense_split_kernel(DenseArgs A) {
     __syncthreads();
     const float wmax = __uint_as_float(*wmax_bits);
     if (wmax == 0.0f || (wmax * sw <= 32768.0f && wmax * sw >= 16.0f)) break;
+    // (fit_weight_scale of split3.h without its test for zero, which the line above has made: with the call in its place the whole
+    // kernel is allocated differently)
     uint32_t eb = (__float_as_uint(wmax) >> 23) & 0xffu;
     eb = eb < 15u ? 15u : (eb > 254u ? 254u : eb);
     sw = __uint_as_float((267u - eb) << 23);        // largest magnitude to [2^13, 2^14)
     __syncthreads();
   }
   const float inv_w = 1.0f / sw;                     // exact: a power of two
-  for (int i = threadIdx.x; i < 4 * DP; i += DENSE_T) {
-    const int g = i / DP, c = i - g * DP;
-    float v = 0.f;
-    if (c < d) {
-      if (g == 0) v = -LOG2E * (A.b_ih[c] + A.b_hh[c]);
-      else if (g == 1) v = -LOG2E * (A.b_ih[d + c] + A.b_hh[d + c]);
-      else if (g == 2) v = -2.0f * LOG2E * A.b_ih[2 * d + c];
-      else v = -2.0f * LOG2E * A.b_hh[2 * d + c];
-    }
-    bias_l[i] = v;
-  }
+  fill_gru_bias<DENSE_T, DP, true, true>(bias_l, A, d);
   __syncthreads();
 
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int li = lane & 15, hq = lane >> 4;
   float4* my_stash = stash + wv * NB * 64 + lane;
 
-  // largest magnitude of the lane's node row (the row is spread over the four lane quarters)
-  auto row_max = [&](const float (&f)[KS], float m) -> float {
-#pragma unroll
-    for (int i = 0; i < KS; ++i) m = fmaxf(m, fabsf(f[i]));
-    m = fmaxf(m, __shfl_xor(m, 16));
-    m = fmaxf(m, __shfl_xor(m, 32));
-    return m;
-  };
   // B fragments of f * sc
   auto split_frag = [&](const float (&f)[KS], float sc, h8 (&fh)[KST], h8 (&fl)[KST]) {
 #pragma unroll
@@ -266,7 +200,7 @@ __global__ __launch_bounds__(DENSE_T, 2) void dense_split_kernel(DenseArgs A) {
       float fx[KS];
 #pragma unroll
       for (int ob = 0; ob < NB; ++ob) { fx[4 * ob] = va[ob].x; fx[4 * ob + 1] = va[ob].y; fx[4 * ob + 2] = va[ob].z; fx[4 * ob + 3] = va[ob].w; }
-      row_scale(row_max(fx, 0.f), sc1, inv1);
+      row_scale(row_abs_max(fx, 0.f), sc1, inv1);
       split_frag(fx, sc1, fh, fl);
     }
     if (any_old) {
@@ -313,10 +247,10 @@ __global__ __launch_bounds__(DENSE_T, 2) void dense_split_kernel(DenseArgs A) {
           const float4 q = my_stash[ob * 64];
           hf[4 * ob] = q.x; hf[4 * ob + 1] = q.y; hf[4 * ob + 2] = q.z; hf[4 * ob + 3] = q.w;
         }
-        row_scale(row_max(hf, row_max(xf, 0.f)), sc, inv);
+        row_scale(row_abs_max(hf, row_abs_max(xf, 0.f)), sc, inv);
         split_frag(hf, sc, hh, hl);
       } else {
-        row_scale(row_max(xf, 0.f), sc, inv);
+        row_scale(row_abs_max(xf, 0.f), sc, inv);
       }
       split_frag(xf, sc, xh, xl);
       const float inv_s = inv * inv_w * -LOG2E, inv_t = inv * inv_w * (-2.0f * LOG2E);
@@ -384,16 +318,14 @@ int launch(const DenseArgs& A, hipStream_t s) {
   constexpr int DP = 16 * NB, SR = DP / 8, NW = DENSE_T / 64;
   const size_t lds = (size_t)(2 * 7 * DP * SR + 2 * 32 * SR) * 16 + 4 * DP * sizeof(float) + (size_t)NW * NB * 64 * sizeof(float4) + 16;
   RG_HIP(hipFuncSetAttribute((const void*)dense_split_kernel<NB, ACT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int64_t tiles = A.n_dev && A.n_hint > 0 ? std::min<int64_t>(A.n_tiles, rg::ceil_div(A.n_hint + A.n_hint / 4, 16)) : A.n_tiles;
-  const int grid = (int)std::max<int64_t>(std::min<int64_t>(rg::ceil_div(tiles, NW), 256), 1);
-  hipLaunchKernelGGL((dense_split_kernel<NB, ACT>), dim3(grid), dim3(DENSE_T), lds, s, A);
+  hipLaunchKernelGGL((dense_split_kernel<NB, ACT>), dim3(dense_grid(A, NW)), dim3(DENSE_T), lds, s, A);
   RG_LAUNCH_CHECK();
   return 0;
 }
 
 template <int NB>
 int launch_act(const DenseArgs& A, hipStream_t s) {
-  return A.act == 0 ? launch<NB, 0>(A, s) : A.act == 1 ? launch<NB, 1>(A, s) : launch<NB, 2>(A, s);
+  return with_act(A.act, [&](auto ACT) { return launch<NB, decltype(ACT)::value>(A, s); });
 }
 
 }  // namespace

@@ -11,9 +11,6 @@
 //   * which leaves no LDS for the old state's lane-private copy: z * h takes h back from its own (exact) split fragments, and the old
 //     rows of the NEXT tile are requested as soon as this tile's are split - a full tile of work ahead of their use.
 // rg_dense_fwd(..., precision = 2).  precision 0 = v_mfma_f32_16x16x4_f32 (dense.hip), 1 = two-term splits (dense_split.hip).
-#include <type_traits>
-#include <utility>
-#include "dense_common.h"
 #include "split3.h"
 
 using namespace rg;
@@ -21,54 +18,17 @@ using namespace rg::sp3;
 
 namespace {
 
-constexpr int DENSE_T = 512;
-constexpr float LOG2E = 1.44269504088896340736f;
-
-// DP in {32, 64}: padded width.  f16 weight images: per row DP values of hi and, in a second image, of mid; the 16-B slot (k-step s,
-// lane quarter hq) holds the row's weights for k = 16 * (2s + j / 4) + 4 * hq + j % 4, j = 0..7 - the k order in which a lane holds
-// its accumulator rows, so that accumulators convert in place into the next B fragment.  Slots are XOR-swizzled with the row so that
-// the 16 rows read by a quarter wave cover the 16 bank groups.  The bf8 lo image has the same slots at 8 B each, swizzled so that bank-conflict
-// free for the one read per product that fetches all its k-steps.
-template <int DP>
-struct Geo {
-  static constexpr int SR = DP / 8;                  // slots per image row
-  static constexpr int SH = DP == 64 ? 1 : 2;        // rows per 256 B of the f16 images
-  static constexpr int KST = DP / 32;                // k-steps of 32 per product
-  __device__ static __forceinline__ int at(int row, int slot) { return row * SR + (slot ^ ((row >> SH) & (SR - 1))); }
-  // bf8 lo image, byte offset of the lane quarter hq's values of a row: DP = 64: 16 B = {k-step 0, k-step 1} (one ds_read_b128 per
-  // product; its 4 x 16 lane groups {0-3, 12-15, 20-27}, ... then cover the 64 banks: slot = hq ^ f(row / 4), f = 0, 3, 2, 1);
-  // DP = 32: 8 B (one k-step), slot = hq ^ 2 (row / 8)
-  __device__ static __forceinline__ int at8(int row, int hq) {
-    if (DP == 64) {
-      const int g = (row >> 2) & 3, f = (4 - g) & 3;
-      return row * 64 + ((hq ^ f) << 4);
-    }
-    return row * 32 + ((hq ^ (((row >> 3) & 1) << 1)) << 3);
-  }
-};
-
-// an empty volatile asm that consumes and redefines a register: volatile asms keep their order, so the instruction that produced the value
-// stays ahead of it and its users stay behind it - the pipelined gate loop fixes its instruction order with these
-#define RG_PIN(x) asm volatile("" : "+v"(x))
-
-template <class Fn, int... I>
-__device__ __forceinline__ void static_for_impl(Fn&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class Fn>
-__device__ __forceinline__ void static_for(Fn&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
-
 template <int KST>
 struct Frag {          // B operand of one node row: hi / mid / lo f16 and the bf8 form of x / 2^8, per k-step
   h8 h[KST], m[KST], l[KST];
   long q[KST];
 };
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 // PROBE: the test-hook build (rg_split3_product_check): writes one of the products instead of the new state
 template <int NB, int ACT, bool PROBE>
 __global__ __launch_bounds__(DENSE_T, 2) void dense_split3_kernel(DenseArgs A) {
   constexpr int DP = 16 * NB;
-  using G = Geo<DP>;
+  using G = Geo<DP>;               // the images' slot order and swizzle (dense_common.h)
   constexpr int SR = G::SR, KST = G::KST;
   constexpr int S = DP / 4;        // float4 chunks per padded row
   constexpr int KS = DP / 4;       // values per lane of a fragment
@@ -159,30 +119,12 @@ __global__ __launch_bounds__(DENSE_T, 2) void dense_split3_kernel(DenseArgs A) {
   load_w(O_E, O_E + P_E, L_E, A.Ws, A.Ws ? A.attn : 0, 0, 16, sw_e);
   load_w(O_E, O_E + P_E, L_E, A.W_final, A.W_final ? 1 : 0, 16, 16, sw_e);
   const float inv_w = 1.0f / sw_g, inv_we = 1.0f / sw_e;                     // exact: powers of two
-  for (int i = threadIdx.x; i < 4 * DP; i += DENSE_T) {
-    const int g = i / DP, c = i - g * DP;
-    float v = 0.f;
-    if (c < d) {
-      if (g == 0) v = -LOG2E * (A.b_ih[c] + A.b_hh[c]);
-      else if (g == 1) v = -LOG2E * (A.b_ih[d + c] + A.b_hh[d + c]);
-      else if (g == 2) v = -2.0f * LOG2E * A.b_ih[2 * d + c];
-      else v = -2.0f * LOG2E * A.b_hh[2 * d + c];
-    }
-    bias_l[i] = v;
-  }
+  fill_gru_bias<DENSE_T, DP, true, true>(bias_l, A, d);
   __syncthreads();
 
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int li = lane & 15, hq = lane >> 4;
 
-  // largest magnitude of the lane's node row (the row is spread over the four lane quarters)
-  auto row_max = [&](const float (&f)[KS], float m) -> float {
-#pragma unroll
-    for (int i = 0; i < KS; ++i) m = fmaxf(m, fabsf(f[i]));
-    m = fmaxf(m, __shfl_xor(m, 16));
-    m = fmaxf(m, __shfl_xor(m, 32));
-    return m;
-  };
   // B fragments of f * sc
   // (the bf8 form is taken from the SAME scaled values: the 2^-8 that pairs it with the weights' lo image, stored times 2^8, is applied
   // where the bf8 chain joins the f16 chain - one fma per accumulator element instead of a multiplication per operand element)
@@ -315,7 +257,7 @@ __global__ __launch_bounds__(DENSE_T, 2) void dense_split3_kernel(DenseArgs A) {
       float fx[KS];
 #pragma unroll
       for (int ob = 0; ob < NB; ++ob) { fx[4 * ob] = va[ob].x; fx[4 * ob + 1] = va[ob].y; fx[4 * ob + 2] = va[ob].z; fx[4 * ob + 3] = va[ob].w; }
-      row_scale(row_max(fx, 0.f), sc1, inv1);
+      row_scale(row_abs_max(fx, 0.f), sc1, inv1);
       split_frag(fx, sc1, F);
     }
     load_agg(t + t_step, va);
@@ -374,10 +316,10 @@ __global__ __launch_bounds__(DENSE_T, 2) void dense_split3_kernel(DenseArgs A) {
 #pragma unroll
         for (int ob = 0; ob < NB; ++ob) { hf[4 * ob] = vh[ob].x; hf[4 * ob + 1] = vh[ob].y; hf[4 * ob + 2] = vh[ob].z; hf[4 * ob + 3] = vh[ob].w; }
         const bool is_old = p_cur >= 0;
-        row_scale(fmaxf(is_old ? row_max(hf, 0.f) : 0.f, row_max(xf, 0.f)), sc, inv);
+        row_scale(fmaxf(is_old ? row_abs_max(hf, 0.f) : 0.f, row_abs_max(xf, 0.f)), sc, inv);
         split_frag(hf, is_old ? sc : 0.f, H);
       } else {
-        row_scale(row_max(xf, 0.f), sc, inv);
+        row_scale(row_abs_max(xf, 0.f), sc, inv);
       }
       // the next tile's old rows go out here, AHEAD of this tile's stores: the memory counter retires in order, so a wait for loads
       // issued after the stores (as a prefetch at the end of the tile was) waits out the stores' acknowledgements and the loads' whole
@@ -633,9 +575,7 @@ int launch(const DenseArgs& A, hipStream_t s) {
   constexpr size_t lds = lds_bytes<NB>();
   static_assert(lds <= 160 * 1024, "weight images exceed the CU's LDS");
   RG_HIP(hipFuncSetAttribute((const void*)dense_split3_kernel<NB, ACT, PROBE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int64_t tiles = A.n_dev && A.n_hint > 0 ? std::min<int64_t>(A.n_tiles, rg::ceil_div(A.n_hint + A.n_hint / 4, 16)) : A.n_tiles;
-  const int grid = (int)std::max<int64_t>(std::min<int64_t>(rg::ceil_div(tiles, NW), 256), 1);
-  hipLaunchKernelGGL((dense_split3_kernel<NB, ACT, PROBE>), dim3(grid), dim3(DENSE_T), lds, s, A);
+  hipLaunchKernelGGL((dense_split3_kernel<NB, ACT, PROBE>), dim3(dense_grid(A, NW)), dim3(DENSE_T), lds, s, A);
   RG_LAUNCH_CHECK();
   return 0;
 }
@@ -643,7 +583,7 @@ int launch(const DenseArgs& A, hipStream_t s) {
 template <int NB>
 int launch_act(const DenseArgs& A, hipStream_t s) {
   if (A.probe) return launch<NB, 0, true>(A, s);        // (the hook runs with the identity activation)
-  return A.act == 0 ? launch<NB, 0, false>(A, s) : A.act == 1 ? launch<NB, 1, false>(A, s) : launch<NB, 2, false>(A, s);
+  return with_act(A.act, [&](auto ACT) { return launch<NB, decltype(ACT)::value, false>(A, s); });
 }
 
 // rg_split3_roundtrip: the device split of n rows of `cols` floats (row scale as the kernels take it) and its reconstruction
@@ -691,12 +631,7 @@ extern "C" int rg_split3_product_check(int32_t which, int64_t n, int32_t d, cons
   RG_CHECK(d >= 4 && d <= 64 && d % 4 == 0 && act >= 0 && act <= 2, "rg_split3_product_check: d=%d act=%d", d, act);
   RG_CHECK(which != 3 || (hidden_prev && prev_idx), "rg_split3_product_check: which = 3 needs the old state");
   if (n == 0) return 0;
-  DenseArgs A;
-  A.n = n; A.n_dev = nullptr; A.d = d; A.ld4 = d / 4;
-  A.agg = (const float4*)agg; A.hprev = (const float4*)hidden_prev; A.prev_idx = prev_idx;
-  A.W_h = W_h; A.w_ih = w_ih; A.w_hh = w_hh; A.b_ih = b_ih; A.b_hh = b_hh;
-  A.Ws = nullptr; A.attn = 0; A.ap = 0; A.a_s_out = nullptr; A.W_final = nullptr; A.nodes = nullptr; A.n_ent = 0; A.scores = nullptr;
-  A.hidden_out = (float4*)out; A.act = act; A.n_tiles = (int)rg::ceil_div(n, 16);
+  DenseArgs A = dense_args(n, d, d, agg, hidden_prev, prev_idx, W_h, act, w_ih, w_hh, b_ih, b_hh, out);
   A.probe = which;
   return rg::dense_split3_launch(A, (hipStream_t)stream);
 }
