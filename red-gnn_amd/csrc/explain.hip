@@ -11,9 +11,10 @@
 //          order-free);
 //   emit:  after an exclusive scan of the counts, every kept edge is written at its word's offset + its rank among the word's
 //          kept edges (ballot prefix): output order (row, tail, CSR position), deterministic.
-// alpha is the forward kernel's arithmetic (layer_fwd_kernel.h), re-evaluated on the marked tails' in-edges only: nothing
-// E_subgraph-sized is read or held.  A last gather puts the hops' lists into (row, hop, ...) order.
-#include "common.h"
+// alpha is the forward kernel's arithmetic - the same attn.h calls in the forward's operand order, so the forward's alpha bit for
+// bit - re-evaluated on the marked tails' in-edges only: nothing E_subgraph-sized is read or held.  A last gather puts the hops'
+// lists into (row, hop, ...) order.
+#include "attn.h"
 
 namespace {
 
@@ -87,24 +88,15 @@ __global__ __launch_bounds__(EX_BLOCK) void explain_kernel(ExArgs A) {
           const int2 hr = A.in_hr[c];
           hd = hr.x; r = hr.y;
           const int2 wp = bm_row[hd >> 5];
-          const uint32_t word = (uint32_t)wp.x, bit = hd & 31;
-          if ((word >> bit) & 1u) {
-            const int s = wp.y + __popc(word & ((1u << bit) - 1u));
-            // layer_fwd_kernel.h's sum, term for term
+          if (rg::bm_has(wp, hd)) {
+            const int s = rg::bm_rank(wp, hd);
             float z = b_alpha;
             for (int k = 0; k < A.ap4; ++k) {
               const float4 as = A.a_s[(int64_t)s * A.ap4 + k];
               const float4 ar = A.a_r[(int64_t)r * A.ap4 + k];
-              const float4 q = aq[k];
-              float w[4];
-#pragma unroll
-              for (int u = 0; u < 4; ++u) w[u] = 4 * k + u < A.attn_dim ? A.w_alpha[4 * k + u] : 0.f;
-              z = fmaf(w[0], fmaxf(as.x + ar.x + q.x, 0.f), z);
-              z = fmaf(w[1], fmaxf(as.y + ar.y + q.y, 0.f), z);
-              z = fmaf(w[2], fmaxf(as.z + ar.z + q.z, 0.f), z);
-              z = fmaf(w[3], fmaxf(as.w + ar.w + q.w, 0.f), z);
+              rg::attn_acc_fwd(z, rg::attn_w4(A.w_alpha, A.attn_dim, k), as, ar, aq[k]);
             }
-            alpha = __builtin_amdgcn_rcpf(1.0f + __expf(-z));
+            alpha = rg::attn_alpha(z);
             keep = alpha >= A.tau;
           }
         }

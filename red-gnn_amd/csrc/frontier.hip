@@ -8,7 +8,7 @@
 //     without sorting anything.
 #include <string.h>
 
-#include "common.h"
+#include "attn.h"
 
 namespace {
 
@@ -198,16 +198,15 @@ __global__ void emit_nodes_kernel(const int2* __restrict__ bm_new, const int2* _
   const int pos = (int)(t & 31);
   if (i >= (int64_t)B * W) return;
   const int2 nw = bm_new[i];
-  const uint32_t bits = (uint32_t)nw.x;
-  if (!((bits >> pos) & 1u)) return;
-  const int64_t idx = nw.y + __popc(bits & ((1u << pos) - 1u));
+  if (!rg::bm_has(nw, pos)) return;
+  const int64_t idx = rg::bm_rank(nw, pos);
   const int b = (int)(i / W), w = (int)(i - (int64_t)b * W);
   if (nodes) reinterpret_cast<int2*>(nodes)[idx] = make_int2(b, w * 32 + pos);
   if (prev_idx || old_new) {
     int prev = -1;
     if (bm_old) {
       const int2 ow = bm_old[i];
-      if (((uint32_t)ow.x >> pos) & 1u) prev = ow.y + __popc((uint32_t)ow.x & ((1u << pos) - 1u));
+      if (rg::bm_has(ow, pos)) prev = rg::bm_rank(ow, pos);
     }
     if (prev_idx) prev_idx[idx] = prev;
     if (old_new && prev >= 0) old_new[prev] = (int32_t)idx;
@@ -217,9 +216,8 @@ __global__ void emit_nodes_kernel(const int2* __restrict__ bm_new, const int2* _
 // ---- materialised edges (compatibility path) -------------------------------------------------------
 __device__ __forceinline__ int rank_in(const int2* __restrict__ bm, int b, int W, int e, bool* present) {
   const int2 wp = bm[(int64_t)b * W + (e >> 5)];
-  const uint32_t word = (uint32_t)wp.x;
-  *present = (word >> (e & 31)) & 1u;
-  return wp.y + __popc(word & ((1u << (e & 31)) - 1u));
+  *present = rg::bm_has(wp, e);
+  return rg::bm_rank(wp, e);
 }
 
 __global__ void edge_count_kernel(const int32_t* __restrict__ nodes_new, int64_t n_new, const int32_t* __restrict__ in_ptr,

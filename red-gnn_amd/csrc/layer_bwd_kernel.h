@@ -18,8 +18,8 @@
 //     dA_s[s] += g_z          (registers -> one store per source / segment)
 //     dA_r[r] += g_z          (LDS)            dw += g_p relu(z), db += g_p (STATIC)   (registers -> block reduce)
 //   dA_q[b] = sum of dA_s over the nodes of query b is left to the caller (a segment sum).
-// The relation (and time) table gradients are separate key-major passes (drel_kernel, tkey_kernel); the projections a_s = H Ws^T
-// etc. and the direction linears are differentiated by the caller (dense GEMMs).
+// The relation (and time) table gradients are the key-major pass of key_bwd_kernel.h; the attention scalar and the bitmap lookup
+// are attn.h's; the projections a_s = H Ws^T etc. and the direction linears are differentiated by the caller (dense GEMMs).
 // Work distribution: walk.h (in-order per-XCD queues; grad_agg rows of the query being processed stay in L2).
 #pragma once
 #include "walk.h"
@@ -91,15 +91,8 @@ __global__ __launch_bounds__(BWD_BLOCK, AP4 >= 4 ? 2 : 4) void layer_bwd_kernel(
   float4* rela_l = red_l + (BLOCK / 64) * (AP4 + 1);                        // [nr][G]  (RELA_LDS)
   int4* recs = reinterpret_cast<int4*>(rela_l + (RELA_LDS ? nr * G : 0));   // [BLOCK] (SPARSE only)
 
-  for (int i = threadIdx.x; i < nr * AP4; i += BLOCK) { ar_l[i] = A.a_r[i]; gar_l[i] = rg::f4zero(); }
-  if (threadIdx.x < AP4) {
-    float w[4];
-    for (int k = 0; k < 4; ++k) {
-      const int j = threadIdx.x * 4 + k;
-      w[k] = j < A.attn_dim ? A.w_alpha[j] : 0.f;
-    }
-    w_l[threadIdx.x] = make_float4(w[0], w[1], w[2], w[3]);
-  }
+  rg::stage_attention<AP4, BLOCK>(ar_l, w_l, A.a_r, nr, A.w_alpha, A.attn_dim);
+  for (int i = threadIdx.x; i < nr * AP4; i += BLOCK) gar_l[i] = rg::f4zero();
   if constexpr (RELA_LDS) {
     for (int i = threadIdx.x; i < nr * G; i += BLOCK) {
       const int r = i / G, c = i - r * G;
@@ -128,9 +121,7 @@ __global__ __launch_bounds__(BWD_BLOCK, AP4 >= 4 ? 2 : 4) void layer_bwd_kernel(
     float4 base[AP4], gas[AP4];
 #pragma unroll
     for (int k = 0; k < AP4; ++k) {
-      const float4 as = A.a_s[(int64_t)s_node * AP4 + k];
-      const float4 aq = A.a_q[(int64_t)b * AP4 + k];
-      base[k] = make_float4(as.x + aq.x, as.y + aq.y, as.z + aq.z, as.w + aq.w);
+      base[k] = rg::f4add(A.a_s[(int64_t)s_node * AP4 + k], A.a_q[(int64_t)b * AP4 + k]);   // hoisted per source (attn.h)
       gas[k] = rg::f4zero();
     }
     float4 hs[ND], acc[ND];
@@ -162,8 +153,7 @@ __global__ __launch_bounds__(BWD_BLOCK, AP4 >= 4 ? 2 : 4) void layer_bwd_kernel(
         int tl;
         if constexpr (PACKED) { const uint32_t pk = A.out_pk[c]; tl = pk & 0xFFFFF; r = pk >> 20; }
         else { const int2 rt = A.out_rt[c]; r = rt.x; tl = rt.y; }
-        const int2 wp = bm_row[tl >> 5];
-        o = wp.y + __popc((uint32_t)wp.x & ((1u << (tl & 31)) - 1u));
+        o = rg::bm_rank(bm_row[tl >> 5], tl);
         rrow = r;
         if constexpr (L == WINDOWED) {
           const int delta = qt - (erow >= A.n_data ? lt : A.row_time[erow]);
@@ -176,17 +166,8 @@ __global__ __launch_bounds__(BWD_BLOCK, AP4 >= 4 ? 2 : 4) void layer_bwd_kernel(
         }
         float z = b_alpha;
 #pragma unroll
-        for (int k = 0; k < AP4; ++k) {
-          const float4 ar = ar_l[r * AP4 + k];
-          const float4 w = w_l[k];
-          zr[k] = make_float4(fmaxf(base[k].x + ar.x, 0.f), fmaxf(base[k].y + ar.y, 0.f),
-                              fmaxf(base[k].z + ar.z, 0.f), fmaxf(base[k].w + ar.w, 0.f));
-          z = fmaf(w.x, zr[k].x, z);
-          z = fmaf(w.y, zr[k].y, z);
-          z = fmaf(w.z, zr[k].z, z);
-          z = fmaf(w.w, zr[k].w, z);
-        }
-        alpha = __builtin_amdgcn_rcpf(1.0f + __expf(-z));
+        for (int k = 0; k < AP4; ++k) rg::attn_acc(z, w_l[k], base[k], ar_l[r * AP4 + k], zr[k]);
+        alpha = rg::attn_alpha(z);
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
       __builtin_amdgcn_wave_barrier();
@@ -333,9 +314,8 @@ __global__ void bwd_combine_kernel(const int4* __restrict__ split, int n_split, 
   const int b = (int)(item / n_split);
   const int4 se = split[item - (int64_t)b * n_split];
   const int2 wp = bm_old[(int64_t)b * W + (se.x >> 5)];
-  const uint32_t word = (uint32_t)wp.x, bit = se.x & 31;
-  if (!((word >> bit) & 1u)) return;
-  const int s = wp.y + __popc(word & ((1u << bit) - 1u));
+  if (!rg::bm_has(wp, se.x)) return;
+  const int s = rg::bm_rank(wp, se.x);
   const bool is_h = c < cols_h;
   const int stride = is_h ? cols_h : ap4;
   const float4* p = (is_h ? hpart : apart) + ((int64_t)b * n_slots + se.y) * stride + (is_h ? c : c - cols_h);
@@ -373,7 +353,7 @@ int launch2(const char* who, const BwdArgs& A, int B, const rg_vrows& vr, const 
   if (!DENSE) lds += (size_t)BWD_BLOCK * sizeof(int4);
   RG_CHECK(lds <= 160 * 1024, "%s: attention tables need %zu B of LDS (> 160 KiB)", who, lds);
   if constexpr (L == STATIC) {
-    // dRel comes from the relation-major pass (drel_kernel); here the rela rows are only read
+    // dRel comes from the relation-major pass (key_bwd_kernel.h); here the rela rows are only read
     const size_t rela = (size_t)A.n_rela_rows * G * sizeof(float4);
     const bool rela_lds = lds + rela <= 80 * 1024;
     if constexpr (DENSE) {

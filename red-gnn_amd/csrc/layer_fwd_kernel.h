@@ -82,15 +82,7 @@ __global__ __launch_bounds__(FWD_BLOCK, TEMPORAL ? 4 : (G >= 32 ? 4 : 6)) void l
   float4* rela_l = w_l + AP4;                            // [n_rela_rows][G] (optional)
   int4* recs = reinterpret_cast<int4*>(rela_l + (RELA_LDS ? A.n_rela_rows * G : 0));   // [BLOCK] (SPARSE only)
 
-  for (int i = threadIdx.x; i < A.n_rela_rows * AP4; i += BLOCK) ar_l[i] = A.a_r[i];
-  if (threadIdx.x < AP4) {
-    float w[4];
-    for (int k = 0; k < 4; ++k) {
-      const int j = threadIdx.x * 4 + k;
-      w[k] = j < A.attn_dim ? A.w_alpha[j] : 0.f;
-    }
-    w_l[threadIdx.x] = make_float4(w[0], w[1], w[2], w[3]);
-  }
+  rg::stage_attention<AP4, BLOCK>(ar_l, w_l, A.a_r, A.n_rela_rows, A.w_alpha, A.attn_dim);
   if constexpr (RELA_LDS) {
     for (int i = threadIdx.x; i < A.n_rela_rows * G; i += BLOCK) {
       const int r = i / G, c = i - r * G;
@@ -103,8 +95,6 @@ __global__ __launch_bounds__(FWD_BLOCK, TEMPORAL ? 4 : (G >= 32 ? 4 : 6)) void l
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int lane_g = lane & (G - 1), gi_w = lane / G;
   float4* my_stage = stage + wv * 64 + gi_w * G;
-  const int gshift = lane & ~(G - 1);
-  const unsigned long long gmask = G == 64 ? ~0ull : ((1ull << G) - 1ull);
   const bool row_lane = lane_g < A.ld4;
   const int lane_c = row_lane ? lane_g : A.ld4 - 1;   // loads never branch: idle lanes re-read the last float4
 
@@ -134,8 +124,7 @@ __global__ __launch_bounds__(FWD_BLOCK, TEMPORAL ? 4 : (G >= 32 ? 4 : 6)) void l
         if constexpr (PACKED) { const uint32_t pk = A.in_pk[c]; hd = pk & 0xFFFFF; r = pk >> 20; }
         else { const int2 hr = A.in_hr[c]; hd = hr.x; r = hr.y; }
         const int2 wp = bm_row[hd >> 5];
-        const uint32_t word = (uint32_t)wp.x, bit = hd & 31;
-        valid = (word >> bit) & 1u;
+        valid = rg::bm_has(wp, hd);
         if constexpr (TEMPORAL) {
           if (A.win_lo && valid) {            // the edge's data row must lie inside the query's time window (self-loops always do)
             const int row = A.in_time[c];
@@ -143,7 +132,7 @@ __global__ __launch_bounds__(FWD_BLOCK, TEMPORAL ? 4 : (G >= 32 ? 4 : 6)) void l
           }
         }
         if (valid) {
-          s = wp.y + __popc(word & ((1u << bit) - 1u));
+          s = rg::bm_rank(wp, hd);
           float z = b_alpha;
           // (a 32-wide attention row fully unrolled keeps sixteen loads live: 182 registers, two waves per SIMD; two steps at a time fit
           // 112 and four waves - same order of the sum)
@@ -154,12 +143,9 @@ __global__ __launch_bounds__(FWD_BLOCK, TEMPORAL ? 4 : (G >= 32 ? 4 : 6)) void l
             const float4 w = w_l[k];
             float4 q;
             if constexpr (AP4 <= 2) q = aq[k]; else q = aq_p[k];
-            z = fmaf(w.x, fmaxf(as.x + ar.x + q.x, 0.f), z);
-            z = fmaf(w.y, fmaxf(as.y + ar.y + q.y, 0.f), z);
-            z = fmaf(w.z, fmaxf(as.z + ar.z + q.z, 0.f), z);
-            z = fmaf(w.w, fmaxf(as.w + ar.w + q.w, 0.f), z);
+            rg::attn_acc_fwd(z, w, as, ar, q);
           }
-          alpha = __builtin_amdgcn_rcpf(1.0f + __expf(-z));
+          alpha = rg::attn_alpha(z);
           if constexpr (TEMPORAL) {
             // direction-specific linears hoisted per node / relation / |dt|: row = 3*id + dir, dir = past 0 / now 1 / future 2
             // (Temporal/interpolation/model_cuda.py:149-157)
@@ -177,15 +163,8 @@ __global__ __launch_bounds__(FWD_BLOCK, TEMPORAL ? 4 : (G >= 32 ? 4 : 6)) void l
           }
         }
       }
-      const unsigned long long m = (__ballot(valid) >> gshift) & gmask;
-      const int cnt = __popcll(m);
-      const int pos = __popcll(m & ((1ull << lane_g) - 1ull));
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // previous round's reads are done
-      __builtin_amdgcn_wave_barrier();
-      if (lane_g >= cnt) my_stage[lane_g] = rg::f4zero();      // pad tuples: alpha = 0, row 0
-      if (valid) my_stage[pos] = make_float4(__int_as_float(s), __int_as_float(r), alpha, __int_as_float(trow));
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
+      const int cnt = rg::group_compact<G, false>(my_stage, lane, valid,
+                                                  make_float4(__int_as_float(s), __int_as_float(r), alpha, __int_as_float(trow)));
 
       // ---- phase 2: one edge per group step, 4 row gathers in flight ---------------------------
       for (int k = 0; k < cnt; k += 4) {
@@ -238,9 +217,8 @@ __global__ void combine_kernel(const int4* __restrict__ split, int n_split, int 
   const int b = (int)(item / n_split);
   const int4 se = split[item - (int64_t)b * n_split];
   const int2 wp = bm_new[(int64_t)b * W + (se.x >> 5)];
-  const uint32_t word = (uint32_t)wp.x, bit = se.x & 31;
-  if (!((word >> bit) & 1u)) return;
-  const int o = wp.y + __popc(word & ((1u << bit) - 1u));
+  if (!rg::bm_has(wp, se.x)) return;
+  const int o = rg::bm_rank(wp, se.x);
   const float4* p = partial + ((int64_t)b * n_slots + se.y) * ld4 + c;
   const uint8_t* wr = written ? written + (int64_t)b * n_slots + se.y : nullptr;
   // eight segments per trip: their rows are loaded together (a hub has up to 133 segments; one dependent load per segment made

@@ -22,6 +22,7 @@
 // Items are group-major; XCD x serves the x-th eighth of them from its own in-order queue, a wave at a time (cf. walk.h): the
 // hidden rows of one group's <= 32 sparse frontiers are what an XCD's L2 holds while it sweeps the packs; n_sub splits a word
 // into 2 or 4 groups when they would not fit.
+#include "attn.h"
 #include "layer_fwd_wp.h"
 
 namespace rgwp {
@@ -58,15 +59,7 @@ __global__ __launch_bounds__(WP_BLOCK, 4) void layer_fwd_wp_kernel(WpArgs A) {
   float4* w_l = ar_l + A.n_rela_rows * AP4;                                      // [AP4]
   float4* rela_l = w_l + AP4;                                                    // [n_rela_rows][RW] (optional)
 
-  for (int i = threadIdx.x; i < A.n_rela_rows * AP4; i += WP_BLOCK) ar_l[i] = A.a_r[i];
-  if (threadIdx.x < AP4) {
-    float w[4];
-    for (int k = 0; k < 4; ++k) {
-      const int j = threadIdx.x * 4 + k;
-      w[k] = j < A.attn_dim ? A.w_alpha[j] : 0.f;
-    }
-    w_l[threadIdx.x] = make_float4(w[0], w[1], w[2], w[3]);
-  }
+  rg::stage_attention<AP4, WP_BLOCK>(ar_l, w_l, A.a_r, A.n_rela_rows, A.w_alpha, A.attn_dim);
   if constexpr (RELA_LDS) {
     for (int i = threadIdx.x; i < A.n_rela_rows * RW; i += WP_BLOCK) {
       const int r = i / RW, c = i - r * RW;
@@ -189,10 +182,10 @@ __global__ __launch_bounds__(WP_BLOCK, 4) void layer_fwd_wp_kernel(WpArgs A) {
           s[j] = 0; out[j] = 0;
           if (valid[j]) {
             const int hd = en[j].x & 0xFFFFF, bq = bw * 32 + (en[j].y >> 8);
-            s[j] = wp[j].y + __popc((uint32_t)wp[j].x & ((1u << (hd & 31)) - 1u));
+            s[j] = rg::bm_rank(wp[j], hd);
             if (dst[j].y < 0) {
               const int2 wn = A.bm_new[(int64_t)bq * A.W + (dst[j].x >> 5)];
-              out[j] = wn.y + __popc((uint32_t)wn.x & ((1u << (dst[j].x & 31)) - 1u));
+              out[j] = rg::bm_rank(wn, dst[j].x);
             } else {
               out[j] = -(bq * A.n_slots + dst[j].y) - 1;
             }
@@ -209,13 +202,9 @@ __global__ __launch_bounds__(WP_BLOCK, 4) void layer_fwd_wp_kernel(WpArgs A) {
               const float4 as = A.a_s[(int64_t)s[j] * AP4 + k];
               const float4 ar = ar_l[r * AP4 + k];
               const float4 w = w_l[k];
-              const float4 q = aq_p[k];
-              z = fmaf(w.x, fmaxf(as.x + ar.x + q.x, 0.f), z);
-              z = fmaf(w.y, fmaxf(as.y + ar.y + q.y, 0.f), z);
-              z = fmaf(w.z, fmaxf(as.z + ar.z + q.z, 0.f), z);
-              z = fmaf(w.w, fmaxf(as.w + ar.w + q.w, 0.f), z);
+              rg::attn_acc_fwd(z, w, as, ar, aq_p[k]);
             }
-            const float alpha = __builtin_amdgcn_rcpf(1.0f + __expf(-z));
+            const float alpha = rg::attn_alpha(z);
             const uint32_t hoff = (uint32_t)s[j] * row_bytes;                 // < 2^32: checked by the launcher
             const uint32_t roff = (uint32_t)r * (RELA_LDS ? (uint32_t)(RW * 16) : row_bytes);
             st[j * 64 + lane] = make_float4(__int_as_float((int)hoff), __int_as_float((int)roff), alpha, __int_as_float(out[j]));

@@ -8,7 +8,7 @@
 // enumerated here: from the heads through the CSR by head.  Unlike the walk by tail (explain.hip, which has to start from marked
 // tails) no candidate edge is read in vain - on a first hop the tails' in-edges outnumber the hop's edges by two orders of magnitude
 // - no bitmap word is looked up per edge, and the a_s row is one per head, shared by the lanes on its out-edges.  alpha is the forward
-// kernel's arithmetic (layer_fwd_kernel.h; the expression of explain.hip), so it is the forward's alpha bit for bit; sums of
+// kernel's arithmetic (the same attn.h calls in the forward's operand order), so it is the forward's alpha bit for bit; sums of
 // integers do not depend on the order of enumeration.
 //
 // Work mapping: blockIdx.y = query, so a workgroup's bins belong to one query.  A wave takes `gw` consecutive words of the
@@ -26,7 +26,7 @@
 // edge into the global buffers with the same integer atomics and reads a_r from memory: slower, same result.
 #include <algorithm>
 
-#include "common.h"
+#include "attn.h"
 
 namespace {
 
@@ -81,10 +81,7 @@ __global__ __launch_bounds__(PF_BLOCK) void profile_kernel(PfArgs A) {
   float4 w[AP4], q[AP4];
 #pragma unroll
   for (int k = 0; k < AP4; ++k) {
-    w[k].x = 4 * k + 0 < A.attn_dim ? A.w_alpha[4 * k + 0] : 0.f;
-    w[k].y = 4 * k + 1 < A.attn_dim ? A.w_alpha[4 * k + 1] : 0.f;
-    w[k].z = 4 * k + 2 < A.attn_dim ? A.w_alpha[4 * k + 2] : 0.f;
-    w[k].w = 4 * k + 3 < A.attn_dim ? A.w_alpha[4 * k + 3] : 0.f;
+    w[k] = rg::attn_w4(A.w_alpha, A.attn_dim, k);
     q[k] = A.a_q[(int64_t)b * AP4 + k];
   }
   const int2* bm_old = A.bm_old + (int64_t)b * A.W;
@@ -134,19 +131,15 @@ __global__ __launch_bounds__(PF_BLOCK) void profile_kernel(PfArgs A) {
           const int r = A.out_rt[beg_s + (x - excl_s)].x;
           const int s = s_base + k0 + sl;
           if ((uint32_t)r < (uint32_t)A.R && s < A.n_old) {
-            // layer_fwd_kernel.h's sum, term for term
             float z = b_alpha;
 #pragma unroll
             for (int k = 0; k < AP4; ++k) {
               const float4 as = A.a_s[(int64_t)s * AP4 + k];
               float4 ar;
               if constexpr (LDS) ar = ar_l[r * AP4 + k]; else ar = A.a_r[(int64_t)r * AP4 + k];
-              z = fmaf(w[k].x, fmaxf(as.x + ar.x + q[k].x, 0.f), z);
-              z = fmaf(w[k].y, fmaxf(as.y + ar.y + q[k].y, 0.f), z);
-              z = fmaf(w[k].z, fmaxf(as.z + ar.z + q[k].z, 0.f), z);
-              z = fmaf(w[k].w, fmaxf(as.w + ar.w + q[k].w, 0.f), z);
+              rg::attn_acc_fwd(z, w[k], as, ar, q[k]);
             }
-            const float alpha = __builtin_amdgcn_rcpf(1.0f + __expf(-z));
+            const float alpha = rg::attn_alpha(z);
             const unsigned long long fx = (unsigned long long)llrintf(alpha * PF_SCALE);
             // results unused: non-returning integer adds, order-free
             if constexpr (LDS) {

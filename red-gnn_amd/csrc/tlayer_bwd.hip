@@ -1,203 +1,14 @@
-// Temporal entry points of the fused layer backward (the source-pull kernel: layer_bwd_kernel.h): rg_tlayer_bwd, the adjoint
-// of rg_tlayer_fwd (T-RED-GNN interpolation), and rg_xlayer_bwd, the adjoint of rg_xlayer_fwd (extrapolation: per-query row
-// windows, one direction; hidden_dir / rela_dir / time_dir are then hidden_p [N_old] / rela_p / time_p [n_time]).
-//   d hidden_dir[3 s + dir] += alpha G[o]      (layer_bwd_kernel: three register accumulators per source, one store per row)
-//   d rela_dir / d time_dir rows += alpha G[o] (separate key-major passes, tkey_kernel: items are 128-edge segments of one
-//                                               relation / one time id, so a whole segment lands in at most three rows / one row
-//                                               and is added once; per-edge float atomics on a 2.5 k-row table cost 20x the forward)
+// Temporal entry points of the fused layer backward: rg_tlayer_bwd, the adjoint of rg_tlayer_fwd (T-RED-GNN interpolation), and
+// rg_xlayer_bwd, the adjoint of rg_xlayer_fwd (extrapolation: per-query row windows, one direction; hidden_dir / rela_dir / time_dir
+// are then hidden_p [N_old] / rela_p / time_p [n_time]).
+//   d hidden_dir[3 s + dir] += alpha G[o]      (layer_bwd_kernel.h: three register accumulators per source, one store per row)
+//   d rela_dir / d time_dir rows += alpha G[o] (key_bwd_kernel.h, TEMPORAL / WINDOWED: one pass keyed by relation, one by time id)
 // The direction linears and the attention's three blocks are differentiated by the caller (dense GEMMs).
 #include "aq_sum.h"
-#include "layer_bwd_kernel.h"
+#include "key_bwd_kernel.h"
 
 namespace rgbwd {
 namespace {
-
-// ---- table gradients, key-major -------------------------------------------------------------------------------------------
-// BY_TIME = false: items = (query, segment of relation r's edge list); an edge's direction follows from its time id, so the
-//                  segment's alpha*G sums go to up to three rows  dir * n_rela_rows + r  of g_rela_dir.
-// BY_TIME = true : items = (query, segment of time id tau's edge list); dt = tau - q_time[b] is the same for the whole segment,
-//                  which therefore lands in the single row  dir * n_time + |dt|  of g_time_dir.
-struct TKeyArgs {
-  rg::WalkArgs walk;          // vrows = CSR-by-relation / CSR-by-time segments; always live
-  const int2* ht;             // {head, tail} per entry
-  const int32_t* aux;         // BY_TIME ? relation : time id, per entry
-  const int32_t* q_time;
-  const int2* bm_old;
-  const int2* bm_new;
-  int W;
-  const float4* a_s;
-  const float4* a_r;
-  const float4* a_q;
-  const float* w_alpha;
-  const float* b_alpha;
-  int attn_dim, n_rela_rows, n_time, ld4;
-  const float4* grad_agg;
-  float* g_table;             // g_rela_dir or g_time_dir
-  // WIN
-  const int32_t* win_lo = nullptr;
-  const int32_t* win_hi = nullptr;
-  const int32_t* row_time = nullptr;
-  const int32_t* loop_time = nullptr;
-  int n_data = 0;
-};
-
-template <int G, int AP4, bool BY_TIME, bool WIN>
-__global__ __launch_bounds__(BWD_BLOCK, 4) void tkey_kernel(TKeyArgs A) {
-  extern __shared__ float4 lds[];
-  constexpr int BLOCK = BWD_BLOCK;
-  const int nr = A.n_rela_rows;
-  float4* stage = lds;                // [BLOCK] {o, alpha, dir}
-  float4* ar_l = stage + BLOCK;       // [nr][AP4]
-  float4* w_l = ar_l + nr * AP4;      // [AP4]
-  for (int i = threadIdx.x; i < nr * AP4; i += BLOCK) ar_l[i] = A.a_r[i];
-  if (threadIdx.x < AP4) {
-    float w[4];
-    for (int k = 0; k < 4; ++k) {
-      const int j = threadIdx.x * 4 + k;
-      w[k] = j < A.attn_dim ? A.w_alpha[j] : 0.f;
-    }
-    w_l[threadIdx.x] = make_float4(w[0], w[1], w[2], w[3]);
-  }
-  __syncthreads();
-  const float b_alpha = A.b_alpha[0];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int lane_g = lane & (G - 1), gi_w = lane / G;
-  float4* my_stage = stage + wv * 64 + gi_w * G;
-  const int gshift = lane & ~(G - 1);
-  const unsigned long long gmask = G == 64 ? ~0ull : ((1ull << G) - 1ull);
-  const bool row_lane = lane_g < A.ld4;
-  const int lane_c = row_lane ? lane_g : A.ld4 - 1;
-
-  rg::walk_items<G, true, 1, BLOCK, true>(A.walk, nullptr, [&](const int4& R, bool live) {
-    const int beg = R.x, b = R.z, key = R.w;
-    int end = R.x + rg::walk_len(R);
-    int wlo = 0, whi = 0;
-    if constexpr (WIN) {
-      wlo = A.win_lo[b]; whi = A.win_hi[b];
-      if (BY_TIME && key < A.n_data && (key < wlo || key >= whi)) end = beg;      // the whole row lies outside the query's window
-    }
-    const int2* old_row = A.bm_old + (int64_t)b * A.W;
-    const int2* new_row = A.bm_new + (int64_t)b * A.W;
-    const int qt = A.q_time[b];
-    float4 aq[AP4];
-#pragma unroll
-    for (int k = 0; k < AP4; ++k) aq[k] = A.a_q[(int64_t)b * AP4 + k];
-    float4 acc[BY_TIME ? 1 : 3];
-#pragma unroll
-    for (int dd = 0; dd < (BY_TIME ? 1 : 3); ++dd) acc[dd] = rg::f4zero();
-    unsigned seen = 0u;      // directions with at least one edge (BY_TIME: bit 0)
-    for (int c0 = beg; c0 < end; c0 += G) {
-      const int c = c0 + lane_g;
-      bool valid = c < end;
-      int o = 0, dir = 0;
-      float alpha = 0.f;
-      if (valid) {
-        const int2 ht = A.ht[c];
-        const int2 wp = old_row[ht.x >> 5];
-        const uint32_t word = (uint32_t)wp.x, bit = ht.x & 31;
-        valid = (word >> bit) & 1u;
-        if constexpr (WIN && !BY_TIME) {
-          if (valid) { const int erow = A.aux[c]; valid = erow >= A.n_data || (erow >= wlo && erow < whi); }
-        }
-        if (valid) {
-          const int s = wp.y + __popc(word & ((1u << bit) - 1u));
-          const int2 wn = new_row[ht.y >> 5];
-          o = wn.y + __popc((uint32_t)wn.x & ((1u << (ht.y & 31)) - 1u));
-          const int other = A.aux[c];
-          const int r = BY_TIME ? other : key;
-          if constexpr (!BY_TIME && !WIN) { const int dt = other - qt; dir = dt > 0 ? 2 : (dt == 0 ? 1 : 0); }
-          float z = b_alpha;
-#pragma unroll
-          for (int k = 0; k < AP4; ++k) {
-            const float4 as = A.a_s[(int64_t)s * AP4 + k];
-            const float4 ar = ar_l[r * AP4 + k];
-            const float4 w = w_l[k];
-            z = fmaf(w.x, fmaxf(as.x + ar.x + aq[k].x, 0.f), z);
-            z = fmaf(w.y, fmaxf(as.y + ar.y + aq[k].y, 0.f), z);
-            z = fmaf(w.z, fmaxf(as.z + ar.z + aq[k].z, 0.f), z);
-            z = fmaf(w.w, fmaxf(as.w + ar.w + aq[k].w, 0.f), z);
-          }
-          alpha = __builtin_amdgcn_rcpf(1.0f + __expf(-z));
-        }
-      }
-      const unsigned long long m = (__ballot(valid) >> gshift) & gmask;
-      const int cnt = __popcll(m);
-      const int pos = __popcll(m & ((1ull << lane_g) - 1ull));
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      __builtin_amdgcn_wave_barrier();
-      if (lane_g >= cnt) my_stage[lane_g] = rg::f4zero();
-      if (valid) my_stage[pos] = make_float4(__int_as_float(o), alpha, __int_as_float(dir), 0.f);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      __builtin_amdgcn_wave_barrier();
-      for (int k = 0; k < cnt; k += 4) {
-        float4 tp[4], gv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) tp[u] = my_stage[k + u];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) gv[u] = A.grad_agg[(int64_t)__float_as_int(tp[u].x) * A.ld4 + lane_c];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const float al = tp[u].y;
-          if constexpr (BY_TIME) {
-            acc[0].x = fmaf(al, gv[u].x, acc[0].x); acc[0].y = fmaf(al, gv[u].y, acc[0].y);
-            acc[0].z = fmaf(al, gv[u].z, acc[0].z); acc[0].w = fmaf(al, gv[u].w, acc[0].w);
-            if (k + u < cnt) seen |= 1u;
-          } else {
-            const int du = __float_as_int(tp[u].z);
-#pragma unroll
-            for (int dd = 0; dd < 3; ++dd) {
-              const float mk = du == dd ? al : 0.f;
-              acc[dd].x = fmaf(mk, gv[u].x, acc[dd].x); acc[dd].y = fmaf(mk, gv[u].y, acc[dd].y);
-              acc[dd].z = fmaf(mk, gv[u].z, acc[dd].z); acc[dd].w = fmaf(mk, gv[u].w, acc[dd].w);
-            }
-            if (k + u < cnt) seen |= 1u << du;
-          }
-        }
-      }
-    }
-    if (live && row_lane) {
-      if constexpr (BY_TIME) {
-        if (seen) {
-          int trow;
-          if constexpr (WIN) {
-            trow = min(max(qt - (key >= A.n_data ? A.loop_time[b] : A.row_time[key]), 0), A.n_time - 1);
-          } else {
-            const int dt = key - qt;
-            const int dir = dt > 0 ? 2 : (dt == 0 ? 1 : 0);
-            trow = dir * A.n_time + (dt < 0 ? -dt : dt);
-          }
-          float* gr = A.g_table + ((int64_t)trow * A.ld4 + lane_g) * 4;
-          atomicAdd(gr + 0, acc[0].x); atomicAdd(gr + 1, acc[0].y); atomicAdd(gr + 2, acc[0].z); atomicAdd(gr + 3, acc[0].w);
-        }
-      } else {
-#pragma unroll
-        for (int dd = 0; dd < (WIN ? 1 : 3); ++dd)
-          if (seen & (1u << dd)) {
-            float* gr = A.g_table + ((int64_t)(dd * nr + key) * A.ld4 + lane_g) * 4;
-            atomicAdd(gr + 0, acc[dd].x); atomicAdd(gr + 1, acc[dd].y); atomicAdd(gr + 2, acc[dd].z); atomicAdd(gr + 3, acc[dd].w);
-          }
-      }
-    }
-  });
-}
-
-template <bool BY_TIME>
-int launch_tkey(const char* who, const TKeyArgs& A, int ap4, hipStream_t s) {
-  return rg::with_g(A.ld4, [&](auto g) {
-    return rg::with_ap4(ap4, who, [&](auto ap) {
-      constexpr int G = decltype(g)::value, AP4 = decltype(ap)::value;
-      const size_t lds = (size_t)(BWD_BLOCK + A.n_rela_rows * AP4 + AP4) * sizeof(float4);
-      RG_CHECK(lds <= 160 * 1024, "%s: attention table needs %zu B of LDS (> 160 KiB)", who, lds);
-      auto kern = A.win_lo ? tkey_kernel<G, AP4, BY_TIME, true> : tkey_kernel<G, AP4, BY_TIME, false>;
-      if (lds > 64 * 1024) RG_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      const int grid = rg::walk_grid(A.walk.n_items, BWD_BLOCK, G, true, lds <= 80 * 1024 ? 2 : 1, 1);
-      if (rg::zero_async(A.walk.queues, RG_QUEUE_BYTES, s)) return 1;
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(BWD_BLOCK), lds, s, A);
-      RG_LAUNCH_CHECK();
-      return 0;
-    });
-  });
-}
 
 struct WinArgs {            // the extrapolation setting's extras; all null / 0 for the interpolation layer
   const int32_t* loop_time = nullptr;
@@ -239,22 +50,12 @@ int tbwd_impl(const char* who, const rg_frontier* f, const rg_graph* g, int32_t 
   if (windowed ? launch<WINDOWED>(who, A, ap / 4, f->B, g->out_vr, bm_old, dense, s)
                : launch<TEMPORAL>(who, A, ap / 4, f->B, g->out_vr, bm_old, dense, s)) return 1;
   if (grad_a_q && rg::launch_aq_sum(bm_old, f->W, f->B, f->n_ent, n_old, grad_a_s, ap, grad_a_q, s)) return 1;
-  // table gradients, key-major (see tkey_kernel)
-  TKeyArgs K;
-  K.q_time = q_time; K.bm_old = bm_old; K.bm_new = f->bm_of(level); K.W = f->W;
-  K.a_s = (const float4*)a_s; K.a_r = (const float4*)a_r; K.a_q = (const float4*)a_q;
-  K.w_alpha = w_alpha; K.b_alpha = b_alpha; K.attn_dim = attn_dim; K.n_rela_rows = g->n_rela_rows; K.n_time = n_time; K.ld4 = ld / 4;
-  K.grad_agg = (const float4*)grad_agg;
-  if (windowed) { K.win_lo = f->win_lo; K.win_hi = f->win_hi; K.row_time = win.row_time; K.loop_time = win.loop_time; K.n_data = win.n_data; }
-  K.walk.n_slots = 0; K.walk.bm_test = nullptr; K.walk.W = f->W; K.walk.queues = f->queues; f->queues_clean = false;
-  K.walk.n_items = (int64_t)f->B * g->rel_vr.n; K.walk.n_vrows = g->rel_vr.n; K.walk.vrows = g->rel_vr.rows;
-  RG_CHECK(K.walk.n_items / 8 + ((int64_t)1 << 26) < ((int64_t)1 << 31), "%s: relation work space too large for 32-bit queue tickets", who);
-  K.ht = g->rel_ht; K.aux = g->rel_tm; K.g_table = grad_rela_dir;
-  if (launch_tkey<false>(who, K, ap / 4, s)) return 1;
-  K.walk.n_items = (int64_t)f->B * g->time_vr.n; K.walk.n_vrows = g->time_vr.n; K.walk.vrows = g->time_vr.rows;
-  RG_CHECK(K.walk.n_items / 8 + ((int64_t)1 << 26) < ((int64_t)1 << 31), "%s: time work space too large for 32-bit queue tickets", who);
-  K.ht = g->time_ht; K.aux = g->time_rel; K.g_table = grad_time_dir;
-  return launch_tkey<true>(who, K, ap / 4, s);
+  // table gradients, key-major: the relation table's over the CSR by relation, then the time table's over the CSR by time id
+  KeyArgs K;
+  if (fill_key(who, "relation", f, g->rel_vr, g->rel_ht, g->rel_tm, bm_old, A, grad_rela_dir, &K)) return 1;
+  if (windowed ? launch_key<WINDOWED, false>(who, K, ap / 4, s) : launch_key<TEMPORAL, false>(who, K, ap / 4, s)) return 1;
+  if (fill_key(who, "time", f, g->time_vr, g->time_ht, g->time_rel, bm_old, A, grad_time_dir, &K)) return 1;
+  return windowed ? launch_key<WINDOWED, true>(who, K, ap / 4, s) : launch_key<TEMPORAL, true>(who, K, ap / 4, s);
 }
 
 }  // namespace

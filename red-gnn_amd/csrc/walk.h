@@ -12,7 +12,7 @@
 // so the per-query rows they gather from stay in that XCD's 4 MiB L2.  Queues only steer speed: a workgroup
 // that finds its queue dry steals from the others; every item is processed exactly once under any placement.
 #pragma once
-#include "common.h"
+#include "attn.h"
 
 namespace rg {
 
@@ -52,10 +52,8 @@ __device__ __forceinline__ void walk_items(const WalkArgs& A, int4* recs, F&& ru
     const int4 row = A.vrows[vr];
     if constexpr (ALWAYS) { rec = make_int4(row.y, row.z, b, row.x); return true; }
     const int2 wp = A.bm_test[(int64_t)b * A.W + (row.x >> 5)];
-    const uint32_t word = (uint32_t)wp.x, bit = row.x & 31;
-    if (!((word >> bit) & 1u)) return false;
-    const int o = wp.y + __popc(word & ((1u << bit) - 1u));
-    rec = make_int4(row.y, row.z | ((row.w + 1) << 8), b, o);
+    if (!bm_has(wp, row.x)) return false;
+    rec = make_int4(row.y, row.z | ((row.w + 1) << 8), b, bm_rank(wp, row.x));
     return true;
   };
 

@@ -19,7 +19,7 @@ FORCE_WALK = 0
 # (start_event, end_event, n_rows) per rg_dense_fwd launch
 KERNEL_EVENTS = None
 DENSE_EVENTS = None
-# ... and (start_event, end_event, n_edges, n_old) per rg_layer_bwd call (its kernels: layer_bwd_kernel, bwd_combine_kernel, drel_kernel)
+# ... and (start_event, end_event, n_edges, n_old) per rg_layer_bwd call (its kernels: layer_bwd_kernel, bwd_combine_kernel, key_bwd_kernel)
 BWD_EVENTS = None
 # tools/probe_explain.py sets this to a list to collect (start_event, end_event, level, n_edges) per hop of explain_hop
 EXPLAIN_EVENTS = None

@@ -14,7 +14,7 @@ for r in rows:
     if name.startswith("Cijk_"):
         tensile += ms
         continue
-    if any(k in name for k in ("layer_bwd", "drel", "bwd_combine", "dense_bwd", "dense_kernel", "gram_", "layer_fwd", "combine_kernel", "aq_sum")):
+    if any(k in name for k in ("layer_bwd", "key_bwd", "drel", "bwd_combine", "dense_bwd", "dense_kernel", "gram_", "layer_fwd", "combine_kernel", "aq_sum")):
         short = name.split("<")[0]
         e = out.setdefault(short, dict(ms_per_step=0.0, launches_per_step=0.0))
         e["ms_per_step"] += ms
