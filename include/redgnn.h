@@ -70,6 +70,10 @@ int64_t rg_graph_n_fact(const rg_graph* g);      /* rows incl. inverse + identit
 /* copy the device CSR back (tests): ptr arrays have n_ent+1 entries, pair arrays 2*n_fact. */
 int rg_graph_export(const rg_graph* g, int32_t* out_ptr_host, int32_t* out_rel_tail_host,
                     int32_t* in_ptr_host, int32_t* in_head_rel_host);
+/* copy the time ids of a temporal graph's CSR entries back (tests): out_time_host int32 [n_fact] beside out_rel_tail, in_time_host
+ * int32 [n_fact] beside in_head_rel (either may be NULL).  With them a test can name the CSR position of an edge whose (head, rel,
+ * tail) repeats at several times.  An error on static graphs. */
+int rg_graph_export_time(const rg_graph* g, int32_t* out_time_host, int32_t* in_time_host);
 
 /* ---- frontier expansion: replaces DataLoader.get_neighbors, load_data.py:106-131 ------------
  * A frontier keeps `n_levels` visited-set snapshots: level 0 = the query nodes, level k = after
@@ -388,6 +392,23 @@ int rg_explain_emit(const rg_frontier* f, const rg_graph* g, int32_t batch, int3
 int rg_explain_gather(int64_t n, int32_t hop, int32_t batch, const int32_t* edges, const float* alpha, const int64_t* row_first,
                       const int64_t* row_base, int64_t n_out, int32_t* edges_out, float* alpha_out, void* stream);
 
+/* ---- the same for a temporal graph (T-RED-GNN interpolation; the reference draws this digraph in
+ * Temporal/interpolation/model_cuda_rule_vis.py): one hop of the r-digraph over a quadruple graph (rg_tgraph_create).  Arguments,
+ * marking walk, scratch, output order and determinism are rg_explain_count / rg_explain_emit's; a_r has n_rela_rows rows and alpha is
+ * rg_tlayer_fwd's (which does not read the edge's time; pass b_alpha = 0).  rg_texplain_emit also writes time_out int32 [E_l]: the time
+ * id of every kept edge (the CSR-by-tail entry's), so that a fact repeated at several times gives one edge per time, in CSR order.
+ * The graph must be temporal (n_time > 0) and the frontier must have no window set (rg_frontier_set_window: extrapolation is not
+ * supported); a static graph, like a temporal one handed to the static entry points, is an argument error.  rg_explain_seed,
+ * rg_explain_gather and rg_explain_scratch_bytes serve both settings. */
+int rg_texplain_count(const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level, const uint32_t* marks,
+                      const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha,
+                      int32_t attn_dim, float min_alpha, uint32_t* marks_prev_out, int32_t* word_ptr_out, void* scratch,
+                      size_t scratch_bytes, int64_t* n_edges_host, void* stream);
+int rg_texplain_emit(const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level, const uint32_t* marks,
+                     const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha,
+                     int32_t attn_dim, float min_alpha, const int32_t* word_ptr, int32_t* edges_out, float* alpha_out,
+                     int32_t* time_out, void* stream);
+
 /* ---- attention profile of a hop: which edge relations a query listens to (the reference's attention_vis table,
  * Temporal/interpolation/model_cuda.py:117-119,163-166: per relation the sum of alpha and the number of edges, there a python loop with
  * two .item() read-backs per relation and layer).  Over the hop-`level` edges e = (b, h, rel, t) the forward aggregates (t in level
@@ -407,6 +428,19 @@ int rg_explain_gather(int64_t n, int32_t hop, int32_t batch, const int32_t* edge
 int rg_attn_profile(const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level, int64_t n_old,
                     const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha,
                     int32_t attn_dim, int64_t* sum_out, int64_t* count_out, void* stream);
+
+/* The attention profile of a hop of a temporal graph (T-RED-GNN interpolation), with the edge's direction as one more axis.  Edges,
+ * enumeration, alpha (rg_tlayer_fwd's, which does not read the time; pass b_alpha = 0), fixed-point sums and limits are
+ * rg_attn_profile's; per edge the kernel also reads the CSR-by-head entry's time id and bins by the forward's direction:
+ * dt = edge time - q_time[b] (q_time device int32 [batch]), dir = 0 past (dt < 0), 1 now (dt == 0), 2 future (dt > 0):
+ *   count_out[b][dir][rel] += 1,   sum_out[b][dir][rel] += llrintf(alpha_e * 2^32)
+ * sum_out / count_out: device int64 [batch][3][n_rela_rows], caller-owned and caller-zeroed; a_r has n_rela_rows rows.  Summed over
+ * dir this is the static table.  The bins live in LDS per workgroup where n_rela_rows * (4 * ap + 36) bytes fit 48 KB (722 relation
+ * rows at ap = 8); above that the kernel adds per edge into the outputs directly (same integers, slower).  The graph must be temporal
+ * and the frontier must have no window set (extrapolation is not supported). */
+int rg_tattn_profile(const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level, int64_t n_old,
+                     const int32_t* q_time, const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha,
+                     const float* b_alpha, int32_t attn_dim, int64_t* sum_out, int64_t* count_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -14,6 +14,10 @@
 // alpha is the forward kernel's arithmetic - the same attn.h calls in the forward's operand order, so the forward's alpha bit for
 // bit - re-evaluated on the marked tails' in-edges only: nothing E_subgraph-sized is read or held.  A last gather puts the hops'
 // lists into (row, hop, ...) order.
+//
+// Temporal graphs (rg_texplain_*, T-RED-GNN interpolation): the same walk over a quadruple graph.  The temporal attention does not
+// read the edge's time, so the count pass IS the static instantiation; the emit pass is the kernel's TIME instantiation, which also
+// writes the entry's time id (in_time[c]) beside the edge, so that a fact repeated at several times stays told apart.
 #include "attn.h"
 
 namespace {
@@ -53,8 +57,13 @@ __global__ void seed_kernel(const int2* __restrict__ bm_last, int B, int W, int 
   reached[b] = ok ? 1 : 0;
 }
 
-template <bool EMIT>
-__global__ __launch_bounds__(EX_BLOCK) void explain_kernel(ExArgs A) {
+struct TExArgs : ExArgs {
+  const int32_t* in_time;    // time id of every CSR-by-tail entry
+  int32_t* time_out;         // emit: in_time[c] of every kept edge
+};
+
+template <bool EMIT, bool TIME = false>
+__global__ __launch_bounds__(EX_BLOCK) void explain_kernel(std::conditional_t<TIME, TExArgs, ExArgs> A) {
   const int lane = threadIdx.x & 63;
   const int64_t w0 = ((int64_t)blockIdx.x * (EX_BLOCK / 64) + (threadIdx.x >> 6)) * 64;
   if (w0 >= A.n_words) return;                       // (uniform over the wave)
@@ -107,6 +116,7 @@ __global__ __launch_bounds__(EX_BLOCK) void explain_kernel(ExArgs A) {
             if (idx < lim) {
               A.edges[idx] = make_int4(b, hd, r, t);
               A.alpha[idx] = alpha;
+              if constexpr (TIME) A.time_out[idx] = A.in_time[c];
             }
           } else {
             atomicOr(&A.marks_prev[(int64_t)b * A.W + (hd >> 5)], 1u << (hd & 31));   // result unused: non-returning
@@ -137,14 +147,19 @@ __global__ void gather_kernel(int64_t n, int hop, const int4* __restrict__ edges
 }
 
 // checks shared by the per-hop entry points
-int check_hop(const char* who, const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level) {
+int check_hop(const char* who, bool temporal, const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level) {
   RG_CHECK(level >= 1 && level < RG_MAX_LEVELS, "%s: level %d not in 1..%d", who, level, RG_MAX_LEVELS - 1);
   RG_CHECK(batch > 0 && n_ent > 0, "%s: batch=%d n_ent=%d must be positive", who, batch, n_ent);
   RG_CHECK(f != nullptr && g != nullptr, "%s: NULL frontier or graph", who);
   RG_CHECK(batch == f->B && n_ent == f->n_ent, "%s: batch=%d n_ent=%d but the frontier has batch %d, n_ent %d", who, batch, n_ent,
            f->B, f->n_ent);
   RG_CHECK(g->n_ent == f->n_ent, "%s: graph has %d entities, frontier %d", who, g->n_ent, f->n_ent);
-  RG_CHECK(g->n_time == 0, "%s: static graphs only (rg_graph_create)", who);
+  if (temporal) {
+    RG_CHECK(g->n_time > 0 && g->in_time, "%s: temporal graphs only (rg_tgraph_create)", who);
+    RG_CHECK(f->win_lo == nullptr, "%s: the frontier has a window set (extrapolation is not supported)", who);
+  } else {
+    RG_CHECK(g->n_time == 0, "%s: static graphs only (rg_graph_create)", who);
+  }
   RG_CHECK(level <= f->level && level > f->level - f->n_levels + 1, "%s: level %d not resident (current %d, %d kept)", who, level,
            f->level, f->n_levels);
   return 0;
@@ -166,6 +181,48 @@ int fill_args(const char* who, const rg_frontier* f, const rg_graph* g, int32_t 
 }
 
 size_t count_bytes(const rg_frontier* f) { return rg::align_up((size_t)f->B * f->W * 4, 256); }
+
+int count_hop(const char* who, bool temporal, const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level,
+              const uint32_t* marks, const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha,
+              const float* b_alpha, int32_t attn_dim, float min_alpha, uint32_t* marks_prev_out, int32_t* word_ptr_out, void* scratch,
+              size_t scratch_bytes, int64_t* n_edges_host, void* stream) {
+  if (check_hop(who, temporal, f, g, batch, n_ent, level)) return 1;
+  ExArgs A;
+  if (fill_args(who, f, g, level, marks, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim, min_alpha, &A)) return 1;
+  RG_CHECK(marks_prev_out && word_ptr_out && n_edges_host, "%s: NULL argument", who);
+  RG_CHECK(scratch && scratch_bytes >= rg_explain_scratch_bytes(f) && ((uintptr_t)scratch & 255) == 0,      // (declared in redgnn.h)
+           "%s: scratch %zu B < required %zu B (or not 256-B aligned)", who, scratch_bytes, rg_explain_scratch_bytes(f));
+  hipStream_t s = (hipStream_t)stream;
+  A.marks_prev = marks_prev_out;
+  A.word_count = (int32_t*)scratch;
+  if (rg::zero_async(marks_prev_out, (size_t)A.n_words * 4, s)) return 1;
+  hipLaunchKernelGGL(explain_kernel<false>, dim3(rg::ceil_div(A.n_words, EX_BLOCK)), dim3(EX_BLOCK), 0, s, A);
+  RG_LAUNCH_CHECK();
+  int32_t* scan_scr = (int32_t*)((char*)scratch + count_bytes(f));
+  if (rg::scan_exclusive((const uint32_t*)A.word_count, word_ptr_out, A.n_words, false, word_ptr_out + A.n_words, scan_scr, s)) return 1;
+  int32_t total = 0;
+  RG_HIP(hipMemcpyAsync(&total, word_ptr_out + A.n_words, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  RG_HIP(hipStreamSynchronize(s));
+  *n_edges_host = total;
+  return 0;
+}
+
+template <bool TIME>
+int emit_hop(const char* who, const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level, const uint32_t* marks,
+             const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha,
+             int32_t attn_dim, float min_alpha, const int32_t* word_ptr, int32_t* edges_out, float* alpha_out, int32_t* time_out,
+             void* stream) {
+  if (check_hop(who, TIME, f, g, batch, n_ent, level)) return 1;
+  std::conditional_t<TIME, TExArgs, ExArgs> A;
+  if (fill_args(who, f, g, level, marks, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim, min_alpha, &A)) return 1;
+  RG_CHECK(word_ptr && edges_out && alpha_out && (!TIME || time_out), "%s: NULL argument", who);
+  RG_CHECK(((uintptr_t)edges_out & 15) == 0, "%s: edges_out must be 16-B aligned", who);
+  A.word_ptr = word_ptr; A.edges = (int4*)edges_out; A.alpha = alpha_out;
+  if constexpr (TIME) { A.in_time = g->in_time; A.time_out = time_out; }
+  hipLaunchKernelGGL((explain_kernel<true, TIME>), dim3(rg::ceil_div(A.n_words, EX_BLOCK)), dim3(EX_BLOCK), 0, (hipStream_t)stream, A);
+  RG_LAUNCH_CHECK();
+  return 0;
+}
 
 }  // namespace
 
@@ -198,39 +255,31 @@ int rg_explain_count(const rg_frontier* f, const rg_graph* g, int32_t batch, int
                      const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha,
                      int32_t attn_dim, float min_alpha, uint32_t* marks_prev_out, int32_t* word_ptr_out, void* scratch,
                      size_t scratch_bytes, int64_t* n_edges_host, void* stream) {
-  if (check_hop("rg_explain_count", f, g, batch, n_ent, level)) return 1;
-  ExArgs A;
-  if (fill_args("rg_explain_count", f, g, level, marks, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim, min_alpha, &A)) return 1;
-  RG_CHECK(marks_prev_out && word_ptr_out && n_edges_host, "rg_explain_count: NULL argument");
-  RG_CHECK(scratch && scratch_bytes >= rg_explain_scratch_bytes(f) && ((uintptr_t)scratch & 255) == 0,
-           "rg_explain_count: scratch %zu B < required %zu B (or not 256-B aligned)", scratch_bytes, rg_explain_scratch_bytes(f));
-  hipStream_t s = (hipStream_t)stream;
-  A.marks_prev = marks_prev_out;
-  A.word_count = (int32_t*)scratch;
-  if (rg::zero_async(marks_prev_out, (size_t)A.n_words * 4, s)) return 1;
-  hipLaunchKernelGGL(explain_kernel<false>, dim3(rg::ceil_div(A.n_words, EX_BLOCK)), dim3(EX_BLOCK), 0, s, A);
-  RG_LAUNCH_CHECK();
-  int32_t* scan_scr = (int32_t*)((char*)scratch + count_bytes(f));
-  if (rg::scan_exclusive((const uint32_t*)A.word_count, word_ptr_out, A.n_words, false, word_ptr_out + A.n_words, scan_scr, s)) return 1;
-  int32_t total = 0;
-  RG_HIP(hipMemcpyAsync(&total, word_ptr_out + A.n_words, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  RG_HIP(hipStreamSynchronize(s));
-  *n_edges_host = total;
-  return 0;
+  return count_hop("rg_explain_count", false, f, g, batch, n_ent, level, marks, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim, min_alpha,
+                   marks_prev_out, word_ptr_out, scratch, scratch_bytes, n_edges_host, stream);
+}
+
+int rg_texplain_count(const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level, const uint32_t* marks,
+                      const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha,
+                      int32_t attn_dim, float min_alpha, uint32_t* marks_prev_out, int32_t* word_ptr_out, void* scratch,
+                      size_t scratch_bytes, int64_t* n_edges_host, void* stream) {
+  return count_hop("rg_texplain_count", true, f, g, batch, n_ent, level, marks, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim, min_alpha,
+                   marks_prev_out, word_ptr_out, scratch, scratch_bytes, n_edges_host, stream);
 }
 
 int rg_explain_emit(const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level, const uint32_t* marks,
                     const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha,
                     int32_t attn_dim, float min_alpha, const int32_t* word_ptr, int32_t* edges_out, float* alpha_out, void* stream) {
-  if (check_hop("rg_explain_emit", f, g, batch, n_ent, level)) return 1;
-  ExArgs A;
-  if (fill_args("rg_explain_emit", f, g, level, marks, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim, min_alpha, &A)) return 1;
-  RG_CHECK(word_ptr && edges_out && alpha_out, "rg_explain_emit: NULL argument");
-  RG_CHECK(((uintptr_t)edges_out & 15) == 0, "rg_explain_emit: edges_out must be 16-B aligned");
-  A.word_ptr = word_ptr; A.edges = (int4*)edges_out; A.alpha = alpha_out;
-  hipLaunchKernelGGL(explain_kernel<true>, dim3(rg::ceil_div(A.n_words, EX_BLOCK)), dim3(EX_BLOCK), 0, (hipStream_t)stream, A);
-  RG_LAUNCH_CHECK();
-  return 0;
+  return emit_hop<false>("rg_explain_emit", f, g, batch, n_ent, level, marks, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim, min_alpha,
+                         word_ptr, edges_out, alpha_out, nullptr, stream);
+}
+
+int rg_texplain_emit(const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level, const uint32_t* marks,
+                     const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha,
+                     int32_t attn_dim, float min_alpha, const int32_t* word_ptr, int32_t* edges_out, float* alpha_out,
+                     int32_t* time_out, void* stream) {
+  return emit_hop<true>("rg_texplain_emit", f, g, batch, n_ent, level, marks, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim, min_alpha,
+                        word_ptr, edges_out, alpha_out, time_out, stream);
 }
 
 int rg_explain_gather(int64_t n, int32_t hop, int32_t batch, const int32_t* edges, const float* alpha, const int64_t* row_first,

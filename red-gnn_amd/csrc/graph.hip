@@ -478,6 +478,14 @@ int rg_graph_export(const rg_graph* g, int32_t* out_ptr, int32_t* out_rt, int32_
   return 0;
 }
 
+int rg_graph_export_time(const rg_graph* g, int32_t* out_time, int32_t* in_time) {
+  RG_CHECK(g != nullptr, "rg_graph_export_time: graph is NULL");
+  RG_CHECK(g->n_time > 0 && g->in_time && g->out_time, "rg_graph_export_time: the graph has no timestamps (build it with rg_tgraph_create)");
+  if (out_time) RG_HIP(hipMemcpy(out_time, g->out_time, g->n_fact * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (in_time) RG_HIP(hipMemcpy(in_time, g->in_time, g->n_fact * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return 0;
+}
+
 // number of memset / memcpy nodes of a captured hipGraph (models._GraphedInference asserts 0: with ROCm 7.2 a replayed graph that holds
 // several memset nodes zeroed correctly on its first launch only, see common.h zero_async); -1 on error
 int rg_hipgraph_fill_nodes(void* graph) {

@@ -24,6 +24,13 @@
 // workgroup in LDS and flushed once with non-returning 64-bit integer atomics into the caller's [B][n_rela_rows] buffers.  Where the
 // table and the bins do not fit 48 KB of LDS (n_rela_rows * (4 * ap + 12) bytes: thousands of relations) the same kernel adds per
 // edge into the global buffers with the same integer atomics and reads a_r from memory: slower, same result.
+//
+// Temporal graphs (rg_tattn_profile, T-RED-GNN interpolation): the kernel's DIR instantiation.  The enumeration is the same; per
+// edge it also reads out_time[entry] (4 B more of CSR) and bins by the forward's direction (tlayer_fwd.hip): dt = edge time -
+// q_time[b], dir 0 past (dt < 0), 1 now (dt == 0), 2 future (dt > 0); bin = dir * n_rela_rows + rel, outputs [B][3][n_rela_rows].  The
+// temporal attention does not read the time, so alpha is the static arithmetic.  Three bins per relation: the LDS path needs
+// n_rela_rows * (4 * ap + 36) bytes beside the 16 KB head list in 64 KB, i.e. at most 49152 / (4 * ap + 36) relation rows (945 at
+// ap = 4, 722 at ap = 8, 491 at ap = 16, 299 at ap = 32); above that the global-atomic path runs (same integers).
 #include <algorithm>
 
 #include "attn.h"
@@ -63,20 +70,28 @@ __device__ __forceinline__ int wave_incl_scan(int v, int lane) {
   return v;
 }
 
-template <int AP4, bool LDS>
-__global__ __launch_bounds__(PF_BLOCK) void profile_kernel(PfArgs A) {
+struct TPfArgs : PfArgs {
+  const int32_t* out_time;   // time id of every CSR-by-head entry
+  const int32_t* q_time;     // [B]
+};
+
+template <int AP4, bool LDS, bool DIR = false>
+__global__ __launch_bounds__(PF_BLOCK) void profile_kernel(std::conditional_t<DIR, TPfArgs, PfArgs> A) {
   extern __shared__ __align__(16) unsigned char pf_smem[];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int b = blockIdx.y;
   uint16_t* heads = (uint16_t*)pf_smem + wv * PF_HEADS;
   float4* ar_l = (float4*)(pf_smem + PF_LIST_BYTES);
+  const int n_bins = DIR ? 3 * A.R : A.R;               // (direction, relation) cells of one query
   unsigned long long* sum_l = (unsigned long long*)(ar_l + (LDS ? A.R * AP4 : 0));
-  uint32_t* cnt_l = (uint32_t*)(sum_l + (LDS ? A.R : 0));
+  uint32_t* cnt_l = (uint32_t*)(sum_l + (LDS ? n_bins : 0));
   if constexpr (LDS) {
     for (int i = threadIdx.x; i < A.R * AP4; i += PF_BLOCK) ar_l[i] = A.a_r[i];
-    for (int i = threadIdx.x; i < A.R; i += PF_BLOCK) { sum_l[i] = 0ull; cnt_l[i] = 0u; }
+    for (int i = threadIdx.x; i < n_bins; i += PF_BLOCK) { sum_l[i] = 0ull; cnt_l[i] = 0u; }
     __syncthreads();
   }
+  int qt = 0;
+  if constexpr (DIR) qt = A.q_time[b];
   const float b_alpha = A.b_alpha[0];
   float4 w[AP4], q[AP4];
 #pragma unroll
@@ -85,8 +100,8 @@ __global__ __launch_bounds__(PF_BLOCK) void profile_kernel(PfArgs A) {
     q[k] = A.a_q[(int64_t)b * AP4 + k];
   }
   const int2* bm_old = A.bm_old + (int64_t)b * A.W;
-  unsigned long long* sum_g = A.sum_out + (int64_t)b * A.R;
-  unsigned long long* cnt_g = A.count_out + (int64_t)b * A.R;
+  unsigned long long* sum_g = A.sum_out + (int64_t)b * n_bins;
+  unsigned long long* cnt_g = A.count_out + (int64_t)b * n_bins;
 
   for (int g = blockIdx.x * PF_WAVES + wv; g < A.n_groups; g += gridDim.x * PF_WAVES) {   // (uniform over the wave)
     // ---- the heads of this step: set bits of gw words, listed in LDS in entity order, with their node ids ----------------
@@ -128,7 +143,8 @@ __global__ __launch_bounds__(PF_BLOCK) void profile_kernel(PfArgs A) {
         }
         const int beg_s = __shfl(beg, sl, 64), excl_s = __shfl(excl_d, sl, 64);
         if (x < total) {
-          const int r = A.out_rt[beg_s + (x - excl_s)].x;
+          const int entry = beg_s + (x - excl_s);
+          const int r = A.out_rt[entry].x;
           const int s = s_base + k0 + sl;
           if ((uint32_t)r < (uint32_t)A.R && s < A.n_old) {
             float z = b_alpha;
@@ -141,13 +157,18 @@ __global__ __launch_bounds__(PF_BLOCK) void profile_kernel(PfArgs A) {
             }
             const float alpha = rg::attn_alpha(z);
             const unsigned long long fx = (unsigned long long)llrintf(alpha * PF_SCALE);
+            int bin = r;
+            if constexpr (DIR) {
+              const int dt = A.out_time[entry] - qt;
+              bin = (dt > 0 ? 2 : (dt == 0 ? 1 : 0)) * A.R + r;
+            }
             // results unused: non-returning integer adds, order-free
             if constexpr (LDS) {
-              atomicAdd(&sum_l[r], fx);
-              atomicAdd(&cnt_l[r], 1u);
+              atomicAdd(&sum_l[bin], fx);
+              atomicAdd(&cnt_l[bin], 1u);
             } else {
-              atomicAdd(&sum_g[r], fx);
-              atomicAdd(&cnt_g[r], 1ull);
+              atomicAdd(&sum_g[bin], fx);
+              atomicAdd(&cnt_g[bin], 1ull);
             }
           }
         }
@@ -158,7 +179,7 @@ __global__ __launch_bounds__(PF_BLOCK) void profile_kernel(PfArgs A) {
   }
   if constexpr (LDS) {
     __syncthreads();
-    for (int i = threadIdx.x; i < A.R; i += PF_BLOCK) {
+    for (int i = threadIdx.x; i < n_bins; i += PF_BLOCK) {
       const uint32_t c = cnt_l[i];
       if (c) {
         atomicAdd(&sum_g[i], sum_l[i]);
@@ -168,17 +189,14 @@ __global__ __launch_bounds__(PF_BLOCK) void profile_kernel(PfArgs A) {
   }
 }
 
-}  // namespace
-
-extern "C" {
-
-int rg_attn_profile(const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level, int64_t n_old,
-                    const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha,
-                    int32_t attn_dim, int64_t* sum_out, int64_t* count_out, void* stream) {
-  const char* who = "rg_attn_profile";
+// the entry points' checks and launch; DIR = the temporal profile (q_time non-NULL)
+template <bool DIR>
+int profile_hop(const char* who, const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level, int64_t n_old,
+                const int32_t* q_time, const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha,
+                const float* b_alpha, int32_t attn_dim, int64_t* sum_out, int64_t* count_out, void* stream) {
   RG_CHECK(level >= 1 && level < RG_MAX_LEVELS, "%s: level %d not in 1..%d", who, level, RG_MAX_LEVELS - 1);
   RG_CHECK(batch > 0 && n_ent > 0, "%s: batch=%d n_ent=%d must be positive", who, batch, n_ent);
-  RG_CHECK(a_s && a_r && a_q && w_alpha && b_alpha && sum_out && count_out, "%s: NULL argument", who);
+  RG_CHECK(a_s && a_r && a_q && w_alpha && b_alpha && sum_out && count_out && (!DIR || q_time), "%s: NULL argument", who);
   RG_CHECK(attn_dim > 0 && ap >= attn_dim && ap % 4 == 0 && ap <= 32, "%s: attn_dim=%d ap=%d (attention widths up to 32, ap a multiple of 4)",
            who, attn_dim, ap);
   RG_CHECK((((uintptr_t)a_s | (uintptr_t)a_r | (uintptr_t)a_q) & 15) == 0, "%s: attention tables must be 16-B aligned", who);
@@ -187,36 +205,60 @@ int rg_attn_profile(const rg_frontier* f, const rg_graph* g, int32_t batch, int3
   RG_CHECK(batch == f->B && n_ent == f->n_ent, "%s: batch=%d n_ent=%d but the frontier has batch %d, n_ent %d", who, batch, n_ent,
            f->B, f->n_ent);
   RG_CHECK(g->n_ent == f->n_ent, "%s: graph has %d entities, frontier %d", who, g->n_ent, f->n_ent);
-  RG_CHECK(g->n_time == 0 && f->win_lo == nullptr, "%s: static graphs only (rg_graph_create)", who);
+  if constexpr (DIR) {
+    RG_CHECK(g->n_time > 0 && g->out_time, "%s: temporal graphs only (rg_tgraph_create)", who);
+    RG_CHECK(f->win_lo == nullptr, "%s: the frontier has a window set (extrapolation is not supported)", who);
+  } else {
+    RG_CHECK(g->n_time == 0 && f->win_lo == nullptr, "%s: static graphs only (rg_graph_create)", who);
+  }
   RG_CHECK(level <= f->level && level > f->level - f->n_levels + 1, "%s: level %d not resident (current %d, %d kept)", who, level,
            f->level, f->n_levels);
   RG_CHECK(batch <= 65535, "%s: batch=%d above 65535 queries per call", who, batch);
   const int64_t n_have = f->n_nodes[(level - 1) % f->n_levels];
   RG_CHECK(n_have >= 0 && n_old == n_have, "%s: n_old=%lld but level %d has %lld nodes", who, (long long)n_old, level - 1, (long long)n_have);
-  PfArgs A;
+  std::conditional_t<DIR, TPfArgs, PfArgs> A;
   RG_CHECK(n_old <= INT32_MAX, "%s: n_old=%lld does not fit int32", who, (long long)n_old);
   A.bm_old = f->bm_of(level - 1); A.W = f->W; A.n_ent = f->n_ent; A.n_old = (int)n_old;
   A.out_ptr = g->out_ptr; A.out_rt = g->out_rt;
   A.a_s = (const float4*)a_s; A.a_r = (const float4*)a_r; A.a_q = (const float4*)a_q;
   A.w_alpha = w_alpha; A.b_alpha = b_alpha; A.attn_dim = attn_dim; A.R = g->n_rela_rows;
   A.sum_out = (unsigned long long*)sum_out; A.count_out = (unsigned long long*)count_out;
+  if constexpr (DIR) { A.out_time = g->out_time; A.q_time = q_time; }
   // words per wave step: 64, less for small batches so that the chip still gets a few thousand wave-sized pieces (any value gives the
   // same integers)
   A.gw = 64;
   while (A.gw > 4 && (int64_t)batch * rg::ceil_div(A.W, A.gw) < 8192) A.gw >>= 1;
   A.n_groups = (int)rg::ceil_div(A.W, A.gw);
   const int per_query = (int)std::min<int64_t>(rg::ceil_div(A.n_groups, PF_WAVES), std::max<int64_t>(1, rg::ceil_div(4096, batch)));
-  const size_t lds_bins = (size_t)A.R * ((size_t)ap * 4 + 12);
+  const size_t lds_bins = (size_t)A.R * ((size_t)ap * 4 + (DIR ? 36 : 12));
   const bool lds = PF_LIST_BYTES + lds_bins <= PF_LDS_MAX;
   const size_t smem = PF_LIST_BYTES + (lds ? lds_bins : 0);
   hipStream_t s = (hipStream_t)stream;
   return rg::with_ap4(ap / 4, who, [&](auto ap4) {
     constexpr int AP4 = decltype(ap4)::value;
-    if (lds) hipLaunchKernelGGL((profile_kernel<AP4, true>), dim3(per_query, batch), dim3(PF_BLOCK), smem, s, A);
-    else hipLaunchKernelGGL((profile_kernel<AP4, false>), dim3(per_query, batch), dim3(PF_BLOCK), smem, s, A);
+    if (lds) hipLaunchKernelGGL((profile_kernel<AP4, true, DIR>), dim3(per_query, batch), dim3(PF_BLOCK), smem, s, A);
+    else hipLaunchKernelGGL((profile_kernel<AP4, false, DIR>), dim3(per_query, batch), dim3(PF_BLOCK), smem, s, A);
     RG_LAUNCH_CHECK();
     return 0;
   });
+}
+
+}  // namespace
+
+extern "C" {
+
+int rg_attn_profile(const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level, int64_t n_old,
+                    const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha,
+                    int32_t attn_dim, int64_t* sum_out, int64_t* count_out, void* stream) {
+  return profile_hop<false>("rg_attn_profile", f, g, batch, n_ent, level, n_old, nullptr, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim,
+                            sum_out, count_out, stream);
+}
+
+int rg_tattn_profile(const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level, int64_t n_old,
+                     const int32_t* q_time, const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha,
+                     const float* b_alpha, int32_t attn_dim, int64_t* sum_out, int64_t* count_out, void* stream) {
+  return profile_hop<true>("rg_tattn_profile", f, g, batch, n_ent, level, n_old, q_time, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim,
+                           sum_out, count_out, stream);
 }
 
 }  // extern "C"

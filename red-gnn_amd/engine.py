@@ -138,6 +138,14 @@ class TemporalGraph(Graph):
         self.n_fact = int(_lib.lib().rg_graph_n_fact(h))
 
 
+    def export_time(self):
+        """(out_time [n_fact], in_time [n_fact]): the time id of every entry of export()'s out_rel_tail / in_head_rel — for tests."""
+        ot = np.empty(self.n_fact, np.int32)
+        it = np.empty(self.n_fact, np.int32)
+        _lib.check(_lib.lib().rg_graph_export_time(self.handle, _lib.ptr(ot), _lib.ptr(it)))
+        return ot, it
+
+
 class Frontier:
     """Per-batch visited-set state (levels of (batch, entity) node sets) in a torch-owned workspace.
     Replaces the state threaded through RED_GNN_trans.forward / DataLoader.get_neighbors
@@ -390,6 +398,39 @@ def explain_hop(frontier, graph, level, marks, a_s, a_r, a_q, w_alpha, b_alpha, 
     return marks_prev, edges, alpha
 
 
+def texplain_hop(frontier, graph, level, marks, a_s, a_r, a_q, w_alpha, b_alpha, attn_dim, min_alpha):
+    """explain_hop on a temporal graph (rg_texplain_count + rg_texplain_emit).  Returns (marks of the heads [B, W], edges int32 [E, 4] =
+    (row, head, rel, tail) in (row, tail, CSR position) order, alpha [E], time int32 [E] = the edges' time ids)."""
+    for t in (a_s, a_r, a_q, w_alpha, b_alpha):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+    ap = a_s.shape[1]
+    assert a_r.shape == (graph.n_rela_rows, ap) and a_q.shape == (frontier.batch, ap)
+    L, dev = _lib.lib(), frontier.device
+    marks_prev = torch.empty_like(marks)
+    word_ptr = torch.empty(marks.numel() + 1, dtype=torch.int32, device=dev)
+    scratch = frontier.scratch(L.rg_explain_scratch_bytes(frontier.handle) + 256)
+    base = scratch.data_ptr()
+    aligned = (base + 255) // 256 * 256
+    n_e = C.c_int64()
+    args = (frontier.handle, graph.handle, frontier.batch, frontier.n_ent, level, _lib.ptr(marks), _lib.ptr(a_s), _lib.ptr(a_r),
+            _lib.ptr(a_q), ap, _lib.ptr(w_alpha), _lib.ptr(b_alpha), attn_dim, float(min_alpha))
+    ev = None
+    if EXPLAIN_EVENTS is not None:
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        ev[0].record()
+    _lib.check(L.rg_texplain_count(*args, _lib.ptr(marks_prev), _lib.ptr(word_ptr), C.c_void_p(aligned),
+                                   scratch.numel() - (aligned - base), C.byref(n_e), _lib.stream_ptr()))
+    edges = torch.empty((n_e.value, 4), dtype=torch.int32, device=dev)
+    alpha = torch.empty(n_e.value, dtype=torch.float32, device=dev)
+    time = torch.empty(n_e.value, dtype=torch.int32, device=dev)
+    if n_e.value:
+        _lib.check(L.rg_texplain_emit(*args, _lib.ptr(word_ptr), _lib.ptr(edges), _lib.ptr(alpha), _lib.ptr(time), _lib.stream_ptr()))
+    if ev is not None:
+        ev[1].record()
+        EXPLAIN_EVENTS.append((ev[0], ev[1], level, n_e.value))
+    return marks_prev, edges, alpha, time
+
+
 def explain_gather(hop, batch, edges, alpha, row_first, row_base, edges_out, alpha_out):
     """rg_explain_gather: one hop's (row, head, rel, tail) list into the (row, hop, head, rel, tail) layout of edges_out [n_out, 5]:
     edge i of row b goes to row_base[b] + i - row_first[b] (int64 [batch] each)."""
@@ -417,6 +458,29 @@ def attn_profile(frontier, graph, level, a_s, a_r, a_q, w_alpha, b_alpha, attn_d
     _lib.check(_lib.lib().rg_attn_profile(frontier.handle, graph.handle, frontier.batch, frontier.n_ent, level, a_s.shape[0],
                                           _lib.ptr(a_s), _lib.ptr(a_r), _lib.ptr(a_q), ap, _lib.ptr(w_alpha), _lib.ptr(b_alpha),
                                           attn_dim, _lib.ptr(sum_out), _lib.ptr(count_out), _lib.stream_ptr()))
+    if ev is not None:
+        ev[1].record()
+        PROFILE_EVENTS.append((ev[0], ev[1], level))
+
+
+def tattn_profile(frontier, graph, level, q_time, a_s, a_r, a_q, w_alpha, b_alpha, attn_dim, sum_out, count_out):
+    """rg_tattn_profile: attn_profile on a temporal graph with the edge direction as an axis.  Adds the hop-`level` edges of every query
+    into sum_out / count_out (int64 [B, 3, n_rela_rows], zeroed by the caller): direction 0 past / 1 now / 2 future of the edge's time
+    against q_time[b] (int32 [B])."""
+    for t in (a_s, a_r, a_q, w_alpha, b_alpha):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+    ap = a_s.shape[1]
+    assert a_r.shape == (graph.n_rela_rows, ap) and a_q.shape == (frontier.batch, ap)      # (the kernel's bins: the graph's rows)
+    assert q_time.is_cuda and q_time.dtype == torch.int32 and q_time.is_contiguous() and q_time.numel() == frontier.batch
+    for t in (sum_out, count_out):
+        assert t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.shape == (frontier.batch, 3, a_r.shape[0])
+    ev = None
+    if PROFILE_EVENTS is not None:
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        ev[0].record()
+    _lib.check(_lib.lib().rg_tattn_profile(frontier.handle, graph.handle, frontier.batch, frontier.n_ent, level, a_s.shape[0],
+                                           _lib.ptr(q_time), _lib.ptr(a_s), _lib.ptr(a_r), _lib.ptr(a_q), ap, _lib.ptr(w_alpha),
+                                           _lib.ptr(b_alpha), attn_dim, _lib.ptr(sum_out), _lib.ptr(count_out), _lib.stream_ptr()))
     if ev is not None:
         ev[1].record()
         PROFILE_EVENTS.append((ev[0], ev[1], level))

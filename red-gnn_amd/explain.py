@@ -8,7 +8,11 @@ s -> o through the query's subgraph (identity self-loops count as steps); each e
     rels_, ents, prod = rd.strongest_paths()         # the path of largest alpha product per row
 
 The extraction runs in HIP (csrc/explain.hip): a forward keeps all L + 1 frontier levels and each layer's attention projection, then
-one backward marking pass per hop reads only the marked tails' CSR rows.  This module holds the result type and the host driver.
+one backward marking pass per hop reads only the marked tails' CSR rows.  This module holds the result type and the host drivers.
+
+Temporal interpolation (T_RED_GNN.explain, rg_texplain_*): ``rd = model.explain(batch, objs)`` with the batch dict of forward; every
+edge also carries its time id (``rd.time``), ``rd.q_time`` is the rows' query time and ``rd.direction()`` the forward's past / now /
+future of each edge.
 """
 from dataclasses import dataclass
 
@@ -30,6 +34,9 @@ class RDigraph:
     reached  bool [B]      o is in the query's level-L node set
     score    float32 [B]   the model's score of o (0 where not reached)
     n_hops   int           L
+    time     int32 [E]     temporal models only (None otherwise): the time id of each edge; a fact repeated at several times is one
+                           edge per time, in CSR order
+    q_time   int32 [B]     temporal models only (None otherwise): the query time of each row
     """
     edges: torch.Tensor
     alpha: torch.Tensor
@@ -37,6 +44,16 @@ class RDigraph:
     reached: torch.Tensor
     score: torch.Tensor
     n_hops: int
+    time: torch.Tensor = None
+    q_time: torch.Tensor = None
+
+    def direction(self):
+        """int8 [E]: each edge's direction against its row's query time, the temporal forward's convention (dt = edge time - query
+        time): 0 past (dt < 0), 1 now (dt == 0), 2 future (dt > 0).  Temporal digraphs only."""
+        if self.time is None or self.q_time is None:
+            raise ValueError("direction: a static r-digraph has no edge times")
+        dt = self.time.long() - self.q_time.long()[self.edges[:, 0].long()]
+        return (dt > 0).to(torch.int8) * 2 + (dt == 0).to(torch.int8)
 
     def strongest_paths(self):
         """Per row, the length-L path s -> o inside the digraph with the largest product of alpha (products in float64, left to right
@@ -155,27 +172,84 @@ def explain(model, subs, rels, objs=None, mode="test", min_alpha=0.0):
             hops = _forward_sweep(hops, L, n_ent)
         rows = torch.arange(n, device=device)
         score = scores[rows, objs_t].contiguous()
-        counts = torch.stack([torch.bincount(hops[l][0][:, 0].long(), minlength=n) for l in range(1, L + 1)])   # [L, B]
-        per_row = counts.sum(0)
-        offsets = torch.zeros(n + 1, dtype=torch.int64, device=device)
-        offsets[1:] = torch.cumsum(per_row, 0)
-        n_total = int(offsets[-1].item())
-        edges = torch.empty((n_total, 5), dtype=torch.int32, device=device)
-        alpha = torch.empty(n_total, dtype=torch.float32, device=device)
-        before = torch.cumsum(counts, 0) - counts          # [L, B]: edges of the row in earlier hops
-        for l in range(1, L + 1):
-            e, al = hops[l]
-            row_first = torch.cumsum(counts[l - 1], 0) - counts[l - 1]
-            engine.explain_gather(l, n, e, al, row_first, offsets[:-1] + before[l - 1], edges, alpha)
+        edges, alpha, offsets, _ = _assemble(hops, n, L, device)
     return RDigraph(edges=edges, alpha=alpha, offsets=offsets, reached=reached, score=score, n_hops=L)
+
+
+def _assemble(hops, n, L, device):
+    """The hops' lists hops[l] = (edges [E_l, 4], alpha [E_l][, time [E_l]]) in (row, tail, CSR position) order put into the
+    (row, hop, ...) layout: (edges int32 [E, 5], alpha [E], offsets int64 [n + 1], time int32 [E] or None)."""
+    counts = torch.stack([torch.bincount(hops[l][0][:, 0].long(), minlength=n) for l in range(1, L + 1)])   # [L, B]
+    per_row = counts.sum(0)
+    offsets = torch.zeros(n + 1, dtype=torch.int64, device=device)
+    offsets[1:] = torch.cumsum(per_row, 0)
+    n_total = int(offsets[-1].item())
+    edges = torch.empty((n_total, 5), dtype=torch.int32, device=device)
+    alpha = torch.empty(n_total, dtype=torch.float32, device=device)
+    time = torch.empty(n_total, dtype=torch.int32, device=device) if len(hops[1]) > 2 else None
+    before = torch.cumsum(counts, 0) - counts          # [L, B]: edges of the row in earlier hops
+    for l in range(1, L + 1):
+        e, al = hops[l][:2]
+        row_first = torch.cumsum(counts[l - 1], 0) - counts[l - 1]
+        row_base = offsets[:-1] + before[l - 1]
+        engine.explain_gather(l, n, e, al, row_first, row_base, edges, alpha)
+        if time is not None:                               # the same placement, as a device index
+            r = e[:, 0].long()
+            time[row_base[r] + torch.arange(e.shape[0], device=device) - row_first[r]] = hops[l][2]
+    return edges, alpha, offsets, time
+
+
+def explain_temporal(model, batch, objs=None, min_alpha=0.0):
+    """T_RED_GNN.explain (see there): the static driver with the temporal hop call; every edge carries its time id."""
+    from .temporal import batch_ids, eval_semantics
+    device = model.linear_classifier.weight.device
+    engine._require_gpu(device)
+    heads_h, _, _ = batch_ids(model, batch, "explain")
+    n, n_ent = len(heads_h), model.n_ent
+    objs_h = None
+    if objs is not None:
+        objs_h = _ids(objs, "objs")
+        if len(objs_h) != n:
+            raise ValueError("explain: %d answers for %d rows" % (len(objs_h), n))
+        if objs_h.min() < 0 or objs_h.max() >= n_ent:
+            raise ValueError("answer id out of range (n_ent=%d)" % n_ent)
+    tau = float(min_alpha)
+    if tau != tau:
+        raise ValueError("explain: min_alpha is NaN")
+    L, a = model.n_layer, model.attn_dim
+    with torch.no_grad(), eval_semantics(model):
+        kept = []
+        scores = model._run(batch, "test", kept=kept)
+        fr, graph, q_time = kept[0]["frontier"], kept[0]["graph"], kept[0]["q_time"]
+        layers = kept[1:]
+        if objs_h is None:
+            objs_t = scores.argmax(1)                    # first maximum = smallest entity id on a tie
+        else:
+            objs_t = torch.as_tensor(objs_h, dtype=torch.int64).to(device)
+        marks, reached = engine.explain_seed(fr, L, objs_t.to(torch.int32).contiguous())
+        zero_b = torch.zeros(1, device=device)           # the temporal attention has no bias
+        hops = [None] * (L + 1)
+        for l in range(L, 0, -1):
+            k = layers[l - 1]
+            marks, e, al, tm = engine.texplain_hop(fr, graph, l, marks, k["a_s"].detach().contiguous(), k["a_r"].detach().contiguous(),
+                                                   k["a_q"].detach().contiguous(), k["w_alpha"].detach().contiguous(), zero_b, a, tau)
+            hops[l] = (e, al, tm)
+        if tau > 0.0:
+            hops = _forward_sweep(hops, L, n_ent)
+        rows = torch.arange(n, device=device)
+        score = scores[rows, objs_t].contiguous()
+        edges, alpha, offsets, time = _assemble(hops, n, L, device)
+    return RDigraph(edges=edges, alpha=alpha, offsets=offsets, reached=reached, score=score, n_hops=L, time=time,
+                    q_time=q_time.clone())
 
 
 def _forward_sweep(hops, L, n_ent):
     """Keep the hop-l edges (l >= 2) whose head is the tail of a kept hop-(l-1) edge of the same row: with min_alpha > 0 the backward
-    marks alone admit edges whose head is reached from s only through edges below the threshold.  On the compact lists."""
+    marks alone admit edges whose head is reached from s only through edges below the threshold.  On the compact lists; a temporal
+    hop's third list (the edges' times) is carried along."""
     for l in range(2, L + 1):
-        prev, (e, al) = hops[l - 1][0], hops[l]
+        prev, e = hops[l - 1][0], hops[l][0]
         reach = torch.unique(prev[:, 0].long() * n_ent + prev[:, 3].long())
         ok = torch.isin(e[:, 0].long() * n_ent + e[:, 1].long(), reach)
-        hops[l] = (e[ok].contiguous(), al[ok].contiguous())
+        hops[l] = tuple(x[ok].contiguous() for x in hops[l])          # (edges, alpha[, time]): the lists stay aligned
     return hops

@@ -6,6 +6,8 @@
 
 The scores are forward()'s; the exclusion and the selection are one HIP launch (csrc/topk.hip, rg_topk) on the score matrix, with the
 known answers as a sorted CSR over the query keys s * (2*n_rel + 1) + r (loader.known_index), copied to the device once.
+Temporal interpolation: ``model.predict(batch, k, known=temporal_known_index(quads, n_rel + 1, n_time))`` with the batch dict of
+forward; the keys are (head * n_rela_rows + rel) * n_time + time.
 """
 from dataclasses import dataclass
 
@@ -60,3 +62,42 @@ def predict(model, subs, rels, k=10, exclude_known=True, mode="test"):
             q_key = torch.as_tensor(subs_h * n_rows + rels_h, dtype=torch.int64).to(device)
         idx, val = engine.topk(scores.contiguous(), k, q_key, known)
     return Prediction(ids=idx.long(), scores=val)
+
+
+def temporal_known_index(quads, n_rela_rows, n_time):
+    """Known-answer index of (head, relation, time) queries from quadruples int [n, 4] = (head, rel, tail, time id), in the layout of
+    load_data.known_index_of: (keys int64 sorted and unique, ptr int64 [len(keys) + 1], idx int32) with key =
+    (head * n_rela_rows + rel) * n_time + time and the tails of key i = idx[ptr[i]:ptr[i + 1]], ascending and unique."""
+    q = np.asarray(quads, dtype=np.int64).reshape(-1, 4)
+    if len(q) and (q[:, 1].min() < 0 or q[:, 1].max() >= n_rela_rows or q[:, 3].min() < 0 or q[:, 3].max() >= n_time or q[:, [0, 2]].min() < 0):
+        raise ValueError("temporal_known_index: relation / time id out of range (n_rela_rows=%d, n_time=%d)" % (n_rela_rows, n_time))
+    key = (q[:, 0] * n_rela_rows + q[:, 1]) * n_time + q[:, 3]
+    pairs = np.unique(np.stack([key, q[:, 2]], 1), axis=0) if len(q) else np.zeros((0, 2), np.int64)      # sorted by (key, tail)
+    keys, first = np.unique(pairs[:, 0], return_index=True)
+    ptr = np.append(first, len(pairs)).astype(np.int64)
+    return keys.astype(np.int64), ptr, pairs[:, 1].astype(np.int32)
+
+
+def predict_temporal(model, batch, k=10, known=None):
+    """T_RED_GNN.predict (see there)."""
+    from .temporal import batch_ids, eval_semantics
+    device = model.linear_classifier.weight.device
+    engine._require_gpu(device)
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)):
+        raise ValueError("predict: k must be an integer in 1..%d (got %r)" % (K_MAX, k))
+    k = int(k)
+    if not 1 <= k <= K_MAX:
+        raise ValueError("predict: k=%d not in 1..%d" % (k, K_MAX))
+    heads_h, rels_h, times_h = batch_ids(model, batch, "predict")
+    with torch.no_grad(), eval_semantics(model):
+        scores = model._run(batch, "test")
+        q_key = None
+        if known is not None:
+            if len(known) != 3:
+                raise ValueError("predict: known must be the (keys, ptr, idx) triple of temporal_known_index")
+            known = tuple(torch.as_tensor(x).to(device=device, dtype=dt).contiguous()
+                          for x, dt in zip(known, (torch.int64, torch.int64, torch.int32)))
+            q_key = torch.as_tensor((heads_h * (model.n_rel + 1) + rels_h) * model.n_time + times_h, dtype=torch.int64).to(device)
+        idx, val = engine.topk(scores.contiguous(), k, q_key, known)
+    return Prediction(ids=idx.long(), scores=val)
+

@@ -12,6 +12,10 @@ count is the number of edges and alpha_sum the sum of their attention, per query
 kernel's arithmetic and adds it as 64-bit fixed point (2^-32 units, per-edge rounding Q = 2^-33), so every cell is an exact integer
 sum: bit-identical across runs, across any split of a batch and any order of its queries.  Grouping by relation is an integer
 index_add on the device; the conversion to float64 is the last step.
+
+Temporal interpolation (T_RED_GNN.attention_profile, rg_tattn_profile): ``prof = model.attention_profile(batch)`` has one more axis,
+the edge's direction against the query time (0 past, 1 now, 2 future): ``prof.count[q, l - 1, dir, rel]``; ``prof.collapse("direction")``
+is the three-axis table, ``prof.top(q, k, direction=2)`` ranks the future edges alone.
 """
 from dataclasses import dataclass
 
@@ -29,7 +33,9 @@ class AttentionProfile:
     """count int64 [G, L, 2R+1] and fixed int64 [G, L, 2R+1] (the sums of alpha in units of 2^-32), on the device that computed them.
     G = 2R+1 query relation ids (group == "relation"; rows of relations not queried are zero) or the B queries in the order given
     (group == "query").  ``axes`` names the dimensions: code that indexes through it keeps working when a setting adds one (the
-    temporal models' edge direction).  Profiles of the same grouping add (``+``): integer sums, exact."""
+    temporal models' edge direction).  Profiles of the same grouping add (``+``): integer sums, exact.
+    A temporal profile (T_RED_GNN.attention_profile) has axes ("group", "hop", "direction", "relation"), shape [G, L, 3, n_rel+1]:
+    direction 0 past / 1 now / 2 future of the edge's time against the query's; ``collapse("direction")`` gives the three-axis table."""
     fixed: torch.Tensor
     count: torch.Tensor
     group: str = "relation"
@@ -54,17 +60,45 @@ class AttentionProfile:
         h = self.axes.index("hop")
         return AttentionProfile(self.fixed.sum(h, keepdim=True), self.count.sum(h, keepdim=True), self.group, self.axes)
 
-    def top(self, row, k=5):
+    def collapse(self, axis_name):
+        """The profile summed over the named axis (integer sums), which leaves ``axes``: collapse("direction") of a temporal profile
+        is the three-axis table of the static models (summed over the hops too: the reference's attention_vis)."""
+        if axis_name in ("group", "hop", "relation") or axis_name not in self.axes:
+            raise ValueError("collapse: only an axis beyond ('group', 'hop', 'relation') can be summed away, e.g. 'direction' "
+                             "(got %r, axes %r); total() sums the hops" % (axis_name, self.axes))
+        i = self.axes.index(axis_name)
+        return AttentionProfile(self.fixed.sum(i), self.count.sum(i), self.group, self.axes[:i] + self.axes[i + 1:])
+
+    def top(self, row, k=5, direction=None):
         """Per hop the k edge relations with the largest mean alpha in row ``row`` (a query relation id, or a query's position with
         group == "query"), ties to the smaller relation id.  Returns (relation ids int64 [L, k], mean alpha float64 [L, k]); where
-        fewer than k relations have edges the row ends in id -1, mean NaN."""
-        n_rows, n_rel_rows = self.count.shape[0], self.count.shape[-1]
+        fewer than k relations have edges the row ends in id -1, mean NaN.  On a profile with a direction axis ``direction`` = 0 / 1 / 2
+        selects the edges of one direction and None means all of them (the profile collapsed over direction); without that axis it
+        must be None."""
+        if "direction" in self.axes:
+            if direction is None:
+                i = self.axes.index("direction")
+                return self._top(self.fixed.sum(i), self.count.sum(i), row, k)
+            if isinstance(direction, (bool, np.bool_)) or not isinstance(direction, (int, np.integer)) or not 0 <= direction <= 2:
+                raise ValueError("top: direction must be None, 0 (past), 1 (now) or 2 (future) (got %r)" % (direction,))
+            i = self.axes.index("direction")
+            return self._top(self.fixed.select(i, int(direction)), self.count.select(i, int(direction)), row, k)
+        if direction is not None:
+            raise ValueError("top: this profile has no direction axis (axes %r)" % (self.axes,))
+        return self._top(self.fixed, self.count, row, k)
+
+    @staticmethod
+    def _top(fixed, count, row, k):
+        """top() on three-axis tables [G, L, relation rows]."""
+        n_rows, n_rel_rows = count.shape[0], count.shape[-1]
         if not 0 <= int(row) < n_rows:
             raise ValueError("top: row %d not in 0..%d" % (int(row), n_rows - 1))
         if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or k < 1:
             raise ValueError("top: k must be a positive integer (got %r)" % (k,))
         k = min(int(k), n_rel_rows)
-        mean = self.mean()[int(row)]                                              # [L, 2R+1]
+        c = count[int(row)].double()                                              # [L, 2R+1]; the mean as mean() forms it
+        mean = torch.where(count[int(row)] > 0, fixed[int(row)].double() * 2.0 ** -FRACTION_BITS / c.clamp(min=1.0),
+                           torch.full_like(c, float("nan")))
         key = torch.where(torch.isnan(mean), torch.full_like(mean, -1.0), mean)   # alpha >= 0: cells without edges sort last
         order = torch.argsort(key, dim=-1, descending=True, stable=True)[:, :k]
         best = torch.gather(mean, 1, order)
@@ -128,6 +162,35 @@ def attention_profile(model, subs, rels, mode="test", group="relation"):
             fixed = torch.zeros((n_rows, L, n_rows), dtype=torch.int64, device=device).index_add_(0, q_rel, fixed)
             count = torch.zeros((n_rows, L, n_rows), dtype=torch.int64, device=device).index_add_(0, q_rel, count)
     return AttentionProfile(fixed=fixed.contiguous(), count=count.contiguous(), group=group)
+
+
+def attention_profile_temporal(model, batch, group="relation"):
+    """T_RED_GNN.attention_profile (see there)."""
+    from .temporal import batch_ids, eval_semantics
+    device = model.linear_classifier.weight.device
+    engine._require_gpu(device)
+    if group not in ("relation", "query"):
+        raise ValueError("attention_profile: group must be 'relation' or 'query' (got %r)" % (group,))
+    heads_h, _, _ = batch_ids(model, batch, "attention_profile")
+    n, L, a, n_rows = len(heads_h), model.n_layer, model.attn_dim, model.n_rel + 1
+    with torch.no_grad(), eval_semantics(model):
+        kept = []
+        model._run(batch, "test", kept=kept)
+        fr, graph, q_rel, q_time = kept[0]["frontier"], kept[0]["graph"], kept[0]["q_rel"], kept[0]["q_time"]
+        layers = kept[1:]
+        zero_b = torch.zeros(1, device=device)           # the temporal attention has no bias
+        fixed = torch.zeros((L, n, 3, n_rows), dtype=torch.int64, device=device)
+        count = torch.zeros((L, n, 3, n_rows), dtype=torch.int64, device=device)
+        for l in range(1, L + 1):
+            k = layers[l - 1]
+            engine.tattn_profile(fr, graph, l, q_time.contiguous(), k["a_s"].detach().contiguous(), k["a_r"].detach().contiguous(),
+                                 k["a_q"].detach().contiguous(), k["w_alpha"].detach().contiguous(), zero_b, a, fixed[l - 1], count[l - 1])
+        fixed, count = fixed.transpose(0, 1), count.transpose(0, 1)               # [B, L, 3, n_rel+1]
+        if group == "relation":                                                  # integer adds: exact whatever their order
+            fixed = torch.zeros((n_rows, L, 3, n_rows), dtype=torch.int64, device=device).index_add_(0, q_rel, fixed)
+            count = torch.zeros((n_rows, L, 3, n_rows), dtype=torch.int64, device=device).index_add_(0, q_rel, count)
+    return AttentionProfile(fixed=fixed.contiguous(), count=count.contiguous(), group=group,
+                            axes=("group", "hop", "direction", "relation"))
 
 
 def split_profile(model, loader, data="test", batch=50, max_queries=None):

@@ -10,13 +10,17 @@ parameter layout of Temporal/interpolation/model.py (one rela_embed / attention_
 What is different inside: the per-call scipy coo build, the dense [B, n_ent] index maps and the python
 attention_vis loop with .item() syncs (model_cuda.py:121-135,163-166,178-184) do not exist; frontier expansion is the
 device bitmap walk, and the per-edge work of a layer is one fused kernel (rg_tlayer_fwd) with the three direction linears
-hoisted per node / relation / |dt| (W(h + r + tau) = Wh + Wr + Wtau).  (The attention_vis table itself - alpha sum and edge count per
-relation - exists for the static models: RED_GNN_trans.attention_profile, red-gnn_amd/profile.py.)
+hoisted per node / relation / |dt| (W(h + r + tau) = Wh + Wr + Wtau).  The attention_vis table itself - alpha sum and edge count per
+relation - is ``attention_profile`` (rg_tattn_profile; with the edge direction past / now / future as one more axis), the r-digraph the
+reference draws in model_cuda_rule_vis.py is ``explain`` (rg_texplain_*; every edge with its time id), and ``predict`` gives the
+filtered top-k answers of (head, relation, time) queries (rg_topk).
 Training: ``mode='train'`` drops the batch's own quadruples (``batch['example_idx']`` rows of ``params.graph``,
 model_cuda.py:103-104) by building a device graph for the batch, applies ``nn.Dropout(params.dropout)`` before the
 activation (:196) and is differentiable: the per-edge work of the backward pass is rg_tlayer_bwd, the hoisted linears are
 ordinary autograd GEMMs.
 """
+import contextlib
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -96,6 +100,34 @@ class T_RED_GNN(nn.Module):
         return self._frontiers.get(self.n_ent, n, n_levels, device)
 
     def forward(self, batch, mode="train"):
+        return self._run(batch, mode)
+
+    def explain(self, batch, objs=None, min_alpha=0.0):
+        """The r-digraph behind the answer objs[b] of every query (head, relation, time) of ``batch`` (the dict forward takes), on the
+        full graph (mode="test": no fact is deleted), under no_grad: explain.RDigraph with ``time`` (the time id of every edge) and
+        ``q_time`` set.  objs=None: the model's own top answer per row.  Edges with attention below min_alpha are left out."""
+        from . import explain as _explain
+        return _explain.explain_temporal(self, batch, objs, min_alpha)
+
+    def attention_profile(self, batch, group="relation"):
+        """Edge count and alpha sum per (query | query relation, hop, direction, edge relation) over the hop edges of the queries of
+        ``batch``, on the full graph, under no_grad: profile.AttentionProfile with axes ("group", "hop", "direction", "relation"),
+        direction 0 past / 1 now / 2 future of the edge's time against the query's.  ``collapse("direction")`` is the table the
+        reference's attention_vis holds."""
+        from . import profile as _profile
+        return _profile.attention_profile_temporal(self, batch, group)
+
+    def predict(self, batch, k=10, known=None):
+        """The k best answers of every query of ``batch`` on the full graph, under no_grad: prediction.Prediction, score descending then
+        entity id ascending, -1 / -inf past the end.  ``known`` = prediction.temporal_known_index(...) (numpy or device tensors): the
+        tails it lists for a query's (head, relation, time) are left out; None excludes nothing."""
+        from . import prediction as _prediction
+        return _prediction.predict_temporal(self, batch, k, known)
+
+    def _run(self, batch, mode, kept=None):
+        """forward(); with ``kept`` (a list) the frontier keeps all n_layer + 1 levels and the list receives dict(frontier, graph, q_rel,
+        q_time) followed per layer by dict(a_s [n_old, ap], a_r [n_rel + 1, ap], a_q [B, ap], w_alpha [attn_dim]): what rg_tlayer_fwd
+        read, for rg_texplain_* and rg_tattn_profile."""
         device = self.linear_classifier.weight.device
         engine._require_gpu(device)
         heads = torch.as_tensor(batch["head"]).to(device=device, dtype=torch.int32)
@@ -107,8 +139,10 @@ class T_RED_GNN(nn.Module):
             drop = np.asarray(torch.as_tensor(batch["example_idx"]).cpu()).reshape(-1)
             graph = engine.TemporalGraph(self.n_ent, self.n_rel + 1, self.n_time, self.quads, device=device, exclude=drop)
         with_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
-        fr = self._frontier(n, self.n_layer + 1 if with_grad else 2, device)
+        fr = self._frontier(n, self.n_layer + 1 if (with_grad or kept is not None) else 2, device)
         fr.reset(heads)
+        if kept is not None:
+            kept.append(dict(frontier=fr, graph=graph, q_rel=q_rel, q_time=q_time))
         lease = engine.FrontierLease(fr) if with_grad else None
         d, a = self.hidden_dim, self.attn_dim
         ld, ap = max(16, _pad4(d)), pad_attn(a)
@@ -131,6 +165,8 @@ class T_RED_GNN(nn.Module):
             hidden_dir = padc(tall_linear(hidden, w_dir).view(n_old * 3, d)).contiguous()        # row 3 s + dir
             rela_dir = padc(F.linear(rela, w_dir).view(-1, 3, d).transpose(0, 1).reshape(-1, d)).contiguous()   # row dir*(R+1) + r
             w_alpha = w2.reshape(-1).contiguous()
+            if kept is not None:
+                kept.append(dict(a_s=a_s, a_r=a_r, a_q=a_q, w_alpha=w_alpha))
             if with_grad:
                 agg = _TAggregate.apply(hidden_dir, rela_dir, time_dir, a_s, a_r, a_q, w_alpha, zero_b, lease, graph, fr.level, n_new,
                                         q_time, d, a)
@@ -146,3 +182,38 @@ class T_RED_GNN(nn.Module):
         self.last_stats = dict(n_edges=n_edges, n_nodes=int(nodes.shape[0]))
         self.last_nodes = nodes
         return score_all.view(n, self.n_ent)
+
+
+@contextlib.contextmanager
+def eval_semantics(model):
+    """The module in eval mode (dropout = identity) for the duration, whatever its mode: explain, attention_profile and predict
+    describe the deterministic model.  Every submodule gets its own flag back."""
+    was = [(m, m.training) for m in model.modules()]
+    model.eval()
+    try:
+        yield
+    finally:
+        for m, flag in was:
+            m.training = flag
+
+
+def batch_ids(model, batch, who):
+    """(head, relation, time) of ``batch`` as int64 numpy arrays, validated against the model's id ranges."""
+    def ids(k):
+        if k not in batch:
+            raise ValueError("%s: the batch needs 'head', 'relation' and 'time' (missing %r)" % (who, k))
+        x = batch[k]
+        a = (x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)).reshape(-1)
+        if a.size and (a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer)):      # (no silent truncation of 1.7 to 1)
+            raise ValueError("%s: batch[%r] must hold integer ids (got dtype %s)" % (who, k, a.dtype))
+        return a.astype(np.int64)
+    h, r, t = ids("head"), ids("relation"), ids("time")
+    n = len(h)
+    if n == 0 or len(r) != n or len(t) != n:
+        raise ValueError("%s: need one relation and one time per head and at least one row (got %d heads, %d relations, %d times)"
+                         % (who, n, len(r), len(t)))
+    if h.min() < 0 or h.max() >= model.n_ent or r.min() < 0 or r.max() > model.n_rel or t.min() < 0 or t.max() >= model.n_time:
+        raise ValueError("query head / relation / time id out of range (n_ent=%d, n_rel+1=%d, n_time=%d)"
+                         % (model.n_ent, model.n_rel + 1, model.n_time))
+    return h, r, t
+
