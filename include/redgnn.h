@@ -315,6 +315,24 @@ int rg_topk(const float* scores, int32_t batch, int32_t n_ent, int32_t k, const 
             const int64_t* known_keys, const int64_t* known_ptr, const int32_t* known_idx, int64_t n_keys,
             int32_t* idx_out, float* score_out, void* stream);
 
+/* ---- ranks of the extrapolation setting: replaces segment_rank_fil (Temporal/extrapolation/segment.py:346-387)
+ * scores device fp32 [n_pairs] and ent device int32 [n_pairs]: score and entity of every visited (query, entity) pair; query q owns
+ * the pairs seg_ptr[q]:seg_ptr[q+1] (device int32 [batch+1], or int64 when seg_ptr_is64 != 0; an empty segment is legal, bounds
+ * outside 0..n_pairs are clamped).  Entities are unique within a segment, in any order.  target device int32 [batch].
+ * Two known-object indexes in rg_topk's layout (keys int64 sorted and unique, ptr int64 [n_keys + 1], idx int32 ascending and
+ * unique per key; n_keys = 0 with NULL arrays: filter nothing): sp_* by (s, p), spt_* by (s, p, t), with the queries' keys key_sp /
+ * key_spt device int64 [batch].  A key its index lacks filters nothing (the reference's defaultdict).
+ * With ts the score of the target's pair, each output is #{kept j: s_j > ts} + (#{kept j: s_j == ts} - 1)/2 + 1 (IEEE comparisons:
+ * a NaN score counts for nothing): rank_out keeps every pair of the segment, rank_fil_out / rank_fil_t_out those whose entity is
+ * not in the key's list of sp_* / spt_*, the target itself always kept.  found_out int32 [batch] = 1; a target that is not in its
+ * segment gets found = 0 and 1e9 in all three ranks.  Integer counting only: each query depends on its own inputs alone and the
+ * results are bitwise reproducible.  No limit on segment or list length. */
+int rg_segment_rank(const float* scores, const int32_t* ent, int64_t n_pairs, const void* seg_ptr, int32_t seg_ptr_is64,
+                    const int32_t* target, int32_t batch,
+                    const int64_t* key_sp, const int64_t* sp_keys, const int64_t* sp_ptr, const int32_t* sp_idx, int64_t n_sp,
+                    const int64_t* key_spt, const int64_t* spt_keys, const int64_t* spt_ptr, const int32_t* spt_idx, int64_t n_spt,
+                    float* rank_out, float* rank_fil_out, float* rank_fil_t_out, int32_t* found_out, void* stream);
+
 /* rg_dense_fwd with the node count read on the device (after rg_frontier_expand_async): n_cap = capacity of the row buffers,
  * n_dev = rg_frontier_count_ptr() of the frontier whose newest level the rows belong to, n_hint = the row count the caller expects
  * (0 = unknown): it only sizes the grid, every row count up to n_cap is processed correctly. */

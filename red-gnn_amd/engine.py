@@ -865,3 +865,35 @@ def topk(scores, k, q_key=None, known=None):
     _lib.check(_lib.lib().rg_topk(_lib.ptr(scores), B, n_ent, int(k), _lib.ptr(q_key), _lib.ptr(keys), _lib.ptr(ptr), _lib.ptr(tails),
                                   n_keys, _lib.ptr(idx), _lib.ptr(val), _lib.stream_ptr()))
     return idx, val
+
+
+def _known_args(known, q_key, batch, who):
+    """(q_key, keys, ptr, idx, n_keys) of a known-object index for the library: None / an empty index is n_keys = 0 with NULL arrays."""
+    if known is None or known[0].numel() == 0:
+        return None, None, None, None, 0
+    keys, ptr, idx = known
+    assert q_key is not None and q_key.dtype == torch.int64 and q_key.is_contiguous() and q_key.numel() == batch, who
+    assert keys.dtype == torch.int64 and ptr.dtype == torch.int64 and idx.dtype == torch.int32, who
+    assert all(t.is_cuda and t.is_contiguous() for t in (q_key, keys, ptr, idx)) and ptr.numel() == keys.numel() + 1, who
+    return q_key, keys, ptr, idx, keys.numel()
+
+
+def segment_rank(scores, ent, seg_ptr, target, key_sp=None, known_sp=None, key_spt=None, known_spt=None):
+    """Raw, (s, p)-filtered and (s, p, t)-filtered ranks (rg_segment_rank) of every query's target among ITS visited entities:
+    (rank, rank_fil, rank_fil_t fp32 [B], found int32 [B]).  ``scores`` fp32 [N] and ``ent`` int32 [N] per visited pair, query q owning
+    seg_ptr[q]:seg_ptr[q+1] (int32 or int64 [B+1]); ``target`` int32 [B]; ``known_*`` = (keys int64, ptr int64, idx int32) device
+    tensors with the rows' keys ``key_*`` int64 [B], None filtering nothing.  Unfound targets: found 0, ranks 1e9."""
+    assert scores.is_cuda and scores.dtype == torch.float32 and scores.is_contiguous() and scores.dim() == 1
+    assert ent.is_cuda and ent.dtype == torch.int32 and ent.is_contiguous() and ent.shape == scores.shape
+    assert target.is_cuda and target.dtype == torch.int32 and target.is_contiguous() and target.dim() == 1
+    B = target.numel()
+    assert seg_ptr.is_cuda and seg_ptr.dtype in (torch.int32, torch.int64) and seg_ptr.is_contiguous() and seg_ptr.numel() == B + 1
+    dev = scores.device
+    rank, rank_fil, rank_fil_t = (torch.empty(B, dtype=torch.float32, device=dev) for _ in range(3))
+    found = torch.empty(B, dtype=torch.int32, device=dev)
+    sp, spt = _known_args(known_sp, key_sp, B, "segment_rank: (s, p) index"), _known_args(known_spt, key_spt, B, "segment_rank: (s, p, t) index")
+    p = _lib.ptr
+    _lib.check(_lib.lib().rg_segment_rank(p(scores), p(ent), scores.numel(), p(seg_ptr), int(seg_ptr.dtype == torch.int64), p(target), B,
+                                          p(sp[0]), p(sp[1]), p(sp[2]), p(sp[3]), sp[4], p(spt[0]), p(spt[1]), p(spt[2]), p(spt[3]), spt[4],
+                                          p(rank), p(rank_fil), p(rank_fil_t), p(found), _lib.stream_ptr()))
+    return rank, rank_fil, rank_fil_t, found

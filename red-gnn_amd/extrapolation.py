@@ -12,11 +12,17 @@ carrying its data-row index); a query's window ``dataset[time_offset_list[begin]
 the frontier hops under those windows (rg_frontier_set_window) and the layer is one fused kernel (rg_xlayer_fwd) with the direction
 matrix hoisted by linearity.  The time embedding of the ~120 distinct relative times of a window is a table computed once per forward.
 
+Evaluation (main.py:353-472) stays on the device as well: ``known_objects_index`` stands in for the reference's sp2o / spt2o
+dictionaries, ``T_RED_GNN.rank_batch`` ranks a batch's softmax scores raw, filtered and time-filtered in one HIP launch
+(csrc/segment_rank.hip, rg_segment_rank) and ``T_RED_GNN.evaluate`` batches a split and returns the reference's metrics from one host
+copy.  ``segment_rank_fil`` is the host restatement the device path is tested against.
+
 Parity: the reference's model file cannot be imported in the build container (torch_scatter, pyvis, rtdl_revisiting_models are absent),
 so this path is checked against the oracle's restatement only - parity UNPINNED - except ``segment_rank_fil``, whose fixture comes
 from the reference's importable ``segment.py``.
 """
 import math
+from dataclasses import dataclass
 
 import numpy as np
 import torch
@@ -145,6 +151,12 @@ class T_RED_GNN(nn.Module):
     def forward(self, X):
         """X: src_idx, rel_idx, ts (numpy arrays, as the reference's batch object).  Returns (score_all [B, n_ent],
         (per-query softmax over the visited entities [N], visited (batch, entity) pairs int64 numpy [N,2])) as :245-261."""
+        _, soft, nodes, score_all = self._run(X, dense=True)
+        return score_all, (soft, nodes.long().cpu().numpy())
+
+    def _run(self, X, dense=False):
+        """The forward on the device: (logits [N], per-query softmax [N], visited (batch, entity) pairs int32 [N,2] sorted, score_all) -
+        score_all [B, n_ent] only with ``dense`` (else None: nothing of size B * n_ent is built, nothing is copied to the host)."""
         device = self.linear_classifier.weight.device
         engine._require_gpu(device)
         src, rel = np.asarray(X.src_idx), np.asarray(X.rel_idx)
@@ -197,7 +209,10 @@ class T_RED_GNN(nn.Module):
             nodes, _, _ = fr.nodes(want_prev=False, want_old_new=False)
             result = tall_linear(hidden, self.linear_classifier.weight, self.linear_classifier.bias).reshape(-1)   # :244
             b_idx = nodes[:, 0].long()
-            score_all = torch.zeros(n * self.n_ent, device=device).index_copy(0, b_idx * self.n_ent + nodes[:, 1].long(), result)
+            score_all = None
+            if dense:
+                score_all = torch.zeros(n * self.n_ent, device=device).index_copy(0, b_idx * self.n_ent + nodes[:, 1].long(), result)
+                score_all = score_all.view(n, self.n_ent)
             # scatter_softmax(result, cur_entity[:, 0]) (:248): per-query softmax over the visited entities
             row_max = torch.full((n,), float("-inf"), device=device).scatter_reduce(0, b_idx, result.detach(), "amax")
             ex = torch.exp(result - row_max[b_idx])
@@ -205,7 +220,74 @@ class T_RED_GNN(nn.Module):
         if not with_grad:
             fr.set_window(None, None, 0)         # (a training forward's frontier keeps its windows for the backward: every reset sets them anew)
         self.last_stats = dict(n_edges=n_edges, n_nodes=int(nodes.shape[0]))
-        return score_all.view(n, self.n_ent), (soft, nodes.long().cpu().numpy())
+        return result, soft, nodes, score_all
+
+    def _index_on_device(self, index, device):
+        """A KnownObjects index as device tensors, copied once per index and device and kept on the model (the last few)."""
+        cache = self.__dict__.setdefault("_known_dev", {})
+        key = (id(index), str(device))
+        hit = cache.get(key)
+        if hit is None or hit[0] is not index:
+            while len(cache) >= 8:
+                cache.pop(next(iter(cache)))
+            hit = cache[key] = (index, _index_tensors(index, device))
+        return hit[1]
+
+    def rank_batch(self, X, targets, sp_index=None, spt_index=None):
+        """Ranks of one batch as main.py:383,404 computes them, on the device: the forward, then the rank of every query's target among
+        ITS visited entities by the per-query softmax - raw, filtered by the other known objects of (s, p) (``sp_index``) and of
+        (s, p, ts) (``spt_index``), both from known_objects_index; None filters nothing.  X as forward's; ``targets`` int [B].
+        Runs without gradients in eval mode (the training flags come back).  Returns a RankBatch of device tensors."""
+        from .temporal import eval_semantics
+        device = engine._require_gpu(self.linear_classifier.weight.device)
+        src, rel, ts = (_int_ids(x, "rank_batch", k) for x, k in ((X.src_idx, "src_idx"), (X.rel_idx, "rel_idx"), (X.ts, "ts")))
+        tgt = _int_ids(targets, "rank_batch", "targets")
+        n = len(src)
+        if n == 0 or len(rel) != n or len(ts) != n or len(tgt) != n:
+            raise ValueError("rank_batch: need one relation, time and target per subject and at least one query (got %d, %d, %d, %d)"
+                             % (n, len(rel), len(ts), len(tgt)))
+        with torch.no_grad(), eval_semantics(self):
+            _, soft, nodes, _ = self._run(X, dense=False)
+            # nodes are sorted by (query, entity): query q owns the pairs seg_ptr[q]:seg_ptr[q+1]
+            seg_ptr = torch.searchsorted(nodes[:, 0].contiguous(), torch.arange(n + 1, dtype=torch.int32, device=device))
+            ent = nodes[:, 1].contiguous()
+            keys, known = [], []
+            for index in (sp_index, spt_index):
+                keys.append(None if index is None else torch.as_tensor(index.query_keys(src, rel, ts)).to(device))
+                known.append(None if index is None else self._index_on_device(index, device))
+            rank, rank_fil, rank_fil_t, found = engine.segment_rank(soft.contiguous(), ent, seg_ptr, torch.as_tensor(tgt, dtype=torch.int32).to(device),
+                                                                    keys[0], known[0], keys[1], known[1])
+        return RankBatch(rank=rank, found=found.bool(), rank_fil=rank_fil, rank_fil_t=rank_fil_t, soft=soft, nodes=nodes)
+
+    def evaluate(self, queries, sp_index=None, spt_index=None, batch_size=64, return_ranks=False):
+        """The validation loop of main.py:353-472 for a split: ``queries`` int [n, 4] = (s, p, o, ts), in batches of ``batch_size``
+        through rank_batch; the rank tensors stay on the device and are copied to the host once.  Returns the reference's quantities
+        with its denominators: hits1 / hits3 / hits10 / mrr (raw, :413-415,426), *_fil (:416-418,429) and *_fil_t (:419-421,430; the
+        reference's time-filtered list holds found queries only) over the number of queries, hits_inf = found / n, mr (:423), and
+        among the found queries hits1_found / hits3_found / hits10_found / mr_found / mrr_found (:455-462; NaN when none is found).
+        Sums in float64.  ``return_ranks``: also (rank, found, rank_fil, rank_fil_t) as numpy arrays [n] (unfound: 1e9)."""
+        q = queries.detach().cpu().numpy() if torch.is_tensor(queries) else np.asarray(queries)
+        if q.dtype == np.bool_ or not np.issubdtype(q.dtype, np.integer):
+            raise ValueError("evaluate: queries must hold integer ids (got dtype %s)" % q.dtype)
+        if q.ndim != 2 or q.shape[1] != 4 or len(q) == 0:
+            raise ValueError("evaluate: queries must be a non-empty int [n, 4] array of (s, p, o, ts) (got shape %s)" % (q.shape,))
+        if isinstance(batch_size, (bool, np.bool_)) or not isinstance(batch_size, (int, np.integer)) or batch_size < 1:
+            raise ValueError("evaluate: batch_size must be a positive integer (got %r)" % (batch_size,))
+        q = q.astype(np.int64)
+        if q[:, [0, 2]].min() < 0 or q[:, [0, 2]].max() >= self.n_ent or q[:, 1].min() < 0 or q[:, 1].max() >= self.n_rel_true:
+            raise ValueError("evaluate: subject / object / relation id out of range (n_ent=%d, n_rel=%d)" % (self.n_ent, self.n_rel_true))
+        day = q[:, 3] // self.time_granularity
+        if q[:, 3].min() < 0 or day.max() >= len(self.time_offset_list):
+            raise ValueError("evaluate: query time outside the model's data (0 <= ts // %d < %d)" % (self.time_granularity, len(self.time_offset_list)))
+        parts = []
+        for lo in range(0, len(q), int(batch_size)):
+            b = q[lo:lo + int(batch_size)]
+            r = self.rank_batch(_Batch(b[:, 0], b[:, 1], b[:, 3]), b[:, 2], sp_index, spt_index)
+            parts.append(torch.stack([r.rank, r.found.float(), r.rank_fil, r.rank_fil_t]))
+        rank, found, rank_fil, rank_fil_t = torch.cat(parts, 1).cpu().numpy().astype(np.float64)      # the one host copy
+        found = found != 0
+        out = extrapolation_metrics(rank, found, rank_fil, rank_fil_t[found])
+        return (out, (rank, found, rank_fil, rank_fil_t)) if return_ranks else out
 
 
 def segment_rank_fil(t, entities, target_idx_l, sp2o, spt2o, queries_sub, queries_pre, queries_ts):
@@ -236,3 +318,132 @@ def segment_rank_fil(t, entities, target_idx_l, sp2o, spt2o, queries_sub, querie
         other_t = np.setdiff1d(spt2o[(queries_sub[i], queries_pre[i], queries_ts[i])], [target_idx_l[i]])
         rank_fil_t.append(one(~np.isin(ents, other_t)))
     return np.array(rank), found, np.array(rank_fil), np.array(rank_fil_t)
+
+
+class _Batch:
+    """The fields of the reference's batch object that the forward reads."""
+    __slots__ = ("src_idx", "rel_idx", "ts")
+
+    def __init__(self, src_idx, rel_idx, ts):
+        self.src_idx, self.rel_idx, self.ts = src_idx, rel_idx, ts
+
+
+@dataclass
+class RankBatch:
+    """T_RED_GNN.rank_batch: rank, rank_fil, rank_fil_t float32 [B] (1e9 where the target was not reached), found bool [B], soft
+    float32 [N] (the per-query softmax that was ranked) and nodes int32 [N, 2] (its (query, entity) pairs), on the model's device."""
+    rank: torch.Tensor
+    found: torch.Tensor
+    rank_fil: torch.Tensor
+    rank_fil_t: torch.Tensor
+    soft: torch.Tensor
+    nodes: torch.Tensor
+
+
+class KnownObjects(tuple):
+    """(keys int64 sorted and unique, ptr int64 [len(keys) + 1], idx int32): the objects of key i are idx[ptr[i]:ptr[i+1]], ascending and
+    unique - the layout of prediction.temporal_known_index.  key = s * n_rel_rows + p, and with ``n_time`` > 0
+    (s * n_rel_rows + p) * n_time + t for the raw timestamp t.  Unpacks as the three arrays."""
+
+    def __new__(cls, keys, ptr, idx, n_rel_rows, n_time=0):
+        self = super().__new__(cls, (np.ascontiguousarray(keys, dtype=np.int64), np.ascontiguousarray(ptr, dtype=np.int64),
+                                     np.ascontiguousarray(idx, dtype=np.int32)))
+        self.n_rel_rows, self.n_time = int(n_rel_rows), int(n_time)
+        return self
+
+    def query_keys(self, s, p, t=None):
+        """int64 keys of the queries (s, p[, t]); -1, which no index holds, where p or t lies outside the index's ranges."""
+        s, p = np.asarray(s, dtype=np.int64), np.asarray(p, dtype=np.int64)
+        ok = (s >= 0) & (p >= 0) & (p < self.n_rel_rows)
+        key = s * self.n_rel_rows + p
+        if self.n_time:
+            t = np.asarray(t, dtype=np.int64)
+            ok &= (t >= 0) & (t < self.n_time)
+            key = key * self.n_time + t
+        return np.where(ok, key, -1).astype(np.int64)
+
+    def objects(self, s, p, t=None):
+        """The objects of one key, as the reference's dictionary lookup (empty when absent)."""
+        k = int(self.query_keys([s], [p], None if t is None else [t])[0])
+        i = int(np.searchsorted(self[0], k))
+        if i == len(self[0]) or self[0][i] != k:
+            return np.zeros(0, np.int32)
+        return self[2][self[1][i]:self[1][i + 1]]
+
+
+def known_objects_index(quads, n_rel_rows, with_time):
+    """The known objects of (s, p) - the reference's get_sp2o() over all data (utils.py:228-240) - or, ``with_time``, of (s, p, t) -
+    get_spt2o(split) over one split (:207-226) - from quadruples int [n, 4] = (s, p, o, raw timestamp), as a KnownObjects index.
+    Vectorised as prediction.temporal_known_index: one np.unique over (key, object) pairs.  With time, n_time = max timestamp + 1."""
+    q = np.asarray(quads)
+    if q.size and (q.dtype == np.bool_ or not np.issubdtype(q.dtype, np.integer)):
+        raise ValueError("known_objects_index: quads must hold integer ids (got dtype %s)" % q.dtype)
+    q = q.astype(np.int64).reshape(-1, 4)
+    if len(q) and (q.min() < 0 or q[:, 1].max() >= n_rel_rows):
+        raise ValueError("known_objects_index: negative id or relation id out of range (n_rel_rows=%d)" % n_rel_rows)
+    n_time = (int(q[:, 3].max()) + 1 if len(q) else 1) if with_time else 0
+    key = q[:, 0] * n_rel_rows + q[:, 1]
+    if with_time:
+        key = key * n_time + q[:, 3]
+    pairs = np.unique(np.stack([key, q[:, 2]], 1), axis=0) if len(q) else np.zeros((0, 2), np.int64)      # sorted by (key, object)
+    keys, first = np.unique(pairs[:, 0], return_index=True)
+    return KnownObjects(keys, np.append(first, len(pairs)), pairs[:, 1], n_rel_rows, n_time)
+
+
+def _int_ids(x, who, name):
+    a = (x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)).reshape(-1)
+    if a.size and (a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer)):      # (no silent truncation of 1.7 to 1)
+        raise ValueError("%s: %s must hold integer ids (got dtype %s)" % (who, name, a.dtype))
+    return a.astype(np.int64)
+
+
+def _index_tensors(index, device):
+    return tuple(torch.as_tensor(a).to(device).contiguous() for a in index)
+
+
+def segment_rank_fil_device(t, entities, target_idx_l, sp_index, spt_index, queries_sub, queries_pre, queries_ts, device="cuda"):
+    """segment_rank_fil computed by rg_segment_rank: the same arguments with KnownObjects indexes (known_objects_index) in place of the
+    two dictionaries, the same results (rank [B], found list, rank_fil [B], rank_fil_t compacted to the found queries).  ``t`` and
+    ``entities`` may be device tensors; the segments are the runs of entities[:, 0], found on the device."""
+    device = engine._require_gpu(t.device if torch.is_tensor(t) and t.is_cuda else device)
+    tgt = _int_ids(target_idx_l, "segment_rank_fil_device", "target_idx_l")
+    B = len(tgt)
+    scores = torch.as_tensor(t).detach().to(device=device, dtype=torch.float32).contiguous()
+    ents = torch.as_tensor(entities).to(device)
+    if ents.dim() != 2 or ents.shape[1] != 2 or ents.shape[0] != scores.numel():
+        raise ValueError("segment_rank_fil_device: entities must be [N, 2] with one row per score (got %s for %d scores)"
+                         % (tuple(ents.shape), scores.numel()))
+    seg = ents[:, 0]
+    starts = torch.nonzero(seg[1:] != seg[:-1]).reshape(-1) + 1
+    seg_ptr = torch.cat([starts.new_zeros(1), starts, starts.new_full((1,), len(seg))])
+    if seg_ptr.numel() != B + 1:
+        raise ValueError("segment_rank_fil_device: %d segments for %d targets" % (seg_ptr.numel() - 1, B))
+    sub, pre, ts = (_int_ids(x, "segment_rank_fil_device", k) for x, k in ((queries_sub, "queries_sub"), (queries_pre, "queries_pre"),
+                                                                            (queries_ts, "queries_ts")))
+    keys = [None if ix is None else torch.as_tensor(ix.query_keys(sub, pre, ts)).to(device) for ix in (sp_index, spt_index)]
+    known = [None if ix is None else _index_tensors(ix, device) for ix in (sp_index, spt_index)]
+    out = engine.segment_rank(scores, ents[:, 1].to(torch.int32).contiguous(), seg_ptr, torch.as_tensor(tgt, dtype=torch.int32).to(device),
+                              keys[0], known[0], keys[1], known[1])
+    rank, rank_fil, rank_fil_t, found = torch.stack([x.float() for x in out]).cpu().numpy().astype(np.float64)
+    found = found != 0
+    return rank, found.tolist(), rank_fil, rank_fil_t[found]
+
+
+def extrapolation_metrics(rank, found, rank_fil, rank_fil_t):
+    """The reference's reported quantities (main.py:413-430,434-463) from the ranks of a split: ``rank`` / ``rank_fil`` [n] (1e9 where not
+    found), ``found`` bool [n], ``rank_fil_t`` over the found queries only, as segment_rank_fil leaves them.  Sums in float64."""
+    rank, rank_fil, rank_fil_t = (np.asarray(x, dtype=np.float64) for x in (rank, rank_fil, rank_fil_t))
+    found = np.asarray(found, dtype=bool)
+    n, n_found = len(rank), int(found.sum())
+    among = lambda v: float(v) / n_found if n_found else float("nan")
+    return {
+        "n": n, "n_found": n_found,
+        "hits1": np.sum(rank == 1) / n, "hits3": np.sum(rank <= 3) / n, "hits10": np.sum(rank <= 10) / n,
+        "hits_inf": n_found / n, "mr": np.sum(rank) / n, "mrr": np.sum(1 / rank) / n,
+        "hits1_fil": np.sum(rank_fil <= 1) / n, "hits3_fil": np.sum(rank_fil <= 3) / n, "hits10_fil": np.sum(rank_fil <= 10) / n,
+        "mrr_fil": np.sum(1 / rank_fil) / n,
+        "hits1_fil_t": np.sum(rank_fil_t <= 1) / n, "hits3_fil_t": np.sum(rank_fil_t <= 3) / n, "hits10_fil_t": np.sum(rank_fil_t <= 10) / n,
+        "mrr_fil_t": np.sum(1 / rank_fil_t) / n,
+        "hits1_found": among(np.sum(rank == 1)), "hits3_found": among(np.sum(rank <= 3)), "hits10_found": among(np.sum(rank <= 10)),
+        "mr_found": among(np.sum(rank[found])), "mrr_found": among(np.sum(1 / rank[found])),
+    }
