@@ -333,6 +333,26 @@ int rg_segment_rank(const float* scores, const int32_t* ent, int64_t n_pairs, co
                     const int64_t* key_spt, const int64_t* spt_keys, const int64_t* spt_ptr, const int32_t* spt_idx, int64_t n_spt,
                     float* rank_out, float* rank_fil_out, float* rank_fil_t_out, int32_t* found_out, void* stream);
 
+/* ---- filtered top-k of the extrapolation setting: the forecasts of (s, p, ?, t) among the entities the query's window reaches
+ * (T_RED_GNN.predict of extrapolation.py) - what rg_topk is for a dense row, in rg_segment_rank's layout.
+ * scores (the logits) / ent / n_pairs / seg_ptr / seg_ptr_is64 / batch as rg_segment_rank: entities unique within a segment, in any
+ * order; bounds clamped to 0..n_pairs; an empty segment is legal; a segment holds fewer than 2^31 pairs.  One known-object index
+ * in rg_topk's layout (known_keys / known_ptr / known_idx / n_keys) with the queries' keys q_key int64 [batch]: n_keys = 0 with NULL
+ * arrays excludes nothing, a key the index lacks excludes nothing, known entities that are not in the segment are ignored.
+ * idx_out int32 [batch, k] / score_out fp32 [batch, k], 1 <= k <= 1024: per query the pairs whose entity is not in the key's list,
+ * ordered by score descending, then entity id ascending, with rg_topk's key order (NaN lowest, -0 == +0); score_out is the input
+ * score bit for bit; past the end -1 / -inf.  prob_out fp32 [batch, k] (may be NULL; past the end 0): the per-query softmax over ALL
+ * pairs of the segment, excluded ones included (scatter_softmax of model_cuda_new_embedding.py:248), exp(s - m) / sum_j exp(s_j - m)
+ * with m the segment's maximum, both reduced in a fixed order (per-thread strided partials, wave shuffle, waves in index order): a
+ * query's probabilities are bitwise reproducible and do not depend on the rest of the batch.  A NaN score (or m = +-inf) makes the
+ * segment's probabilities NaN.  One workgroup per query; integer atomics only in the selection; each query depends on its own
+ * segment and list alone.  A known list of up to 256 entities is searched in LDS, a longer one in memory; a segment of up to 24576
+ * pairs keeps its keys and kept flags in LDS, a longer one is re-read on every pass of the select.  Nothing outside [0, n_pairs) or
+ * outside the index arrays is read; a known list that is not ascending gives an unspecified, in-bounds result, as for rg_topk. */
+int rg_segment_topk(const float* scores, const int32_t* ent, int64_t n_pairs, const void* seg_ptr, int32_t seg_ptr_is64,
+                    int32_t batch, int32_t k, const int64_t* q_key, const int64_t* known_keys, const int64_t* known_ptr,
+                    const int32_t* known_idx, int64_t n_keys, int32_t* idx_out, float* score_out, float* prob_out, void* stream);
+
 /* rg_dense_fwd with the node count read on the device (after rg_frontier_expand_async): n_cap = capacity of the row buffers,
  * n_dev = rg_frontier_count_ptr() of the frontier whose newest level the rows belong to, n_hint = the row count the caller expects
  * (0 = unknown): it only sizes the grid, every row count up to n_cap is processed correctly. */
@@ -415,8 +435,8 @@ int rg_explain_gather(int64_t n, int32_t hop, int32_t batch, const int32_t* edge
  * marking walk, scratch, output order and determinism are rg_explain_count / rg_explain_emit's; a_r has n_rela_rows rows and alpha is
  * rg_tlayer_fwd's (which does not read the edge's time; pass b_alpha = 0).  rg_texplain_emit also writes time_out int32 [E_l]: the time
  * id of every kept edge (the CSR-by-tail entry's), so that a fact repeated at several times gives one edge per time, in CSR order.
- * The graph must be temporal (n_time > 0) and the frontier must have no window set (rg_frontier_set_window: extrapolation is not
- * supported); a static graph, like a temporal one handed to the static entry points, is an argument error.  rg_explain_seed,
+ * The graph must be temporal (n_time > 0) and the frontier must have no window set (rg_frontier_set_window: that is
+ * rg_xexplain_*, below); a static graph, like a temporal one handed to the static entry points, is an argument error.  rg_explain_seed,
  * rg_explain_gather and rg_explain_scratch_bytes serve both settings. */
 int rg_texplain_count(const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level, const uint32_t* marks,
                       const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha,
@@ -426,6 +446,22 @@ int rg_texplain_emit(const rg_frontier* f, const rg_graph* g, int32_t batch, int
                      const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha,
                      int32_t attn_dim, float min_alpha, const int32_t* word_ptr, int32_t* edges_out, float* alpha_out,
                      int32_t* time_out, void* stream);
+
+/* ---- the same for the extrapolation model (extrapolation.py: ONE quadruple graph whose time field is the edge's data row, self-loops
+ * row >= n_data, and per-query row windows on the frontier).  The marking walk of rg_explain_count / rg_explain_emit with the forward's
+ * window test in both passes: an edge counts for query b only if its row is a self-loop or win_lo[b] <= row < win_hi[b] (rg_xlayer_fwd).
+ * alpha is rg_xlayer_fwd's (a_s / a_r / a_q of [h_s | rel | rel_q], no time; pass b_alpha = 0).  rg_xexplain_emit also writes row_out
+ * int32 [E_l]: the data row of every kept edge (>= n_data for a self-loop).  The frontier must have its windows set
+ * (rg_frontier_set_window; n_data is taken from it) and the graph must carry row ids (rg_tgraph_create).  Arguments, scratch, output
+ * order and determinism as rg_explain_count / rg_explain_emit; rg_explain_seed and rg_explain_gather serve this setting too. */
+int rg_xexplain_count(const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level, const uint32_t* marks,
+                      const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha,
+                      int32_t attn_dim, float min_alpha, uint32_t* marks_prev_out, int32_t* word_ptr_out, void* scratch,
+                      size_t scratch_bytes, int64_t* n_edges_host, void* stream);
+int rg_xexplain_emit(const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level, const uint32_t* marks,
+                     const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha,
+                     int32_t attn_dim, float min_alpha, const int32_t* word_ptr, int32_t* edges_out, float* alpha_out,
+                     int32_t* row_out, void* stream);
 
 /* ---- attention profile of a hop: which edge relations a query listens to (the reference's attention_vis table,
  * Temporal/interpolation/model_cuda.py:117-119,163-166: per relation the sum of alpha and the number of edges, there a python loop with

@@ -21,7 +21,8 @@ SYMBOLS = [
     "rg_topk",
     "rg_attn_profile",
     "rg_graph_export_time", "rg_texplain_count", "rg_texplain_emit", "rg_tattn_profile",
-    "rg_segment_rank",
+    "rg_segment_rank", "rg_segment_topk",
+    "rg_xexplain_count", "rg_xexplain_emit",
 ]
 
 _lib = None
@@ -122,6 +123,9 @@ def lib():
     L.rg_texplain_emit.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, i32, C.c_float, vp, vp, vp, vp, vp]
     L.rg_tattn_profile.argtypes = [vp, vp, i32, i32, i32, i64, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp]
     L.rg_segment_rank.argtypes = [vp, vp, i64, vp, i32, vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp]
+    L.rg_segment_topk.argtypes = [vp, vp, i64, vp, i32, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp]
+    L.rg_xexplain_count.argtypes = L.rg_explain_count.argtypes
+    L.rg_xexplain_emit.argtypes = L.rg_texplain_emit.argtypes
     _lib = L
     return L
 

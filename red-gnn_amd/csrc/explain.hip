@@ -18,6 +18,10 @@
 // Temporal graphs (rg_texplain_*, T-RED-GNN interpolation): the same walk over a quadruple graph.  The temporal attention does not
 // read the edge's time, so the count pass IS the static instantiation; the emit pass is the kernel's TIME instantiation, which also
 // writes the entry's time id (in_time[c]) beside the edge, so that a fact repeated at several times stays told apart.
+//
+// Extrapolation (rg_xexplain_*, the one-graph layout of extrapolation.py): in_time[c] is the edge's data row and the frontier carries
+// the queries' row windows.  The WINDOW instantiation keeps an edge of query b only if its row is a self-loop (row >= n_data) or lies
+// in [win_lo[b], win_hi[b]) - the forward's test (layer_fwd_kernel.h), needed in BOTH passes - and its emit pass writes the data row.
 #include "attn.h"
 
 namespace {
@@ -62,8 +66,15 @@ struct TExArgs : ExArgs {
   int32_t* time_out;         // emit: in_time[c] of every kept edge
 };
 
-template <bool EMIT, bool TIME = false>
-__global__ __launch_bounds__(EX_BLOCK) void explain_kernel(std::conditional_t<TIME, TExArgs, ExArgs> A) {
+struct XExArgs : TExArgs {   // in_time = data row of every CSR-by-tail entry
+  const int32_t* win_lo;     // [B] first data row of the query's window
+  const int32_t* win_hi;     // [B] one past its last
+  int32_t n_data;            // rows >= n_data are the self-loops
+};
+
+template <bool EMIT, bool TIME = false, bool WINDOW = false>
+__global__ __launch_bounds__(EX_BLOCK) void explain_kernel(
+    std::conditional_t<WINDOW, XExArgs, std::conditional_t<TIME, TExArgs, ExArgs>> A) {
   const int lane = threadIdx.x & 63;
   const int64_t w0 = ((int64_t)blockIdx.x * (EX_BLOCK / 64) + (threadIdx.x >> 6)) * 64;
   if (w0 >= A.n_words) return;                       // (uniform over the wave)
@@ -84,6 +95,8 @@ __global__ __launch_bounds__(EX_BLOCK) void explain_kernel(std::conditional_t<TI
     const int32_t base = EMIT ? A.word_ptr[wj] : 0;
     const int32_t lim = EMIT ? A.word_ptr[wj + 1] : 0;   // (the count pass's total for this word: never written past)
     int32_t cnt = 0;                                   // kept edges of this word so far (uniform)
+    int wlo = 0, whi = 0;
+    if constexpr (WINDOW) { wlo = A.win_lo[b]; whi = A.win_hi[b]; }
     while (bits) {
       const int t = e0 + __ffs((int)bits) - 1;
       bits &= bits - 1u;
@@ -97,7 +110,12 @@ __global__ __launch_bounds__(EX_BLOCK) void explain_kernel(std::conditional_t<TI
           const int2 hr = A.in_hr[c];
           hd = hr.x; r = hr.y;
           const int2 wp = bm_row[hd >> 5];
-          if (rg::bm_has(wp, hd)) {
+          bool valid = rg::bm_has(wp, hd);
+          if constexpr (WINDOW) {
+            const int row = A.in_time[c];
+            valid = valid && (row >= A.n_data || (row >= wlo && row < whi));
+          }
+          if (valid) {
             const int s = rg::bm_rank(wp, hd);
             float z = b_alpha;
             for (int k = 0; k < A.ap4; ++k) {
@@ -147,16 +165,21 @@ __global__ void gather_kernel(int64_t n, int hop, const int4* __restrict__ edges
 }
 
 // checks shared by the per-hop entry points
-int check_hop(const char* who, bool temporal, const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level) {
+enum Setting { STATIC, TEMPORAL, WINDOWED };
+
+int check_hop(const char* who, Setting setting, const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level) {
   RG_CHECK(level >= 1 && level < RG_MAX_LEVELS, "%s: level %d not in 1..%d", who, level, RG_MAX_LEVELS - 1);
   RG_CHECK(batch > 0 && n_ent > 0, "%s: batch=%d n_ent=%d must be positive", who, batch, n_ent);
   RG_CHECK(f != nullptr && g != nullptr, "%s: NULL frontier or graph", who);
   RG_CHECK(batch == f->B && n_ent == f->n_ent, "%s: batch=%d n_ent=%d but the frontier has batch %d, n_ent %d", who, batch, n_ent,
            f->B, f->n_ent);
   RG_CHECK(g->n_ent == f->n_ent, "%s: graph has %d entities, frontier %d", who, g->n_ent, f->n_ent);
-  if (temporal) {
+  if (setting == WINDOWED) {
+    RG_CHECK(g->n_time > 0 && g->in_time, "%s: the graph has no row ids (build it with rg_tgraph_create, time field = data row)", who);
+    RG_CHECK(f->win_lo && f->win_hi, "%s: call rg_frontier_set_window first", who);
+  } else if (setting == TEMPORAL) {
     RG_CHECK(g->n_time > 0 && g->in_time, "%s: temporal graphs only (rg_tgraph_create)", who);
-    RG_CHECK(f->win_lo == nullptr, "%s: the frontier has a window set (extrapolation is not supported)", who);
+    RG_CHECK(f->win_lo == nullptr, "%s: the frontier has a window set (use rg_xexplain_count / rg_xexplain_emit)", who);
   } else {
     RG_CHECK(g->n_time == 0, "%s: static graphs only (rg_graph_create)", who);
   }
@@ -182,12 +205,20 @@ int fill_args(const char* who, const rg_frontier* f, const rg_graph* g, int32_t 
 
 size_t count_bytes(const rg_frontier* f) { return rg::align_up((size_t)f->B * f->W * 4, 256); }
 
-int count_hop(const char* who, bool temporal, const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level,
+// the extrapolation setting's part of the arguments: the frontier's windows and the graph's row ids
+void fill_window(const rg_frontier* f, const rg_graph* g, XExArgs* A) {
+  A->in_time = g->in_time; A->time_out = nullptr;
+  A->win_lo = f->win_lo; A->win_hi = f->win_hi; A->n_data = f->win_n_data;
+}
+
+template <Setting SETTING>
+int count_hop(const char* who, const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level,
               const uint32_t* marks, const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha,
               const float* b_alpha, int32_t attn_dim, float min_alpha, uint32_t* marks_prev_out, int32_t* word_ptr_out, void* scratch,
               size_t scratch_bytes, int64_t* n_edges_host, void* stream) {
-  if (check_hop(who, temporal, f, g, batch, n_ent, level)) return 1;
-  ExArgs A;
+  if (check_hop(who, SETTING, f, g, batch, n_ent, level)) return 1;
+  std::conditional_t<SETTING == WINDOWED, XExArgs, ExArgs> A;     // (the temporal attention does not read the time: the static pass)
+  if constexpr (SETTING == WINDOWED) fill_window(f, g, &A);
   if (fill_args(who, f, g, level, marks, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim, min_alpha, &A)) return 1;
   RG_CHECK(marks_prev_out && word_ptr_out && n_edges_host, "%s: NULL argument", who);
   RG_CHECK(scratch && scratch_bytes >= rg_explain_scratch_bytes(f) && ((uintptr_t)scratch & 255) == 0,      // (declared in redgnn.h)
@@ -196,7 +227,7 @@ int count_hop(const char* who, bool temporal, const rg_frontier* f, const rg_gra
   A.marks_prev = marks_prev_out;
   A.word_count = (int32_t*)scratch;
   if (rg::zero_async(marks_prev_out, (size_t)A.n_words * 4, s)) return 1;
-  hipLaunchKernelGGL(explain_kernel<false>, dim3(rg::ceil_div(A.n_words, EX_BLOCK)), dim3(EX_BLOCK), 0, s, A);
+  hipLaunchKernelGGL((explain_kernel<false, false, SETTING == WINDOWED>), dim3(rg::ceil_div(A.n_words, EX_BLOCK)), dim3(EX_BLOCK), 0, s, A);
   RG_LAUNCH_CHECK();
   int32_t* scan_scr = (int32_t*)((char*)scratch + count_bytes(f));
   if (rg::scan_exclusive((const uint32_t*)A.word_count, word_ptr_out, A.n_words, false, word_ptr_out + A.n_words, scan_scr, s)) return 1;
@@ -207,19 +238,20 @@ int count_hop(const char* who, bool temporal, const rg_frontier* f, const rg_gra
   return 0;
 }
 
-template <bool TIME>
+template <bool TIME, bool WINDOW = false>
 int emit_hop(const char* who, const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level, const uint32_t* marks,
              const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha,
              int32_t attn_dim, float min_alpha, const int32_t* word_ptr, int32_t* edges_out, float* alpha_out, int32_t* time_out,
              void* stream) {
-  if (check_hop(who, TIME, f, g, batch, n_ent, level)) return 1;
-  std::conditional_t<TIME, TExArgs, ExArgs> A;
+  if (check_hop(who, WINDOW ? WINDOWED : TIME ? TEMPORAL : STATIC, f, g, batch, n_ent, level)) return 1;
+  std::conditional_t<WINDOW, XExArgs, std::conditional_t<TIME, TExArgs, ExArgs>> A;
+  if constexpr (WINDOW) fill_window(f, g, &A);
   if (fill_args(who, f, g, level, marks, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim, min_alpha, &A)) return 1;
   RG_CHECK(word_ptr && edges_out && alpha_out && (!TIME || time_out), "%s: NULL argument", who);
   RG_CHECK(((uintptr_t)edges_out & 15) == 0, "%s: edges_out must be 16-B aligned", who);
   A.word_ptr = word_ptr; A.edges = (int4*)edges_out; A.alpha = alpha_out;
   if constexpr (TIME) { A.in_time = g->in_time; A.time_out = time_out; }
-  hipLaunchKernelGGL((explain_kernel<true, TIME>), dim3(rg::ceil_div(A.n_words, EX_BLOCK)), dim3(EX_BLOCK), 0, (hipStream_t)stream, A);
+  hipLaunchKernelGGL((explain_kernel<true, TIME, WINDOW>), dim3(rg::ceil_div(A.n_words, EX_BLOCK)), dim3(EX_BLOCK), 0, (hipStream_t)stream, A);
   RG_LAUNCH_CHECK();
   return 0;
 }
@@ -255,7 +287,7 @@ int rg_explain_count(const rg_frontier* f, const rg_graph* g, int32_t batch, int
                      const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha,
                      int32_t attn_dim, float min_alpha, uint32_t* marks_prev_out, int32_t* word_ptr_out, void* scratch,
                      size_t scratch_bytes, int64_t* n_edges_host, void* stream) {
-  return count_hop("rg_explain_count", false, f, g, batch, n_ent, level, marks, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim, min_alpha,
+  return count_hop<STATIC>("rg_explain_count", f, g, batch, n_ent, level, marks, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim, min_alpha,
                    marks_prev_out, word_ptr_out, scratch, scratch_bytes, n_edges_host, stream);
 }
 
@@ -263,7 +295,7 @@ int rg_texplain_count(const rg_frontier* f, const rg_graph* g, int32_t batch, in
                       const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha,
                       int32_t attn_dim, float min_alpha, uint32_t* marks_prev_out, int32_t* word_ptr_out, void* scratch,
                       size_t scratch_bytes, int64_t* n_edges_host, void* stream) {
-  return count_hop("rg_texplain_count", true, f, g, batch, n_ent, level, marks, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim, min_alpha,
+  return count_hop<TEMPORAL>("rg_texplain_count", f, g, batch, n_ent, level, marks, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim, min_alpha,
                    marks_prev_out, word_ptr_out, scratch, scratch_bytes, n_edges_host, stream);
 }
 
@@ -280,6 +312,22 @@ int rg_texplain_emit(const rg_frontier* f, const rg_graph* g, int32_t batch, int
                      int32_t* time_out, void* stream) {
   return emit_hop<true>("rg_texplain_emit", f, g, batch, n_ent, level, marks, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim, min_alpha,
                         word_ptr, edges_out, alpha_out, time_out, stream);
+}
+
+int rg_xexplain_count(const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level, const uint32_t* marks,
+                      const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha,
+                      int32_t attn_dim, float min_alpha, uint32_t* marks_prev_out, int32_t* word_ptr_out, void* scratch,
+                      size_t scratch_bytes, int64_t* n_edges_host, void* stream) {
+  return count_hop<WINDOWED>("rg_xexplain_count", f, g, batch, n_ent, level, marks, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim,
+                   min_alpha, marks_prev_out, word_ptr_out, scratch, scratch_bytes, n_edges_host, stream);
+}
+
+int rg_xexplain_emit(const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level, const uint32_t* marks,
+                     const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha,
+                     int32_t attn_dim, float min_alpha, const int32_t* word_ptr, int32_t* edges_out, float* alpha_out,
+                     int32_t* row_out, void* stream) {
+  return emit_hop<true, true>("rg_xexplain_emit", f, g, batch, n_ent, level, marks, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim,
+                              min_alpha, word_ptr, edges_out, alpha_out, row_out, stream);
 }
 
 int rg_explain_gather(int64_t n, int32_t hop, int32_t batch, const int32_t* edges, const float* alpha, const int64_t* row_first,

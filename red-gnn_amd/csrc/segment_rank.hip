@@ -7,7 +7,7 @@
 // kept.  The known objects come as the sorted CSR rg_topk reads (keys / ptr / idx); a key the index lacks filters nothing.
 //
 // Only integer counters, reduced in a fixed order: a query's result depends on its own segment and lists alone, bit for bit.
-#include "common.h"
+#include "select.h"
 
 namespace {
 
@@ -18,33 +18,6 @@ constexpr int LIST_LDS = 256;           // a known-object list of up to this man
 __device__ __forceinline__ long long wave_sum(long long v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
   return v;
-}
-
-// [kb, ke) = the index's list of `key`; kb == ke when the index lacks it
-__device__ __forceinline__ void key_range(const int64_t* __restrict__ keys, const int64_t* __restrict__ ptr, int64_t n_keys, int64_t key,
-                                          int64_t* kb, int64_t* ke) {
-  int64_t lo = 0, hi = n_keys;          // first index with keys[i] >= key
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (keys[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  *kb = *ke = 0;
-  if (lo < n_keys && keys[lo] == key) {
-    *kb = ptr[lo];
-    *ke = max(ptr[lo + 1], *kb);
-  }
-}
-
-// is x among list[0, n) (ascending)?
-__device__ __forceinline__ bool list_has(const int32_t* list, int64_t n, int32_t x) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    const int32_t v = list[mid];
-    if (v == x) return true;
-    if (v < x) lo = mid + 1; else hi = mid;
-  }
-  return false;
 }
 
 template <typename PTR>

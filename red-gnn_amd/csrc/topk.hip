@@ -12,7 +12,7 @@
 //
 // STAGED: the row's key32 values are kept in LDS after the first pass (rows up to TOPK_STAGE_MAX entities); otherwise each pass
 // re-reads the row from global memory (L2 / MALL).  Only integer LDS atomics: the result does not depend on timing.
-#include "common.h"
+#include "select.h"
 
 namespace {
 
@@ -24,15 +24,6 @@ constexpr int32_t TOPK_STAGE_MAX = 32768;    // 128 KiB of key32 + 16 KiB of his
 // layout of the dynamic LDS: [sub-histograms int32 TW x 256][candidates uint64 TOPK_MAX][control int32 16][key32 n_ent (STAGED)]
 constexpr size_t LDS_HIST = (size_t)TW * 256 * 4, LDS_CAND = (size_t)TOPK_MAX * 8, LDS_CTRL = 16 * 4;
 constexpr size_t LDS_FIXED = LDS_HIST + LDS_CAND + LDS_CTRL;
-
-__device__ __forceinline__ uint32_t key32(float x) {
-  uint32_t u = __float_as_uint(x);
-  if (x != x) return 0u;                         // NaN below -inf (whose key is 0x007FFFFF)
-  if (u == 0x80000000u) u = 0u;                  // -0 == +0
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ uint64_t order_key(uint32_t k32, uint32_t j) { return ((uint64_t)k32 << 32) | (uint64_t)(0xFFFFFFFFu - j); }
 
 // key32 of the row's entries j0 + u*TT, u < UNR, all loads issued before any is used (UNR of them in flight per thread: a wide row is
 // re-read from L2 / MALL on every pass, and one workgroup per row leaves most CUs with few waves to hide that latency); past the row: 0

@@ -398,9 +398,10 @@ def explain_hop(frontier, graph, level, marks, a_s, a_r, a_q, w_alpha, b_alpha, 
     return marks_prev, edges, alpha
 
 
-def texplain_hop(frontier, graph, level, marks, a_s, a_r, a_q, w_alpha, b_alpha, attn_dim, min_alpha):
+def texplain_hop(frontier, graph, level, marks, a_s, a_r, a_q, w_alpha, b_alpha, attn_dim, min_alpha, entry="rg_texplain"):
     """explain_hop on a temporal graph (rg_texplain_count + rg_texplain_emit).  Returns (marks of the heads [B, W], edges int32 [E, 4] =
     (row, head, rel, tail) in (row, tail, CSR position) order, alpha [E], time int32 [E] = the edges' time ids)."""
+    count, emit = getattr(_lib.lib(), entry + "_count"), getattr(_lib.lib(), entry + "_emit")
     for t in (a_s, a_r, a_q, w_alpha, b_alpha):
         assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
     ap = a_s.shape[1]
@@ -418,17 +419,23 @@ def texplain_hop(frontier, graph, level, marks, a_s, a_r, a_q, w_alpha, b_alpha,
     if EXPLAIN_EVENTS is not None:
         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         ev[0].record()
-    _lib.check(L.rg_texplain_count(*args, _lib.ptr(marks_prev), _lib.ptr(word_ptr), C.c_void_p(aligned),
+    _lib.check(count(*args, _lib.ptr(marks_prev), _lib.ptr(word_ptr), C.c_void_p(aligned),
                                    scratch.numel() - (aligned - base), C.byref(n_e), _lib.stream_ptr()))
     edges = torch.empty((n_e.value, 4), dtype=torch.int32, device=dev)
     alpha = torch.empty(n_e.value, dtype=torch.float32, device=dev)
     time = torch.empty(n_e.value, dtype=torch.int32, device=dev)
     if n_e.value:
-        _lib.check(L.rg_texplain_emit(*args, _lib.ptr(word_ptr), _lib.ptr(edges), _lib.ptr(alpha), _lib.ptr(time), _lib.stream_ptr()))
+        _lib.check(emit(*args, _lib.ptr(word_ptr), _lib.ptr(edges), _lib.ptr(alpha), _lib.ptr(time), _lib.stream_ptr()))
     if ev is not None:
         ev[1].record()
         EXPLAIN_EVENTS.append((ev[0], ev[1], level, n_e.value))
     return marks_prev, edges, alpha, time
+
+
+def xexplain_hop(frontier, graph, level, marks, a_s, a_r, a_q, w_alpha, b_alpha, attn_dim, min_alpha):
+    """explain_hop of the extrapolation model (rg_xexplain_count + rg_xexplain_emit) on a frontier with its row windows set: as
+    texplain_hop, the fourth result being the edges' data rows int32 [E] (>= the number of data rows for a self-loop)."""
+    return texplain_hop(frontier, graph, level, marks, a_s, a_r, a_q, w_alpha, b_alpha, attn_dim, min_alpha, entry="rg_xexplain")
 
 
 def explain_gather(hop, batch, edges, alpha, row_first, row_base, edges_out, alpha_out):
@@ -897,3 +904,27 @@ def segment_rank(scores, ent, seg_ptr, target, key_sp=None, known_sp=None, key_s
                                           p(sp[0]), p(sp[1]), p(sp[2]), p(sp[3]), sp[4], p(spt[0]), p(spt[1]), p(spt[2]), p(spt[3]), spt[4],
                                           p(rank), p(rank_fil), p(rank_fil_t), p(found), _lib.stream_ptr()))
     return rank, rank_fil, rank_fil_t, found
+
+
+SEGMENT_TOPK_STAGE_MAX = 24576       # csrc/segment_topk.hip: SEG_STAGE_MAX (longer segments are re-read on every pass of the select)
+SEGMENT_TOPK_LIST_LDS = 256          # ... SEG_LIST_LDS (longer known lists are searched in memory)
+
+
+def segment_topk(scores, ent, seg_ptr, k, q_key=None, known=None, want_prob=True):
+    """Filtered top-k (rg_segment_topk) of every query's segment of visited pairs: (ids int32 [B, k], scores fp32 [B, k], prob fp32
+    [B, k] or None), score descending then entity id ascending, -1 / -inf / 0 past the query's kept pairs.  ``scores`` (logits) fp32
+    [N], ``ent`` int32 [N] and ``seg_ptr`` int32 or int64 [B+1] as segment_rank; ``known`` = (keys int64, ptr int64, idx int32) device
+    tensors with the queries' keys ``q_key`` int64 [B], None excluding nothing.  prob: the per-query softmax over the whole segment."""
+    assert scores.is_cuda and scores.dtype == torch.float32 and scores.is_contiguous() and scores.dim() == 1
+    assert ent.is_cuda and ent.dtype == torch.int32 and ent.is_contiguous() and ent.shape == scores.shape
+    assert seg_ptr.is_cuda and seg_ptr.dtype in (torch.int32, torch.int64) and seg_ptr.is_contiguous() and seg_ptr.dim() == 1
+    B = seg_ptr.numel() - 1
+    dev = scores.device
+    idx = torch.empty((B, k), dtype=torch.int32, device=dev)
+    val = torch.empty((B, k), dtype=torch.float32, device=dev)
+    prob = torch.empty((B, k), dtype=torch.float32, device=dev) if want_prob else None
+    kn = _known_args(known, q_key, B, "segment_topk: known-object index")
+    p = _lib.ptr
+    _lib.check(_lib.lib().rg_segment_topk(p(scores), p(ent), scores.numel(), p(seg_ptr), int(seg_ptr.dtype == torch.int64), B, int(k),
+                                          p(kn[0]), p(kn[1]), p(kn[2]), p(kn[3]), kn[4], p(idx), p(val), p(prob), _lib.stream_ptr()))
+    return idx, val, prob

@@ -13,6 +13,10 @@ one backward marking pass per hop reads only the marked tails' CSR rows.  This m
 Temporal interpolation (T_RED_GNN.explain, rg_texplain_*): ``rd = model.explain(batch, objs)`` with the batch dict of forward; every
 edge also carries its time id (``rd.time``), ``rd.q_time`` is the rows' query time and ``rd.direction()`` the forward's past / now /
 future of each edge.
+
+Temporal extrapolation (extrapolation.T_RED_GNN.explain, rg_xexplain_*): ``rd = model.explain(X, objs)`` with the batch object of
+forward; ``rd.data_row`` names the past fact behind every edge (-1: a self-loop, relation id n_rel), ``rd.time`` its day and
+``rd.lag()`` how many days before the query it lies.
 """
 from dataclasses import dataclass
 
@@ -37,6 +41,9 @@ class RDigraph:
     time     int32 [E]     temporal models only (None otherwise): the time id of each edge; a fact repeated at several times is one
                            edge per time, in CSR order
     q_time   int32 [B]     temporal models only (None otherwise): the query time of each row
+    data_row int32 [E]     extrapolation only (None otherwise): the edge's index into the model's data array, -1 for a self-loop;
+                           there ``time`` is the day the forward used for the edge (the row's day; a self-loop's: the first day of
+                           the row's window) and ``q_time`` the query's day
     """
     edges: torch.Tensor
     alpha: torch.Tensor
@@ -46,6 +53,7 @@ class RDigraph:
     n_hops: int
     time: torch.Tensor = None
     q_time: torch.Tensor = None
+    data_row: torch.Tensor = None
 
     def direction(self):
         """int8 [E]: each edge's direction against its row's query time, the temporal forward's convention (dt = edge time - query
@@ -54,6 +62,13 @@ class RDigraph:
             raise ValueError("direction: a static r-digraph has no edge times")
         dt = self.time.long() - self.q_time.long()[self.edges[:, 0].long()]
         return (dt > 0).to(torch.int8) * 2 + (dt == 0).to(torch.int8)
+
+    def lag(self):
+        """int32 [E]: query time of the edge's row - edge time, the row of the relative-time table the extrapolation forward read for
+        the edge.  Temporal digraphs only."""
+        if self.time is None or self.q_time is None:
+            raise ValueError("lag: a static r-digraph has no edge times")
+        return self.q_time[self.edges[:, 0].long()] - self.time
 
     def strongest_paths(self):
         """Per row, the length-L path s -> o inside the digraph with the largest product of alpha (products in float64, left to right
@@ -241,6 +256,63 @@ def explain_temporal(model, batch, objs=None, min_alpha=0.0):
         edges, alpha, offsets, time = _assemble(hops, n, L, device)
     return RDigraph(edges=edges, alpha=alpha, offsets=offsets, reached=reached, score=score, n_hops=L, time=time,
                     q_time=q_time.clone())
+
+
+def explain_extrapolation(model, X, objs=None, min_alpha=0.0):
+    """extrapolation.T_RED_GNN.explain (see there): the temporal driver on the one-graph layout, the hop call testing every edge
+    against its query's row window; the third list carried along is the edges' data row."""
+    from .extrapolation import _int_ids, check_batch
+    from .temporal import eval_semantics
+    src, _, _ = check_batch(model, X, "explain")
+    n, n_ent = len(src), model.n_ent
+    objs_h = None
+    if objs is not None:
+        objs_h = _int_ids(objs, "explain", "objs")
+        if len(objs_h) != n:
+            raise ValueError("explain: %d answers for %d rows" % (len(objs_h), n))
+        if objs_h.min() < 0 or objs_h.max() >= n_ent:
+            raise ValueError("answer id out of range (n_ent=%d)" % n_ent)
+    tau = float(min_alpha)
+    if tau != tau:
+        raise ValueError("explain: min_alpha is NaN")
+    device = engine._require_gpu(model.linear_classifier.weight.device)
+    L, a = model.n_layer, model.attn_dim
+    kept = []
+    try:
+        with torch.no_grad(), eval_semantics(model):
+            logits, _, nodes, _ = model._run(X, dense=False, kept=kept)
+            fr, graph, q_time, loop_time = (kept[0][k] for k in ("frontier", "graph", "q_time", "loop_time"))
+            layers = kept[1:]
+            seg_ptr = torch.searchsorted(nodes[:, 0].contiguous(), torch.arange(n + 1, dtype=torch.int32, device=device))
+            ent = nodes[:, 1].contiguous()
+            if objs_h is None:                               # each row's own top answer: the smallest id on a tie
+                objs_t = engine.segment_topk(logits.contiguous(), ent, seg_ptr, 1, want_prob=False)[0].reshape(-1).long()
+            else:
+                objs_t = torch.as_tensor(objs_h, dtype=torch.int64).to(device)
+            marks, reached = engine.explain_seed(fr, L, objs_t.to(torch.int32).contiguous())
+            zero_b = torch.zeros(1, device=device)           # the attention has no bias
+            hops = [None] * (L + 1)
+            for l in range(L, 0, -1):
+                k = layers[l - 1]
+                marks, e, al, row = engine.xexplain_hop(fr, graph, l, marks, k["a_s"].detach().contiguous(), k["a_r"].detach().contiguous(),
+                                                        k["a_q"].detach().contiguous(), k["w_alpha"].detach().contiguous(), zero_b, a, tau)
+                hops[l] = (e, al, row)
+            if tau > 0.0:
+                hops = _forward_sweep(hops, L, n_ent)
+            # the logit of o: its pair's position in the sorted (query, entity) keys
+            key = nodes[:, 0].long() * n_ent + nodes[:, 1].long()
+            want = torch.arange(n, device=device) * n_ent + objs_t.clamp(min=0)
+            pos = torch.searchsorted(key, want).clamp_(max=max(key.numel() - 1, 0))
+            score = torch.where(reached & (key[pos] == want), logits[pos], torch.zeros_like(logits[pos])).contiguous()
+            edges, alpha, offsets, row = _assemble(hops, n, L, device)
+            loop = row >= model.n_data
+            time = torch.where(loop, loop_time[edges[:, 0].long()], model.row_time[row.clamp(max=max(model.n_data - 1, 0)).long()])
+            data_row = torch.where(loop, torch.full_like(row, -1), row)
+    finally:
+        if kept:                                             # an exception must not leave a windowed frontier in the pool
+            kept[0]["frontier"].set_window(None, None, 0)
+    return RDigraph(edges=edges, alpha=alpha, offsets=offsets, reached=reached, score=score, n_hops=L, time=time.to(torch.int32),
+                    q_time=q_time.clone(), data_row=data_row)
 
 
 def _forward_sweep(hops, L, n_ent):

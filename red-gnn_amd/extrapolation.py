@@ -17,6 +17,11 @@ dictionaries, ``T_RED_GNN.rank_batch`` ranks a batch's softmax scores raw, filte
 (csrc/segment_rank.hip, rg_segment_rank) and ``T_RED_GNN.evaluate`` batches a split and returns the reference's metrics from one host
 copy.  ``segment_rank_fil`` is the host restatement the device path is tested against.
 
+Forecasts and their explanation: ``T_RED_GNN.predict(X, k, known)`` returns each query's k best objects among the entities its window
+reaches, known objects excluded, in one HIP launch on the forward's pairs (csrc/segment_topk.hip, rg_segment_topk), and
+``T_RED_GNN.explain(X, objs)`` the r-digraph of past facts behind a forecast, every edge with its attention and data row
+(csrc/explain.hip, rg_xexplain_count / rg_xexplain_emit; the driver is explain.explain_extrapolation).
+
 Parity: the reference's model file cannot be imported in the build container (torch_scatter, pyvis, rtdl_revisiting_models are absent),
 so this path is checked against the oracle's restatement only - parity UNPINNED - except ``segment_rank_fil``, whose fixture comes
 from the reference's importable ``segment.py``.
@@ -154,9 +159,11 @@ class T_RED_GNN(nn.Module):
         _, soft, nodes, score_all = self._run(X, dense=True)
         return score_all, (soft, nodes.long().cpu().numpy())
 
-    def _run(self, X, dense=False):
+    def _run(self, X, dense=False, kept=None):
         """The forward on the device: (logits [N], per-query softmax [N], visited (batch, entity) pairs int32 [N,2] sorted, score_all) -
-        score_all [B, n_ent] only with ``dense`` (else None: nothing of size B * n_ent is built, nothing is copied to the host)."""
+        score_all [B, n_ent] only with ``dense`` (else None: nothing of size B * n_ent is built, nothing is copied to the host).
+        ``kept`` (a list, for explain): the frontier keeps all n_layer + 1 levels and its windows stay set - the caller clears them; the
+        list receives dict(frontier, graph, q_rel, q_time, loop_time, win_lo, win_hi), then per layer dict(a_s, a_r, a_q, w_alpha)."""
         device = self.linear_classifier.weight.device
         engine._require_gpu(device)
         src, rel = np.asarray(X.src_idx), np.asarray(X.rel_idx)
@@ -169,8 +176,10 @@ class T_RED_GNN(nn.Module):
         q_time, loop_time = to32(cur_t), to32(begin)                                # self-loops carry time begin * granularity (:172)
         q_rel = torch.as_tensor(rel, dtype=torch.int64).to(device)
         with_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
-        fr = self._frontiers.get(self.n_ent, n, self.n_layer + 1 if with_grad else 2, device)
+        fr = self._frontiers.get(self.n_ent, n, self.n_layer + 1 if with_grad or kept is not None else 2, device)
         fr.set_window(win_lo, win_hi, self.n_data)
+        if kept is not None:
+            kept.append(dict(frontier=fr, graph=self.graph, q_rel=q_rel, q_time=q_time, loop_time=loop_time, win_lo=win_lo, win_hi=win_hi))
         fr.reset(to32(src))
         lease = engine.FrontierLease(fr) if with_grad else None
         d, a = self.hidden_dim, self.attn_dim
@@ -199,6 +208,8 @@ class T_RED_GNN(nn.Module):
                 hidden_p = padc(tall_linear(hidden, w_past)).contiguous()                         # W_past (h + r + tau) = W_past h + ... (:203-205)
                 rela_p = padc(F.linear(rela, w_past)).contiguous()
                 w_alpha = w2.reshape(-1).contiguous()
+                if kept is not None:
+                    kept.append(dict(a_s=a_s, a_r=a_r, a_q=a_q, w_alpha=w_alpha))
                 if with_grad:
                     agg = _XAggregate.apply(hidden_p, rela_p, time_p, a_s, a_r, a_q, w_alpha, zero_b, lease, self.graph, fr.level, n_new,
                                             q_time, loop_time, self.row_time, self.n_data, d, a)
@@ -217,7 +228,7 @@ class T_RED_GNN(nn.Module):
             row_max = torch.full((n,), float("-inf"), device=device).scatter_reduce(0, b_idx, result.detach(), "amax")
             ex = torch.exp(result - row_max[b_idx])
             soft = ex / torch.zeros(n, device=device).index_add(0, b_idx, ex)[b_idx]
-        if not with_grad:
+        if not with_grad and kept is None:
             fr.set_window(None, None, 0)         # (a training forward's frontier keeps its windows for the backward: every reset sets them anew)
         self.last_stats = dict(n_edges=n_edges, n_nodes=int(nodes.shape[0]))
         return result, soft, nodes, score_all
@@ -258,6 +269,42 @@ class T_RED_GNN(nn.Module):
             rank, rank_fil, rank_fil_t, found = engine.segment_rank(soft.contiguous(), ent, seg_ptr, torch.as_tensor(tgt, dtype=torch.int32).to(device),
                                                                     keys[0], known[0], keys[1], known[1])
         return RankBatch(rank=rank, found=found.bool(), rank_fil=rank_fil, rank_fil_t=rank_fil_t, soft=soft, nodes=nodes)
+
+    def predict(self, X, k=10, known=None):
+        """The k best forecasts of every query (s, p, ?, t) among the entities its window reaches - the reference ranks a query only
+        there (main.py:383) - without those ``known`` lists for it: a KnownObjects index of the (s, p) or the (s, p, t) kind
+        (known_objects_index); None excludes nothing.  X as forward's.  Returns prediction.Prediction: ids int64 [B, k] (-1 where the
+        query has fewer than k candidates), scores = the logits (-inf there), prob = the per-query softmax over ALL visited entities
+        (0 there), ordered by logit descending, then entity id ascending.  The forward without the [B, n_ent] matrix, then one HIP
+        launch (csrc/segment_topk.hip); nothing is copied to the host.  No gradients, eval mode (the training flags come back)."""
+        from .prediction import K_MAX, Prediction
+        from .temporal import eval_semantics
+        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)):
+            raise ValueError("predict: k must be an integer in 1..%d (got %r)" % (K_MAX, k))
+        k = int(k)
+        if not 1 <= k <= K_MAX:
+            raise ValueError("predict: k=%d not in 1..%d" % (k, K_MAX))
+        src, rel, ts = check_batch(self, X, "predict")
+        device = engine._require_gpu(self.linear_classifier.weight.device)
+        n = len(src)
+        with torch.no_grad(), eval_semantics(self):
+            logits, _, nodes, _ = self._run(X, dense=False)
+            seg_ptr = torch.searchsorted(nodes[:, 0].contiguous(), torch.arange(n + 1, dtype=torch.int32, device=device))
+            q_key = known_dev = None
+            if known is not None:
+                q_key = torch.as_tensor(known.query_keys(src, rel, ts)).to(device)
+                known_dev = self._index_on_device(known, device)
+            idx, val, prob = engine.segment_topk(logits.contiguous(), nodes[:, 1].contiguous(), seg_ptr, k, q_key, known_dev)
+        return Prediction(ids=idx.long(), scores=val, prob=prob)
+
+    def explain(self, X, objs=None, min_alpha=0.0):
+        """The past facts a forecast is built on: for row b = (s, p, t) of X and the answer objs[b] (None: the row's own top
+        forecast, predict(k=1) without a filter) the r-digraph of explain.RDigraph - the union of the length-L paths s -> o inside the
+        row's window, every edge with its attention alpha (>= min_alpha; the paths are re-closed after the cut).  ``data_row`` is the
+        edge's index into the model's data array (-1 for a self-loop, whose relation id is n_rel), ``time`` the day the forward used
+        for it, ``q_time`` the query's day and ``lag()`` their difference.  Extraction in HIP (rg_xexplain_*, csrc/explain.hip)."""
+        from .explain import explain_extrapolation
+        return explain_extrapolation(self, X, objs, min_alpha)
 
     def evaluate(self, queries, sp_index=None, spt_index=None, batch_size=64, return_ranks=False):
         """The validation loop of main.py:353-472 for a split: ``queries`` int [n, 4] = (s, p, o, ts), in batches of ``batch_size``
@@ -395,6 +442,21 @@ def _int_ids(x, who, name):
     if a.size and (a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer)):      # (no silent truncation of 1.7 to 1)
         raise ValueError("%s: %s must hold integer ids (got dtype %s)" % (who, name, a.dtype))
     return a.astype(np.int64)
+
+
+def check_batch(model, X, who):
+    """(src, rel, ts) int64 [B] of a batch object, checked on the host as evaluate checks its queries: integer ids, one relation and
+    time per subject, at least one query, ids and times inside the model's data."""
+    src, rel, ts = (_int_ids(x, who, k) for x, k in ((X.src_idx, "src_idx"), (X.rel_idx, "rel_idx"), (X.ts, "ts")))
+    n = len(src)
+    if n == 0 or len(rel) != n or len(ts) != n:
+        raise ValueError("%s: need one relation and time per subject and at least one query (got %d, %d, %d)" % (who, n, len(rel), len(ts)))
+    if src.min() < 0 or src.max() >= model.n_ent or rel.min() < 0 or rel.max() >= model.n_rel_true:
+        raise ValueError("%s: subject / relation id out of range (n_ent=%d, n_rel=%d)" % (who, model.n_ent, model.n_rel_true))
+    if ts.min() < 0 or (ts // model.time_granularity).max() >= len(model.time_offset_list):
+        raise ValueError("%s: query time outside the model's data (0 <= ts // %d < %d)"
+                         % (who, model.time_granularity, len(model.time_offset_list)))
+    return src, rel, ts
 
 
 def _index_tensors(index, device):

@@ -8,6 +8,8 @@ The scores are forward()'s; the exclusion and the selection are one HIP launch (
 known answers as a sorted CSR over the query keys s * (2*n_rel + 1) + r (loader.known_index), copied to the device once.
 Temporal interpolation: ``model.predict(batch, k, known=temporal_known_index(quads, n_rel + 1, n_time))`` with the batch dict of
 forward; the keys are (head * n_rela_rows + rel) * n_time + time.
+Temporal extrapolation: ``model.predict(X, k, known=known_objects_index(...))`` (extrapolation.py) selects among the entities each
+query's window reaches (csrc/segment_topk.hip, rg_segment_topk) and also returns the softmax ``pred.prob``.
 """
 from dataclasses import dataclass
 
@@ -23,9 +25,11 @@ K_MAX = 1024
 @dataclass
 class Prediction:
     """ids int64 [B, k] (entity ids, -1 where the row has fewer than k candidates), scores float32 [B, k] (forward's scores of those
-    ids, -inf past the end).  Tensors on the device that computed them."""
+    ids, -inf past the end).  Tensors on the device that computed them.  ``prob`` (extrapolation only, None otherwise) float32 [B, k]:
+    the per-query softmax over the entities the query's window reaches, 0 past the end."""
     ids: torch.Tensor
     scores: torch.Tensor
+    prob: torch.Tensor = None
 
 
 def _known_on_device(loader, mode, device):
