@@ -385,6 +385,14 @@ int rg_dense_train_fwd_as(int64_t n, int32_t d, const float* agg, const float* h
 int rg_rows_addmm(const float* base, int64_t ldb, const float* g, int64_t ldg, int32_t k, const float* W, int32_t n, int64_t n_rows,
                   float* out, int64_t ldo, void* stream);
 
+/* out[r, :n] = x[r, :k] W^T (+ bias[:n] when bias is non-NULL) for n_rows node rows: W device float [n][k] (a linear layer's weight),
+ * row strides ldx >= k and ldo >= n in floats.  Every output element is one fmaf chain over k = 0..k-1 in order, so a row's result does
+ * not depend on the number of rows of the call (a GEMM library picks its kernel, and its order of additions, by the shape): the
+ * extrapolation model's inference forward uses it so that a query computes the same bits in every batch.  1 <= k <= 4096, n >= 1;
+ * columns are tiled so that a tile's weights fit 64 KB of LDS.  Allocates nothing, asynchronous on `stream`. */
+int rg_rows_linear(const float* x, int64_t n_rows, int64_t ldx, int32_t k, const float* w, const float* bias, int32_t n,
+                   float* out, int64_t ldo, void* stream);
+
 /* Adjoint of rg_dense_train_fwd for the node-row quantities (autograd of models.py:41,81-83): from grad_hidden [n,d] and the saved
  * x / gates_ws (/ mask, keep = 1 - p) it writes grad_gates_i, grad_gates_h [n,3d] (GRU pre-activation gradients, for the weight and
  * bias gradients the caller forms), grad_pre [n,d] (gradient at W_h's output, for dW_h), grad_agg [n,d] and grad_h0 [n,d] (the
@@ -494,6 +502,29 @@ int rg_attn_profile(const rg_frontier* f, const rg_graph* g, int32_t batch, int3
  * and the frontier must have no window set (extrapolation is not supported). */
 int rg_tattn_profile(const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level, int64_t n_old,
                      const int32_t* q_time, const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha,
+                     const float* b_alpha, int32_t attn_dim, int64_t* sum_out, int64_t* count_out, void* stream);
+
+/* The attention profile of a hop of the extrapolation model (extrapolation.py's one-graph layout: the time field of an edge is its data
+ * row, the frontier carries the queries' row windows), with the edge's lag in days, binned, as one more axis.  The edges are exactly the
+ * hop-`level` edges rg_xlayer_fwd aggregates for query b: the out-edges of b's level-(level-1) nodes whose data row is a self-loop
+ * (row >= n_data) or lies in [win_lo[b], win_hi[b]); n_data and the windows are the frontier's (rg_frontier_set_window), as for
+ * rg_xexplain_*.  Enumeration, alpha (rg_xlayer_fwd's, which does not read the time; pass b_alpha = 0) and the fixed-point sums are
+ * rg_attn_profile's.  Per edge the kernel forms the forward's time-table row
+ *   lag = min(max(q_time[b] - (row >= n_data ? loop_time[b] : row_time[row]), 0), n_lag - 1),   bin = lag_bin[lag]
+ * (q_time, loop_time device int32 [batch], row_time device int32 [n_data], lag_bin device uint8 [n_lag]) and adds
+ *   count_out[b][bin][rel] += 1,   sum_out[b][bin][rel] += llrintf(alpha_e * 2^32)
+ * sum_out / count_out: device int64 [batch][n_bins][n_rela_rows], caller-owned and caller-zeroed; the call adds.  An entry of lag_bin
+ * >= n_bins drops the edge: whatever the table holds, nothing is written outside the outputs.  1 <= n_bins <= 256,
+ * 1 <= n_lag <= 16384 (the table is staged in LDS).  Sums are exact integers: bit-identical across runs, across splits of a batch and
+ * across query order.  The bins live in LDS per workgroup where
+ *   16384 + n_rela_rows * (4 * ap + 12 * n_bins) + n_lag <= 81920 bytes (80 KiB: two workgroups per CU; 462 relation rows at ap = 8
+ * with 8 bins fit) - which budget is faster has not been measured - and above that the kernel adds per edge into the outputs directly
+ * (same integers, slower).  The graph must carry row ids (rg_tgraph_create) and the frontier must have its windows set.  Allocates
+ * nothing, asynchronous on `stream`. */
+int rg_xattn_profile(const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level, int64_t n_old,
+                     const int32_t* q_time, const int32_t* loop_time, const int32_t* row_time,
+                     const uint8_t* lag_bin, int32_t n_lag, int32_t n_bins,
+                     const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha,
                      const float* b_alpha, int32_t attn_dim, int64_t* sum_out, int64_t* count_out, void* stream);
 
 #ifdef __cplusplus

@@ -31,6 +31,24 @@
 // temporal attention does not read the time, so alpha is the static arithmetic.  Three bins per relation: the LDS path needs
 // n_rela_rows * (4 * ap + 36) bytes beside the 16 KB head list in 64 KB, i.e. at most 49152 / (4 * ap + 36) relation rows (945 at
 // ap = 4, 722 at ap = 8, 491 at ap = 16, 299 at ap = 32); above that the global-atomic path runs (same integers).
+//
+// Extrapolation (rg_xattn_profile, extrapolation.py's one-graph layout): the kernel's LAG instantiation.  out_time[entry] is the edge's
+// data row and the frontier carries the queries' row windows.  An out-edge of a level-(l-1) node of query b is a hop-l edge of b iff its
+// row is a self-loop (row >= n_data) or lies in [win_lo[b], win_hi[b]) - the forward's test (layer_fwd_kernel.h), n_data and the windows
+// taken from the frontier as rg_xexplain_* takes them.  Enumeration from the heads stays valid under a window: the windowed
+// rg_frontier_expand (hop_or_window_kernel) makes level l precisely the set of tails of these edges, so every edge that passes the
+// test ends in level l and no tail bitmap is read.  A head's CSR row is read over all times and filtered per edge, as the forward
+// does it.  The time does not enter alpha.  The edge is binned by the forward's time-table row:
+//   lag = min(max(q_time[b] - (row >= n_data ? loop_time[b] : row_time[row]), 0), n_lag - 1),  bin = lag_bin[lag]
+// with lag_bin a device uint8 [n_lag] table staged in LDS on both paths; cell = bin * n_rela_rows + rel, outputs
+// [B][n_bins][n_rela_rows].  An entry >= n_bins drops the edge, so no table content can make the kernel write outside the outputs.
+// 1 <= n_bins <= 256, 1 <= n_lag <= 16384.
+// LDS budget of this mode: 80 KiB per workgroup (two workgroups per CU of 160 KiB; hipFuncAttributeMaxDynamicSharedMemorySize is
+// raised above 64 KB), and the LDS path runs where
+//   16384 (head list) + n_rela_rows * (4 * ap + 12 * n_bins) + n_lag <= 81920
+// - ICEWS14's 462 relation rows at ap = 8 with 8 bins need 75.9 KB.  Which budget is faster has NOT been measured: 160 KiB would keep
+// larger tables in LDS at one workgroup (four waves) per CU, 64 KB would keep three workgroups per CU and send ICEWS14 to the
+// global-atomic path.  Above the budget the global-atomic path runs with the head list and the lag table in LDS (same integers).
 #include <algorithm>
 
 #include "attn.h"
@@ -75,14 +93,36 @@ struct TPfArgs : PfArgs {
   const int32_t* q_time;     // [B]
 };
 
-template <int AP4, bool LDS, bool DIR = false>
-__global__ __launch_bounds__(PF_BLOCK) void profile_kernel(std::conditional_t<DIR, TPfArgs, PfArgs> A) {
+struct XPfArgs : PfArgs {
+  const int32_t* out_time;   // data row of every CSR-by-head entry (>= n_data: a self-loop)
+  const int32_t* q_time;     // [B]
+  const int32_t* loop_time;  // [B] the day the forward gives query b's self-loops
+  const int32_t* row_time;   // [n_data] day of every data row
+  const int32_t* win_lo;     // [B] first data row of the query's window
+  const int32_t* win_hi;     // [B] one past its last
+  const uint8_t* lag_bin;    // [n_lag]
+  int n_data, n_lag, n_lbins;
+};
+
+constexpr int XPF_N_LAG_MAX = 16384;                   // the lag table is staged in LDS on both paths
+#ifndef RG_XPF_LDS_KIB
+#define RG_XPF_LDS_KIB 80                              // the LAG mode's budget (two workgroups per CU); -DRG_XPF_LDS_KIB=64..160 builds an A/B variant
+#endif
+constexpr size_t XPF_LDS_MAX = (size_t)RG_XPF_LDS_KIB * 1024;
+static_assert(RG_XPF_LDS_KIB >= 64 && RG_XPF_LDS_KIB <= 160, "the LAG budget: 64..160 KiB");
+
+template <bool DIR, bool LAG>
+using PfArgsOf = std::conditional_t<LAG, XPfArgs, std::conditional_t<DIR, TPfArgs, PfArgs>>;
+
+template <int AP4, bool LDS, bool DIR = false, bool LAG = false>
+__global__ __launch_bounds__(PF_BLOCK) void profile_kernel(PfArgsOf<DIR, LAG> A) {
   extern __shared__ __align__(16) unsigned char pf_smem[];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int b = blockIdx.y;
   uint16_t* heads = (uint16_t*)pf_smem + wv * PF_HEADS;
   float4* ar_l = (float4*)(pf_smem + PF_LIST_BYTES);
-  const int n_bins = DIR ? 3 * A.R : A.R;               // (direction, relation) cells of one query
+  int n_bins = DIR ? 3 * A.R : A.R;                     // (direction | lag bin, relation) cells of one query
+  if constexpr (LAG) n_bins = A.n_lbins * A.R;
   unsigned long long* sum_l = (unsigned long long*)(ar_l + (LDS ? A.R * AP4 : 0));
   uint32_t* cnt_l = (uint32_t*)(sum_l + (LDS ? n_bins : 0));
   if constexpr (LDS) {
@@ -92,6 +132,13 @@ __global__ __launch_bounds__(PF_BLOCK) void profile_kernel(std::conditional_t<DI
   }
   int qt = 0;
   if constexpr (DIR) qt = A.q_time[b];
+  int wlo = 0, whi = 0, loop_t = 0;
+  uint8_t* lag_l = (uint8_t*)(cnt_l + (LDS ? n_bins : 0));
+  if constexpr (LAG) {
+    qt = A.q_time[b]; loop_t = A.loop_time[b]; wlo = A.win_lo[b]; whi = A.win_hi[b];
+    for (int i = threadIdx.x; i < A.n_lag; i += PF_BLOCK) lag_l[i] = A.lag_bin[i];
+    __syncthreads();
+  }
   const float b_alpha = A.b_alpha[0];
   float4 w[AP4], q[AP4];
 #pragma unroll
@@ -146,7 +193,21 @@ __global__ __launch_bounds__(PF_BLOCK) void profile_kernel(std::conditional_t<DI
           const int entry = beg_s + (x - excl_s);
           const int r = A.out_rt[entry].x;
           const int s = s_base + k0 + sl;
-          if ((uint32_t)r < (uint32_t)A.R && s < A.n_old) {
+          bool keep = (uint32_t)r < (uint32_t)A.R && s < A.n_old;
+          int bin = r;
+          if constexpr (LAG) {
+            if (keep) {                               // the forward's window test and time-table row (layer_fwd_kernel.h)
+              const int row = A.out_time[entry];
+              keep = row >= A.n_data || (row >= wlo && row < whi);
+              if (keep) {
+                const int lag = min(max(qt - (row >= A.n_data ? loop_t : A.row_time[row]), 0), A.n_lag - 1);
+                const int lb = lag_l[lag];
+                keep = lb < A.n_lbins;                // an entry outside the bins drops the edge: never a cell past the outputs
+                bin = lb * A.R + r;
+              }
+            }
+          }
+          if (keep) {
             float z = b_alpha;
 #pragma unroll
             for (int k = 0; k < AP4; ++k) {
@@ -157,7 +218,6 @@ __global__ __launch_bounds__(PF_BLOCK) void profile_kernel(std::conditional_t<DI
             }
             const float alpha = rg::attn_alpha(z);
             const unsigned long long fx = (unsigned long long)llrintf(alpha * PF_SCALE);
-            int bin = r;
             if constexpr (DIR) {
               const int dt = A.out_time[entry] - qt;
               bin = (dt > 0 ? 2 : (dt == 0 ? 1 : 0)) * A.R + r;
@@ -189,14 +249,27 @@ __global__ __launch_bounds__(PF_BLOCK) void profile_kernel(std::conditional_t<DI
   }
 }
 
-// the entry points' checks and launch; DIR = the temporal profile (q_time non-NULL)
-template <bool DIR>
+// the lag arguments of rg_xattn_profile
+struct LagTable {
+  const int32_t* loop_time;
+  const int32_t* row_time;
+  const uint8_t* lag_bin;
+  int32_t n_lag, n_bins;
+};
+
+// the entry points' checks and launch; DIR = the temporal profile (q_time non-NULL), LAG = the extrapolation profile (q_time and x)
+template <bool DIR, bool LAG = false>
 int profile_hop(const char* who, const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level, int64_t n_old,
                 const int32_t* q_time, const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha,
-                const float* b_alpha, int32_t attn_dim, int64_t* sum_out, int64_t* count_out, void* stream) {
+                const float* b_alpha, int32_t attn_dim, int64_t* sum_out, int64_t* count_out, void* stream, const LagTable* x = nullptr) {
   RG_CHECK(level >= 1 && level < RG_MAX_LEVELS, "%s: level %d not in 1..%d", who, level, RG_MAX_LEVELS - 1);
   RG_CHECK(batch > 0 && n_ent > 0, "%s: batch=%d n_ent=%d must be positive", who, batch, n_ent);
-  RG_CHECK(a_s && a_r && a_q && w_alpha && b_alpha && sum_out && count_out && (!DIR || q_time), "%s: NULL argument", who);
+  RG_CHECK(a_s && a_r && a_q && w_alpha && b_alpha && sum_out && count_out && (!(DIR || LAG) || q_time), "%s: NULL argument", who);
+  if constexpr (LAG) {
+    RG_CHECK(x->loop_time && x->row_time && x->lag_bin, "%s: NULL argument", who);
+    RG_CHECK(x->n_bins >= 1 && x->n_bins <= 256, "%s: n_bins=%d not in 1..256", who, x->n_bins);
+    RG_CHECK(x->n_lag >= 1 && x->n_lag <= XPF_N_LAG_MAX, "%s: n_lag=%d not in 1..%d", who, x->n_lag, XPF_N_LAG_MAX);
+  }
   RG_CHECK(attn_dim > 0 && ap >= attn_dim && ap % 4 == 0 && ap <= 32, "%s: attn_dim=%d ap=%d (attention widths up to 32, ap a multiple of 4)",
            who, attn_dim, ap);
   RG_CHECK((((uintptr_t)a_s | (uintptr_t)a_r | (uintptr_t)a_q) & 15) == 0, "%s: attention tables must be 16-B aligned", who);
@@ -205,7 +278,10 @@ int profile_hop(const char* who, const rg_frontier* f, const rg_graph* g, int32_
   RG_CHECK(batch == f->B && n_ent == f->n_ent, "%s: batch=%d n_ent=%d but the frontier has batch %d, n_ent %d", who, batch, n_ent,
            f->B, f->n_ent);
   RG_CHECK(g->n_ent == f->n_ent, "%s: graph has %d entities, frontier %d", who, g->n_ent, f->n_ent);
-  if constexpr (DIR) {
+  if constexpr (LAG) {
+    RG_CHECK(g->n_time > 0 && g->out_time, "%s: the graph has no row ids (build it with rg_tgraph_create, time field = data row)", who);
+    RG_CHECK(f->win_lo && f->win_hi, "%s: the frontier has no window set (call rg_frontier_set_window first)", who);
+  } else if constexpr (DIR) {
     RG_CHECK(g->n_time > 0 && g->out_time, "%s: temporal graphs only (rg_tgraph_create)", who);
     RG_CHECK(f->win_lo == nullptr, "%s: the frontier has a window set (extrapolation is not supported)", who);
   } else {
@@ -216,28 +292,40 @@ int profile_hop(const char* who, const rg_frontier* f, const rg_graph* g, int32_
   RG_CHECK(batch <= 65535, "%s: batch=%d above 65535 queries per call", who, batch);
   const int64_t n_have = f->n_nodes[(level - 1) % f->n_levels];
   RG_CHECK(n_have >= 0 && n_old == n_have, "%s: n_old=%lld but level %d has %lld nodes", who, (long long)n_old, level - 1, (long long)n_have);
-  std::conditional_t<DIR, TPfArgs, PfArgs> A;
+  PfArgsOf<DIR, LAG> A;
   RG_CHECK(n_old <= INT32_MAX, "%s: n_old=%lld does not fit int32", who, (long long)n_old);
   A.bm_old = f->bm_of(level - 1); A.W = f->W; A.n_ent = f->n_ent; A.n_old = (int)n_old;
   A.out_ptr = g->out_ptr; A.out_rt = g->out_rt;
   A.a_s = (const float4*)a_s; A.a_r = (const float4*)a_r; A.a_q = (const float4*)a_q;
   A.w_alpha = w_alpha; A.b_alpha = b_alpha; A.attn_dim = attn_dim; A.R = g->n_rela_rows;
   A.sum_out = (unsigned long long*)sum_out; A.count_out = (unsigned long long*)count_out;
-  if constexpr (DIR) { A.out_time = g->out_time; A.q_time = q_time; }
+  if constexpr (DIR || LAG) { A.out_time = g->out_time; A.q_time = q_time; }
+  if constexpr (LAG) {
+    RG_CHECK((int64_t)x->n_bins * A.R <= INT32_MAX, "%s: n_bins=%d x %d relation rows does not fit int32", who, x->n_bins, A.R);
+    A.loop_time = x->loop_time; A.row_time = x->row_time; A.lag_bin = x->lag_bin; A.n_lag = x->n_lag; A.n_lbins = x->n_bins;
+    A.win_lo = f->win_lo; A.win_hi = f->win_hi; A.n_data = f->win_n_data;
+  }
   // words per wave step: 64, less for small batches so that the chip still gets a few thousand wave-sized pieces (any value gives the
   // same integers)
   A.gw = 64;
   while (A.gw > 4 && (int64_t)batch * rg::ceil_div(A.W, A.gw) < 8192) A.gw >>= 1;
   A.n_groups = (int)rg::ceil_div(A.W, A.gw);
   const int per_query = (int)std::min<int64_t>(rg::ceil_div(A.n_groups, PF_WAVES), std::max<int64_t>(1, rg::ceil_div(4096, batch)));
-  const size_t lds_bins = (size_t)A.R * ((size_t)ap * 4 + (DIR ? 36 : 12));
-  const bool lds = PF_LIST_BYTES + lds_bins <= PF_LDS_MAX;
-  const size_t smem = PF_LIST_BYTES + (lds ? lds_bins : 0);
+  size_t lds_bins = (size_t)A.R * ((size_t)ap * 4 + (DIR ? 36 : 12)), lds_fixed = PF_LIST_BYTES, lds_max = PF_LDS_MAX;
+  if constexpr (LAG) {       // n_rela_rows * (4 * ap + 12 * n_bins) beside the head list and the lag table in 80 KiB
+    lds_bins = (size_t)A.R * ((size_t)ap * 4 + 12 * (size_t)x->n_bins); lds_fixed += (size_t)x->n_lag; lds_max = XPF_LDS_MAX;
+  }
+  const bool lds = lds_fixed + lds_bins <= lds_max;
+  const size_t smem = lds_fixed + (lds ? lds_bins : 0);
   hipStream_t s = (hipStream_t)stream;
   return rg::with_ap4(ap / 4, who, [&](auto ap4) {
     constexpr int AP4 = decltype(ap4)::value;
-    if (lds) hipLaunchKernelGGL((profile_kernel<AP4, true, DIR>), dim3(per_query, batch), dim3(PF_BLOCK), smem, s, A);
-    else hipLaunchKernelGGL((profile_kernel<AP4, false, DIR>), dim3(per_query, batch), dim3(PF_BLOCK), smem, s, A);
+    if constexpr (LAG) {     // (only this mode asks for more than the default 64 KB of dynamic LDS)
+      if (smem > PF_LDS_MAX)
+        RG_HIP(hipFuncSetAttribute((const void*)profile_kernel<AP4, true, DIR, LAG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    }
+    if (lds) hipLaunchKernelGGL((profile_kernel<AP4, true, DIR, LAG>), dim3(per_query, batch), dim3(PF_BLOCK), smem, s, A);
+    else hipLaunchKernelGGL((profile_kernel<AP4, false, DIR, LAG>), dim3(per_query, batch), dim3(PF_BLOCK), smem, s, A);
     RG_LAUNCH_CHECK();
     return 0;
   });
@@ -259,6 +347,15 @@ int rg_tattn_profile(const rg_frontier* f, const rg_graph* g, int32_t batch, int
                      const float* b_alpha, int32_t attn_dim, int64_t* sum_out, int64_t* count_out, void* stream) {
   return profile_hop<true>("rg_tattn_profile", f, g, batch, n_ent, level, n_old, q_time, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim,
                            sum_out, count_out, stream);
+}
+
+int rg_xattn_profile(const rg_frontier* f, const rg_graph* g, int32_t batch, int32_t n_ent, int32_t level, int64_t n_old,
+                     const int32_t* q_time, const int32_t* loop_time, const int32_t* row_time, const uint8_t* lag_bin, int32_t n_lag,
+                     int32_t n_bins, const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha,
+                     const float* b_alpha, int32_t attn_dim, int64_t* sum_out, int64_t* count_out, void* stream) {
+  const LagTable x{loop_time, row_time, lag_bin, n_lag, n_bins};
+  return profile_hop<false, true>("rg_xattn_profile", f, g, batch, n_ent, level, n_old, q_time, a_s, a_r, a_q, ap, w_alpha, b_alpha,
+                                  attn_dim, sum_out, count_out, stream, &x);
 }
 
 }  // extern "C"

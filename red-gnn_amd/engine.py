@@ -493,6 +493,35 @@ def tattn_profile(frontier, graph, level, q_time, a_s, a_r, a_q, w_alpha, b_alph
         PROFILE_EVENTS.append((ev[0], ev[1], level))
 
 
+def xattn_profile(frontier, graph, level, q_time, loop_time, row_time, lag_bin, n_bins, a_s, a_r, a_q, w_alpha, b_alpha, attn_dim, sum_out,
+                  count_out):
+    """rg_xattn_profile: attn_profile of the extrapolation model on a frontier with its row windows set, with the edge's binned lag as an
+    axis.  Adds the hop-`level` edges of every query into sum_out / count_out (int64 [B, n_bins, n_rela_rows], zeroed by the caller):
+    bin = lag_bin[the forward's time-table row of the edge] (lag_bin uint8 [n_lag]; an entry >= n_bins drops the edge), the row being
+    q_time[b] - row_time[data row], or q_time[b] - loop_time[b] for a self-loop, clamped to 0..n_lag - 1 (int32 tensors)."""
+    for t in (a_s, a_r, a_q, w_alpha, b_alpha):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+    ap = a_s.shape[1]
+    assert a_r.shape == (graph.n_rela_rows, ap) and a_q.shape == (frontier.batch, ap)      # (the kernel's bins: the graph's rows)
+    for t in (q_time, loop_time, row_time):
+        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()
+    assert q_time.numel() == frontier.batch and loop_time.numel() == frontier.batch
+    assert lag_bin.is_cuda and lag_bin.dtype == torch.uint8 and lag_bin.is_contiguous() and lag_bin.dim() == 1 and lag_bin.numel() >= 1
+    for t in (sum_out, count_out):
+        assert t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.shape == (frontier.batch, n_bins, a_r.shape[0])
+    ev = None
+    if PROFILE_EVENTS is not None:
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        ev[0].record()
+    _lib.check(_lib.lib().rg_xattn_profile(frontier.handle, graph.handle, frontier.batch, frontier.n_ent, level, a_s.shape[0],
+                                           _lib.ptr(q_time), _lib.ptr(loop_time), _lib.ptr(row_time), _lib.ptr(lag_bin), lag_bin.numel(),
+                                           int(n_bins), _lib.ptr(a_s), _lib.ptr(a_r), _lib.ptr(a_q), ap, _lib.ptr(w_alpha),
+                                           _lib.ptr(b_alpha), attn_dim, _lib.ptr(sum_out), _lib.ptr(count_out), _lib.stream_ptr()))
+    if ev is not None:
+        ev[1].record()
+        PROFILE_EVENTS.append((ev[0], ev[1], level))
+
+
 def layer_fwd_plan(frontier, graph, level, n_old, n_new, n_edges, ld):
     """The walk rg_layer_fwd picks for a hop of these sizes (rg_layer_fwd_plan): recorded from an eager forward for graph replay."""
     return int(_lib.lib().rg_layer_fwd_plan(frontier.handle, graph.handle, level, n_old, n_new, n_edges, ld))
@@ -787,6 +816,23 @@ def rows_addmm(base, g, W):
     Wc = W.detach().contiguous()
     _lib.check(_lib.lib().rg_rows_addmm(C.c_void_p(base.data_ptr()), base.stride(0), C.c_void_p(g.data_ptr()), g.stride(0), k, _lib.ptr(Wc), n,
                                         n_rows, _lib.ptr(out), n, _lib.stream_ptr()))
+    return out
+
+
+def rows_linear(x, weight, bias=None):
+    """F.linear(x, weight, bias) for node-row matrices x [N, k] (rows may be spaced, unit-stride columns) by rg_rows_linear: every
+    output element is one fmaf chain over k in order, so a row's result does not depend on N.  No autograd.  Returns [N, n]."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
+    if x.stride(1) != 1 or x.stride(0) < x.shape[1]:
+        x = x.contiguous()
+    w = weight.detach().to(torch.float32).contiguous()
+    b = None if bias is None else bias.detach().to(torch.float32).contiguous()
+    n_rows, k = x.shape
+    n = w.shape[0]
+    assert w.shape == (n, k) and (b is None or b.numel() == n)
+    out = torch.empty((n_rows, n), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().rg_rows_linear(_lib.ptr(x), n_rows, x.stride(0), k, _lib.ptr(w), _lib.ptr(b), n, _lib.ptr(out), n,
+                                         _lib.stream_ptr()))
     return out
 
 

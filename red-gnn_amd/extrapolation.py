@@ -20,7 +20,11 @@ copy.  ``segment_rank_fil`` is the host restatement the device path is tested ag
 Forecasts and their explanation: ``T_RED_GNN.predict(X, k, known)`` returns each query's k best objects among the entities its window
 reaches, known objects excluded, in one HIP launch on the forward's pairs (csrc/segment_topk.hip, rg_segment_topk), and
 ``T_RED_GNN.explain(X, objs)`` the r-digraph of past facts behind a forecast, every edge with its attention and data row
-(csrc/explain.hip, rg_xexplain_count / rg_xexplain_emit; the driver is explain.explain_extrapolation).
+(csrc/explain.hip, rg_xexplain_count / rg_xexplain_emit; the driver is explain.explain_extrapolation).  ``T_RED_GNN.attention_profile``
+sums the attention of a batch's edges per hop, edge relation and lag bin (csrc/profile.hip, rg_xattn_profile; the driver is
+profile.attention_profile_extrapolation), ``attention_profile_all`` over a split.
+Without gradients the per-row products of the forward (attention inputs, W_past products, time table, classifier) run through
+rg_rows_linear (csrc/rows_linear.hip), whose rows do not depend on the row count: a query computes the same bits in every batch.
 
 Parity: the reference's model file cannot be imported in the build container (torch_scatter, pyvis, rtdl_revisiting_models are absent),
 so this path is checked against the oracle's restatement only - parity UNPINNED - except ``segment_rank_fil``, whose fixture comes
@@ -36,6 +40,7 @@ import torch.nn.functional as F
 
 from . import engine
 from .models import pad_attn, tall_linear
+from .profile import DEFAULT_LAG_EDGES
 
 
 class _XAggregate(torch.autograd.Function):
@@ -163,7 +168,8 @@ class T_RED_GNN(nn.Module):
         """The forward on the device: (logits [N], per-query softmax [N], visited (batch, entity) pairs int32 [N,2] sorted, score_all) -
         score_all [B, n_ent] only with ``dense`` (else None: nothing of size B * n_ent is built, nothing is copied to the host).
         ``kept`` (a list, for explain): the frontier keeps all n_layer + 1 levels and its windows stay set - the caller clears them; the
-        list receives dict(frontier, graph, q_rel, q_time, loop_time, win_lo, win_hi), then per layer dict(a_s, a_r, a_q, w_alpha)."""
+        list receives dict(frontier, graph, q_rel, q_time, loop_time, win_lo, win_hi, n_tab = the rows of the forward's time table),
+        then per layer dict(a_s, a_r, a_q, w_alpha)."""
         device = self.linear_classifier.weight.device
         engine._require_gpu(device)
         src, rel = np.asarray(X.src_idx), np.asarray(X.rel_idx)
@@ -192,20 +198,31 @@ class T_RED_GNN(nn.Module):
         lo_h, hi_h = off[begin], off[cur_t]
         oldest = np.where(lo_h < hi_h, self._row_time_host[np.minimum(lo_h, self.n_data - 1)], begin) if self.n_data else begin
         n_tab = int(np.maximum(cur_t - oldest, cur_t - begin).max()) + 1 if n else 1
+        if kept is not None:
+            kept[0]["n_tab"] = n_tab
         deltas = torch.arange(n_tab, dtype=torch.float32, device=device)
         hidden = torch.zeros((n, d), device=device)
         zero_b = torch.zeros(1, device=device)
         n_edges = []
         with torch.set_grad_enabled(with_grad):
-            time_p = padc(F.linear(self.time_embed(deltas.view(-1, 1)).squeeze(1), w_past)).contiguous()     # W_past time_embed(delta)  (:201,205)
+            # the per-row products: autograd's library GEMMs when training; without gradients rg_rows_linear, whose rows do not depend
+            # on the row count, so that a query computes the same bits in every batch (the library picks its kernel by the shape)
+            lin = tall_linear if with_grad else engine.rows_linear
+            if with_grad:
+                t_emb = self.time_embed(deltas.view(-1, 1)).squeeze(1)
+            else:                                    # time_embed for x >= 0: relu(linear_pos([cos | sin](2 pi w x))) (PeriodicEmbeddings.forward)
+                z = 2 * math.pi * self.time_embed.periodic.weight * deltas.view(-1, 1)
+                pos = self.time_embed.linear_pos
+                t_emb = torch.relu(lin(torch.cat([torch.cos(z), torch.sin(z)], -1), pos.weight[0].t(), pos.bias[0]))
+            time_p = padc(lin(t_emb, w_past)).contiguous()                                                   # W_past time_embed(delta)  (:201,205)
             for i in range(self.n_layer):
                 rela, w1, w2 = self.rela_embed_layer[i].weight, self.attention_1_layer[i].weight, self.attention_2_layer[i].weight
                 n_new, n_e, n_old = fr.expand(self.graph)
                 n_edges.append(n_e)
-                a_s = tall_linear(hidden, pad_rows(w1[:, :d])).contiguous()                       # attention_1 on [h_s | rel | rel_q] (:207-208)
+                a_s = lin(hidden, pad_rows(w1[:, :d])).contiguous()                       # attention_1 on [h_s | rel | rel_q] (:207-208)
                 a_r = F.linear(rela, pad_rows(w1[:, d:2 * d])).contiguous()
-                a_q = F.linear(rela[q_rel], pad_rows(w1[:, 2 * d:])).contiguous()
-                hidden_p = padc(tall_linear(hidden, w_past)).contiguous()                         # W_past (h + r + tau) = W_past h + ... (:203-205)
+                a_q = lin(rela[q_rel], pad_rows(w1[:, 2 * d:])).contiguous()
+                hidden_p = padc(lin(hidden, w_past)).contiguous()                         # W_past (h + r + tau) = W_past h + ... (:203-205)
                 rela_p = padc(F.linear(rela, w_past)).contiguous()
                 w_alpha = w2.reshape(-1).contiguous()
                 if kept is not None:
@@ -218,7 +235,7 @@ class T_RED_GNN(nn.Module):
                                             time_p, d, a_s, a_r, a_q, w_alpha, zero_b, a)
                 hidden = self.act(agg[:, :d])                                                     # :238-239
             nodes, _, _ = fr.nodes(want_prev=False, want_old_new=False)
-            result = tall_linear(hidden, self.linear_classifier.weight, self.linear_classifier.bias).reshape(-1)   # :244
+            result = lin(hidden, self.linear_classifier.weight, self.linear_classifier.bias).reshape(-1)   # :244
             b_idx = nodes[:, 0].long()
             score_all = None
             if dense:
@@ -230,7 +247,7 @@ class T_RED_GNN(nn.Module):
             soft = ex / torch.zeros(n, device=device).index_add(0, b_idx, ex)[b_idx]
         if not with_grad and kept is None:
             fr.set_window(None, None, 0)         # (a training forward's frontier keeps its windows for the backward: every reset sets them anew)
-        self.last_stats = dict(n_edges=n_edges, n_nodes=int(nodes.shape[0]))
+        self.last_stats = dict(n_edges=n_edges, n_nodes=int(nodes.shape[0]), n_tab=n_tab)
         return result, soft, nodes, score_all
 
     def _index_on_device(self, index, device):
@@ -306,6 +323,31 @@ class T_RED_GNN(nn.Module):
         from .explain import explain_extrapolation
         return explain_extrapolation(self, X, objs, min_alpha)
 
+    def attention_profile(self, X, group="relation", lag_edges=DEFAULT_LAG_EDGES):
+        """When the model forecasts relation p, which past relations does it listen to, and how far back?  profile.AttentionProfile
+        with axes ("group", "hop", "lag", "relation"), shape [G, L, len(lag_edges) + 1, n_rel + 1]: over the hop-l edges the forward
+        aggregates for the queries of X (as forward's), the number of edges and the sum of their attention per edge relation and lag
+        bin - the edge's lag in days (query day minus the edge's day) binned by ``lag_edges`` (profile.DEFAULT_LAG_EDGES: days 0-1,
+        2-3, 4-7, 8-14, 15-30, 31-60, 61-120, 121+; lags above 120 occur: the reference's offsets put older rows in front of a window
+        after days without rows).  G = the n_rel + 1 relation rows (group="relation", rows of relations not queried are zero) or the B
+        queries in the order given (group="query").  The self-loop of every visited entity is an edge too: it lands in the self-loop
+        relation's column, n_rel_true, at the lag the forward uses for it (query day minus the window's first day, 120 for a full
+        window) - leave that column out to see data rows only.  One forward, then one HIP launch per hop (rg_xattn_profile,
+        csrc/profile.hip); integer sums, bit-identical across runs, splits and orders of a batch.  No gradients, eval mode."""
+        from .profile import attention_profile_extrapolation
+        return attention_profile_extrapolation(self, X, group, lag_edges)
+
+    def attention_profile_all(self, queries, batch_size=64, lag_edges=DEFAULT_LAG_EDGES):
+        """The group="relation" attention profile of ``queries`` int [n, 4] = (s, p, o, ts) (checked as evaluate's; the objects are
+        not read), in batches of ``batch_size``, their integer tables added."""
+        q = check_queries(self, queries, batch_size, "attention_profile_all")
+        prof = None
+        for lo in range(0, len(q), int(batch_size)):
+            b = q[lo:lo + int(batch_size)]
+            part = self.attention_profile(_Batch(b[:, 0], b[:, 1], b[:, 3]), "relation", lag_edges)
+            prof = part if prof is None else prof + part
+        return prof
+
     def evaluate(self, queries, sp_index=None, spt_index=None, batch_size=64, return_ranks=False):
         """The validation loop of main.py:353-472 for a split: ``queries`` int [n, 4] = (s, p, o, ts), in batches of ``batch_size``
         through rank_batch; the rank tensors stay on the device and are copied to the host once.  Returns the reference's quantities
@@ -313,19 +355,7 @@ class T_RED_GNN(nn.Module):
         reference's time-filtered list holds found queries only) over the number of queries, hits_inf = found / n, mr (:423), and
         among the found queries hits1_found / hits3_found / hits10_found / mr_found / mrr_found (:455-462; NaN when none is found).
         Sums in float64.  ``return_ranks``: also (rank, found, rank_fil, rank_fil_t) as numpy arrays [n] (unfound: 1e9)."""
-        q = queries.detach().cpu().numpy() if torch.is_tensor(queries) else np.asarray(queries)
-        if q.dtype == np.bool_ or not np.issubdtype(q.dtype, np.integer):
-            raise ValueError("evaluate: queries must hold integer ids (got dtype %s)" % q.dtype)
-        if q.ndim != 2 or q.shape[1] != 4 or len(q) == 0:
-            raise ValueError("evaluate: queries must be a non-empty int [n, 4] array of (s, p, o, ts) (got shape %s)" % (q.shape,))
-        if isinstance(batch_size, (bool, np.bool_)) or not isinstance(batch_size, (int, np.integer)) or batch_size < 1:
-            raise ValueError("evaluate: batch_size must be a positive integer (got %r)" % (batch_size,))
-        q = q.astype(np.int64)
-        if q[:, [0, 2]].min() < 0 or q[:, [0, 2]].max() >= self.n_ent or q[:, 1].min() < 0 or q[:, 1].max() >= self.n_rel_true:
-            raise ValueError("evaluate: subject / object / relation id out of range (n_ent=%d, n_rel=%d)" % (self.n_ent, self.n_rel_true))
-        day = q[:, 3] // self.time_granularity
-        if q[:, 3].min() < 0 or day.max() >= len(self.time_offset_list):
-            raise ValueError("evaluate: query time outside the model's data (0 <= ts // %d < %d)" % (self.time_granularity, len(self.time_offset_list)))
+        q = check_queries(self, queries, batch_size, "evaluate")
         parts = []
         for lo in range(0, len(q), int(batch_size)):
             b = q[lo:lo + int(batch_size)]
@@ -457,6 +487,25 @@ def check_batch(model, X, who):
         raise ValueError("%s: query time outside the model's data (0 <= ts // %d < %d)"
                          % (who, model.time_granularity, len(model.time_offset_list)))
     return src, rel, ts
+
+
+def check_queries(model, queries, batch_size, who):
+    """``queries`` as int64 [n, 4] = (s, p, o, ts) with ids and times inside the model's data; ValueError otherwise."""
+    q = queries.detach().cpu().numpy() if torch.is_tensor(queries) else np.asarray(queries)
+    if q.dtype == np.bool_ or not np.issubdtype(q.dtype, np.integer):
+        raise ValueError("%s: queries must hold integer ids (got dtype %s)" % (who, q.dtype))
+    if q.ndim != 2 or q.shape[1] != 4 or len(q) == 0:
+        raise ValueError("%s: queries must be a non-empty int [n, 4] array of (s, p, o, ts) (got shape %s)" % (who, q.shape))
+    if isinstance(batch_size, (bool, np.bool_)) or not isinstance(batch_size, (int, np.integer)) or batch_size < 1:
+        raise ValueError("%s: batch_size must be a positive integer (got %r)" % (who, batch_size))
+    q = q.astype(np.int64)
+    if q[:, [0, 2]].min() < 0 or q[:, [0, 2]].max() >= model.n_ent or q[:, 1].min() < 0 or q[:, 1].max() >= model.n_rel_true:
+        raise ValueError("%s: subject / object / relation id out of range (n_ent=%d, n_rel=%d)" % (who, model.n_ent, model.n_rel_true))
+    day = q[:, 3] // model.time_granularity
+    if q[:, 3].min() < 0 or day.max() >= len(model.time_offset_list):
+        raise ValueError("%s: query time outside the model's data (0 <= ts // %d < %d)"
+                         % (who, model.time_granularity, len(model.time_offset_list)))
+    return q
 
 
 def _index_tensors(index, device):
