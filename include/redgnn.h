@@ -353,6 +353,35 @@ int rg_segment_topk(const float* scores, const int32_t* ent, int64_t n_pairs, co
                     int32_t batch, int32_t k, const int64_t* q_key, const int64_t* known_keys, const int64_t* known_ptr,
                     const int32_t* known_idx, int64_t n_keys, int32_t* idx_out, float* score_out, float* prob_out, void* stream);
 
+/* ---- evaluation of the interpolation setting: the per-query loss term and filtered rank counts of the validation loop of
+ * Temporal/interpolation/main.py:125-183 (F.softmax over [B, n_ent], nll_loss(log(p + 1e-12)), topk, argsort, .item() per query),
+ * in rg_segment_rank's layout, without the [B, n_ent] matrix.
+ * scores (the logits) / ent / n_pairs / seg_ptr / seg_ptr_is64 / target / batch as rg_segment_rank: entities unique within a segment
+ * and inside 0..n_ent-1, in any order; bounds clamped to 0..n_pairs; an empty segment is legal.  n_ent > 0: the width of the dense
+ * row.  Two known-answer indexes in rg_topk's layout, a_* and b_*, with the queries' keys key_a / key_b int64 [batch]: n_keys = 0
+ * with NULL arrays filters nothing, a key the index lacks filters nothing, listed entities outside 0..n_ent-1 are ignored.
+ * Everything is defined on the dense row x[e] = the score of the pair (query, e) if the segment has one, else +0.0 - which is never
+ * built.  With t the target, ts = x[t], n_seg the segment's length and n_zero = n_ent - n_seg:
+ *   logp_out fp32 [batch] = log(exp(ts - m) / Z + 1e-12), m = max_e x[e] (0 takes part only if n_zero > 0), Z = sum_seg exp(s_j - m)
+ *     + n_zero exp(-m), the second term only formed when n_zero > 0 (on a full row of very negative scores exp(-m) overflows): the
+ *     per-row term of main.py:146.  expf / logf; m and the sum reduced in a fixed order (per-thread strided
+ *     partials, wave shuffle, waves in index order).  A NaN score anywhere in the segment makes logp NaN.
+ *   count_out int32 [batch, 6] = (gt, eq) for three keep-sets - every entity; the entities not in the key's list of a_*; of b_* - the
+ *     target always kept: gt = #{kept e: x[e] > ts}, eq = #{kept e != t: x[e] == ts} (IEEE comparisons: NaN counts for nothing,
+ *     -0.0 == +0.0).  The implicit zeros are counted arithmetically: a list L hides #{x in L, 0 <= x < n_ent, x != t} - #{pairs whose
+ *     entity is in L, != t} of them, n_zero - [t not visited] - hidden are kept and join gt if 0 > ts, eq if 0 == ts.
+ *   visited_out int32 [batch] = 1 if the target has a pair in the segment.  A target without one is no error: it scores 0 and ranks
+ *     among the zeros, as the reference's dense argsort ranks it.
+ * One workgroup of 256 threads per query; integer counters; each query depends on its own segment and lists alone and its results
+ * are bitwise reproducible.  A known list of up to 256 entities is searched in LDS, a longer one in memory.  No limit on segment or
+ * list length.  Nothing outside [0, n_pairs) or outside the index arrays is read; a list that is not ascending and unique gives an
+ * unspecified, in-bounds result, as for rg_topk. */
+int rg_segment_eval(const float* scores, const int32_t* ent, int64_t n_pairs, const void* seg_ptr, int32_t seg_ptr_is64,
+                    const int32_t* target, int32_t batch, int32_t n_ent,
+                    const int64_t* key_a, const int64_t* a_keys, const int64_t* a_ptr, const int32_t* a_idx, int64_t n_a,
+                    const int64_t* key_b, const int64_t* b_keys, const int64_t* b_ptr, const int32_t* b_idx, int64_t n_b,
+                    float* logp_out, int32_t* count_out, int32_t* visited_out, void* stream);
+
 /* rg_dense_fwd with the node count read on the device (after rg_frontier_expand_async): n_cap = capacity of the row buffers,
  * n_dev = rg_frontier_count_ptr() of the frontier whose newest level the rows belong to, n_hint = the row count the caller expects
  * (0 = unknown): it only sizes the grid, every row count up to n_cap is processed correctly. */

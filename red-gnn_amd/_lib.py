@@ -24,6 +24,7 @@ SYMBOLS = [
     "rg_segment_rank", "rg_segment_topk",
     "rg_xexplain_count", "rg_xexplain_emit",
     "rg_xattn_profile", "rg_rows_linear",
+    "rg_segment_eval",
 ]
 
 _lib = None
@@ -125,6 +126,7 @@ def lib():
     L.rg_tattn_profile.argtypes = [vp, vp, i32, i32, i32, i64, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp]
     L.rg_segment_rank.argtypes = [vp, vp, i64, vp, i32, vp, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp]
     L.rg_segment_topk.argtypes = [vp, vp, i64, vp, i32, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp]
+    L.rg_segment_eval.argtypes = [vp, vp, i64, vp, i32, vp, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp]
     L.rg_xexplain_count.argtypes = L.rg_explain_count.argtypes
     L.rg_xexplain_emit.argtypes = L.rg_texplain_emit.argtypes
     L.rg_rows_linear.argtypes = [vp, i64, i64, i32, vp, vp, i32, vp, i64, vp]

@@ -952,6 +952,30 @@ def segment_rank(scores, ent, seg_ptr, target, key_sp=None, known_sp=None, key_s
     return rank, rank_fil, rank_fil_t, found
 
 
+def segment_eval(scores, ent, seg_ptr, target, n_ent, key_a=None, known_a=None, key_b=None, known_b=None):
+    """Loss term and rank counts (rg_segment_eval) of every query's target on ITS dense score row - the visited pairs plus an exact
+    0 for each of the other n_ent - n_seg entities - without building it: (logp fp32 [B], counts int32 [B, 6], visited int32 [B]).
+    logp = log(softmax(row)[target] + 1e-12); counts = (gt, eq) over every entity, over those the list of ``known_a`` keeps and over
+    those the list of ``known_b`` keeps (the target always kept, never its own tie); visited = 1 where the target has a pair.
+    ``scores`` (logits) fp32 [N], ``ent`` int32 [N], ``seg_ptr`` int32 or int64 [B+1], ``target`` int32 [B] and the two indexes with
+    their per-query keys as segment_rank."""
+    assert scores.is_cuda and scores.dtype == torch.float32 and scores.is_contiguous() and scores.dim() == 1
+    assert ent.is_cuda and ent.dtype == torch.int32 and ent.is_contiguous() and ent.shape == scores.shape
+    assert target.is_cuda and target.dtype == torch.int32 and target.is_contiguous() and target.dim() == 1
+    B = target.numel()
+    assert seg_ptr.is_cuda and seg_ptr.dtype in (torch.int32, torch.int64) and seg_ptr.is_contiguous() and seg_ptr.numel() == B + 1
+    dev = scores.device
+    logp = torch.empty(B, dtype=torch.float32, device=dev)
+    counts = torch.empty((B, 6), dtype=torch.int32, device=dev)
+    visited = torch.empty(B, dtype=torch.int32, device=dev)
+    ka, kb = _known_args(known_a, key_a, B, "segment_eval: first index"), _known_args(known_b, key_b, B, "segment_eval: second index")
+    p = _lib.ptr
+    _lib.check(_lib.lib().rg_segment_eval(p(scores), p(ent), scores.numel(), p(seg_ptr), int(seg_ptr.dtype == torch.int64), p(target), B,
+                                          int(n_ent), p(ka[0]), p(ka[1]), p(ka[2]), p(ka[3]), ka[4], p(kb[0]), p(kb[1]), p(kb[2]), p(kb[3]),
+                                          kb[4], p(logp), p(counts), p(visited), _lib.stream_ptr()))
+    return logp, counts, visited
+
+
 SEGMENT_TOPK_STAGE_MAX = 24576       # csrc/segment_topk.hip: SEG_STAGE_MAX (longer segments are re-read on every pass of the select)
 SEGMENT_TOPK_LIST_LDS = 256          # ... SEG_LIST_LDS (longer known lists are searched in memory)
 

@@ -82,6 +82,19 @@ def temporal_known_index(quads, n_rela_rows, n_time):
     return keys.astype(np.int64), ptr, pairs[:, 1].astype(np.int32)
 
 
+def temporal_static_known_index(quads, n_rela_rows):
+    """The time-independent counterpart of temporal_known_index, for the static filter of T_RED_GNN.rank_batch / evaluate: the same
+    layout with key = head * n_rela_rows + rel and the tails of (head, rel) at any time, ascending and unique."""
+    q = np.asarray(quads, dtype=np.int64).reshape(-1, 4)
+    if len(q) and (q[:, 1].min() < 0 or q[:, 1].max() >= n_rela_rows or q[:, [0, 2]].min() < 0):
+        raise ValueError("temporal_static_known_index: relation id outside 0..%d or a negative head / tail id" % (n_rela_rows - 1))
+    key = q[:, 0] * n_rela_rows + q[:, 1]
+    pairs = np.unique(np.stack([key, q[:, 2]], 1), axis=0) if len(q) else np.zeros((0, 2), np.int64)      # sorted by (key, tail)
+    keys, first = np.unique(pairs[:, 0], return_index=True)
+    ptr = np.append(first, len(pairs)).astype(np.int64)
+    return keys.astype(np.int64), ptr, pairs[:, 1].astype(np.int32)
+
+
 def predict_temporal(model, batch, k=10, known=None):
     """T_RED_GNN.predict (see there)."""
     from .temporal import batch_ids, eval_semantics

@@ -13,7 +13,8 @@ device bitmap walk, and the per-edge work of a layer is one fused kernel (rg_tla
 hoisted per node / relation / |dt| (W(h + r + tau) = Wh + Wr + Wtau).  The attention_vis table itself - alpha sum and edge count per
 relation - is ``attention_profile`` (rg_tattn_profile; with the edge direction past / now / future as one more axis), the r-digraph the
 reference draws in model_cuda_rule_vis.py is ``explain`` (rg_texplain_*; every edge with its time id), and ``predict`` gives the
-filtered top-k answers of (head, relation, time) queries (rg_topk).
+filtered top-k answers of (head, relation, time) queries (rg_topk).  The validation loop of main.py:125-183 is ``evaluate`` /
+``rank_batch`` (evaluation.py, rg_segment_eval): loss, raw and filtered ranks from the visited pairs, without the [B, n_ent] matrix.
 Training: ``mode='train'`` drops the batch's own quadruples (``batch['example_idx']`` rows of ``params.graph``,
 model_cuda.py:103-104) by building a device graph for the batch, applies ``nn.Dropout(params.dropout)`` before the
 activation (:196) and is differentiable: the per-edge work of the backward pass is rg_tlayer_bwd, the hoisted linears are
@@ -124,10 +125,35 @@ class T_RED_GNN(nn.Module):
         from . import prediction as _prediction
         return _prediction.predict_temporal(self, batch, k, known)
 
-    def _run(self, batch, mode, kept=None):
+    def rank_batch(self, batch, tails=None, known=None, known_static=None):
+        """Loss term and ranks of one batch as the validation loop of main.py:140-164 computes them, on the device and without the
+        [B, n_ent] matrix: the forward on the full graph, then rg_segment_eval on its visited pairs.  ``batch`` is forward's dict;
+        ``tails`` int [B] defaults to batch["tail"].  ``known`` = prediction.temporal_known_index(...) hides the other known tails
+        of a query's (head, relation, time) - the time-aware filter - and ``known_static`` =
+        prediction.temporal_static_known_index(...) those of its (head, relation); numpy triples or device tensors, None filters
+        nothing.  No gradients, eval mode (the training flags come back).  Returns evaluation.TemporalRanks."""
+        from . import evaluation as _evaluation
+        return _evaluation.rank_batch_temporal(self, batch, tails, known, known_static)
+
+    def evaluate(self, quads, known=None, known_static=None, batch_size=64, return_ranks=False):
+        """Loss and ranking metrics of ``quads`` int [n, 4] = (head, rel, tail, time id), the layout of params.graph, in batches of
+        ``batch_size`` through rank_batch; the results stay on the device and are copied to the host once.  Returns a dict: n, loss
+        (mean of -logp), unreached (share of targets the forward never visited), and hits1 / hits3 / hits10 / mrr / mr raw, *_fil_t
+        (time-aware filter, ``known``) and *_fil (static filter, ``known_static``), sums in float64.  ``return_ranks`` adds
+        "per_query": the numpy arrays logp, visited, gt / eq, gt_fil_t / eq_fil_t, gt_fil / eq_fil and rank, rank_fil_t, rank_fil.
+
+        Relation to the reference: ``loss`` is main.py:146,170.  Its own rank (main.py:161-163, an argsort) and hits (util.py:42-51,
+        topk) place a tied answer at any of the tied places - and every unreached entity scores exactly 0, so ties are the normal
+        case; they always lie in [gt + 1, gt + eq + 1].  This method reports the mean of that interval, gt + eq / 2 + 1, the
+        convention of rg_rank and rg_segment_rank.  The reference has no filtered metric."""
+        from . import evaluation as _evaluation
+        return _evaluation.evaluate_temporal(self, quads, known, known_static, batch_size, return_ranks)
+
+    def _run(self, batch, mode, kept=None, dense=True):
         """forward(); with ``kept`` (a list) the frontier keeps all n_layer + 1 levels and the list receives dict(frontier, graph, q_rel,
         q_time) followed per layer by dict(a_s [n_old, ap], a_r [n_rel + 1, ap], a_q [B, ap], w_alpha [attn_dim]): what rg_tlayer_fwd
-        read, for rg_texplain_* and rg_tattn_profile."""
+        read, for rg_texplain_* and rg_tattn_profile.  dense=False: (result fp32 [N], nodes int32 [N, 2]) - the logit of every visited
+        (query, entity) pair, sorted by query then entity - instead of the [B, n_ent] matrix, which is then never built."""
         device = self.linear_classifier.weight.device
         engine._require_gpu(device)
         heads = torch.as_tensor(batch["head"]).to(device=device, dtype=torch.int32)
@@ -177,10 +203,12 @@ class T_RED_GNN(nn.Module):
             hidden = self.act(self.dropout(agg[:, :d]))                               # model_cuda.py:196
         nodes, _, _ = fr.nodes(want_prev=False, want_old_new=False)
         result = tall_linear(hidden, self.linear_classifier.weight, self.linear_classifier.bias).reshape(-1)   # model_cuda.py:210
-        key_idx = nodes[:, 0].long() * self.n_ent + nodes[:, 1].long()
-        score_all = torch.zeros(n * self.n_ent, device=device).index_copy(0, key_idx, result)
         self.last_stats = dict(n_edges=n_edges, n_nodes=int(nodes.shape[0]))
         self.last_nodes = nodes
+        if not dense:
+            return result, nodes
+        key_idx = nodes[:, 0].long() * self.n_ent + nodes[:, 1].long()
+        score_all = torch.zeros(n * self.n_ent, device=device).index_copy(0, key_idx, result)
         return score_all.view(n, self.n_ent)
 
 
