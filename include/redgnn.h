@@ -382,6 +382,23 @@ int rg_segment_eval(const float* scores, const int32_t* ent, int64_t n_pairs, co
                     const int64_t* key_b, const int64_t* b_keys, const int64_t* b_ptr, const int32_t* b_idx, int64_t n_b,
                     float* logp_out, int32_t* count_out, int32_t* visited_out, void* stream);
 
+/* ---- the k best paths behind an answer: a selection on the compact r-digraph of rg_explain_* (explain.RDigraph), no counterpart
+ * in the reference (model_cuda_rule_vis.py enumerates with networkx.all_simple_paths).
+ * edges int32 [E, 5] = (row, hop, head, rel, tail) ordered by (row, hop, tail, CSR position), alpha fp32 [E], offsets int64 [B + 1]
+ * non-decreasing with offsets[B] <= E (the caller checks that; everything read from the edge list itself is bounded by the row's
+ * offsets, so a malformed list gives wrong paths, never an access outside the arrays).  n_hops = L in 1..32, k in 1..8.
+ * A path of row b is L of its edges e_1..e_L with hop(e_l) = l, tail(e_l) = head(e_l+1) and e_L in the run of (hop, tail) that ends
+ * the row, which must be a hop-L run; every hop-1 edge starts one.  Its product is ((1.0 * a_1) * a_2) ... * a_L in float64.  P comes
+ * before Q at level l if P's product is larger; else if P's last edge has the smaller (head, rel, edge index); else, with the same
+ * last edge, if P's prefix comes before Q's at level l - 1.  Per row the first min(k, number of paths) paths in that order:
+ *   path_edge int64 [B, k, L] edge indices (-1 past the count), path_prod float64 [B, k] (0 past it), path_count int32 [B].
+ * Rows row_lo..row_hi-1 are computed (rows of the full arrays: the outputs are indexed by the row itself), one workgroup per row,
+ * and scratch holds rg_paths_scratch_bytes(offsets[row_hi] - offsets[row_lo], k) bytes (0: n_edges or k out of range).  A row's
+ * result depends on its own edges alone, bit for bit, however the rows are cut into calls. */
+size_t rg_paths_scratch_bytes(int64_t n_edges, int32_t k);
+int rg_paths_topk(const int32_t* edges, const float* alpha, const int64_t* offsets, int32_t row_lo, int32_t row_hi, int32_t n_hops,
+                  int32_t k, void* scratch, int64_t* path_edge, double* path_prod, int32_t* path_count, void* stream);
+
 /* rg_dense_fwd with the node count read on the device (after rg_frontier_expand_async): n_cap = capacity of the row buffers,
  * n_dev = rg_frontier_count_ptr() of the frontier whose newest level the rows belong to, n_hint = the row count the caller expects
  * (0 = unknown): it only sizes the grid, every row count up to n_cap is processed correctly. */

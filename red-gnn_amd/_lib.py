@@ -25,6 +25,7 @@ SYMBOLS = [
     "rg_xexplain_count", "rg_xexplain_emit",
     "rg_xattn_profile", "rg_rows_linear",
     "rg_segment_eval",
+    "rg_paths_scratch_bytes", "rg_paths_topk",
 ]
 
 _lib = None
@@ -131,6 +132,9 @@ def lib():
     L.rg_xexplain_emit.argtypes = L.rg_texplain_emit.argtypes
     L.rg_rows_linear.argtypes = [vp, i64, i64, i32, vp, vp, i32, vp, i64, vp]
     L.rg_xattn_profile.argtypes = [vp, vp, i32, i32, i32, i64, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp]
+    L.rg_paths_scratch_bytes.argtypes = [i64, i32]
+    L.rg_paths_scratch_bytes.restype = sz
+    L.rg_paths_topk.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     _lib = L
     return L
 

@@ -213,3 +213,11 @@ class BaseModel(object):
         only the first so many queries of the split.  Not sharded: under a process group every rank computes the whole table."""
         from .profile import split_profile
         return split_profile(self.model, self.loader, data, self.n_tbatch, max_queries)
+
+    # ---- rules of a whole split ------------------------------------------------------------------------------------
+    def rules(self, data="test", k=1, max_queries=None):
+        """model.rules over the valid or test split: every (h, r, answer) of its first ``max_queries`` queries (default: all) is one
+        row, the rows are walked in n_tbatch batches and the tables added (integer sums: the result does not depend on n_tbatch).
+        Returns an explain.RuleTable.  Not sharded: under a process group every rank computes the whole table."""
+        from .explain import split_rules
+        return split_rules(self.model, self.loader, data, k, self.n_tbatch, max_queries)

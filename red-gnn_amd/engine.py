@@ -998,3 +998,46 @@ def segment_topk(scores, ent, seg_ptr, k, q_key=None, known=None, want_prob=True
     _lib.check(_lib.lib().rg_segment_topk(p(scores), p(ent), scores.numel(), p(seg_ptr), int(seg_ptr.dtype == torch.int64), B, int(k),
                                           p(kn[0]), p(kn[1]), p(kn[2]), p(kn[3]), kn[4], p(idx), p(val), p(prob), _lib.stream_ptr()))
     return idx, val, prob
+
+
+PATHS_MAX_K = 8                      # csrc/paths.hip: PATHS_MAX_K
+PATHS_SCRATCH_BYTES = 256 << 20      # default scratch budget of paths_topk
+
+
+def paths_scratch_bytes(n_edges, k):
+    return int(_lib.lib().rg_paths_scratch_bytes(int(n_edges), int(k)))
+
+
+def paths_topk(edges, alpha, offsets, n_hops, k, scratch_bytes=PATHS_SCRATCH_BYTES, offsets_host=None):
+    """The k best paths (rg_paths_topk) of every row of a compact r-digraph: (edge int64 [B, k, L] indices into ``edges``, -1 past
+    the row's count; product float64 [B, k], 0 past it; count int32 [B]).  ``edges`` int32 [E, 5], ``alpha`` fp32 [E], ``offsets``
+    int64 [B+1] (validated by the caller: non-decreasing, ending at E; ``offsets_host``: its copy as a numpy array, if at hand).
+    The rows are walked in chunks whose scratch stays within ``scratch_bytes`` (one row at least per chunk); rows are independent,
+    so the chunking changes no bit of the result."""
+    assert edges.is_cuda and edges.dtype == torch.int32 and edges.is_contiguous() and edges.dim() == 2 and edges.shape[1] == 5
+    assert alpha.is_cuda and alpha.dtype == torch.float32 and alpha.is_contiguous() and alpha.shape == (edges.shape[0],)
+    assert offsets.is_cuda and offsets.dtype == torch.int64 and offsets.is_contiguous() and offsets.dim() == 1
+    B, L, dev = offsets.numel() - 1, int(n_hops), edges.device
+    path_edge = torch.full((B, k, L), -1, dtype=torch.int64, device=dev)
+    path_prod = torch.zeros((B, k), dtype=torch.float64, device=dev)
+    path_count = torch.zeros(B, dtype=torch.int32, device=dev)
+    if B == 0 or edges.shape[0] == 0:
+        return path_edge, path_prod, path_count
+    off = offsets.cpu().numpy() if offsets_host is None else offsets_host
+    chunks, lo = [], 0
+    while lo < B:                    # the longest run of rows from lo whose edges fit the budget
+        hi = lo + 1
+        while hi < B and 0 < paths_scratch_bytes(off[hi + 1] - off[lo], k) <= scratch_bytes:
+            hi += 1
+        chunks.append((lo, hi))
+        lo = hi
+    need = [paths_scratch_bytes(off[hi] - off[lo], k) for lo, hi in chunks]
+    if min(need) == 0:
+        raise ValueError("paths_topk: a chunk of %d edges is beyond the kernel's 2^31 edge indices"
+                         % max(off[hi] - off[lo] for lo, hi in chunks))
+    scratch = torch.empty(max(need), dtype=torch.uint8, device=dev)
+    p = _lib.ptr
+    for lo, hi in chunks:
+        _lib.check(_lib.lib().rg_paths_topk(p(edges), p(alpha), p(offsets), lo, hi, L, int(k), p(scratch), p(path_edge), p(path_prod),
+                                            p(path_count), _lib.stream_ptr()))
+    return path_edge, path_prod, path_count

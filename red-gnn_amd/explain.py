@@ -6,6 +6,8 @@ s -> o through the query's subgraph (identity self-loops count as steps); each e
     rd = model.explain(subs, rels, objs)            # objs=None: the model's own top answer per row
     rd.edges[rd.offsets[b]:rd.offsets[b + 1]]       # (row, hop, head, rel, tail) of row b, hop 1..L
     rels_, ents, prod = rd.strongest_paths()         # the path of largest alpha product per row
+    paths = rd.top_paths(k=4)                        # the k best paths per row (HIP: csrc/paths.hip), an explain.PathSet
+    table = model.rules(subs, rels, objs, k=2)       # their relation sequences counted as rules: an explain.RuleTable
 
 The extraction runs in HIP (csrc/explain.hip): a forward keeps all L + 1 frontier levels and each layer's attention projection, then
 one backward marking pass per hop reads only the marked tails' CSR rows.  This module holds the result type and the host drivers.
@@ -25,6 +27,7 @@ import torch
 
 from . import engine
 from .models import _pad4, pad_attn
+from .profile import FRACTION_BITS                       # sums in units of 2^-32, as the attention profile's
 
 
 @dataclass
@@ -129,6 +132,210 @@ class RDigraph:
         ents_out[none] = -1
         prod_out[none] = 0.0
         return rels_out, ents_out, prod_out
+
+    def top_paths(self, k=1, scratch_bytes=engine.PATHS_SCRATCH_BYTES):
+        """Per row the k best length-L paths s -> o inside the digraph, as a PathSet: by alpha product (float64, left to right, as
+        strongest_paths forms it), then by the smaller (head, rel, edge index) of the last edge, then by the order of the prefixes one
+        level down.  k = 1 is strongest_paths' path.  One HIP launch per chunk of rows (rg_paths_topk; csrc/paths.hip) on the compact
+        edge list: no graph and no model, so static, inductive, temporal and min_alpha-pruned digraphs all work.  ``scratch_bytes``
+        bounds the kernel's tables; the rows are walked in chunks that fit (one row at least) and the result does not depend on it.
+        The digraph is checked on the host first (ValueError); it must live on the device."""
+        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= k <= engine.PATHS_MAX_K:
+            raise ValueError("top_paths: k must be an integer in 1..%d (got %r)" % (engine.PATHS_MAX_K, k))
+        if isinstance(scratch_bytes, (bool, np.bool_)) or not isinstance(scratch_bytes, (int, np.integer)) or scratch_bytes < 0:
+            raise ValueError("top_paths: scratch_bytes must be a non-negative integer (got %r)" % (scratch_bytes,))
+        if isinstance(self.n_hops, (bool, np.bool_)) or not isinstance(self.n_hops, (int, np.integer)) or not 1 <= self.n_hops <= 32:
+            raise ValueError("top_paths: n_hops must be an integer in 1..32 (got %r)" % (self.n_hops,))
+        e, a, o = self.edges, self.alpha, self.offsets
+        if not all(torch.is_tensor(t) for t in (e, a, o)):
+            raise ValueError("top_paths: edges, alpha and offsets must be tensors")
+        if e.dtype != torch.int32 or e.dim() != 2 or e.shape[1] != 5:
+            raise ValueError("top_paths: edges must be int32 [E, 5] (got %s %s)" % (e.dtype, tuple(e.shape)))
+        if a.dtype != torch.float32 or a.shape != (e.shape[0],):
+            raise ValueError("top_paths: alpha must be float32 [%d] (got %s %s)" % (e.shape[0], a.dtype, tuple(a.shape)))
+        if o.dtype != torch.int64 or o.dim() != 1 or o.numel() < 1:
+            raise ValueError("top_paths: offsets must be int64 [B + 1] (got %s %s)" % (o.dtype, tuple(o.shape)))
+        off = o.detach().cpu().numpy()
+        if off[0] != 0 or off[-1] != e.shape[0] or (np.diff(off) < 0).any():
+            raise ValueError("top_paths: offsets must start at 0, never decrease and end at the number of edges (%d)" % e.shape[0])
+        if not (e.is_cuda and a.is_cuda and o.is_cuda):
+            raise ValueError("top_paths: the selection runs in HIP and needs the digraph on the device (got CPU tensors); "
+                             "strongest_paths() works on the host")
+        edge, product, count = engine.paths_topk(e.contiguous(), a.contiguous(), o.contiguous(), int(self.n_hops), int(k),
+                                                 int(scratch_bytes), offsets_host=off)
+        return PathSet(edge=edge, product=product, count=count, digraph=self)
+
+
+@dataclass
+class PathSet:
+    """The k best paths of every row of an r-digraph (RDigraph.top_paths), best first.  Tensors on the digraph's device.
+
+    edge     int64 [B, k, L]  indices into digraph.edges, hop 1..L; -1 where the row has fewer than k paths
+    product  float64 [B, k]   the paths' alpha products; 0 where absent
+    count    int32 [B]        paths found for the row (<= k)
+    digraph  RDigraph         the digraph the indices point into
+    """
+    edge: torch.Tensor
+    product: torch.Tensor
+    count: torch.Tensor
+    digraph: RDigraph
+
+    def _gather(self, column, absent):
+        """column [E] read through ``edge``; ``absent`` where there is no path."""
+        if column.shape[0] == 0:
+            return torch.full(self.edge.shape, absent, dtype=column.dtype, device=self.edge.device)
+        got = column[self.edge.clamp(min=0)]
+        return torch.where(self.edge >= 0, got, torch.full_like(got, absent))
+
+    def rels(self):
+        """int64 [B, k, L]: the relation of every step, -1 where absent."""
+        return self._gather(self.digraph.edges[:, 3].long(), -1)
+
+    def entities(self):
+        """int64 [B, k, L+1]: the entities from s to o, -1 where absent."""
+        e = self.digraph.edges
+        return torch.cat([self._gather(e[:, 2].long(), -1), self._gather(e[:, 4].long(), -1)[..., -1:]], -1)
+
+    def alphas(self):
+        """float32 [B, k, L]: the attention of every step, 0 where absent."""
+        return self._gather(self.digraph.alpha, 0.0)
+
+    def times(self):
+        """int32 [B, k, L]: the time id of every step, -1 where absent.  Temporal digraphs only."""
+        if self.digraph.time is None:
+            raise ValueError("times: a static r-digraph has no edge times")
+        return self._gather(self.digraph.time, -1)
+
+    def data_rows(self):
+        """int32 [B, k, L]: the data row of the fact behind every step (-1: a self-loop, or absent).  Extrapolation digraphs only."""
+        if self.digraph.data_row is None:
+            raise ValueError("data_rows: this r-digraph carries no data rows (extrapolation digraphs do)")
+        return self._gather(self.digraph.data_row, -1)
+
+
+@dataclass
+class RuleTable:
+    """Paths counted as rules: one row per distinct (query relation, relation sequence r_1..r_L), sorted by (head, body).
+
+    head     int64 [R]      the query relation
+    body     int64 [R, L]   the relations of the steps (the identity id 2 * n_rel kept as is)
+    support  int64 [R]      paths counted
+    fixed    int64 [R]      the sum of their alpha products in units of 2^-32, each path rounded once: tables add exactly
+    n_rel    int            the KG's relation count (ids >= n_rel are inverses, 2 * n_rel the identity)
+    """
+    head: torch.Tensor
+    body: torch.Tensor
+    support: torch.Tensor
+    fixed: torch.Tensor
+    n_rel: int
+
+    def product_sum(self):
+        """float64 [R]: the sum of the alpha products of each rule's paths."""
+        return self.fixed.double() * 2.0 ** -FRACTION_BITS
+
+    def mean(self):
+        """float64 [R]: the mean alpha product of each rule's paths."""
+        return self.product_sum() / self.support.double()
+
+    def top(self, q_rel, n):
+        """The n rules of query relation ``q_rel`` with the largest support (ties: the smaller body), as a RuleTable in that order."""
+        if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or n < 1:
+            raise ValueError("top: n must be a positive integer (got %r)" % (n,))
+        rows = torch.nonzero(self.head == int(q_rel)).reshape(-1)                 # ascending: body order
+        rows = rows[torch.argsort(-self.support[rows], stable=True)][:int(n)]
+        return RuleTable(self.head[rows], self.body[rows], self.support[rows], self.fixed[rows], self.n_rel)
+
+    def __add__(self, other):
+        if not isinstance(other, RuleTable):
+            return NotImplemented
+        if other.n_rel != self.n_rel or other.body.shape[1] != self.body.shape[1]:
+            raise ValueError("rule tables of different relation count or path length do not add (n_rel %d / %d, L %d / %d)"
+                             % (self.n_rel, other.n_rel, self.body.shape[1], other.body.shape[1]))
+        key = torch.cat([torch.cat([self.head[:, None], self.body], 1), torch.cat([other.head[:, None], other.body], 1)], 0)
+        return _table(key, torch.cat([self.support, other.support]), torch.cat([self.fixed, other.fixed]), self.n_rel)
+
+    def cpu(self):
+        return RuleTable(self.head.cpu(), self.body.cpu(), self.support.cpu(), self.fixed.cpu(), self.n_rel)
+
+    def format(self, id2rel=None):
+        """One string per rule, ``r1(x,z1) ^ r2^-1(z1,y) -> q(x,y)``: identity steps dropped, ids >= n_rel printed as inverses of
+        id - n_rel; ``id2rel`` names the relations (a sequence or dict), else r<id>."""
+        def name(r):
+            if r == 2 * self.n_rel:
+                return "id"
+            base = r - self.n_rel if r >= self.n_rel else r
+            label = str(id2rel[base]) if id2rel is not None else "r%d" % base
+            return label + ("^-1" if r >= self.n_rel else "")
+        out = []
+        for h, b in zip(self.head.tolist(), self.body.tolist()):
+            steps = [r for r in b if r != 2 * self.n_rel]
+            var = ["x"] + ["z%d" % i for i in range(1, len(steps))] + ["y"]
+            lhs = " ^ ".join("%s(%s,%s)" % (name(r), var[i], var[i + 1]) for i, r in enumerate(steps)) if steps else "x=y"
+            out.append("%s -> %s(x,y)" % (lhs, name(h)))
+        return out
+
+
+def _table(key, support, fixed, n_rel):
+    """RuleTable of rows key int64 [P, 1 + L] = (head, body) with their counts and fixed-point sums, equal keys merged."""
+    if key.shape[0] == 0:
+        z = torch.zeros(0, dtype=torch.int64, device=key.device)
+        return RuleTable(z, key[:, 1:], z, z.clone(), n_rel)
+    uniq, inv = torch.unique(key, dim=0, sorted=True, return_inverse=True)
+    zero = torch.zeros(uniq.shape[0], dtype=torch.int64, device=key.device)
+    return RuleTable(uniq[:, 0].contiguous(), uniq[:, 1:].contiguous(), zero.index_add(0, inv, support), zero.index_add(0, inv, fixed),
+                     n_rel)
+
+
+def rules_from_paths(paths, q_rel, n_rel):
+    """The RuleTable of a PathSet: every present path of row b counts once for the rule (q_rel[b], its relation sequence), with its
+    product rounded once, in float64, to floor(p * 2^32 + 0.5) units of 2^-32.  ``q_rel``: one query relation per row."""
+    B, k, L = paths.edge.shape
+    dev = paths.edge.device
+    q = torch.as_tensor(_ids(q_rel, "q_rel")).to(dev)
+    if q.numel() != B:
+        raise ValueError("rules_from_paths: %d query relations for %d rows" % (q.numel(), B))
+    n_rel = int(n_rel)
+    if n_rel < 1 or (B > 0 and (int(q.min()) < 0 or int(q.max()) > 2 * n_rel)):
+        raise ValueError("rules_from_paths: query relation id out of range (2*n_rel+1=%d)" % (2 * n_rel + 1))
+    have = torch.arange(k, device=dev)[None, :] < paths.count.long()[:, None]                # [B, k]
+    key = torch.cat([q[:, None, None].expand(B, k, 1), paths.rels()], -1)[have]              # [P, 1 + L]
+    fixed = torch.floor(paths.product[have] * 2.0 ** FRACTION_BITS + 0.5).long()
+    return _table(key, torch.ones_like(fixed), fixed, n_rel)
+
+
+def rules(model, subs, rels, objs=None, k=1, mode="test", min_alpha=0.0):
+    """RED_GNN_trans.rules (see there)."""
+    rd = model.explain(subs, rels, objs, mode=mode, min_alpha=min_alpha)
+    return rules_from_paths(rd.top_paths(k), rels, model.n_rel)
+
+
+def split_rows(loader, data="test", max_queries=None):
+    """(subs, rels, objs int64 arrays, mode): one row per (h, r, answer) of the first ``max_queries`` queries of the valid or test
+    split, the answers of a query in ascending order."""
+    if data not in ("valid", "test"):
+        raise ValueError("rules: data must be 'valid' or 'test' (got %r)" % (data,))
+    query, answer = (loader.valid_q, loader.valid_a) if data == "valid" else (loader.test_q, loader.test_a)
+    n = len(query) if max_queries is None else min(len(query), int(max_queries))
+    if n <= 0:
+        raise ValueError("rules: no queries in the %s split (n=%d)" % (data, n))
+    rows = [(int(query[i][0]), int(query[i][1]), int(o)) for i in range(n) for o in sorted(int(x) for x in answer[i])]
+    if not rows:
+        raise ValueError("rules: the first %d queries of the %s split have no answers" % (n, data))
+    rows = np.array(rows, dtype=np.int64)
+    mode = loader.eval_mode(data) if hasattr(loader, "eval_mode") else data
+    return rows[:, 0], rows[:, 1], rows[:, 2], mode
+
+
+def split_rules(model, loader, data="test", k=1, batch=50, max_queries=None):
+    """BaseModel.rules: the rule tables of the split's rows (split_rows), walked in batches of ``batch`` rows and added."""
+    subs, rels, objs, mode = split_rows(loader, data, max_queries)
+    if batch <= 0:
+        raise ValueError("rules: batch must be positive (got %d)" % batch)
+    table = None
+    for lo in range(0, len(subs), batch):
+        part = model.rules(subs[lo:lo + batch], rels[lo:lo + batch], objs[lo:lo + batch], k=k, mode=mode)
+        table = part if table is None else table + part
+    return table
 
 
 def _ids(x, name):

@@ -397,6 +397,13 @@ class RED_GNN_trans(nn.Module):
         from . import explain as _explain
         return _explain.explain(self, subs, rels, objs, mode, min_alpha)
 
+    def rules(self, subs, rels, objs=None, k=1, mode="test", min_alpha=0.0):
+        """The relation sequences of the k best paths behind each row (s, r, o), counted as rules r_1 ^ ... ^ r_L -> r: explain, then
+        RDigraph.top_paths(k) (one HIP launch, rg_paths_topk), then explain.rules_from_paths.  Returns an explain.RuleTable (device
+        tensors); tables of different batches add exactly.  ``objs=None``: each row's own top answer, as explain."""
+        from . import explain as _explain
+        return _explain.rules(self, subs, rels, objs, k, mode, min_alpha)
+
     def predict(self, subs, rels, k=10, exclude_known=True, mode="test"):
         """The k best answers of each query (s, r, ?): prediction.Prediction(ids int64 [B, k], scores fp32 [B, k]) on the device,
         ordered by score descending, then entity id ascending (-0.0 == +0.0, NaN last).  ``exclude_known``: the tails the loader's
@@ -620,6 +627,9 @@ class RED_GNN_induc(RED_GNN_trans):
 
     def explain(self, subs, rels, objs=None, mode="transductive", min_alpha=0.0):
         return super().explain(subs, rels, objs=objs, mode=mode, min_alpha=min_alpha)
+
+    def rules(self, subs, rels, objs=None, k=1, mode="transductive", min_alpha=0.0):
+        return super().rules(subs, rels, objs=objs, k=k, mode=mode, min_alpha=min_alpha)
 
     def predict(self, subs, rels, k=10, exclude_known=True, mode="transductive"):
         return super().predict(subs, rels, k=k, exclude_known=exclude_known, mode=mode)
