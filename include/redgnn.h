@@ -70,6 +70,12 @@ int64_t rg_graph_n_fact(const rg_graph* g);      /* rows incl. inverse + identit
 /* copy the device CSR back (tests): ptr arrays have n_ent+1 entries, pair arrays 2*n_fact. */
 int rg_graph_export(const rg_graph* g, int32_t* out_ptr_host, int32_t* out_rel_tail_host,
                     int32_t* in_ptr_host, int32_t* in_head_rel_host);
+/* copy the out-list ordered by tail back (tests; static graphs only): a second CSR-by-head over the same out_ptr in which every head's
+ * out-edges are ordered by (tail, position of the edge in the CSR-by-tail), so that the edges head -> t appear in the order the
+ * CSR-by-tail lists them - the order every walk of rg_layer_fwd sums a destination in.  rel_tail_host int32 [n_fact, 2] = {rel, tail},
+ * pos_host int32 [n_fact] = the edge's index in in_head_rel, packed_host uint32 [n_fact] = (rel << 20 | tail) (an error where the graph
+ * has no packed entries: n_ent > 2^20 or more than 2^12 relation rows).  Any pointer may be NULL. */
+int rg_graph_export_out_by_tail(const rg_graph* g, int32_t* rel_tail_host, int32_t* pos_host, uint32_t* packed_host);
 /* copy the time ids of a temporal graph's CSR entries back (tests): out_time_host int32 [n_fact] beside out_rel_tail, in_time_host
  * int32 [n_fact] beside in_head_rel (either may be NULL).  With them a test can name the CSR position of an edge whose (head, rel,
  * tail) repeats at several times.  An error on static graphs. */
@@ -137,17 +143,23 @@ int rg_frontier_edges(const rg_frontier* f, const rg_graph* g, int32_t level,
  * frontier.  scratch: device memory of rg_layer_fwd_scratch_bytes() bytes (partial sums of hub
  * destinations that are cut into segments), 16-B aligned.
  *
- * walk: how the edges are enumerated (the sums and their order are the same; results are bitwise equal):
+ * walk (0 .. 8): how the edges are enumerated (the sums and their order are the same; results are bitwise equal):
  *   0  let the library pick from the sizes of the hop (known on the host after rg_frontier_expand);
  *   1  per-query walk: every live destination tests its KG in-edges against the previous frontier;
  *   2 .. 7  word-parallel walk for hops whose SOURCE frontier is sparse (as the reference expands from the frontier's
  *      nodes, load_data.py:115-118): 32 / 16 / 8 / 4 / 2 / 1 queries per work item straight from the entity-major bitmaps; only for
  *      level == the newest hop of a static graph.
- * rg_layer_fwd_plan returns what walk 0 would pick for given sizes (n_old, n_new nodes, n_edges of the hop): callers that
- * enqueue without read-backs (rg_frontier_expand_async) record it from an eager run and pass it explicitly. */
+ *   8  single-source walk, hop 0 of a query batch: level == 1 of a frontier started by rg_frontier_reset (one node per query, its
+ *      subject, which the frontier keeps) on a static graph.  Every query enumerates its subject's out-edges from an out-list ordered by
+ *      tail, in runs of equal tail, and forms each destination's whole sum in one place (no partial rows, no second launch); hidden
+ *      and a_s are read at row b of query b.  Any other level or frontier: an error.  What walk 0 runs whenever it applies.
+ * rg_layer_fwd_plan returns what walk 0 would pick among the general walks 1 .. 7 for given sizes (n_old, n_new nodes, n_edges of the
+ * hop), and rg_layer_fwd_single_source whether walk 8 applies to `level` (1 or 0), which walk 0 then takes ahead of that plan: callers
+ * that enqueue without read-backs (rg_frontier_expand_async) record the code from an eager run and pass it explicitly. */
 size_t rg_layer_fwd_scratch_bytes(const rg_frontier* f, const rg_graph* g, int32_t ld);
 int rg_layer_fwd_plan(const rg_frontier* f, const rg_graph* g, int32_t level, int64_t n_old, int64_t n_new,
                       int64_t n_edges, int32_t ld);
+int rg_layer_fwd_single_source(const rg_frontier* f, const rg_graph* g, int32_t level);
 int rg_layer_fwd(const rg_frontier* f, const rg_graph* g, int32_t level, int64_t n_new,
                  const float* hidden, const float* rela, int32_t d, int32_t ld,
                  const float* a_s, const float* a_r, const float* a_q, int32_t ap,
@@ -247,7 +259,8 @@ int rg_xlayer_bwd(const rg_frontier* f, const rg_graph* g, int32_t level, int64_
  * W_h [d,d], weight_ih_l0 / weight_hh_l0 [3d,d] (gate rows r,z,n), bias_* [3d], Ws_next [attn,d] or NULL,
  * W_final [d] or NULL.  agg [n,ld], hidden_prev [n_old,ld], prev_idx int32 [n] (-1 = new node; NULL = all
  * new), a_s_out [n,ap], nodes int32 [n,2], scores_all [B*n_ent] (pre-zeroed; only visited entries are
- * written), hidden_out [n,ld].  act: 0 identity, 1 relu, 2 tanh.  Supported: d <= 64 or d == 128, attn_dim <= 16
+ * written), hidden_out [n,ld] - or NULL on the last layer (W_final given, Ws_next NULL), when nobody reads the new state: the kernels then
+ * skip its stores and the scores are bit for bit the same; NULL in any other call is an error.  act: 0 identity, 1 relu, 2 tanh.  Supported: d <= 64 or d == 128, attn_dim <= 16
  * (rg_dense_fwd_supported); other shapes return an error and the caller keeps its own dense path. */
 int rg_dense_fwd_supported(int32_t d, int32_t attn_dim);
 int rg_dense_fwd(int64_t n, int32_t d, int32_t ld, const float* agg, const float* hidden_prev,

@@ -152,6 +152,14 @@ struct rg_graph {
   // halves the structure bytes every query streams through its XCD's L2
   uint32_t* in_pk = nullptr;
   uint32_t* out_pk = nullptr;   // same packing for the CSR-by-head: (rel << 20 | tail)
+  // CSR-by-head once more, each head's out-edges ordered by (tail, position in the CSR-by-tail): static graphs only (nullptr otherwise).
+  // The single-source walk (layer_fwd_src1.hip) enumerates a subject's edges from it in runs of equal tail; inside a run the edges
+  // come in the order the CSR-by-tail lists them, which is the order every walk sums a destination in.  Rows by out_ptr.
+  // out_bt_rt[n_fact] = {rel, tail}, out_bt_pk[n_fact] = (rel << 20 | tail) where out_pk exists, out_bt_pos[n_fact] = the edge's
+  // position in the CSR-by-tail (which 128-entry segment of a cut row it belongs to: (pos - in_ptr[tail]) / RG_VROW_MAX).
+  int2* out_bt_rt = nullptr;
+  uint32_t* out_bt_pk = nullptr;
+  int32_t* out_bt_pos = nullptr;
   rg_vrows in_vr, out_vr;
   rg_packs in_pk_packs;         // static graphs with packed entries only (n = 0 otherwise)
   // CSR by relation (rows = relation ids): rel_ht[n_fact] = {head, tail}; its virtual rows carry the relation id in the
@@ -200,6 +208,8 @@ struct rg_frontier {
   int tcur = 0;                      // which bitsT holds the newest level
   int64_t n_nodes[RG_MAX_LEVELS] = {};  // per slot
   int64_t n_edges = 0;
+  bool single_source = false;        // level 0 is one node per query (rg_frontier_reset), whose entity is sub[b]
+  int32_t* sub = nullptr;            // device [B]: the queries' subjects as rg_frontier_reset saw them (-1: out of range)
   int64_t edge_hint = -1;            // the caller's expectation of n_edges while it is unknown on the host (after rg_frontier_expand_async)
   const int2* bm_of(int lvl) const { return bm[lvl % n_levels]; }
 };

@@ -309,7 +309,7 @@ __global__ __launch_bounds__(DENSE_T, 2) void dense_kernel(DenseArgs A) {
 #pragma unroll
     for (int it = 0; it < 16 * S / 64; ++it) {
       const int e = it * 64 + lane, r = e / S, sl = e - r * S;
-      if (row0 + r < A.n && sl < A.ld4) A.hidden_out[(row0 + r) * A.ld4 + sl] = tile[sw<DP>(r, sl)];
+      if (A.hidden_out && row0 + r < A.n && sl < A.ld4) A.hidden_out[(row0 + r) * A.ld4 + sl] = tile[sw<DP>(r, sl)];
     }
   }
 }
@@ -338,7 +338,9 @@ static int dense_fwd_impl(int64_t n, const int32_t* n_dev, int64_t n_hint, int32
                           const float* b_ih, const float* b_hh, const float* Ws_next, int32_t attn_dim, int32_t ap,
                           float* a_s_out, const float* W_final, const int32_t* nodes, int32_t n_ent, float* scores_all,
                           float* hidden_out, int32_t precision, void* scratch, int64_t scratch_bytes, void* stream) {
-  RG_CHECK(agg && W_h && w_ih && w_hh && b_ih && b_hh && hidden_out, "rg_dense_fwd: NULL argument");
+  RG_CHECK(agg && W_h && w_ih && w_hh && b_ih && b_hh, "rg_dense_fwd: NULL argument");
+  // the new state may be left unstored only where nothing reads it: the last layer (readout given, no next layer's projection)
+  RG_CHECK(hidden_out || (W_final && !Ws_next), "rg_dense_fwd: hidden_out is NULL (allowed only with W_final and without Ws_next)");
   RG_CHECK(precision >= 0 && precision <= 2, "rg_dense_fwd: precision=%d (0 = f32 MFMA, 1 = two-term f16 split, 2 = exact three-term f16 split)",
            precision);
   RG_CHECK(!prev_idx || hidden_prev, "rg_dense_fwd: prev_idx given without hidden_prev");

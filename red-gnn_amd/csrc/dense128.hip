@@ -287,7 +287,7 @@ __global__ __launch_bounds__(T, 2) void dense128_kernel(DenseArgs A) {
 #pragma unroll
     for (int it = 0; it < NL; ++it) {
       const int e = it * 64 + lane, r = e / S, sl = e - r * S;
-      if (row0 + r < A.n) A.hidden_out[(row0 + r) * S + sl] = tile[swz(r, sl)];
+      if (A.hidden_out && row0 + r < A.n) A.hidden_out[(row0 + r) * S + sl] = tile[swz(r, sl)];
     }
   }
 }

@@ -267,7 +267,7 @@ __global__ __launch_bounds__(T, 2) void dense128_split_kernel(DenseArgs A, const
         const float ng = fmaf(2.0f, __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(fmaf(rg, th, ti))), -1.0f);
         hnv[r] = fmaf(zg, hov[r] - ng, ng);       // (1 - z) n + z h
       }
-      if (node_ok) (A.hidden_out + row0 * S)[lane_off + 4 * ob] = make_float4(hnv[0], hnv[1], hnv[2], hnv[3]);
+      if (A.hidden_out && node_ok) (A.hidden_out + row0 * S)[lane_off + 4 * ob] = make_float4(hnv[0], hnv[1], hnv[2], hnv[3]);
       h4 ch, cl;
       split4(hnv[0], hnv[1], hnv[2], hnv[3], ch, cl);
       if (ob & 1) {

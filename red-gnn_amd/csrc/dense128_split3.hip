@@ -326,8 +326,10 @@ __global__ __launch_bounds__(T, 1) void dense128_split3_kernel(DenseArgs A, cons
     float hn[KS];
     // new-state rows go out through a buffer descriptor of this tile's valid rows (no branch inside the interleaved stream)
     const int rows_valid = (int)(A.n - row0 < 16 ? (A.n - row0 > 0 ? A.n - row0 : 0) : 16);
-    const __amdgpu_buffer_rsrc_t r_out = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(A.hidden_out + row0 * S), 0,
-                                                                            rows_valid * S * 16, 0x00020000);
+    // (no hidden_out: a descriptor of zero bytes over the input rows, every store is dropped)
+    const __amdgpu_buffer_rsrc_t r_out = __builtin_amdgcn_make_buffer_rsrc(
+        A.hidden_out ? reinterpret_cast<char*>(A.hidden_out + row0 * S) : reinterpret_cast<char*>(const_cast<float4*>(A.agg)), 0,
+        A.hidden_out ? rows_valid * S * 16 : 0, 0x00020000);
     // The loop over output blocks is software-pipelined by one block: the gate arithmetic of block ob - 1 (joins of the bf8 chains, the
     // three gates, the new state and its store: 105 operations) is issued between the MFMAs of block ob's two chunks.
     auto gate_loop = [&](auto HH_) {

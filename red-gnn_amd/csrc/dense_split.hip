@@ -284,7 +284,7 @@ __global__ __launch_bounds__(DENSE_T, 2) void dense_split_kernel(DenseArgs A) {
           const float ng = fmaf(2.0f, __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(fmaf(rg, th, ti))), -1.0f);
           hnv[r] = fmaf(zg, hov[r] - ng, ng);       // (1 - z) n + z h
         }
-        if (node_ok && ((col_ok >> ob) & 1u))
+        if (A.hidden_out && node_ok && ((col_ok >> ob) & 1u))
           (A.hidden_out + row0 * A.ld4)[lane_off + 4 * ob] = make_float4(hnv[0], hnv[1], hnv[2], hnv[3]);
         h4 ch, cl;                                              // |h| <= 1 in the model; any finite state below 65504 is carried
         split4(hnv[0], hnv[1], hnv[2], hnv[3], ch, cl);

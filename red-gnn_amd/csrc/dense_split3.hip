@@ -305,8 +305,10 @@ __global__ __launch_bounds__(DENSE_T, 2) void dense_split3_kernel(DenseArgs A) {
     // new-state rows go out through a buffer descriptor of this tile's valid rows: lanes beyond them (and columns beyond the row) are
     // dropped by its range check instead of by a branch, so that the whole gate loop is ONE scheduling region
     const int rows_valid = (int)(A.n - row0 < 16 ? (A.n - row0 > 0 ? A.n - row0 : 0) : 16);
+    // (no hidden_out - the last layer of a forward nobody traces: a descriptor of zero bytes over the input rows, every store is dropped)
     const __amdgpu_buffer_rsrc_t r_out = __builtin_amdgcn_make_buffer_rsrc(
-        reinterpret_cast<char*>(A.hidden_out + row0 * A.ld4), 0, rows_valid * A.ld4 * 16, 0x00020000);
+        A.hidden_out ? reinterpret_cast<char*>(A.hidden_out + row0 * A.ld4) : reinterpret_cast<char*>(const_cast<float4*>(A.agg)), 0,
+        A.hidden_out ? rows_valid * A.ld4 * 16 : 0, 0x00020000);
     auto gru = [&](auto has_old) {
       constexpr bool OLD = decltype(has_old)::value;
       Frag<KST> H;

@@ -17,7 +17,7 @@ namespace {
 // bm[0][b][w] = {bit of q_sub[b] if it falls in word w, b + (w beyond that word)}; the same kernel sets the entity-major bits
 // (bitsT zeroed before) and the counters (N = B; the error flag for an id out of range).
 __global__ void reset_level0_kernel(const int32_t* __restrict__ q_sub, int B, int n_ent, int BW, int W, uint32_t* __restrict__ bitsT,
-                                    int2* __restrict__ bm0, int32_t* __restrict__ counters) {
+                                    int2* __restrict__ bm0, int32_t* __restrict__ counters, int32_t* __restrict__ sub) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (int64_t)B * W) return;
   const int b = (int)(i / W), w = (int)(i - (int64_t)b * W);
@@ -27,6 +27,7 @@ __global__ void reset_level0_kernel(const int32_t* __restrict__ q_sub, int B, in
   // nodes of earlier queries: b minus the invalid ones among them would be exact, but an invalid id is an error anyway
   bm0[i] = make_int2(w == ew ? (int)(1u << (e & 31)) : 0, b + (w > ew ? 1 : 0));
   if (w == 0) {
+    sub[b] = ok ? e : -1;         // the single-source walk of hop 0 starts from here (layer_fwd_src1.hip)
     if (ok) atomicOr(&bitsT[(int64_t)e * BW + (b >> 5)], 1u << (b & 31));
     else atomicOr((unsigned*)&counters[1], 1u);
     if (b == 0) { counters[0] = B; counters[4] = B; }
@@ -348,6 +349,7 @@ size_t ws_layout(int32_t n_ent, int32_t B, int32_t n_levels, size_t* off /*[8]*/
   off[4] = take(rg::scan_scratch_elems((int64_t)B * W) * 4); // scan scratch
   off[5] = take(1024 + RG_QUEUE_BYTES);                      // counters + per-level snapshots (1 KB), then the work-queue heads
   off[6] = take((size_t)n_levels * B * W * 8);               // bm levels
+  off[7] = take((size_t)B * 4);                              // the queries' subjects (rg_frontier_reset)
   return o;
 }
 
@@ -383,6 +385,7 @@ int rg_frontier_create(int32_t n_ent, int32_t batch, int32_t n_levels, void* ws,
   f->counters = (int32_t*)(base + off[5]);
   f->queues = f->counters + 256;
   for (int l = 0; l < n_levels; ++l) f->bm[l] = (int2*)(base + off[6] + (size_t)l * batch * f->W * 8);
+  f->sub = (int32_t*)(base + off[7]);
   if (hipHostMalloc((void**)&f->counts_pinned, 1024, hipHostMallocDefault) != hipSuccess) {
     delete f;
     rg::set_error("rg_frontier_create: hipHostMalloc failed");
@@ -422,8 +425,9 @@ int rg_frontier_reset(rg_frontier* f, const int32_t* q_sub, void* stream) {
   f->queues_clean = false;
   const int64_t nw = (int64_t)f->B * f->W;
   hipLaunchKernelGGL(reset_level0_kernel, dim3(rg::ceil_div(nw, 256)), dim3(256), 0, s, q_sub, f->B, f->n_ent, f->BW, f->W,
-                     f->bitsT[0], f->bm[0], f->counters);
+                     f->bitsT[0], f->bm[0], f->counters, f->sub);
   RG_LAUNCH_CHECK();
+  f->single_source = true;
   f->n_nodes[0] = f->B;   // one node per query; an out-of-range q_sub is reported by the next expand
   return 0;
 }
@@ -448,6 +452,7 @@ int rg_frontier_reset_nodes(rg_frontier* f, const int32_t* nodes, int64_t n, voi
   }
   if (build_level(f, s)) return 1;
   if (rg::copy_words_async(&f->counters[4], &f->counters[0], 1, s)) return 1;
+  f->single_source = false;
   f->n_nodes[0] = n;   // duplicates or out-of-range ids are reported by the next expand
   return 0;
 }

@@ -288,7 +288,7 @@ struct Arena {
 extern "C" {
 
 const char* rg_last_error(void) { return rg::g_err.c_str(); }
-int rg_version(void) { return 10; }   // bumped whenever a kernel on the bench path changes: keys profiles/traffic_layer_fwd.json
+int rg_version(void) { return 11; }   // bumped whenever a kernel on the bench path changes: keys profiles/traffic_layer_fwd.json
 
 // rows (H, R, T [, TIME]) -> device CSRs, packed entries, virtual rows
 static int build_graph(int32_t n_ent, int32_t n_rel, int32_t n_rela_rows, const std::vector<int32_t>& H,
@@ -344,6 +344,27 @@ static int build_graph(int32_t n_ent, int32_t n_rel, int32_t n_rela_rows, const 
       out_pk[i] = ((uint32_t)out_rt[i].x << 20) | (uint32_t)out_rt[i].y;
     }
     A.add(&g->in_pk, in_pk); A.add(&g->out_pk, out_pk);
+  }
+  // static graphs: the out-list ordered by (tail, CSR-by-tail position) of the single-source walk (common.h).  The CSR-by-tail read
+  // front to back is ordered by exactly that pair, so one stable counting pass by head over its positions gives the order.
+  std::vector<int2> out_bt_rt;
+  std::vector<uint32_t> out_bt_pk;
+  std::vector<int32_t> out_bt_pos;
+  if (!TIME) {
+    out_bt_rt.resize(n_fact); out_bt_pos.resize(n_fact);
+    std::vector<int32_t> po(out_ptr.begin(), out_ptr.end() - 1);
+    for (int32_t t = 0; t < n_ent; ++t)
+      for (int32_t q = in_ptr[t]; q < in_ptr[t + 1]; ++q) {
+        const int32_t j = po[in_hr[q].x]++;
+        out_bt_rt[j] = make_int2(in_hr[q].y, t);
+        out_bt_pos[j] = q;
+      }
+    A.add(&g->out_bt_rt, out_bt_rt); A.add(&g->out_bt_pos, out_bt_pos);
+    if (!in_pk.empty()) {
+      out_bt_pk.resize(n_fact);
+      for (int64_t j = 0; j < n_fact; ++j) out_bt_pk[j] = ((uint32_t)out_bt_rt[j].x << 20) | (uint32_t)out_bt_rt[j].y;
+      A.add(&g->out_bt_pk, out_bt_pk);
+    }
   }
   // CSR by relation (and, for temporal graphs, by time id)
   std::vector<int32_t> rel_ptr(n_rela_rows + 1, 0), rel_tm(TIME ? n_fact : 0);
@@ -475,6 +496,16 @@ int rg_graph_export(const rg_graph* g, int32_t* out_ptr, int32_t* out_rt, int32_
   if (in_ptr) RG_HIP(hipMemcpy(in_ptr, g->in_ptr, (g->n_ent + 1) * sizeof(int32_t), hipMemcpyDeviceToHost));
   if (out_rt) RG_HIP(hipMemcpy(out_rt, g->out_rt, g->n_fact * sizeof(int2), hipMemcpyDeviceToHost));
   if (in_hr) RG_HIP(hipMemcpy(in_hr, g->in_hr, g->n_fact * sizeof(int2), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int rg_graph_export_out_by_tail(const rg_graph* g, int32_t* rel_tail, int32_t* pos, uint32_t* packed) {
+  RG_CHECK(g != nullptr, "rg_graph_export_out_by_tail: graph is NULL");
+  RG_CHECK(g->out_bt_rt && g->out_bt_pos, "rg_graph_export_out_by_tail: the graph has no out-list by tail (static graphs only)");
+  RG_CHECK(!packed || g->out_bt_pk, "rg_graph_export_out_by_tail: the graph's entries are not packed");
+  if (rel_tail) RG_HIP(hipMemcpy(rel_tail, g->out_bt_rt, g->n_fact * sizeof(int2), hipMemcpyDeviceToHost));
+  if (pos) RG_HIP(hipMemcpy(pos, g->out_bt_pos, g->n_fact * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (packed) RG_HIP(hipMemcpy(packed, g->out_bt_pk, g->n_fact * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return 0;
 }
 

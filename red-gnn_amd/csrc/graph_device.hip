@@ -59,12 +59,23 @@ __global__ void iota_kernel(uint32_t* __restrict__ v, int64_t n) {
   if (i < n) v[i] = (uint32_t)i;
 }
 
-template <int MODE>   // key of row i: 0 = tail, 1 = (head, relation), 2 = relation
+template <int MODE>   // key of row i: 0 = tail, 1 = (head, relation), 2 = relation, 3 = (head, tail) with rel_bits = the entity bits
 __global__ void keys_kernel(const int32_t* __restrict__ H, const int32_t* __restrict__ R, const int32_t* __restrict__ T, int rel_bits,
                             uint64_t* __restrict__ keys, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  keys[i] = MODE == 0 ? (uint64_t)T[i] : (MODE == 1 ? (((uint64_t)H[i] << rel_bits) | (uint64_t)R[i]) : (uint64_t)R[i]);
+  keys[i] = MODE == 0 ? (uint64_t)T[i] : (MODE == 1 ? (((uint64_t)H[i] << rel_bits) | (uint64_t)R[i])
+                                       : (MODE == 2 ? (uint64_t)R[i] : (((uint64_t)H[i] << rel_bits) | (uint64_t)T[i])));
+}
+
+// inv[perm[q]] = q: where a fact row went
+__global__ void invert_perm_kernel(const uint32_t* __restrict__ perm, int32_t* __restrict__ inv, int64_t n) {
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q < n) inv[perm[q]] = (int32_t)q;
+}
+__global__ void gather_words_kernel(const uint32_t* __restrict__ perm, const int32_t* __restrict__ in, int32_t* __restrict__ out, int64_t n) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < n) out[j] = in[perm[j]];
 }
 
 __global__ void hist_kernel(const int32_t* __restrict__ key, int64_t n, uint32_t* __restrict__ cnt) {
@@ -243,7 +254,7 @@ extern "C" int rg_graph_create_device(int32_t n_ent, int32_t n_rel, const int32_
   int rel_bits = 1, ent_bits = 1;
   while ((1 << rel_bits) < n_rela_rows) ++rel_bits;
   while (((int64_t)1 << ent_bits) < n_ent) ++ent_bits;
-  Tmp tmp((size_t)n_fact * 160 + (size_t)n_ent * 96 + ((size_t)8 << 20));       // (rows, keys, permutations, CSRs, sort scratch, virtual rows)
+  Tmp tmp((size_t)n_fact * 208 + (size_t)n_ent * 96 + ((size_t)8 << 20));       // (rows, keys, permutations, CSRs, sort scratch, virtual rows)
   int32_t* H = tmp.get<int32_t>(n_fact); int32_t* R = tmp.get<int32_t>(n_fact); int32_t* T = tmp.get<int32_t>(n_fact);
   uint64_t* keys = tmp.get<uint64_t>(n_fact);
   uint32_t* perm_in = tmp.get<uint32_t>(n_fact); uint32_t* perm_out = tmp.get<uint32_t>(n_fact); uint32_t* perm_rel = tmp.get<uint32_t>(n_fact);
@@ -266,6 +277,17 @@ extern "C" int rg_graph_create_device(int32_t n_ent, int32_t n_rel, const int32_
   hipLaunchKernelGGL(gather_pairs_kernel, dim3(blocks(n_fact)), dim3(256), 0, s, perm_in, H, R, in_hr, in_pk, 0, n_fact);
   hipLaunchKernelGGL(gather_pairs_kernel, dim3(blocks(n_fact)), dim3(256), 0, s, perm_out, R, T, out_rt, out_pk, 1, n_fact);
   hipLaunchKernelGGL(gather_pairs_kernel, dim3(blocks(n_fact)), dim3(256), 0, s, perm_rel, H, T, rel_ht, (uint32_t*)nullptr, 0, n_fact);
+  // the out-list ordered by (tail, CSR-by-tail position) of the single-source walk: the CSR-by-tail keeps fact order inside a tail, so a
+  // stable sort of the fact rows by (head, tail) is that order; an edge's CSR-by-tail position is where perm_in put its fact row
+  uint32_t* perm_bt = tmp.get<uint32_t>(n_fact); int32_t* inv_in = tmp.get<int32_t>(n_fact);
+  int2* out_bt_rt = tmp.get<int2>(n_fact); int32_t* out_bt_pos = tmp.get<int32_t>(n_fact);
+  uint32_t* out_bt_pk = packed ? tmp.get<uint32_t>(n_fact) : nullptr;
+  RG_CHECK(perm_bt && inv_in && out_bt_rt && out_bt_pos && (!packed || out_bt_pk), "rg_graph_create_device: out of device memory");
+  hipLaunchKernelGGL(keys_kernel<3>, dim3(blocks(n_fact)), dim3(256), 0, s, H, R, T, ent_bits, keys, n_fact);
+  if (sort_perm(tmp, keys, 2 * ent_bits, n_fact, perm_bt, s)) return 1;
+  hipLaunchKernelGGL(invert_perm_kernel, dim3(blocks(n_fact)), dim3(256), 0, s, perm_in, inv_in, n_fact);
+  hipLaunchKernelGGL(gather_pairs_kernel, dim3(blocks(n_fact)), dim3(256), 0, s, perm_bt, R, T, out_bt_rt, out_bt_pk, 1, n_fact);
+  hipLaunchKernelGGL(gather_words_kernel, dim3(blocks(n_fact)), dim3(256), 0, s, perm_bt, inv_in, out_bt_pos, n_fact);
   if (build_ptr(tmp, T, n_fact, n_ent, in_ptr, s) || build_ptr(tmp, H, n_fact, n_ent, out_ptr, s) || build_ptr(tmp, R, n_fact, n_rela_rows, rel_ptr, s)) return 1;
   hipLaunchKernelGGL(max_kernel, dim3(blocks(n_ent)), dim3(256), 0, s, in_ptr, n_ent, &flags[1]);
   hipLaunchKernelGGL(max_kernel, dim3(blocks(n_ent)), dim3(256), 0, s, out_ptr, n_ent, &flags[2]);
@@ -318,6 +340,8 @@ extern "C" int rg_graph_create_device(int32_t n_ent, int32_t n_rel, const int32_
   add((void**)&g->out_ptr, out_ptr, (size_t)(n_ent + 1) * 4); add((void**)&g->in_ptr, in_ptr, (size_t)(n_ent + 1) * 4);
   add((void**)&g->out_rt, out_rt, (size_t)n_fact * 8); add((void**)&g->in_hr, in_hr, (size_t)n_fact * 8);
   if (packed) { add((void**)&g->in_pk, in_pk, (size_t)n_fact * 4); add((void**)&g->out_pk, out_pk, (size_t)n_fact * 4); }
+  add((void**)&g->out_bt_rt, out_bt_rt, (size_t)n_fact * 8); add((void**)&g->out_bt_pos, out_bt_pos, (size_t)n_fact * 4);
+  if (packed) add((void**)&g->out_bt_pk, out_bt_pk, (size_t)n_fact * 4);
   add((void**)&g->rel_ptr, rel_ptr, (size_t)(n_rela_rows + 1) * 4); add((void**)&g->rel_ht, rel_ht, (size_t)n_fact * 8);
   add((void**)&g->in_vr.rows, vin.rows, (size_t)g->in_vr.n * 16); add((void**)&g->in_vr.split, vin.split, (size_t)g->in_vr.n_split * 16);
   add((void**)&g->out_vr.rows, vout.rows, (size_t)g->out_vr.n * 16); add((void**)&g->out_vr.split, vout.split, (size_t)g->out_vr.n_split * 16);

@@ -1,6 +1,7 @@
 // Static RED-GNN entry point of the fused forward kernels (per-query walk: layer_fwd_kernel.h; word-parallel form for hops
-// whose source frontier is sparse: layer_fwd_wp.hip).
+// whose source frontier is sparse: layer_fwd_wp.hip; single-source walk for hop 0 of a query batch: layer_fwd_src1.hip).
 #include "layer_fwd_kernel.h"
+#include "layer_fwd_src1.h"
 #include "layer_fwd_wp.h"
 
 extern "C" size_t rg_layer_fwd_scratch_bytes(const rg_frontier* f, const rg_graph* g, int32_t ld) {
@@ -9,8 +10,14 @@ extern "C" size_t rg_layer_fwd_scratch_bytes(const rg_frontier* f, const rg_grap
   return rg::align_up((size_t)f->B * g->in_vr.n_slots * ld * sizeof(float), 256) + rg::align_up((size_t)f->B * g->in_vr.n_slots, 256) + 256;
 }
 
-// walk codes: 1 = per-query walk; 2, 3, 4, 5 = word-parallel with 32, 16, 8, 4 queries per item
-static int plan_walk(const rg_frontier* f, const rg_graph* g, int32_t level, int64_t n_old, int64_t n_new, int64_t n_edges, int32_t ld) {
+// the single-source walk applies to hop 0 of a batch that rg_frontier_reset started (one node per query, whose entity the frontier
+// kept), on a static graph (which carries the out-list ordered by tail), without row windows
+static bool src1_applies(const rg_frontier* f, const rg_graph* g, int32_t level) {
+  return level == 1 && f->level >= 1 && f->single_source && f->sub && !f->win_lo && g->n_time == 0 && g->out_bt_pos && g->out_bt_rt;
+}
+
+// walk codes of the general walks: 1 = per-query walk; 2, 3, 4, 5 = word-parallel with 32, 16, 8, 4 queries per item
+static int plan_general(const rg_frontier* f, const rg_graph* g, int32_t level, int64_t n_old, int64_t n_new, int64_t n_edges, int32_t ld) {
   if (g->in_pk_packs.n == 0 || level != f->level || n_old < 0 || n_new <= 0 || n_edges < 0 || !rgwp::offsets_fit(n_old, ld)) return 1;
   // per-query walk: tests every in-edge of every live destination (~ n_new * mean in-degree candidates) after testing all
   // B * n_vrows items; word-parallel: touches the valid edges only, 32 queries' source rows per XCD at a time
@@ -32,10 +39,19 @@ static int plan_walk(const rg_frontier* f, const rg_graph* g, int32_t level, int
   return code;
 }
 
+// what walk 0 runs: the single-source walk (8) wherever it applies, else the general plan
+static int plan_walk(const rg_frontier* f, const rg_graph* g, int32_t level, int64_t n_old, int64_t n_new, int64_t n_edges, int32_t ld) {
+  return src1_applies(f, g, level) ? 8 : plan_general(f, g, level, n_old, n_new, n_edges, ld);
+}
+
+extern "C" int rg_layer_fwd_single_source(const rg_frontier* f, const rg_graph* g, int32_t level) {
+  return f && g && src1_applies(f, g, level) ? 1 : 0;
+}
+
 extern "C" int rg_layer_fwd_plan(const rg_frontier* f, const rg_graph* g, int32_t level, int64_t n_old, int64_t n_new,
                                  int64_t n_edges, int32_t ld) {
   if (!f || !g) return 1;
-  return plan_walk(f, g, level, n_old, n_new, n_edges, ld);
+  return plan_general(f, g, level, n_old, n_new, n_edges, ld);
 }
 
 extern "C" int rg_layer_fwd(const rg_frontier* f, const rg_graph* g, int32_t level, int64_t n_new, const float* hidden,
@@ -45,7 +61,9 @@ extern "C" int rg_layer_fwd(const rg_frontier* f, const rg_graph* g, int32_t lev
   RG_CHECK(f && g && hidden && rela && a_s && a_r && a_q && w_alpha && b_alpha && agg_out, "rg_layer_fwd: NULL argument");
   RG_CHECK((((uintptr_t)hidden | (uintptr_t)rela | (uintptr_t)a_s | (uintptr_t)a_r | (uintptr_t)a_q | (uintptr_t)agg_out |
              (uintptr_t)scratch) & 15) == 0, "rg_layer_fwd: float buffers must be 16-B aligned");
-  RG_CHECK(walk >= 0 && walk <= 7, "rg_layer_fwd: walk=%d not in 0..7", walk);
+  RG_CHECK(walk >= 0 && walk <= 8, "rg_layer_fwd: walk=%d not in 0..8", walk);
+  RG_CHECK(walk != 8 || src1_applies(f, g, level), "rg_layer_fwd: the single-source walk (8) needs level 1 of a frontier started by "
+           "rg_frontier_reset, on a static graph (level %d, newest %d)", level, f->level);
   rgfwd::FwdArgs A;
   if (rgfwd::fill_common("rg_layer_fwd", f, g, level, n_new, d, ld, ap, attn_dim, scratch, scratch_bytes,
                          rg_layer_fwd_scratch_bytes(f, g, ld), &A)) return 1;
@@ -58,6 +76,15 @@ extern "C" int rg_layer_fwd(const rg_frontier* f, const rg_graph* g, int32_t lev
   if (walk == 0)      // sizes known on the host (after rg_frontier_expand): pick; after expand_async the caller says which
     walk = plan_walk(f, g, level, f->n_nodes[(level - 1) % f->n_levels], f->n_nodes[level % f->n_levels],
                      level == f->level ? f->n_edges : -1, ld);
+  if (walk == 8) {
+    rgsrc1::Src1Args S;
+    S.B = f->B; S.W = f->W; S.sub = f->sub; S.out_ptr = g->out_ptr; S.in_ptr = g->in_ptr;
+    S.list_pk = g->out_bt_pk; S.list_rt = g->out_bt_rt; S.list_pos = g->out_bt_pos; S.bm_new = A.bm_new;
+    S.hidden = A.hidden; S.rela = A.rela; S.ld4 = A.ld4; S.a_s = A.a_s; S.a_r = A.a_r; S.a_q = A.a_q;
+    S.w_alpha = w_alpha; S.b_alpha = b_alpha; S.attn_dim = attn_dim; S.agg = A.agg;
+    f->queues_clean = A.walk.queues_clean;      // (this walk takes no tickets: the heads stay as they were)
+    return rgsrc1::launch(S, ld / 4, ap / 4, g->max_out_deg, s);
+  }
   if (walk >= 2 && f->n_nodes[(level - 1) % f->n_levels] < 0 && !rgwp::offsets_fit((int64_t)f->B * f->n_ent, ld))
     walk = 1;       // sizes unknown on the host (expand_async) and the full grid would overflow the 32-bit row offsets: per-query walk
   if (walk >= 2) {

@@ -12,7 +12,7 @@ from . import _lib
 
 
 # tests set this to 1 (per-query walk) or 2..5 (word-parallel, 32/16/8/4 queries per item) to force rg_layer_fwd's edge walk; 0 = the
-# library picks from the hop's sizes
+# library picks from the hop's sizes (8, the single-source walk, on hop 0 of a batch of queries)
 FORCE_WALK = 0
 
 # bench.py sets these to lists to collect (start_event, end_event, n_edges, n_new) per rg_layer_fwd launch and
@@ -102,6 +102,14 @@ class Graph:
         ihr = np.empty((self.n_fact, 2), np.int32)
         _lib.check(_lib.lib().rg_graph_export(self.handle, _lib.ptr(op), _lib.ptr(ort), _lib.ptr(ip), _lib.ptr(ihr)))
         return op, ort, ip, ihr
+
+    def export_out_by_tail(self):
+        """(rel_tail [n_fact,2], pos [n_fact]) of the out-list ordered by (tail, CSR-by-tail position) as numpy — for tests.  Rows by
+        export()'s out_ptr; pos indexes export()'s in_head_rel."""
+        rt = np.empty((self.n_fact, 2), np.int32)
+        pos = np.empty(self.n_fact, np.int32)
+        _lib.check(_lib.lib().rg_graph_export_out_by_tail(self.handle, _lib.ptr(rt), _lib.ptr(pos), None))
+        return rt, pos
 
     def close(self):
         if getattr(self, "handle", None) is not None and _lib._lib is not None:
@@ -523,8 +531,16 @@ def xattn_profile(frontier, graph, level, q_time, loop_time, row_time, lag_bin, 
 
 
 def layer_fwd_plan(frontier, graph, level, n_old, n_new, n_edges, ld):
-    """The walk rg_layer_fwd picks for a hop of these sizes (rg_layer_fwd_plan): recorded from an eager forward for graph replay."""
+    """The general walk (1 .. 7) rg_layer_fwd picks for a hop of these sizes (rg_layer_fwd_plan)."""
     return int(_lib.lib().rg_layer_fwd_plan(frontier.handle, graph.handle, level, n_old, n_new, n_edges, ld))
+
+
+def layer_fwd_walk(frontier, graph, level, n_old, n_new, n_edges, ld):
+    """The walk rg_layer_fwd's walk 0 runs on this hop: 8 (single-source walk) where it applies, else the general plan.  Recorded from
+    an eager forward for graph replay."""
+    if _lib.lib().rg_layer_fwd_single_source(frontier.handle, graph.handle, level):
+        return 8
+    return layer_fwd_plan(frontier, graph, level, n_old, n_new, n_edges, ld)
 
 
 def layer_fwd_scratch_bytes(frontier, graph, ld):
@@ -733,13 +749,14 @@ def dense_scratch(d, precision, device):
 
 
 def dense_fwd(agg, hidden_prev, prev_idx, d, W_h, act, gate, Ws_next=None, attn_dim=0, ap=0, W_final=None, nodes=None,
-              n_ent=0, scores_all=None, precision="f32"):
+              n_ent=0, scores_all=None, precision="f32", want_hidden=True):
     """Fused W_h + act + GRU step (+ next layer's a_s, + readout) on the matrix cores (rg_dense_fwd).  precision: "f32" = exact
     fp32 MFMA, "f16x3" = exact three-term f16 splits of every operand (fp32 arithmetic on the f16 pipe), "f16x2" = two-term f16
     splits (22 bits, fp32 accumulation); see include/redgnn.h.
-    Returns (hidden_new [n, ld], a_s_next [n, ap] or None)."""
+    want_hidden=False (last layer only: W_final given, no Ws_next): the new state is neither allocated nor stored.
+    Returns (hidden_new [n, ld] or None, a_s_next [n, ap] or None)."""
     n, ld = agg.shape
-    hidden = torch.empty_like(agg)
+    hidden = torch.empty_like(agg) if want_hidden else None
     a_s = torch.empty((n, ap), dtype=torch.float32, device=agg.device) if Ws_next is not None else None
     c = lambda t: None if t is None else t.detach().contiguous()
     W_h, w_ih, w_hh, b_ih, b_hh = c(W_h), c(gate.weight_ih_l0), c(gate.weight_hh_l0), c(gate.bias_ih_l0), c(gate.bias_hh_l0)

@@ -325,7 +325,7 @@ class _GraphedInference:
             engine.layer_fwd_into(fr, graph, fr.level, n_hint, hidden, rela_p, d, a_s, a_r, a_q,
                                   layer.w_alpha.weight.reshape(-1).contiguous(), layer.w_alpha.bias, a, self.agg, self.scratch, walk=walk)
             last = i + 1 == m.n_layer
-            out_h, out_a = self.hid[i % 2], self.a_s[i % 2]
+            out_h, out_a = None if last else self.hid[i % 2], self.a_s[i % 2]      # (nobody reads the last layer's state)
             engine.dense_fwd_dev(self.cap, fr.count_ptr(), self.agg, hidden, self.prev, d, layer.W_h.weight, m.act_name, m.gate, out_h,
                                  Ws_next=None if last else m.gnn_layers[i + 1].Ws_attn.weight, attn_dim=a, ap=ap,
                                  a_s_out=None if last else out_a, W_final=m.W_final.weight if last else None,
@@ -596,7 +596,7 @@ class RED_GNN_trans(nn.Module):
             n_new, n_e, n_old = fr.expand(graph)
             nodes, prev_idx, old_new = fr.nodes(want_prev=True, want_old_new=trace is not None)
             n_edges.append(n_e)
-            sizes.append((n_new, engine.layer_fwd_plan(fr, graph, fr.level, n_old, n_new, n_e, ld), n_e))
+            sizes.append((n_new, engine.layer_fwd_walk(fr, graph, fr.level, n_old, n_new, n_e, ld), n_e))
             layer = self.gnn_layers[i]
             if kept is not None:
                 kept.append(dict(a_s=a_s, tables=tables[i]))
@@ -606,7 +606,7 @@ class RED_GNN_trans(nn.Module):
                 agg, hidden, prev_idx, d, layer.W_h.weight, self.act_name, self.gate,
                 Ws_next=None if last else self.gnn_layers[i + 1].Ws_attn.weight, attn_dim=a, ap=ap,
                 W_final=self.W_final.weight if last else None, nodes=nodes, n_ent=n_ent, scores_all=scores_all,
-                precision=self.dense_precision)
+                precision=self.dense_precision, want_hidden=not last or trace is not None or kept is not None)
             if trace is not None:
                 trace.append(dict(nodes=nodes, old_nodes_new_idx=old_new, n_edges=n_e, hidden=hidden[:, :d]))
         self.last_stats = dict(n_edges=n_edges, n_nodes=int(nodes.shape[0]))

@@ -16,8 +16,8 @@ for walk in (0, 3, 4, 5, 6, 0):
     engine.FORCE_WALK = walk
     bm = BaseModel(Opt, loader)
     if walk:      # a forced walk overrides the recorded per-hop plan of the replayed forwards
-        orig = engine.layer_fwd_plan
-        engine.layer_fwd_plan = lambda *a, **k: walk
+        orig = engine.layer_fwd_walk
+        engine.layer_fwd_walk = lambda *a, **k: walk
     for _ in range(4):
         bm.evaluate()
     torch.cuda.synchronize(); t0 = time.perf_counter()
@@ -25,7 +25,7 @@ for walk in (0, 3, 4, 5, 6, 0):
         mrr, out = bm.evaluate()
     torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / 4
     if walk:
-        engine.layer_fwd_plan = orig
+        engine.layer_fwd_walk = orig
     nq = loader.n_valid + loader.n_test
     print("walk %d: %.0f queries/s  mrr %.4f" % (walk, nq / dt, mrr), flush=True)
 engine.FORCE_WALK = 0
