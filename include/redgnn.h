@@ -123,9 +123,13 @@ int rg_frontier_nodes(const rg_frontier* f, int32_t* nodes_out, int32_t* prev_id
                       int32_t* old_nodes_new_idx_out, void* stream);
 /* materialised edge list of hop `level-1 -> level` (API parity with sampled_edges,
  * load_data.py:118-125): edges_out int32 [E,6] = (batch, head, rel, tail, old_idx, new_idx),
- * grouped by new_idx (destination-segmented); row_ptr_out int32 [N_new+1].
- * nodes_new: device int32 [N_new,2] from rg_frontier_nodes.  scratch: device memory of
- * rg_frontier_edges_scratch_bytes(N_new) bytes. */
+ * grouped by new_idx (destination-segmented) and, inside a destination, in the order the
+ * CSR-by-tail lists its in-edges (fact-row order); row_ptr_out int32 [N_new+1].
+ * nodes_new: device int32 [N_new,2] from rg_frontier_nodes (may be NULL where N_new == 0:
+ * row_ptr_out = {0}).  scratch: device memory of rg_frontier_edges_scratch_bytes(N_new) bytes.
+ * `level` must still be resident together with its source level: level in
+ * (current - n_levels + 1, current].  An error on a frontier that has windows set
+ * (rg_frontier_set_window): the edge list of a windowed hop is not materialised. */
 size_t rg_frontier_edges_scratch_bytes(int64_t n_new);
 int rg_frontier_edges(const rg_frontier* f, const rg_graph* g, int32_t level,
                       const int32_t* nodes_new, int64_t n_new, int32_t* edges_out,

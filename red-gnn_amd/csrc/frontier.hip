@@ -562,8 +562,11 @@ int rg_frontier_level_counts(const rg_frontier* f, int64_t* counts_host, void* s
   hipStream_t s = (hipStream_t)stream;
   int32_t* host = (int32_t*)f->counts_pinned + 16;      // pinned: [0..7] is rg_frontier_expand's, snapshots behind it
   RG_HIP(hipMemcpyAsync(host, &f->counters[64], sizeof(int32_t) * 8 * (f->level + 1), hipMemcpyDeviceToHost, s));
+  // N of level 0 from the device (its snapshot slot is unused): the host's n_nodes[0] is the slot of every level that is a multiple
+  // of n_levels, overwritten once the ring wraps (and -1 after an asynchronous hop)
+  RG_HIP(hipMemcpyAsync(host, &f->counters[4], sizeof(int32_t), hipMemcpyDeviceToHost, s));
   RG_HIP(hipStreamSynchronize(s));
-  counts_host[0] = f->n_nodes[0]; counts_host[1] = 0;
+  counts_host[0] = host[0]; counts_host[1] = 0;
   for (int l = 1; l <= f->level; ++l) {
     const int32_t* c = host + 8 * l;
     RG_CHECK(c[1] == 0, "rg_frontier_level_counts: a start node had batch or entity id out of range");
@@ -592,7 +595,8 @@ size_t rg_frontier_edges_scratch_bytes(int64_t n_new) {
 
 int rg_frontier_edges(const rg_frontier* f, const rg_graph* g, int32_t level, const int32_t* nodes_new, int64_t n_new,
                       int32_t* edges, int32_t* row_ptr, void* scratch, void* stream) {
-  RG_CHECK(f && g && nodes_new && row_ptr && scratch, "rg_frontier_edges: NULL argument");
+  RG_CHECK(f && g && (nodes_new || n_new == 0) && row_ptr && scratch, "rg_frontier_edges: NULL argument");
+  RG_CHECK(!f->win_lo, "rg_frontier_edges: windows are set: the edge list of a windowed hop is not materialised");
   RG_CHECK(level >= 1 && level <= f->level && level > f->level - f->n_levels + 1,
            "rg_frontier_edges: level %d not resident (current %d, %d kept)", level, f->level, f->n_levels);
   RG_CHECK(n_new == f->n_nodes[level % f->n_levels], "rg_frontier_edges: n_new=%lld but level %d has %lld nodes",

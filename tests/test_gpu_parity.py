@@ -208,9 +208,10 @@ def test_forward_vs_oracle_c2_shape_small_batch():
 @pytest.mark.parametrize("B", [3, 6, 40, 400])
 def test_level_build_paths_give_the_reference_node_lists(B):
     """The ways a new level's node list is built - one workgroup with its node list fused (B x ceil(n_ent / 32) <= 1 024 words) or as
-    a launch of its own (<= 9 216 words), the general multi-launch transpose + scan + pack - against a dense numpy expansion on C2
-    (313 words per query: 3 / 6 / 40 and 400 queries): node lists in (query, entity) order, links to the previous level, and the edge
-    count of every hop."""
+    a launch of its own (<= 12 288 words), the general multi-launch transpose + scan + pack - against a dense numpy expansion on C2
+    (313 words per query: 3 queries = 939 words, 6 = 1 878; 40 = 12 520 and 400 are the general path): node lists in (query, entity)
+    order, links to the previous level, and the edge count of every hop.  expand() + nodes() pass no node buffer into the level build:
+    the fused and the split node emission are tests/test_frontier_gpu.py's."""
     from red_gnn_amd import engine
     _, kg, ids, loader = _shape_loader("C2")
     g = loader.graph_for("test")
