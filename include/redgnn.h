@@ -416,6 +416,30 @@ size_t rg_paths_scratch_bytes(int64_t n_edges, int32_t k);
 int rg_paths_topk(const int32_t* edges, const float* alpha, const int64_t* offsets, int32_t row_lo, int32_t row_hi, int32_t n_hops,
                   int32_t k, void* scratch, int64_t* path_edge, double* path_prod, int32_t* path_count, void* stream);
 
+/* ---- rule quality: support and confidence of rules (head h, body r_1..r_L) counted on the whole graph; no counterpart in the
+ * reference (its *_rule_vis.py scripts only draw).  The graph is used as built, inverse and identity rows included: for a relation id
+ * r in 0..n_rela_rows-1, A_r(x, y) holds iff the graph has at least one row (x, r, y) (a repeated fact counts once), and body(x, y)
+ * holds iff there are z_0 = x, .., z_L = y with A_{r_l}(z_{l-1}, z_l) for every l (identity steps are ordinary steps).
+ * head int32 [n_rules], body int32 [n_rules, n_hops], sources int32 [n_sources] (distinct entity ids) and counts are DEVICE arrays;
+ * n_hops in 1..32, n_rules <= 65535.  counts int64 [n_rules, 4] is ADDED to (caller-zeroed; calls over disjoint source sets sum):
+ *   [0] body_pairs      #{(x, y): x a source, body(x, y)}
+ *   [1] hits            #{(x, y): x a source, body(x, y) and A_h(x, y)}                 (AMIE's support)
+ *   [2] pca_body_pairs  #{(x, y): x a source, body(x, y) and A_h(x, y') for some y'}
+ *   [3] head_pairs      #{(x, y): x a source, A_h(x, y)}
+ * so hits <= pca_body_pairs <= body_pairs and hits <= head_pairs.  A chain of boolean sparse products on entity-major bitmaps over
+ * the sources (csrc/rule_ground.hip): per hop |edges of r_l| * ceil(n_sources / 32) words are read and ORed with integer atomics,
+ * then one counting pass; OR and integer adds are order-independent, so every count is exact, the same in every run and the same
+ * however the rules and sources are cut into calls.  scratch holds rg_rule_ground_scratch_bytes(n_ent, n_rules, n_sources) bytes
+ * (three bitmaps uint32 [n_rules][n_ent][ceil(n_sources / 32)] and one word row per rule; 0: an argument < 1, n_rules > 65535 or
+ * more than 2^40 words per bitmap), 4-B aligned, and is zeroed by the call.  Errors: a temporal graph (n_time != 0: a temporal rule
+ * would have to say what it does with time), a graph without its CSR by relation, n_rules / n_hops / n_sources out of range.  A
+ * relation id outside 0..n_rela_rows-1 reads nothing (that rule's body or head is empty) and a source outside 0..n_ent-1 is skipped:
+ * nothing outside the graph's arrays or the scratch is touched whatever the id arrays hold; the caller validates them (engine.py).
+ * Allocates nothing, asynchronous on `stream`. */
+size_t rg_rule_ground_scratch_bytes(int32_t n_ent, int32_t n_rules, int32_t n_sources);
+int rg_rule_ground(const rg_graph* g, const int32_t* head, const int32_t* body, int32_t n_rules, int32_t n_hops,
+                   const int32_t* sources, int32_t n_sources, void* scratch, int64_t* counts, void* stream);
+
 /* rg_dense_fwd with the node count read on the device (after rg_frontier_expand_async): n_cap = capacity of the row buffers,
  * n_dev = rg_frontier_count_ptr() of the frontier whose newest level the rows belong to, n_hint = the row count the caller expects
  * (0 = unknown): it only sizes the grid, every row count up to n_cap is processed correctly. */

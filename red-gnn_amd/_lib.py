@@ -26,6 +26,7 @@ SYMBOLS = [
     "rg_xattn_profile", "rg_rows_linear",
     "rg_segment_eval",
     "rg_paths_scratch_bytes", "rg_paths_topk",
+    "rg_rule_ground_scratch_bytes", "rg_rule_ground",
 ]
 
 _lib = None
@@ -137,6 +138,9 @@ def lib():
     L.rg_paths_scratch_bytes.argtypes = [i64, i32]
     L.rg_paths_scratch_bytes.restype = sz
     L.rg_paths_topk.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    L.rg_rule_ground_scratch_bytes.argtypes = [i32, i32, i32]
+    L.rg_rule_ground_scratch_bytes.restype = sz
+    L.rg_rule_ground.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp, vp, vp]
     _lib = L
     return L
 

@@ -221,3 +221,10 @@ class BaseModel(object):
         Returns an explain.RuleTable.  Not sharded: under a process group every rank computes the whole table."""
         from .explain import split_rules
         return split_rules(self.model, self.loader, data, k, self.n_tbatch, max_queries)
+
+    def rule_quality(self, table=None, data="test", k=1, max_queries=None):
+        """model.rule_quality of a rule table on the graph the valid or test split is scored on (the mode ``rules`` explains in), over
+        every entity as a source.  ``table=None``: the table is mined first, ``self.rules(data, k, max_queries)``.  Returns an
+        explain.RuleQuality.  Static and inductive models; not sharded."""
+        from .explain import split_rule_quality
+        return split_rule_quality(self, table, data, k, max_queries)

@@ -1058,3 +1058,105 @@ def paths_topk(edges, alpha, offsets, n_hops, k, scratch_bytes=PATHS_SCRATCH_BYT
         _lib.check(_lib.lib().rg_paths_topk(p(edges), p(alpha), p(offsets), lo, hi, L, int(k), p(scratch), p(path_edge), p(path_prod),
                                             p(path_count), _lib.stream_ptr()))
     return path_edge, path_prod, path_count
+
+
+RULE_MAX_HOPS = 32                   # csrc/rule_ground.hip: RULE_MAX_HOPS
+RULE_MAX_RULES = 65535               # ... RULE_MAX_RULES (rules of one call)
+RULE_SCRATCH_BYTES = 1 << 30         # default scratch budget of rule_ground
+# tools/probe_rule_quality.py sets this to a list to collect (start_event, end_event, n_rules, n_sources) per chunk of rule_ground
+RULE_EVENTS = None
+
+
+def rule_ground_scratch_bytes(n_ent, n_rules, n_sources):
+    return int(_lib.lib().rg_rule_ground_scratch_bytes(int(n_ent), int(n_rules), int(n_sources)))
+
+
+def _int_array(x, name, who):
+    a = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+    if a.dtype not in (np.int32, np.int64):
+        raise ValueError("%s: %s must be int32 or int64 (got %s)" % (who, name, a.dtype))
+    return a
+
+
+def check_rules(n_ent, n_rel, head, body, sources=None):
+    """The host validation of rule_ground: (head int32 [R], body int32 [R, L], sources int32 [S]) as contiguous numpy arrays, or
+    ValueError.  ``sources=None``: every entity."""
+    who = "rule_ground"
+    h, b = _int_array(head, "head", who), _int_array(body, "body", who)
+    if h.ndim != 1 or b.ndim != 2 or b.shape[0] != h.shape[0]:
+        raise ValueError("%s: head must be [R] and body [R, L] (got %s and %s)" % (who, h.shape, b.shape))
+    if not 1 <= b.shape[1] <= RULE_MAX_HOPS:
+        raise ValueError("%s: the body length %d is not in 1..%d" % (who, b.shape[1], RULE_MAX_HOPS))
+    n_ent, n_rel = int(n_ent), int(n_rel)
+    if h.size and (min(h.min(), b.min()) < 0 or max(h.max(), b.max()) > 2 * n_rel):
+        raise ValueError("%s: relation id out of range 0..%d (2*n_rel; got %d..%d)"
+                         % (who, 2 * n_rel, min(h.min(), b.min()), max(h.max(), b.max())))
+    if sources is None:
+        s = np.arange(n_ent, dtype=np.int32)
+    else:
+        s = _int_array(sources, "sources", who)
+        if s.ndim != 1:
+            raise ValueError("%s: sources must be [S] (got %s)" % (who, s.shape))
+        if s.size and (s.min() < 0 or s.max() >= n_ent):
+            raise ValueError("%s: source id out of range 0..%d (got %d..%d)" % (who, n_ent - 1, s.min(), s.max()))
+        if np.unique(s).size != s.size:
+            raise ValueError("%s: duplicate sources (%d ids, %d distinct)" % (who, s.size, np.unique(s).size))
+    as32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+    return as32(h), as32(b), as32(s)
+
+
+def rule_chunking(n_ent, n_rules, n_sources, scratch_bytes):
+    """(rules per chunk, sources per block) of rule_ground: all sources in one block if one rule's scratch fits the budget then, else
+    the largest multiple of 32 that does (at least 32); then as many rules as fit (at least one)."""
+    def fits(r, s):
+        return 0 < rule_ground_scratch_bytes(n_ent, r, s) <= scratch_bytes
+
+    def largest(hi, ok):             # the largest x in 1..hi with ok(x), ok being monotone; 1 if none
+        lo = 1
+        while lo < hi:
+            mid = (lo + hi + 1) // 2
+            lo, hi = (mid, hi) if ok(mid) else (lo, mid - 1)
+        return lo
+    blocks = (n_sources + 31) // 32
+    s_c = 32 * largest(blocks, lambda k: fits(1, 32 * k))
+    n_r = largest(min(n_rules, RULE_MAX_RULES), lambda r: fits(r, s_c))
+    if rule_ground_scratch_bytes(n_ent, n_r, s_c) == 0:
+        raise ValueError("rule_ground: %d entities are beyond the bitmaps' range" % n_ent)
+    return n_r, s_c
+
+
+def rule_ground(graph, head, body, sources=None, scratch_bytes=RULE_SCRATCH_BYTES):
+    """The four counts of every rule (head[i], body[i]) on ``graph`` (rg_rule_ground): int64 [R, 4] on the device = (body_pairs, hits,
+    pca_body_pairs, head_pairs) over the pairs (x, y) with x in ``sources`` (distinct entity ids; None: every entity).  Relation ids
+    are the graph's, 0..2*n_rel (inverses and the identity included).  Ids are validated on the host (ValueError).  The work is cut
+    into chunks of (rules x source blocks of a multiple of 32) whose bitmaps fit ``scratch_bytes`` (one rule and 32 sources at least);
+    the scratch is allocated once and the counts are integers added per chunk, so the result does not depend on the budget."""
+    if getattr(graph, "n_time", 0):
+        raise ValueError("rule_ground: temporal graph: rules are grounded on static and inductive graphs only "
+                         "(a temporal rule would have to say what it does with time)")
+    if isinstance(scratch_bytes, (bool, np.bool_)) or not isinstance(scratch_bytes, (int, np.integer)) or scratch_bytes < 0:
+        raise ValueError("rule_ground: scratch_bytes must be a non-negative integer (got %r)" % (scratch_bytes,))
+    h, b, s = check_rules(graph.n_ent, graph.n_rel, head, body, sources)
+    dev = _require_gpu(graph.device)
+    R, L, S = h.shape[0], b.shape[1], s.shape[0]
+    counts = torch.zeros((R, 4), dtype=torch.int64, device=dev)
+    if R == 0 or S == 0:
+        return counts
+    n_r, s_c = rule_chunking(graph.n_ent, R, S, int(scratch_bytes))
+    h_d, b_d, s_d = (torch.from_numpy(a).to(dev) for a in (h, b, s))
+    p = _lib.ptr
+    with torch.cuda.device(dev):
+        scratch = torch.empty(rule_ground_scratch_bytes(graph.n_ent, min(n_r, R), min(s_c, S)), dtype=torch.uint8, device=dev)
+        for r0 in range(0, R, n_r):
+            r1 = min(r0 + n_r, R)
+            for s0 in range(0, S, s_c):
+                s1 = min(s0 + s_c, S)
+                if RULE_EVENTS is not None:
+                    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                    ev[0].record()
+                _lib.check(_lib.lib().rg_rule_ground(graph.handle, p(h_d[r0:r1]), p(b_d[r0:r1]), r1 - r0, L, p(s_d[s0:s1]), s1 - s0,
+                                                     p(scratch), p(counts[r0:r1]), _lib.stream_ptr()))
+                if RULE_EVENTS is not None:
+                    ev[1].record()
+                    RULE_EVENTS.append((ev[0], ev[1], r1 - r0, s1 - s0))
+    return counts

@@ -275,6 +275,102 @@ class RuleTable:
         return out
 
 
+@dataclass
+class RuleQuality:
+    """How the rules of a RuleTable hold in a knowledge graph (engine.rule_ground; csrc/rule_ground.hip): exact counts over the pairs
+    (x, y) with x one of ``n_sources`` source entities, on the graph as built (inverse and identity rows included, a repeated fact
+    counted once).  body(x, y): the rule's relation sequence leads from x to y, identity steps being ordinary steps.
+
+    table           RuleTable  the rules, row by row
+    body_pairs      int64 [R]  pairs the body connects
+    hits            int64 [R]  ... that the head relation connects too (AMIE's support; ``table.support`` counts explained paths)
+    pca_body_pairs  int64 [R]  pairs the body connects whose x has some fact of the head relation
+    head_pairs      int64 [R]  pairs the head relation connects
+    n_sources       int        number of source entities
+
+    hits <= pca_body_pairs <= body_pairs and hits <= head_pairs.
+    """
+    table: RuleTable
+    body_pairs: torch.Tensor
+    hits: torch.Tensor
+    pca_body_pairs: torch.Tensor
+    head_pairs: torch.Tensor
+    n_sources: int
+
+    def _ratio(self, den):
+        num, den = self.hits.double(), den.double()
+        return torch.where(den > 0, num / den.clamp(min=1.0), torch.zeros_like(num))
+
+    def confidence(self):
+        """float64 [R]: hits / body_pairs (standard confidence), 0.0 where the body connects nothing."""
+        return self._ratio(self.body_pairs)
+
+    def pca_confidence(self):
+        """float64 [R]: hits / pca_body_pairs (confidence under the partial-completeness assumption), 0.0 where that is 0."""
+        return self._ratio(self.pca_body_pairs)
+
+    def head_coverage(self):
+        """float64 [R]: hits / head_pairs, 0.0 where the head relation has no fact from a source."""
+        return self._ratio(self.head_pairs)
+
+    def trivial(self):
+        """bool [R]: the body with its identity steps dropped is exactly [head]; such a rule has confidence 1 by construction."""
+        step = self.table.body != 2 * self.table.n_rel
+        return (step.sum(1) == 1) & ((self.table.body * step).sum(1) == self.table.head)
+
+    def cpu(self):
+        return RuleQuality(self.table.cpu(), self.body_pairs.cpu(), self.hits.cpu(), self.pca_body_pairs.cpu(), self.head_pairs.cpu(),
+                           self.n_sources)
+
+    def top(self, q_rel, n, by="confidence", min_hits=1, drop_trivial=True):
+        """Row indices (int64, at most n) of the best rules of query relation ``q_rel`` by "confidence", "pca_confidence" or "hits",
+        among those with hits >= min_hits (and not trivial).  Ties go to the larger hits, then to the smaller body."""
+        if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or n < 1:
+            raise ValueError("top: n must be a positive integer (got %r)" % (n,))
+        if by not in ("confidence", "pca_confidence", "hits"):
+            raise ValueError("top: by must be 'confidence', 'pca_confidence' or 'hits' (got %r)" % (by,))
+        q = self.cpu()                                   # a few thousand rows at most: ordered on the host
+        score = (q.hits.double() if by == "hits" else getattr(q, by)()).numpy()
+        hits, body = q.hits.numpy(), q.table.body.numpy()
+        keep = (q.table.head == int(q_rel)) & (q.hits >= int(min_hits))
+        if drop_trivial:
+            keep = keep & ~q.trivial()
+        rows = np.nonzero(keep.numpy())[0]
+        keys = [body[rows, c] for c in reversed(range(body.shape[1]))] + [-hits[rows], -score[rows]]     # lexsort: last key first
+        rows = rows[np.lexsort(keys)][:int(n)] if rows.size else rows
+        return torch.as_tensor(rows, dtype=torch.int64).to(self.hits.device)
+
+    def format(self, id2rel=None):
+        """table.format() with ``hits/body_pairs conf=... pca=...`` appended to every line."""
+        q = self.cpu()
+        conf, pca = q.confidence().tolist(), q.pca_confidence().tolist()
+        return ["%s  %d/%d conf=%.4f pca=%.4f" % (line, h, b, c, p)
+                for line, h, b, c, p in zip(q.table.format(id2rel), q.hits.tolist(), q.body_pairs.tolist(), conf, pca)]
+
+
+def rule_quality(model, table, mode="test", sources=None, scratch_bytes=engine.RULE_SCRATCH_BYTES):
+    """RED_GNN_trans.rule_quality (see there)."""
+    if not isinstance(table, RuleTable):
+        raise ValueError("rule_quality: table must be an explain.RuleTable (got %s)" % type(table).__name__)
+    if table.n_rel != model.n_rel:
+        raise ValueError("rule_quality: the table has n_rel=%d, the model n_rel=%d" % (table.n_rel, model.n_rel))
+    graph = model.loader.graph_for(mode)
+    counts = engine.rule_ground(graph, table.head, table.body, sources, scratch_bytes)
+    n_sources = graph.n_ent if sources is None else int(len(sources))
+    return RuleQuality(table, *(counts[:, c].contiguous() for c in range(4)), n_sources)
+
+
+def split_rule_quality(base, table=None, data="test", k=1, max_queries=None):
+    """BaseModel.rule_quality: the table (default: base.rules(data, k, max_queries)) counted on the graph split_rows picks for
+    ``data``."""
+    if data not in ("valid", "test"):
+        raise ValueError("rule_quality: data must be 'valid' or 'test' (got %r)" % (data,))
+    if table is None:
+        table = base.rules(data, k, max_queries)
+    mode = base.loader.eval_mode(data) if hasattr(base.loader, "eval_mode") else data
+    return base.model.rule_quality(table, mode=mode)
+
+
 def _table(key, support, fixed, n_rel):
     """RuleTable of rows key int64 [P, 1 + L] = (head, body) with their counts and fixed-point sums, equal keys merged."""
     if key.shape[0] == 0:

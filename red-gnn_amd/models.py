@@ -404,6 +404,17 @@ class RED_GNN_trans(nn.Module):
         from . import explain as _explain
         return _explain.rules(self, subs, rels, objs, k, mode, min_alpha)
 
+    def rule_quality(self, table, mode="test", sources=None, scratch_bytes=engine.RULE_SCRATCH_BYTES):
+        """How the rules of an explain.RuleTable hold in the graph of ``mode`` (loader.graph_for): per rule the number of entity pairs
+        the body connects, how many of them the head connects too (AMIE's support), and standard / PCA confidence and head coverage
+        from them.  ``sources``: the distinct entity ids x the pairs (x, y) start from (None: every entity).  Exact integer counts from
+        one HIP pass over the graph per chunk of rules (rg_rule_ground); they do not depend on ``scratch_bytes``, which bounds the
+        bitmaps.  The counts are taken on that graph as built, so the facts of the split being scored are not in it.  ValueError if
+        ``table.n_rel`` is not the model's.  Returns an explain.RuleQuality (device tensors).  Static and inductive models only: a
+        temporal rule would have to say what it does with time."""
+        from . import explain as _explain
+        return _explain.rule_quality(self, table, mode, sources, scratch_bytes)
+
     def predict(self, subs, rels, k=10, exclude_known=True, mode="test"):
         """The k best answers of each query (s, r, ?): prediction.Prediction(ids int64 [B, k], scores fp32 [B, k]) on the device,
         ordered by score descending, then entity id ascending (-0.0 == +0.0, NaN last).  ``exclude_known``: the tails the loader's
@@ -630,6 +641,9 @@ class RED_GNN_induc(RED_GNN_trans):
 
     def rules(self, subs, rels, objs=None, k=1, mode="transductive", min_alpha=0.0):
         return super().rules(subs, rels, objs=objs, k=k, mode=mode, min_alpha=min_alpha)
+
+    def rule_quality(self, table, mode="transductive", sources=None, scratch_bytes=engine.RULE_SCRATCH_BYTES):
+        return super().rule_quality(table, mode=mode, sources=sources, scratch_bytes=scratch_bytes)
 
     def predict(self, subs, rels, k=10, exclude_known=True, mode="transductive"):
         return super().predict(subs, rels, k=k, exclude_known=exclude_known, mode=mode)
