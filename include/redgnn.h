@@ -440,6 +440,35 @@ size_t rg_rule_ground_scratch_bytes(int32_t n_ent, int32_t n_rules, int32_t n_so
 int rg_rule_ground(const rg_graph* g, const int32_t* head, const int32_t* body, int32_t n_rules, int32_t n_hops,
                    const int32_t* sources, int32_t n_sources, void* scratch, int64_t* counts, void* stream);
 
+/* ---- rule application: which answers weighted rules predict for queries (s, r, ?), and which rule is behind each; no counterpart in
+ * the reference.  The graph, A_r(x, y) and body(x, y) are exactly those of rg_rule_ground.  The rules are (head[i], body[i][0..L-1],
+ * weight[i]), i = 0..n_rules-1, head non-decreasing, weight fp32 in (0, 1] and miss[i] = fl32(1 - weight[i]) formed by the caller (in
+ * the kernel the compiler could contract surv * (1 - w) into one rounding).  The queries are (sub[b], rel[b]), b = 0..batch-1,
+ * duplicates allowed, given sorted by relation (stably): q_sub int32 [batch] the subjects in sorted order, q_row int32 [batch] the
+ * caller's row b of each sorted position, q_ptr int32 [n_rela_rows + 1] with the sorted positions of relation r = q_ptr[r]..q_ptr[r+1].
+ * Rule i fires for cell (b, y) iff head[i] == rel[b] and body_i(sub[b], y).  The four outputs, fp32 / fp32 / int32 / int32
+ * [batch, n_ent] with row stride n_ent, are initialised by the caller (best = 0, surv = 1, best_rule = -1, fired = 0 before the first
+ * rule) and carried through: per cell the rules that fire are visited in ascending i,
+ *   fired += 1;  surv = fl32(surv * miss[i]);  if (weight[i] > best) { best = weight[i]; best_rule = rule_base + i; }
+ * (strict: the first of equal weights wins).  "max" aggregation is best, noisy-or is fl32(1 - surv), taken by the caller.  Only the
+ * order of i matters: every output is the same bit for bit in every run and however the rules are cut into consecutive calls on one
+ * stream (rule_base = the first rule's index in the whole list).
+ * Rule i has S_i = q_ptr[h+1] - q_ptr[h] sources (h = head[i]), W_i = ceil(S_i / 32) words per entity, and two bitmaps that are slabs
+ * of n_ent * W_i words starting at word slab[i] of the two halves of the scratch; slab int64 [n_rules + 1] is the exclusive prefix of
+ * n_ent * W_i, computed by the caller, n_words = slab[n_rules], and scratch holds rg_rule_apply_scratch_bytes(n_words) bytes (0:
+ * n_words < 1 or > 2^40), 4-B aligned.  phases: 1 = zero the scratch, seed and hop (leaves the bitmaps in the scratch), 2 = aggregate
+ * from them, 3 = both (a timing probe issues them apart).  All arrays are DEVICE arrays.  Errors: a NULL or temporal graph (as
+ * rg_rule_ground), a graph without its CSR by relation, n_hops outside 1..32, n_rules > 65535, n_words out of range.  A relation id
+ * outside 0..n_rela_rows-1 is tested before any load and reads nothing, an edge end or subject outside 0..n_ent-1 and a q_row outside
+ * 0..batch-1 are skipped, q_ptr entries are clamped to 0..batch, a slab outside 0..n_words is left out; an unsorted head makes the
+ * result unspecified: nothing outside the graph's arrays, the scratch or the four outputs is touched whatever the arrays hold; the
+ * caller validates them (engine.py).  Allocates nothing, asynchronous on `stream`. */
+size_t rg_rule_apply_scratch_bytes(int64_t n_words);
+int rg_rule_apply(const rg_graph* g, const int32_t* head, const int32_t* body, const float* weight, const float* miss,
+                  int32_t n_rules, int32_t n_hops, int32_t rule_base, const int32_t* q_sub, const int32_t* q_row,
+                  const int32_t* q_ptr, int32_t batch, const int64_t* slab, int64_t n_words, void* scratch, int32_t phases,
+                  float* best, float* surv, int32_t* best_rule, int32_t* fired, void* stream);
+
 /* rg_dense_fwd with the node count read on the device (after rg_frontier_expand_async): n_cap = capacity of the row buffers,
  * n_dev = rg_frontier_count_ptr() of the frontier whose newest level the rows belong to, n_hint = the row count the caller expects
  * (0 = unknown): it only sizes the grid, every row count up to n_cap is processed correctly. */

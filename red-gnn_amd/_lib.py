@@ -27,6 +27,7 @@ SYMBOLS = [
     "rg_segment_eval",
     "rg_paths_scratch_bytes", "rg_paths_topk",
     "rg_rule_ground_scratch_bytes", "rg_rule_ground",
+    "rg_rule_apply_scratch_bytes", "rg_rule_apply",
 ]
 
 _lib = None
@@ -141,6 +142,9 @@ def lib():
     L.rg_rule_ground_scratch_bytes.argtypes = [i32, i32, i32]
     L.rg_rule_ground_scratch_bytes.restype = sz
     L.rg_rule_ground.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp, vp, vp]
+    L.rg_rule_apply_scratch_bytes.argtypes = [i64]
+    L.rg_rule_apply_scratch_bytes.restype = sz
+    L.rg_rule_apply.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, i64, vp, i32, vp, vp, vp, vp, vp]
     _lib = L
     return L
 

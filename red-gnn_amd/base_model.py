@@ -228,3 +228,20 @@ class BaseModel(object):
         explain.RuleQuality.  Static and inductive models; not sharded."""
         from .explain import split_rule_quality
         return split_rule_quality(self, table, data, k, max_queries)
+
+    def rule_evaluate(self, quality=None, data="test", mine="valid", k=1, agg="noisy_or", batch=256, max_queries=None,
+                      by="confidence", laplace=0.0, min_hits=1, drop_trivial=True):
+        """How well mined rules predict on their own, next to ``evaluate``'s numbers for the network: filtered MRR / hits@1 / hits@10
+        of model.rule_scores over the first ``max_queries`` queries (default: all) of the ``data`` split, and how many of its answers
+        any rule reaches.  ``quality=None``: the rules are mined on the OTHER split, ``self.rule_quality(data=mine, k=k,
+        max_queries=max_queries)``, so no answer being scored was explained; their confidences are counted on the graph ``mine`` is
+        scored on (inductive setting: the training graph, while the rules are applied on the inductive one).  The split is walked in
+        batches of ``batch`` queries (the memory knob: 16 bytes per query and entity) through loader.get_batch_csr and cal_ranks_csr,
+        the ranker ``evaluate`` uses.  Every entity no rule reaches scores 0, so ties are frequent: rg_rank gives the mean of the tie
+        interval, (entities above) + (entities tied + 1) / 2, which for an unreached answer is the middle of all unreached entities.
+        Returns dict(mrr, h1, h10 from cal_performance, n = answers ranked, coverage = the share of them with fired > 0, an integer
+        count over n).  ``by``, ``laplace``, ``min_hits``, ``drop_trivial`` as model.rule_scores.  Static and inductive models; not
+        sharded: under a process group every rank computes the whole result."""
+        from .explain import split_rule_evaluate
+        return split_rule_evaluate(self, quality, data, mine, k, agg, batch, max_queries, by=by, laplace=laplace, min_hits=min_hits,
+                                   drop_trivial=drop_trivial)

@@ -1,0 +1,227 @@
+// Application of weighted rules to queries (include/redgnn.h: rg_rule_apply): for every query (s, r) and entity y, which of the rules
+// with head r connect s to y, folded in rule order into (best weight, its rule, product of the misses, number of rules that fired).
+//
+// The orientation of rule_ground.hip - entity-major bitmaps over the sources, "OR a source's word into a destination's" - with one
+// difference: a rule's sources are only the queries of its head relation.  The host sorts the queries by relation (q_sub, q_row in
+// sorted order, q_ptr by relation id), so rule i with head h has S_i = q_ptr[h + 1] - q_ptr[h] sources, W_i = ceil(S_i / 32) words
+// per entity, and bit j of its bitmaps is the query at sorted position q_ptr[h] + j.  Its bitmaps are slabs of n_ent * W_i words at
+// word slab[i] of two regions of the scratch:
+//   cur, next : uint32 [n_words]       n_words = slab[n_rules]; bit j of word slab[i] + y * W_i + j / 32: source j reaches y under rule i
+// A rule without queries has no slab and every kernel leaves it at once.  Word indices are int64 throughout.
+//
+//   fill       the whole scratch is zeroed by rg::zero_async (a kernel: common.h says why no memset node)
+//   seed       bit j of cur_i[q_sub[q_ptr[h] + j]]
+//   hop l      for the edges (u, v) of relation body[i][l] and every word w: x = cur_i[u][w]; if x != 0: atomicOr(&next_i[v][w], x).
+//              Then cur <-> next, and the new next is zeroed before the next hop
+//   aggregate  one thread per cell (sorted position p, entity y), the lanes of a wave along y: the rules of the call whose head is p's
+//              relation are found by binary search in `head` and visited in ascending order; where bit p - q_ptr[h] of cur_i[y] is set
+//              the rule fires.  The four outputs of the cell, at [q_row[p]][y], are read when the first rule fires and stored once at the
+//              end: a cell no rule of the call reaches costs no output traffic.  No atomics: a cell has one thread, and the calls that
+//              carry the arrays from one range of rules to the next are ordered by the stream.
+//
+// The hop's inner loop is rule_ground.hip's rule_hop_kernel written once more (that kernel takes one W per call and collects `any`;
+// here W, the slab and the lane group follow the rule): the rule is blockIdx.y, a group of G lanes owns one edge and runs along w,
+// G the power of two >= W_i capped at 64, uniform within the workgroup.  OR is order-independent and the fold's order is the rule
+// order, so every output is the same bit for bit in every run and however the rules are cut into calls.
+//
+// Bounds.  A relation id outside 0..n_rela_rows-1 is tested before any load and reads nothing; an edge end or subject outside
+// 0..n_ent-1 and a q_row outside 0..batch-1 are skipped; q_ptr entries are clamped to 0..batch; a slab that does not lie inside
+// 0..n_words is left out.  Whatever the arrays hold, nothing outside the graph, the scratch or the four outputs is touched.
+#include <algorithm>
+
+#include "common.h"
+
+namespace {
+
+constexpr int AT = 256;                           // threads per workgroup
+constexpr int APPLY_MAX_HOPS = 32;
+constexpr int APPLY_MAX_RULES = 65535;            // the rule is blockIdx.y
+constexpr size_t APPLY_ALIGN = 256;
+constexpr int64_t APPLY_MAX_WORDS = (int64_t)1 << 40;   // per region (4 TiB): keeps every byte count far inside size_t
+
+inline size_t region_bytes(int64_t n_words) { return rg::align_up((size_t)n_words * 4, APPLY_ALIGN); }
+
+struct Queries {
+  const int32_t* sub;    // [batch] subjects in sorted order
+  const int32_t* row;    // [batch] the caller's row of each sorted position
+  const int32_t* ptr;    // [n_rela_rows + 1] sorted positions by relation
+  int32_t batch, n_rela_rows;
+};
+
+struct Slab {
+  int64_t base;          // first word
+  int32_t p0, S, W;      // first sorted position, sources, words per entity
+};
+
+__device__ __forceinline__ int32_t clamp_pos(int32_t p, int32_t batch) { return p < 0 ? 0 : (p > batch ? batch : p); }
+
+// the sources and slab of a rule with head h; false: no such relation, no query of it, or a slab outside the scratch
+__device__ __forceinline__ bool rule_slab(const Queries& q, int32_t h, const int64_t* __restrict__ slab, int64_t i, int32_t n_ent,
+                                          int64_t n_words, Slab* out) {
+  if (h < 0 || h >= q.n_rela_rows) return false;
+  const int32_t p0 = clamp_pos(q.ptr[h], q.batch), p1 = clamp_pos(q.ptr[h + 1], q.batch);
+  if (p1 <= p0) return false;
+  const int32_t W = (p1 - p0 + 31) >> 5;
+  const int64_t base = slab[i];
+  if (base < 0 || base > n_words || (int64_t)n_ent * W > n_words - base) return false;
+  out->base = base; out->p0 = p0; out->S = p1 - p0; out->W = W;
+  return true;
+}
+
+__global__ __launch_bounds__(AT) void apply_seed_kernel(Queries q, const int32_t* __restrict__ head, const int64_t* __restrict__ slab,
+                                                        int32_t n_ent, int64_t n_words, uint32_t* __restrict__ cur) {
+  const int64_t i = blockIdx.y;
+  Slab sl;
+  if (!rule_slab(q, head[i], slab, i, n_ent, n_words, &sl)) return;
+  for (int32_t j = blockIdx.x * AT + threadIdx.x; j < sl.S; j += gridDim.x * AT) {
+    const uint32_t s = (uint32_t)q.sub[sl.p0 + j];
+    if (s < (uint32_t)n_ent) atomicOr(&cur[sl.base + (int64_t)s * sl.W + (j >> 5)], 1u << (j & 31));
+  }
+}
+
+// step l of every rule: to_i[v] |= from_i[u] over the edges (u, v) of relation body[i][l].  No barrier: a workgroup whose rule has no
+// query, no such relation, or fewer edges than the grid covers, leaves.
+__global__ __launch_bounds__(AT) void apply_hop_kernel(const int32_t* __restrict__ rel_ptr, const int2* __restrict__ rel_ht, Queries q,
+                                                       const int32_t* __restrict__ head, const int32_t* __restrict__ body,
+                                                       int32_t n_hops, int32_t l, const int64_t* __restrict__ slab, int32_t n_ent,
+                                                       int64_t n_words, const uint32_t* __restrict__ from, uint32_t* __restrict__ to) {
+  const int64_t i = blockIdx.y;
+  const int32_t r = body[i * n_hops + l];
+  if (r < 0 || r >= q.n_rela_rows) return;
+  Slab sl;
+  if (!rule_slab(q, head[i], slab, i, n_ent, n_words, &sl)) return;
+  const int32_t W = sl.W;
+  int32_t g_shift = 0;
+  while (g_shift < 6 && (1 << g_shift) < W) ++g_shift;
+  const int64_t e0 = rel_ptr[r], e1 = rel_ptr[r + 1];
+  const int32_t G = 1 << g_shift, w0 = threadIdx.x & (G - 1);
+  const int64_t per_block = AT >> g_shift;
+  for (int64_t e = e0 + blockIdx.x * per_block + (threadIdx.x >> g_shift); e < e1; e += gridDim.x * per_block) {
+    const int2 ht = rel_ht[e];
+    if ((uint32_t)ht.x >= (uint32_t)n_ent || (uint32_t)ht.y >= (uint32_t)n_ent) continue;
+    const uint32_t* __restrict__ src = from + sl.base + (int64_t)ht.x * W;
+    uint32_t* dst = to + sl.base + (int64_t)ht.y * W;
+    for (int32_t w = w0; w < W; w += G) {
+      const uint32_t x = src[w];
+      if (x != 0) atomicOr(&dst[w], x);
+    }
+  }
+}
+
+// blockIdx.y (strided) is the sorted position p, the threads run along y: p's relation, rule range and slabs are uniform in the
+// workgroup, the four stores of a wave are 256 contiguous bytes each and so are its bitmap loads where W = 1.
+__global__ __launch_bounds__(AT) void apply_aggregate_kernel(Queries q, const int32_t* __restrict__ head, const float* __restrict__ weight,
+                                                             const float* __restrict__ miss, int32_t n_rules, int32_t rule_base,
+                                                             const int64_t* __restrict__ slab, int32_t n_ent, int64_t n_words,
+                                                             const uint32_t* __restrict__ cur, float* __restrict__ best,
+                                                             float* __restrict__ surv, int32_t* __restrict__ best_rule,
+                                                             int32_t* __restrict__ fired) {
+  const int32_t y = blockIdx.x * AT + threadIdx.x;
+  for (int32_t p = blockIdx.y; p < q.batch; p += gridDim.y) {
+    const int32_t row = q.row[p];
+    if ((uint32_t)row >= (uint32_t)q.batch) continue;
+    int32_t lo = 0, hi = q.n_rela_rows;                   // the relation h with q_ptr[h] <= p < q_ptr[h + 1]: the last h with q_ptr[h] <= p
+    while (hi - lo > 1) {
+      const int32_t mid = (lo + hi) >> 1;
+      if (clamp_pos(q.ptr[mid], q.batch) <= p) lo = mid; else hi = mid;
+    }
+    const int32_t h = lo;
+    int32_t a = 0, b = n_rules;                           // first rule with head >= h
+    while (a < b) {
+      const int32_t mid = (a + b) >> 1;
+      if (head[mid] < h) a = mid + 1; else b = mid;
+    }
+    if (a >= n_rules || head[a] != h || y >= n_ent) continue;
+    const int64_t cell = (int64_t)row * n_ent + y;
+    float c_best = 0.f, c_surv = 1.f;
+    int32_t c_rule = -1, c_fired = 0;
+    bool loaded = false;
+    Slab sl;                                              // p0, S and W are the relation's: only the base changes with the rule
+    if (!rule_slab(q, h, slab, a, n_ent, n_words, &sl)) continue;
+    const int32_t j = p - sl.p0;
+    if (j < 0 || j >= sl.S) continue;
+    const int64_t word = (int64_t)y * sl.W + (j >> 5), span = (int64_t)n_ent * sl.W;
+    for (int32_t i = a; i < n_rules && head[i] == h; ++i) {
+      const int64_t base = slab[i];
+      if (base < 0 || base > n_words || span > n_words - base) continue;
+      const uint32_t x = cur[base + word];
+      if (!((x >> (j & 31)) & 1u)) continue;
+      if (!loaded) {
+        c_best = best[cell]; c_surv = surv[cell]; c_rule = best_rule[cell]; c_fired = fired[cell];
+        loaded = true;
+      }
+      const float w = weight[i];
+      c_fired += 1;
+      c_surv = __fmul_rn(c_surv, miss[i]);
+      if (w > c_best) { c_best = w; c_rule = rule_base + i; }
+    }
+    if (loaded) {
+      best[cell] = c_best; surv[cell] = c_surv; best_rule[cell] = c_rule; fired[cell] = c_fired;
+    }
+  }
+}
+
+// blocks along x for `items` units of work at `per_block` a pass, a few passes each, with the rules in y
+unsigned grid_x(int64_t items, int64_t per_block, int32_t n_rules) {
+  const int64_t want = rg::ceil_div(std::max<int64_t>(items, 1), per_block * 8);
+  return (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, std::max<int64_t>(1, std::min<int64_t>(1024, 65536 / n_rules))));
+}
+
+}  // namespace
+
+extern "C" size_t rg_rule_apply_scratch_bytes(int64_t n_words) {
+  if (n_words < 1 || n_words > APPLY_MAX_WORDS) return 0;
+  return 2 * region_bytes(n_words);
+}
+
+extern "C" int rg_rule_apply(const rg_graph* g, const int32_t* head, const int32_t* body, const float* weight, const float* miss,
+                             int32_t n_rules, int32_t n_hops, int32_t rule_base, const int32_t* q_sub, const int32_t* q_row,
+                             const int32_t* q_ptr, int32_t batch, const int64_t* slab, int64_t n_words, void* scratch, int32_t phases,
+                             float* best, float* surv, int32_t* best_rule, int32_t* fired, void* stream) {
+  RG_CHECK(g, "rg_rule_apply: NULL graph");
+  RG_CHECK(g->n_time == 0, "rg_rule_apply: temporal graph (n_time=%d): rules are grounded on static and inductive graphs only",
+           g->n_time);
+  RG_CHECK(g->rel_ptr && g->rel_ht, "rg_rule_apply: the graph has no CSR by relation (rel_ptr is NULL)");
+  RG_CHECK(n_rules >= 0 && n_rules <= APPLY_MAX_RULES, "rg_rule_apply: n_rules=%d not in 0..%d", n_rules, APPLY_MAX_RULES);
+  RG_CHECK(n_hops >= 1 && n_hops <= APPLY_MAX_HOPS, "rg_rule_apply: n_hops=%d not in 1..%d", n_hops, APPLY_MAX_HOPS);
+  RG_CHECK(batch >= 0, "rg_rule_apply: batch=%d", batch);
+  RG_CHECK(phases >= 1 && phases <= 3, "rg_rule_apply: phases=%d not in 1..3 (1: seed and hops, 2: aggregate)", phases);
+  RG_CHECK(rule_base >= 0 && rule_base <= INT32_MAX - APPLY_MAX_RULES, "rg_rule_apply: rule_base=%d", rule_base);
+  if (n_rules == 0 || batch == 0) return 0;
+  RG_CHECK(head && body && weight && miss && q_sub && q_row && q_ptr && slab && scratch && best && surv && best_rule && fired,
+           "rg_rule_apply: NULL argument");
+  const size_t bytes = rg_rule_apply_scratch_bytes(n_words);
+  RG_CHECK(bytes != 0, "rg_rule_apply: n_words=%lld is outside the bitmaps' range 1..2^40", (long long)n_words);
+  const hipStream_t s = (hipStream_t)stream;
+  const int32_t n_ent = g->n_ent;
+  const Queries q{q_sub, q_row, q_ptr, batch, g->n_rela_rows};
+  uint32_t* cur = static_cast<uint32_t*>(scratch);
+  uint32_t* next = reinterpret_cast<uint32_t*>(static_cast<unsigned char*>(scratch) + bytes / 2);
+  const size_t map_bytes = (size_t)n_words * 4;
+
+  if (phases & 1) {
+    int32_t g_shift = 0;                                  // of the widest rule there can be: sizes the grid only
+    while (g_shift < 6 && (1 << g_shift) < rg::ceil_div(batch, 32)) ++g_shift;
+    const dim3 hop_grid(grid_x(g->n_fact, AT >> g_shift, n_rules), n_rules);
+    if (rg::zero_async(scratch, bytes, s)) return 1;
+    hipLaunchKernelGGL(apply_seed_kernel, dim3(grid_x(batch, AT, n_rules), n_rules), dim3(AT), 0, s, q, head, slab, n_ent, n_words,
+                       cur);
+    RG_LAUNCH_CHECK();
+    for (int32_t l = 0; l < n_hops; ++l) {
+      hipLaunchKernelGGL(apply_hop_kernel, hop_grid, dim3(AT), 0, s, g->rel_ptr, g->rel_ht, q, head, body, n_hops, l, slab, n_ent,
+                         n_words, cur, next);
+      RG_LAUNCH_CHECK();
+      std::swap(cur, next);
+      if (l + 1 < n_hops && rg::zero_async(next, map_bytes, s)) return 1;
+    }
+  } else if (n_hops & 1) {
+    std::swap(cur, next);                                 // where phase 1 left the result: one swap per hop
+  }
+  if (phases & 2) {
+    const dim3 grid((unsigned)rg::ceil_div(n_ent, AT), (unsigned)std::min<int32_t>(batch, 65535));
+    hipLaunchKernelGGL(apply_aggregate_kernel, grid, dim3(AT), 0, s, q, head, weight, miss, n_rules, rule_base, slab, n_ent, n_words,
+                       cur, best, surv, best_rule, fired);
+    RG_LAUNCH_CHECK();
+  }
+  return 0;
+}

@@ -1078,10 +1078,9 @@ def _int_array(x, name, who):
     return a
 
 
-def check_rules(n_ent, n_rel, head, body, sources=None):
+def check_rules(n_ent, n_rel, head, body, sources=None, who="rule_ground"):
     """The host validation of rule_ground: (head int32 [R], body int32 [R, L], sources int32 [S]) as contiguous numpy arrays, or
     ValueError.  ``sources=None``: every entity."""
-    who = "rule_ground"
     h, b = _int_array(head, "head", who), _int_array(body, "body", who)
     if h.ndim != 1 or b.ndim != 2 or b.shape[0] != h.shape[0]:
         raise ValueError("%s: head must be [R] and body [R, L] (got %s and %s)" % (who, h.shape, b.shape))
@@ -1160,3 +1159,121 @@ def rule_ground(graph, head, body, sources=None, scratch_bytes=RULE_SCRATCH_BYTE
                     ev[1].record()
                     RULE_EVENTS.append((ev[0], ev[1], r1 - r0, s1 - s0))
     return counts
+
+
+RULE_APPLY_ALIGN = 256               # csrc/rule_apply.hip: APPLY_ALIGN
+RULE_APPLY_MAX_WORDS = 1 << 40       # ... APPLY_MAX_WORDS (words of one bitmap region)
+# tools/probe_rule_apply.py sets this to a list to collect (start, after seed + hops, end events, n_rules, n_words) per call of rule_apply
+RULE_APPLY_EVENTS = None
+
+
+def rule_apply_scratch_bytes(n_words):
+    """Bytes of the two bitmap regions of ``n_words`` words each (rg_rule_apply_scratch_bytes, restated so that the chunking is a pure
+    function; tests hold the two equal): 0 where n_words is outside 1..2^40."""
+    n_words = int(n_words)
+    if n_words < 1 or n_words > RULE_APPLY_MAX_WORDS:
+        return 0
+    return 2 * ((4 * n_words + RULE_APPLY_ALIGN - 1) // RULE_APPLY_ALIGN * RULE_APPLY_ALIGN)
+
+
+def rule_apply_chunking(words, scratch_bytes):
+    """The calls of rule_apply: consecutive rule ranges [(r0, r1), ...] covering 0..R in order, given ``words[i]`` = the words of rule
+    i's slab (n_ent * ceil(queries of its head relation / 32)).  Greedy: a range takes rules while its slabs' scratch fits
+    ``scratch_bytes`` and it has fewer than RULE_MAX_RULES rules; a rule that does not fit alone is a range of its own."""
+    words = [int(w) for w in words]
+    out, lo, R = [], 0, len(words)
+    while lo < R:
+        hi, total = lo + 1, words[lo]
+        while hi < R and hi - lo < RULE_MAX_RULES and rule_apply_scratch_bytes(max(total + words[hi], 1)) <= scratch_bytes \
+                and total + words[hi] <= RULE_APPLY_MAX_WORDS:
+            total += words[hi]
+            hi += 1
+        out.append((lo, hi))
+        lo = hi
+    return out
+
+
+def check_rule_apply(n_ent, n_rel, head, body, weight, subs, rels):
+    """The host validation of rule_apply: (head int32 [R], body int32 [R, L], weight fp32 [R], subs int32 [B], rels int32 [B]) as
+    contiguous numpy arrays, or ValueError."""
+    who = "rule_apply"
+    h, b, _ = check_rules(n_ent, n_rel, head, body, np.zeros(0, np.int32), who=who)
+    if h.size > 1 and (np.diff(h) < 0).any():
+        at = int(np.argmax(np.diff(h) < 0))
+        raise ValueError("%s: head must be non-decreasing (rule %d has head %d after %d)" % (who, at + 1, h[at + 1], h[at]))
+    w = weight.detach().cpu().numpy() if torch.is_tensor(weight) else np.asarray(weight)
+    if w.dtype.kind != "f" or w.ndim != 1 or w.shape[0] != h.shape[0]:
+        raise ValueError("%s: weight must be a float array [R] (got %s %s for %d rules)" % (who, w.dtype, w.shape, h.shape[0]))
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    if w.size and not (np.isfinite(w).all() and (w > 0).all() and (w <= 1).all()):
+        bad = int(np.argmax(~(np.isfinite(w) & (w > 0) & (w <= 1))))
+        raise ValueError("%s: weights must be finite and in (0, 1] as float32 (rule %d has %r)" % (who, bad, float(w[bad])))
+    s, r = _int_array(subs, "subs", who), _int_array(rels, "rels", who)
+    if s.ndim != 1 or r.ndim != 1 or s.shape[0] != r.shape[0]:
+        raise ValueError("%s: need one relation per subject (got subs %s, rels %s)" % (who, s.shape, r.shape))
+    n_ent, n_rel = int(n_ent), int(n_rel)
+    if s.size and (s.min() < 0 or s.max() >= n_ent):
+        raise ValueError("%s: subject id out of range 0..%d (got %d..%d)" % (who, n_ent - 1, s.min(), s.max()))
+    if r.size and (r.min() < 0 or r.max() > 2 * n_rel):
+        raise ValueError("%s: query relation id out of range 0..%d (2*n_rel; got %d..%d)" % (who, 2 * n_rel, r.min(), r.max()))
+    as32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+    return h, b, w, as32(s), as32(r)
+
+
+def rule_apply(graph, head, body, weight, subs, rels, scratch_bytes=RULE_SCRATCH_BYTES):
+    """The rules (head[i], body[i], weight[i]) applied to the queries (subs[b], rels[b], ?) on ``graph`` (rg_rule_apply): four device
+    tensors [B, n_ent], ``best`` fp32 (the largest weight among the rules that connect the subject to the entity, 0 where none does),
+    ``surv`` fp32 (the product of their 1 - weight, in rule order), ``best_rule`` int32 (the first rule of that weight, -1) and
+    ``fired`` int32 (how many do).  ``head`` non-decreasing, weights in (0, 1], relation ids the graph's (0..2*n_rel), duplicate queries
+    allowed; all validated on the host (ValueError).  The rules are cut into consecutive ranges whose bitmaps fit ``scratch_bytes``
+    (rule_apply_chunking; one rule at least per call); the calls run in rule order on the current stream and carry the four tensors, so
+    no bit of the result depends on the budget.  Memory: 16 bytes per (query, entity) cell plus the scratch."""
+    if getattr(graph, "n_time", 0):
+        raise ValueError("rule_apply: temporal graph: rules are grounded on static and inductive graphs only "
+                         "(a temporal rule would have to say what it does with time)")
+    if isinstance(scratch_bytes, (bool, np.bool_)) or not isinstance(scratch_bytes, (int, np.integer)) or scratch_bytes < 0:
+        raise ValueError("rule_apply: scratch_bytes must be a non-negative integer (got %r)" % (scratch_bytes,))
+    h, b, w, s, r = check_rule_apply(graph.n_ent, graph.n_rel, head, body, weight, subs, rels)
+    dev = _require_gpu(graph.device)
+    R, L, B, n_ent = h.shape[0], b.shape[1], s.shape[0], int(graph.n_ent)
+    best = torch.zeros((B, n_ent), dtype=torch.float32, device=dev)
+    surv = torch.ones((B, n_ent), dtype=torch.float32, device=dev)
+    best_rule = torch.full((B, n_ent), -1, dtype=torch.int32, device=dev)
+    fired = torch.zeros((B, n_ent), dtype=torch.int32, device=dev)
+    if R == 0 or B == 0:
+        return best, surv, best_rule, fired
+    n_rows = 2 * int(graph.n_rel) + 1
+    order = np.argsort(r, kind="stable")
+    q_ptr = np.searchsorted(r[order], np.arange(n_rows + 1)).astype(np.int32)
+    words = n_ent * ((np.diff(q_ptr).astype(np.int64)[h] + 31) // 32)             # per rule
+    chunks = [(r0, r1) for r0, r1 in rule_apply_chunking(words, int(scratch_bytes)) if words[r0:r1].sum() > 0]
+    if not chunks:
+        return best, surv, best_rule, fired
+    slabs = [np.concatenate([[0], np.cumsum(words[r0:r1])]).astype(np.int64) for r0, r1 in chunks]
+    need = [rule_apply_scratch_bytes(sl[-1]) for sl in slabs]
+    if min(need) == 0:
+        raise ValueError("rule_apply: a rule's bitmap of %d words is beyond the bitmaps' range (fewer queries per call)" % max(words))
+    miss = (np.float32(1.0) - w).astype(np.float32)
+    to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    h_d, b_d, w_d, m_d, qs_d, qr_d, qp_d = (to(a) for a in (h, b, w, miss, s[order], order.astype(np.int32), q_ptr))
+    slab_d = to(np.concatenate(slabs))
+    off = np.concatenate([[0], np.cumsum([len(sl) for sl in slabs])])
+    p = _lib.ptr
+    with torch.cuda.device(dev):
+        scratch = torch.empty(max(need), dtype=torch.uint8, device=dev)
+        for c, (r0, r1) in enumerate(chunks):
+            def call(phases):
+                _lib.check(_lib.lib().rg_rule_apply(graph.handle, p(h_d[r0:r1]), p(b_d[r0:r1]), p(w_d[r0:r1]), p(m_d[r0:r1]), r1 - r0, L,
+                                                    r0, p(qs_d), p(qr_d), p(qp_d), B, p(slab_d[off[c]:off[c + 1]]), int(slabs[c][-1]),
+                                                    p(scratch), phases, p(best), p(surv), p(best_rule), p(fired), _lib.stream_ptr()))
+            if RULE_APPLY_EVENTS is None:
+                call(3)
+            else:
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+                ev[0].record()
+                call(1)
+                ev[1].record()
+                call(2)
+                ev[2].record()
+                RULE_APPLY_EVENTS.append((ev[0], ev[1], ev[2], r1 - r0, int(slabs[c][-1])))
+    return best, surv, best_rule, fired

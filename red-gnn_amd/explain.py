@@ -371,6 +371,173 @@ def split_rule_quality(base, table=None, data="test", k=1, max_queries=None):
     return base.model.rule_quality(table, mode=mode)
 
 
+AGGREGATIONS = ("noisy_or", "max")
+
+
+def _check_agg(agg, who):
+    if agg not in AGGREGATIONS:
+        raise ValueError("%s: agg must be 'noisy_or' or 'max' (got %r)" % (who, agg))
+
+
+@dataclass
+class RuleScores:
+    """What the rules of a RuleQuality predict for a batch of queries (s, r, ?) (engine.rule_apply; csrc/rule_apply.hip), per (query,
+    entity) cell over the rules kept.  A rule fires for (b, y) iff its head is the query relation and its body leads from s to y in
+    the graph; the rules that fire are folded in table order.  Tensors on the device that computed them, [B, n_ent] each.
+
+    best       float32  the largest weight among the rules that fire (0 where none does)
+    surv       float32  the product of their (1 - weight), each factor and each product rounded to float32, in table order
+    best_rule  int32    the table row of the first rule with weight ``best`` (-1 where none fires)
+    fired      int32    how many rules fire
+    rows       int64 [K] the table rows of the rules kept, ascending (the weights were formed for these)
+    """
+    best: torch.Tensor
+    surv: torch.Tensor
+    best_rule: torch.Tensor
+    fired: torch.Tensor
+    rows: torch.Tensor
+
+    def score(self, agg="noisy_or"):
+        """float32 [B, n_ent]: 'noisy_or' = fl32(1 - surv), 'max' = best (AnyBURL's max aggregation); 0 where no rule fires."""
+        _check_agg(agg, "score")
+        return self.best if agg == "max" else 1.0 - self.surv
+
+    def covered(self):
+        """bool [B, n_ent]: some rule reaches the entity."""
+        return self.fired > 0
+
+
+@dataclass
+class RulePrediction:
+    """The k best answers of each query by rule score.  ids int64 [B, k] (-1 past the row's remaining entities), scores float32 [B, k]
+    (-inf past the end), rule int64 [B, k] the table row of the answer's best rule (-1: no rule reaches it, or past the end), fired
+    int32 [B, k] how many rules reach it (0 past the end).  An answer with score 0 and fired 0 is one no rule reaches: it is listed
+    only because fewer than k entities are reached.  ``table``: the RuleTable the rows refer to."""
+    ids: torch.Tensor
+    scores: torch.Tensor
+    rule: torch.Tensor
+    fired: torch.Tensor
+    table: RuleTable = None
+
+    def format(self, id2rel=None):
+        """One line per answer, B * k in row order: ``row b #j: entity <id> score <s> fired <n>  <the best rule as RuleTable.format>``;
+        ``-`` for the rule where none fires."""
+        lines = self.table.cpu().format(id2rel) if self.table is not None else None
+        ids, sc, rule, fired = (t.cpu().tolist() for t in (self.ids, self.scores, self.rule, self.fired))
+        out = []
+        for b in range(len(ids)):
+            for j in range(len(ids[b])):
+                r = rule[b][j]
+                text = "-" if r < 0 else (lines[r] if lines is not None else "rule %d" % r)
+                out.append("row %d #%d: entity %d score %.6f fired %d  %s" % (b, j, ids[b][j], sc[b][j], fired[b][j], text))
+        return out
+
+
+def rule_weights(quality, by="confidence", laplace=0.0, min_hits=1, drop_trivial=True):
+    """(rows int64 [K], weight float32 [K]) on the host: the rules of ``quality`` kept for scoring, in table order, and their weights
+    float32(hits / (den + laplace)) formed in float64, den = body_pairs (by="confidence") or pca_body_pairs ("pca_confidence").  Kept:
+    hits >= min_hits, weight > 0, and not trivial() unless ``drop_trivial`` is False."""
+    if not isinstance(quality, RuleQuality):
+        raise ValueError("rule_scores: quality must be an explain.RuleQuality (got %s)" % type(quality).__name__)
+    if by not in ("confidence", "pca_confidence"):
+        raise ValueError("rule_scores: by must be 'confidence' or 'pca_confidence' (got %r)" % (by,))
+    laplace = float(laplace)
+    if not (np.isfinite(laplace) and laplace >= 0.0):
+        raise ValueError("rule_scores: laplace must be a finite number >= 0 (got %r)" % (laplace,))
+    q = quality.cpu()
+    hits = q.hits.numpy().astype(np.float64)
+    den = (q.body_pairs if by == "confidence" else q.pca_body_pairs).numpy().astype(np.float64) + laplace
+    weight = np.where(den > 0, hits / np.where(den > 0, den, 1.0), 0.0).astype(np.float32)
+    keep = (q.hits.numpy() >= int(min_hits)) & (weight > 0)
+    if drop_trivial:
+        keep &= ~q.trivial().numpy()
+    rows = np.nonzero(keep)[0].astype(np.int64)
+    return rows, weight[rows]
+
+
+def rule_scores(model, quality, subs, rels, by="confidence", laplace=0.0, min_hits=1, drop_trivial=True, mode="test",
+                scratch_bytes=engine.RULE_SCRATCH_BYTES):
+    """RED_GNN_trans.rule_scores (see there)."""
+    rows, weight = rule_weights(quality, by, laplace, min_hits, drop_trivial)
+    table = quality.table
+    if table.n_rel != model.n_rel:
+        raise ValueError("rule_scores: the table has n_rel=%d, the model n_rel=%d" % (table.n_rel, model.n_rel))
+    graph = model.loader.graph_for(mode)
+    head, body = table.head.cpu().numpy()[rows], table.body.cpu().numpy()[rows]
+    best, surv, best_rule, fired = engine.rule_apply(graph, head, body, weight, _ids(subs, "subs"), _ids(rels, "rels"), scratch_bytes)
+    rows_d = torch.as_tensor(rows).to(best.device)
+    if rows_d.numel():                                   # kept-rule index -> table row
+        best_rule = torch.where(best_rule >= 0, rows_d.int()[best_rule.clamp(min=0).long()], best_rule)
+    return RuleScores(best, surv, best_rule, fired, rows_d)
+
+
+def rule_predict(model, quality, subs, rels, k=10, agg="noisy_or", exclude_known=True, mode="test", **kw):
+    """RED_GNN_trans.rule_predict (see there)."""
+    from .prediction import K_MAX, _known_on_device
+    _check_agg(agg, "rule_predict")
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= k <= K_MAX:
+        raise ValueError("rule_predict: k must be an integer in 1..%d (got %r)" % (K_MAX, k))
+    subs_h, rels_h = _ids(subs, "subs"), _ids(rels, "rels")
+    rs = rule_scores(model, quality, subs_h, rels_h, mode=mode, **kw)
+    device = rs.best.device
+    B = rs.best.shape[0]
+    known, q_key = None, None
+    if exclude_known:
+        known = _known_on_device(model.loader, mode, device)
+        q_key = torch.as_tensor(subs_h * (2 * model.n_rel + 1) + rels_h, dtype=torch.int64).to(device)
+    if B == 0:
+        z = lambda dt, fill: torch.full((0, int(k)), fill, dtype=dt, device=device)
+        return RulePrediction(z(torch.int64, -1), z(torch.float32, 0.0), z(torch.int64, -1), z(torch.int32, 0), quality.table)
+    idx, val = engine.topk(rs.score(agg).contiguous(), int(k), q_key, known)
+    ids = idx.long()
+    at = ids.clamp(min=0)
+    rule = torch.where(ids >= 0, rs.best_rule.gather(1, at).long(), torch.full_like(ids, -1))
+    fired = torch.where(ids >= 0, rs.fired.gather(1, at), torch.zeros_like(idx))
+    return RulePrediction(ids, val, rule, fired, quality.table)
+
+
+def split_rule_ranks(base, quality, data="test", agg="noisy_or", batch=256, max_queries=None, **kw):
+    """(ranks float64 [n] on the device in (query, ascending answer) order, number of answers some rule reaches) of the rule scores
+    over the first ``max_queries`` queries of a split, walked in batches of ``batch`` queries: the body of BaseModel.rule_evaluate."""
+    from .utils import cal_ranks_csr
+    if data not in ("valid", "test"):
+        raise ValueError("rule_evaluate: data must be 'valid' or 'test' (got %r)" % (data,))
+    _check_agg(agg, "rule_evaluate")
+    if isinstance(batch, (bool, np.bool_)) or not isinstance(batch, (int, np.integer)) or batch < 1:
+        raise ValueError("rule_evaluate: batch must be a positive integer (got %r)" % (batch,))
+    loader = base.loader
+    n_all = len(loader.valid_q if data == "valid" else loader.test_q)
+    n = n_all if max_queries is None else min(n_all, int(max_queries))
+    if n <= 0:
+        raise ValueError("rule_evaluate: no queries in the %s split (n=%d)" % (data, n))
+    mode = loader.eval_mode(data) if hasattr(loader, "eval_mode") else data
+    ranks, covered = [], 0
+    for lo in range(0, n, int(batch)):
+        idx = np.arange(lo, min(lo + int(batch), n))
+        subs, rels, ans_ptr, ans_idx, filt_ptr, filt_idx = loader.get_batch_csr(idx, data=data)
+        rs = base.model.rule_scores(quality, subs, rels, mode=mode, **kw)
+        ranks.append(cal_ranks_csr(rs.score(agg), ans_ptr, ans_idx, filt_ptr, filt_idx))
+        q_of = torch.repeat_interleave(torch.arange(len(idx), device=ans_ptr.device), (ans_ptr[1:] - ans_ptr[:-1]).long())
+        covered += int((rs.fired[q_of, ans_idx.long()] > 0).sum())
+    return torch.cat(ranks).double(), covered
+
+
+def split_rule_evaluate(base, quality=None, data="test", mine="valid", k=1, agg="noisy_or", batch=256, max_queries=None, **kw):
+    """BaseModel.rule_evaluate (see there)."""
+    from .utils import cal_performance
+    if data not in ("valid", "test"):
+        raise ValueError("rule_evaluate: data must be 'valid' or 'test' (got %r)" % (data,))
+    if mine not in ("valid", "test"):
+        raise ValueError("rule_evaluate: mine must be 'valid' or 'test' (got %r)" % (mine,))
+    _check_agg(agg, "rule_evaluate")
+    if quality is None:
+        quality = base.rule_quality(data=mine, k=k, max_queries=max_queries)
+    ranks, covered = split_rule_ranks(base, quality, data, agg, batch, max_queries, **kw)
+    mrr, h1, h10 = cal_performance(ranks.cpu().numpy())
+    n = int(ranks.numel())
+    return dict(mrr=float(mrr), h1=float(h1), h10=float(h10), n=n, coverage=covered / n)
+
+
 def _table(key, support, fixed, n_rel):
     """RuleTable of rows key int64 [P, 1 + L] = (head, body) with their counts and fixed-point sums, equal keys merged."""
     if key.shape[0] == 0:

@@ -415,6 +415,32 @@ class RED_GNN_trans(nn.Module):
         from . import explain as _explain
         return _explain.rule_quality(self, table, mode, sources, scratch_bytes)
 
+    def rule_scores(self, quality, subs, rels, by="confidence", laplace=0.0, min_hits=1, drop_trivial=True, mode="test",
+                    scratch_bytes=engine.RULE_SCRATCH_BYTES):
+        """What the rules of an explain.RuleQuality predict for the queries (s, r, ?) on the graph of ``mode``, without the network:
+        explain.RuleScores with ``best`` / ``surv`` fp32, ``best_rule`` / ``fired`` int32 [B, n_ent] on the device.  A rule's weight is
+        float32(hits / (den + laplace)), formed in float64, den = body_pairs (by="confidence") or pca_body_pairs ("pca_confidence");
+        the rules kept, in table order, have hits >= min_hits, weight > 0 and are not trivial() unless ``drop_trivial=False``.  A rule
+        fires for (b, y) iff its head is rels[b] and its body leads from subs[b] to y; ``.score("max")`` is the largest weight that
+        fires, ``.score("noisy_or")`` 1 - prod(1 - weight) folded in table order in float32, ``best_rule`` the table row behind the
+        maximum (the first of equal weights), ``.covered()`` where any rule fires.  Per-query sparse boolean products in HIP
+        (rg_rule_apply), bit-identical across runs and for every ``scratch_bytes`` (the bitmaps' budget).  Memory: 16 bytes per
+        (query, entity) cell plus the bitmaps; batch the queries to bound it.  ValueError if ``quality.table.n_rel`` is not the
+        model's.  Static and inductive models only."""
+        from . import explain as _explain
+        return _explain.rule_scores(self, quality, subs, rels, by, laplace, min_hits, drop_trivial, mode, scratch_bytes)
+
+    def rule_predict(self, quality, subs, rels, k=10, agg="noisy_or", exclude_known=True, by="confidence", laplace=0.0, min_hits=1,
+                     drop_trivial=True, mode="test"):
+        """The k best answers of each query by rule score (rule_scores, then rg_topk with the loader's known index exactly as
+        predict): explain.RulePrediction(ids int64, scores fp32, rule int64, fired int32), each [B, k], ordered by score descending
+        then entity id ascending.  ``rule`` is the table row of the answer's best rule and ``fired`` the number of rules that reach
+        it, -1 / 0 past the end of a row.  An entity with score 0 may appear where fewer than k are reached: ``fired == 0`` says no
+        rule reached it.  ``.format(id2rel)`` gives one line per answer with the rule as RuleTable.format prints it."""
+        from . import explain as _explain
+        return _explain.rule_predict(self, quality, subs, rels, k, agg, exclude_known, mode, by=by, laplace=laplace,
+                                     min_hits=min_hits, drop_trivial=drop_trivial)
+
     def predict(self, subs, rels, k=10, exclude_known=True, mode="test"):
         """The k best answers of each query (s, r, ?): prediction.Prediction(ids int64 [B, k], scores fp32 [B, k]) on the device,
         ordered by score descending, then entity id ascending (-0.0 == +0.0, NaN last).  ``exclude_known``: the tails the loader's
@@ -644,6 +670,16 @@ class RED_GNN_induc(RED_GNN_trans):
 
     def rule_quality(self, table, mode="transductive", sources=None, scratch_bytes=engine.RULE_SCRATCH_BYTES):
         return super().rule_quality(table, mode=mode, sources=sources, scratch_bytes=scratch_bytes)
+
+    def rule_scores(self, quality, subs, rels, by="confidence", laplace=0.0, min_hits=1, drop_trivial=True, mode="transductive",
+                    scratch_bytes=engine.RULE_SCRATCH_BYTES):
+        return super().rule_scores(quality, subs, rels, by=by, laplace=laplace, min_hits=min_hits, drop_trivial=drop_trivial, mode=mode,
+                                   scratch_bytes=scratch_bytes)
+
+    def rule_predict(self, quality, subs, rels, k=10, agg="noisy_or", exclude_known=True, by="confidence", laplace=0.0, min_hits=1,
+                     drop_trivial=True, mode="transductive"):
+        return super().rule_predict(quality, subs, rels, k=k, agg=agg, exclude_known=exclude_known, by=by, laplace=laplace,
+                                    min_hits=min_hits, drop_trivial=drop_trivial, mode=mode)
 
     def predict(self, subs, rels, k=10, exclude_known=True, mode="transductive"):
         return super().predict(subs, rels, k=k, exclude_known=exclude_known, mode=mode)
