@@ -431,14 +431,47 @@ int rg_paths_topk(const int32_t* edges, const float* alpha, const int64_t* offse
  * then one counting pass; OR and integer adds are order-independent, so every count is exact, the same in every run and the same
  * however the rules and sources are cut into calls.  scratch holds rg_rule_ground_scratch_bytes(n_ent, n_rules, n_sources) bytes
  * (three bitmaps uint32 [n_rules][n_ent][ceil(n_sources / 32)] and one word row per rule; 0: an argument < 1, n_rules > 65535 or
- * more than 2^40 words per bitmap), 4-B aligned, and is zeroed by the call.  Errors: a temporal graph (n_time != 0: a temporal rule
- * would have to say what it does with time), a graph without its CSR by relation, n_rules / n_hops / n_sources out of range.  A
- * relation id outside 0..n_rela_rows-1 reads nothing (that rule's body or head is empty) and a source outside 0..n_ent-1 is skipped:
+ * more than 2^40 words per bitmap), 4-B aligned, and is zeroed by the call.  Errors: a temporal graph (n_time != 0: temporal rules
+ * carry a direction per step and are grounded by rg_trule_ground), a graph without its CSR by relation, n_rules / n_hops /
+ * n_sources out of range.  A relation id outside 0..n_rela_rows-1 reads nothing (that rule's body or head is empty) and a source
+ * outside 0..n_ent-1 is skipped:
  * nothing outside the graph's arrays or the scratch is touched whatever the id arrays hold; the caller validates them (engine.py).
  * Allocates nothing, asynchronous on `stream`. */
 size_t rg_rule_ground_scratch_bytes(int32_t n_ent, int32_t n_rules, int32_t n_sources);
 int rg_rule_ground(const rg_graph* g, const int32_t* head, const int32_t* body, int32_t n_rules, int32_t n_hops,
                    const int32_t* sources, int32_t n_sources, void* scratch, int64_t* counts, void* stream);
+
+/* ---- temporal rule quality: rg_rule_ground for the quadruple graph of the interpolation model (n_time != 0); no counterpart in the
+ * reference.  A temporal rule is a head relation h and a body of L steps (r_l, d_l); d is the forward's direction of an edge of time id
+ * tau against a query time id t (dt = tau - t): 0 past (dt < 0), 1 now (dt == 0), 2 future (dt > 0), and 3 = any edge time.  An anchor
+ * is a pair (x, t) of an entity and a query time id.  On the graph as built, rows (head, rel, tail, time) with inverse and identity
+ * rows as the caller's quadruples hold them, a repeated row counting once: A_{r,d}(u, v | t) holds iff the graph has a row
+ * (u, r, v, tau) whose direction against t is d (any such row if d == 3); body(x, y | t) iff there are z_0 = x, .., z_L = y with
+ * A_{r_l,d_l}(z_{l-1}, z_l | t) for every l (identity steps are ordinary steps); head(x, y | t) iff the graph has the row (x, h, y, t):
+ * the head is a "now" step.  counts int64 [n_rules, 4] is ADDED to (caller-zeroed; calls over disjoint anchor sets sum):
+ *   [0] body_pairs      #{((x, t), y): body(x, y | t)}
+ *   [1] hits            #{((x, t), y): body(x, y | t) and head(x, y | t)}
+ *   [2] pca_body_pairs  #{((x, t), y): body(x, y | t) and head(x, y' | t) for some y'}
+ *   [3] head_pairs      #{((x, t), y): head(x, y | t)}
+ * over the anchors of the call, so hits <= pca_body_pairs <= body_pairs and hits <= head_pairs.  head int32 [n_rules], body and dir
+ * int32 [n_rules, n_hops] (dir in 0..3); the anchors are j = 0..n_anchors-1, distinct and sorted by time id: anchor_ent int32
+ * [n_anchors] holds their entities and anchor_ptr int32 [n_time + 1] the first j whose time is >= tau, anchor_ptr[n_time] = n_anchors,
+ * so the times are implied.  All arrays are DEVICE arrays; n_hops in 1..32, n_rules <= 65535.  The bitmaps of rg_rule_ground with
+ * anchors for columns (csrc/trule_ground.hip): an edge (u, v, tau) moves one contiguous column range, past [ptr[tau+1], S), now
+ * [ptr[tau], ptr[tau+1]), future [0, ptr[tau]), any [0, S); per hop |edges of r_l| * (words in range) words are read, masked and ORed
+ * with integer atomics, then one counting pass.  OR and integer adds are order-independent, so every count is exact, the same in every
+ * run and the same however the rules and the sorted anchors are cut into calls.  scratch holds rg_trule_ground_scratch_bytes(n_ent,
+ * n_rules, n_anchors) bytes (the layout and the 0 cases of rg_rule_ground_scratch_bytes), 4-B aligned, and is zeroed by the call.
+ * Errors: a NULL graph, a static graph (n_time == 0: use rg_rule_ground), a graph without its CSR by relation and edge times, n_hops
+ * outside 1..32, n_rules > 65535, n_anchors < 0; n_rules == 0 or n_anchors == 0 does nothing.  A relation id outside 0..n_rela_rows-1
+ * is tested before any load and reads nothing, a direction outside 0..3 makes the step empty, an edge end or anchor entity outside
+ * 0..n_ent-1 and an edge time outside 0..n_time-1 are skipped, anchor_ptr entries are clamped to 0..n_anchors and an empty range moves
+ * nothing: nothing outside the graph's arrays or the scratch is touched whatever the id arrays hold; the caller validates them
+ * (engine.py).  Allocates nothing, asynchronous on `stream`. */
+size_t rg_trule_ground_scratch_bytes(int32_t n_ent, int32_t n_rules, int32_t n_anchors);
+int rg_trule_ground(const rg_graph* g, const int32_t* head, const int32_t* body, const int32_t* dir, int32_t n_rules, int32_t n_hops,
+                    const int32_t* anchor_ent, const int32_t* anchor_ptr, int32_t n_anchors, void* scratch, int64_t* counts,
+                    void* stream);
 
 /* ---- rule application: which answers weighted rules predict for queries (s, r, ?), and which rule is behind each; no counterpart in
  * the reference.  The graph, A_r(x, y) and body(x, y) are exactly those of rg_rule_ground.  The rules are (head[i], body[i][0..L-1],

@@ -23,48 +23,11 @@
 //
 // Bounds.  A relation id outside 0..n_rela_rows-1 reads nothing (the rule then has no grounding); an edge end or a source outside
 // 0..n_ent-1 is skipped.  The bits of the last word beyond the source count are never set by the seed, and a hop only moves bits.
-#include <algorithm>
-
-#include "common.h"
+#include "rule_maps.h"
 
 namespace {
 
-constexpr int RT = 256;                           // threads per workgroup
-constexpr int RULE_MAX_HOPS = 32;
-constexpr int RULE_MAX_RULES = 65535;             // the rule is blockIdx.y
-constexpr size_t RULE_ALIGN = 256;
-constexpr int64_t RULE_MAX_WORDS = (int64_t)1 << 40;   // per bitmap (4 TiB): keeps every byte count far inside size_t
-
-struct Maps {
-  uint32_t* cur;
-  uint32_t* next;
-  uint32_t* head;
-  uint32_t* any;
-};
-
-inline size_t up(size_t x) { return (x + RULE_ALIGN - 1) / RULE_ALIGN * RULE_ALIGN; }
-
-// slices of the scratch for n_r rules, W words per entity; returns the bytes used
-size_t carve(void* scratch, int64_t n_ent, int64_t n_r, int64_t W, Maps* m) {
-  unsigned char* p = static_cast<unsigned char*>(scratch);
-  const size_t map = up((size_t)(n_r * n_ent * W) * 4);
-  if (m) {
-    m->cur = reinterpret_cast<uint32_t*>(p);
-    m->next = reinterpret_cast<uint32_t*>(p + map);
-    m->head = reinterpret_cast<uint32_t*>(p + 2 * map);
-    m->any = reinterpret_cast<uint32_t*>(p + 3 * map);
-  }
-  return 3 * map + up((size_t)(n_r * W) * 4);
-}
-
-__global__ __launch_bounds__(RT) void rule_seed_kernel(const int32_t* __restrict__ sources, int32_t n_sources, int32_t n_ent, int32_t W,
-                                                       uint32_t* __restrict__ cur) {
-  const int64_t base = (int64_t)blockIdx.y * n_ent * W;
-  for (int32_t j = blockIdx.x * RT + threadIdx.x; j < n_sources; j += gridDim.x * RT) {
-    const uint32_t s = (uint32_t)sources[j];
-    if (s < (uint32_t)n_ent) atomicOr(&cur[base + (int64_t)s * W + (j >> 5)], 1u << (j & 31));
-  }
-}
+using namespace rgrule;      // the scratch layout, the seed and count kernels and the grid rule, shared with trule_ground.hip
 
 // one step of every rule: to[i][v] |= from[i][u] over the edges (u, v) of relation rel_of[i * rel_stride]; `any` (or NULL) collects
 // per word the bits that moved.  No barrier: a workgroup whose rule has no such relation, or fewer edges than the grid covers, leaves.
@@ -96,60 +59,10 @@ __global__ __launch_bounds__(RT) void rule_hop_kernel(const int32_t* __restrict_
   }
 }
 
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__global__ __launch_bounds__(RT) void rule_count_kernel(int32_t n_ent, int32_t W, const uint32_t* __restrict__ cur,
-                                                        const uint32_t* __restrict__ head, const uint32_t* __restrict__ any,
-                                                        unsigned long long* __restrict__ counts) {
-  __shared__ unsigned long long s_part[RT / 64][4];
-  const int64_t i = blockIdx.y, n = (int64_t)n_ent * W, stride = (int64_t)gridDim.x * RT;
-  const uint32_t* __restrict__ c = cur + i * n;
-  const uint32_t* __restrict__ h = head + i * n;
-  const uint32_t* __restrict__ m = any + i * W;
-  int64_t idx = (int64_t)blockIdx.x * RT + threadIdx.x;
-  int32_t w = (int32_t)(idx % W);
-  const int32_t w_step = (int32_t)(stride % W);
-  unsigned long long body = 0, hits = 0, pca = 0, heads = 0;
-  for (; idx < n; idx += stride) {
-    const uint32_t x = c[idx], y = h[idx];
-    if ((x | y) != 0) {
-      body += __popc(x);
-      hits += __popc(x & y);
-      pca += __popc(x & m[w]);
-      heads += __popc(y);
-    }
-    w += w_step;
-    if (w >= W) w -= W;
-  }
-  body = wave_sum(body); hits = wave_sum(hits); pca = wave_sum(pca); heads = wave_sum(heads);
-  if ((threadIdx.x & 63) == 0) {
-    unsigned long long* p = s_part[threadIdx.x >> 6];
-    p[0] = body; p[1] = hits; p[2] = pca; p[3] = heads;
-  }
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    unsigned long long t = 0;
-    for (int k = 0; k < RT / 64; ++k) t += s_part[k][threadIdx.x];
-    if (t != 0) atomicAdd(&counts[i * 4 + threadIdx.x], t);
-  }
-}
-
-// blocks along x for `items` units of work at `per_block` a pass, a few passes each, with the rules in y
-unsigned grid_x(int64_t items, int64_t per_block, int32_t n_rules) {
-  const int64_t want = rg::ceil_div(std::max<int64_t>(items, 1), per_block * 8);
-  return (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, std::max<int64_t>(1, std::min<int64_t>(1024, 65536 / n_rules))));
-}
-
 }  // namespace
 
 extern "C" size_t rg_rule_ground_scratch_bytes(int32_t n_ent, int32_t n_rules, int32_t n_sources) {
-  if (n_ent < 1 || n_rules < 1 || n_rules > RULE_MAX_RULES || n_sources < 1) return 0;
-  const int64_t W = rg::ceil_div(n_sources, 32);
-  if ((int64_t)n_ent * W > RULE_MAX_WORDS / n_rules) return 0;
-  return carve(nullptr, n_ent, n_rules, W, nullptr);
+  return rgrule::scratch_bytes(n_ent, n_rules, n_sources);
 }
 
 extern "C" int rg_rule_ground(const rg_graph* g, const int32_t* head, const int32_t* body, int32_t n_rules, int32_t n_hops,
@@ -168,8 +81,7 @@ extern "C" int rg_rule_ground(const rg_graph* g, const int32_t* head, const int3
            n_sources);
   const hipStream_t s = (hipStream_t)stream;
   const int32_t n_ent = g->n_ent, W = (int32_t)rg::ceil_div(n_sources, 32);
-  int32_t g_shift = 0;
-  while (g_shift < 6 && (1 << g_shift) < W) ++g_shift;
+  const int32_t g_shift = group_shift(W);
   Maps m;
   carve(scratch, n_ent, n_rules, W, &m);
   const size_t map_bytes = (size_t)((int64_t)n_rules * n_ent * W) * 4;

@@ -1,0 +1,117 @@
+// What rule_ground.hip (static rules, columns = source entities) and trule_ground.hip (temporal rules, columns = anchors (entity,
+// time id)) share: the scratch layout, the seed kernel, the counting kernel and the grid rule.  Both ground a rule as a chain of boolean
+// products on entity-major bitmaps; a call covers n_r rules and S columns, W = ceil(S / 32) words per entity, and the scratch holds
+//   cur, next, head : uint32 [n_r][n_ent][W]      bit j of word (i, y, j / 32): column j reaches y under rule i
+//   any             : uint32 [n_r][W]             bit j: column j has some fact of the rule's head relation
+// Word indices are int64 throughout (n_r * n_ent * W passes 2^31 on a mid-sized graph with all entities as sources).  Only the hop
+// kernels differ, and each file keeps its own.
+#pragma once
+#include <algorithm>
+
+#include "common.h"
+
+namespace rgrule {
+namespace {
+
+constexpr int RT = 256;                           // threads per workgroup
+constexpr int RULE_MAX_HOPS = 32;
+constexpr int RULE_MAX_RULES = 65535;             // the rule is blockIdx.y
+constexpr size_t RULE_ALIGN = 256;
+constexpr int64_t RULE_MAX_WORDS = (int64_t)1 << 40;   // per bitmap (4 TiB): keeps every byte count far inside size_t
+
+struct Maps {
+  uint32_t* cur;
+  uint32_t* next;
+  uint32_t* head;
+  uint32_t* any;
+};
+
+inline size_t up(size_t x) { return (x + RULE_ALIGN - 1) / RULE_ALIGN * RULE_ALIGN; }
+
+// slices of the scratch for n_r rules, W words per entity; returns the bytes used
+inline size_t carve(void* scratch, int64_t n_ent, int64_t n_r, int64_t W, Maps* m) {
+  unsigned char* p = static_cast<unsigned char*>(scratch);
+  const size_t map = up((size_t)(n_r * n_ent * W) * 4);
+  if (m) {
+    m->cur = reinterpret_cast<uint32_t*>(p);
+    m->next = reinterpret_cast<uint32_t*>(p + map);
+    m->head = reinterpret_cast<uint32_t*>(p + 2 * map);
+    m->any = reinterpret_cast<uint32_t*>(p + 3 * map);
+  }
+  return 3 * map + up((size_t)(n_r * W) * 4);
+}
+
+// the bytes of a call's scratch; 0: an argument < 1, n_rules > RULE_MAX_RULES or more than RULE_MAX_WORDS words per bitmap
+inline size_t scratch_bytes(int32_t n_ent, int32_t n_rules, int32_t n_cols) {
+  if (n_ent < 1 || n_rules < 1 || n_rules > RULE_MAX_RULES || n_cols < 1) return 0;
+  const int64_t W = rg::ceil_div(n_cols, 32);
+  if ((int64_t)n_ent * W > RULE_MAX_WORDS / n_rules) return 0;
+  return carve(nullptr, n_ent, n_rules, W, nullptr);
+}
+
+// bit j of cur[i][sources[j]] for every rule i; a source outside 0..n_ent-1 is skipped
+__global__ __launch_bounds__(RT) void rule_seed_kernel(const int32_t* __restrict__ sources, int32_t n_sources, int32_t n_ent, int32_t W,
+                                                       uint32_t* __restrict__ cur) {
+  const int64_t base = (int64_t)blockIdx.y * n_ent * W;
+  for (int32_t j = blockIdx.x * RT + threadIdx.x; j < n_sources; j += gridDim.x * RT) {
+    const uint32_t s = (uint32_t)sources[j];
+    if (s < (uint32_t)n_ent) atomicOr(&cur[base + (int64_t)s * W + (j >> 5)], 1u << (j & 31));
+  }
+}
+
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(RT) void rule_count_kernel(int32_t n_ent, int32_t W, const uint32_t* __restrict__ cur,
+                                                        const uint32_t* __restrict__ head, const uint32_t* __restrict__ any,
+                                                        unsigned long long* __restrict__ counts) {
+  __shared__ unsigned long long s_part[RT / 64][4];
+  const int64_t i = blockIdx.y, n = (int64_t)n_ent * W, stride = (int64_t)gridDim.x * RT;
+  const uint32_t* __restrict__ c = cur + i * n;
+  const uint32_t* __restrict__ h = head + i * n;
+  const uint32_t* __restrict__ m = any + i * W;
+  int64_t idx = (int64_t)blockIdx.x * RT + threadIdx.x;
+  int32_t w = (int32_t)(idx % W);
+  const int32_t w_step = (int32_t)(stride % W);
+  unsigned long long body = 0, hits = 0, pca = 0, heads = 0;
+  for (; idx < n; idx += stride) {
+    const uint32_t x = c[idx], y = h[idx];
+    if ((x | y) != 0) {
+      body += __popc(x);
+      hits += __popc(x & y);
+      pca += __popc(x & m[w]);
+      heads += __popc(y);
+    }
+    w += w_step;
+    if (w >= W) w -= W;
+  }
+  body = wave_sum(body); hits = wave_sum(hits); pca = wave_sum(pca); heads = wave_sum(heads);
+  if ((threadIdx.x & 63) == 0) {
+    unsigned long long* p = s_part[threadIdx.x >> 6];
+    p[0] = body; p[1] = hits; p[2] = pca; p[3] = heads;
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    unsigned long long t = 0;
+    for (int k = 0; k < RT / 64; ++k) t += s_part[k][threadIdx.x];
+    if (t != 0) atomicAdd(&counts[i * 4 + threadIdx.x], t);
+  }
+}
+
+// blocks along x for `items` units of work at `per_block` a pass, a few passes each, with the rules in y
+inline unsigned grid_x(int64_t items, int64_t per_block, int32_t n_rules) {
+  const int64_t want = rg::ceil_div(std::max<int64_t>(items, 1), per_block * 8);
+  return (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, std::max<int64_t>(1, std::min<int64_t>(1024, 65536 / n_rules))));
+}
+
+// the power of two >= words, at most 64 (a wave), as a shift: the lanes that own one edge in a hop
+inline int32_t group_shift(int64_t words) {
+  int32_t s = 0;
+  while (s < 6 && (1 << s) < words) ++s;
+  return s;
+}
+
+}  // namespace
+}  // namespace rgrule

@@ -144,7 +144,22 @@ class TemporalGraph(Graph):
                                                                  _lib.ptr(ex), len(ex), C.byref(h)))
         self.handle = h
         self.n_fact = int(_lib.lib().rg_graph_n_fact(h))
+        self._rows = (q, None if exclude is None else ex)      # a reference to the caller's rows: default_anchors reads them once
+        self._anchors = None
 
+    def default_anchors(self):
+        """int64 [S, 2] = (entity, time id) sorted by (time, entity): the distinct (head, time) pairs of the graph's rows whose
+        relation is not the identity (n_rela_rows - 1), the anchors trule_ground counts over when given none.  Formed on first use
+        from the rows given at construction (kept by reference), then cached."""
+        if self._anchors is None:
+            q, ex = self._rows
+            if ex is not None:
+                q = np.delete(q, ex, axis=0)
+            q = q[q[:, 1] != self.n_rela_rows - 1]
+            key = np.unique(q[:, 3].astype(np.int64) * self.n_ent + q[:, 0])
+            self._anchors = np.stack([key % self.n_ent, key // self.n_ent], 1)
+            self._rows = None
+        return self._anchors
 
     def export_time(self):
         """(out_time [n_fact], in_time [n_fact]): the time id of every entry of export()'s out_rel_tail / in_head_rel — for tests."""
@@ -1132,7 +1147,7 @@ def rule_ground(graph, head, body, sources=None, scratch_bytes=RULE_SCRATCH_BYTE
     the scratch is allocated once and the counts are integers added per chunk, so the result does not depend on the budget."""
     if getattr(graph, "n_time", 0):
         raise ValueError("rule_ground: temporal graph: rules are grounded on static and inductive graphs only "
-                         "(a temporal rule would have to say what it does with time)")
+                         "(temporal rules, whose steps carry a direction, are grounded by trule_ground)")
     if isinstance(scratch_bytes, (bool, np.bool_)) or not isinstance(scratch_bytes, (int, np.integer)) or scratch_bytes < 0:
         raise ValueError("rule_ground: scratch_bytes must be a non-negative integer (got %r)" % (scratch_bytes,))
     h, b, s = check_rules(graph.n_ent, graph.n_rel, head, body, sources)
@@ -1158,6 +1173,92 @@ def rule_ground(graph, head, body, sources=None, scratch_bytes=RULE_SCRATCH_BYTE
                 if RULE_EVENTS is not None:
                     ev[1].record()
                     RULE_EVENTS.append((ev[0], ev[1], r1 - r0, s1 - s0))
+    return counts
+
+
+# tools/probe_trule_quality.py sets this to a list to collect (start_event, end_event, n_rules, n_anchors) per chunk of trule_ground
+TRULE_EVENTS = None
+TRULE_DIRECTIONS = ("past", "now", "future", "any")      # the step directions 0..3 of a temporal rule
+
+
+def trule_ground_scratch_bytes(n_ent, n_rules, n_anchors):
+    return int(_lib.lib().rg_trule_ground_scratch_bytes(int(n_ent), int(n_rules), int(n_anchors)))
+
+
+def check_trules(graph, head, body, direction, anchors=None, who="trule_ground"):
+    """The host validation of trule_ground: (head int32 [R], body int32 [R, L], direction int32 [R, L], anchors int64 [S, 2] =
+    (entity, time id) sorted by (time, entity)) as contiguous numpy arrays, or ValueError.  ``graph`` needs n_ent, n_rela_rows and
+    n_time (and default_anchors() where ``anchors`` is None); no device is touched."""
+    n_time = int(getattr(graph, "n_time", 0) or 0)
+    if n_time == 0:
+        raise ValueError("%s: static graph (no time ids): static rules are grounded by rule_ground" % who)
+    n_ent, n_rows = int(graph.n_ent), int(graph.n_rela_rows)
+    h, b, d = _int_array(head, "head", who), _int_array(body, "body", who), _int_array(direction, "direction", who)
+    if h.ndim != 1 or b.ndim != 2 or b.shape[0] != h.shape[0] or d.shape != b.shape:
+        raise ValueError("%s: head must be [R], body and direction [R, L] (got %s, %s and %s)" % (who, h.shape, b.shape, d.shape))
+    if not 1 <= b.shape[1] <= RULE_MAX_HOPS:
+        raise ValueError("%s: the body length %d is not in 1..%d" % (who, b.shape[1], RULE_MAX_HOPS))
+    if h.size and (min(h.min(), b.min()) < 0 or max(h.max(), b.max()) >= n_rows):
+        raise ValueError("%s: relation id out of range 0..%d (got %d..%d)"
+                         % (who, n_rows - 1, min(h.min(), b.min()), max(h.max(), b.max())))
+    if d.size and (d.min() < 0 or d.max() > 3):
+        raise ValueError("%s: direction out of range 0..3 (past, now, future, any; got %d..%d)" % (who, d.min(), d.max()))
+    if anchors is None:
+        a = graph.default_anchors()
+    else:
+        a = _int_array(anchors, "anchors", who)
+        if a.ndim != 2 or a.shape[1] != 2:
+            raise ValueError("%s: anchors must be [S, 2] = (entity, time id) (got %s)" % (who, a.shape))
+        a = a.astype(np.int64)
+        if a.size and (a[:, 0].min() < 0 or a[:, 0].max() >= n_ent or a[:, 1].min() < 0 or a[:, 1].max() >= n_time):
+            raise ValueError("%s: anchor out of range (entity 0..%d, time id 0..%d; got %d..%d and %d..%d)"
+                             % (who, n_ent - 1, n_time - 1, a[:, 0].min(), a[:, 0].max(), a[:, 1].min(), a[:, 1].max()))
+        key = np.sort(a[:, 1] * n_ent + a[:, 0])
+        if np.unique(key).size != key.size:
+            raise ValueError("%s: duplicate anchors (%d pairs, %d distinct)" % (who, key.size, np.unique(key).size))
+        a = np.stack([key % n_ent, key // n_ent], 1)
+    as32 = lambda x: np.ascontiguousarray(x, dtype=np.int32)
+    return as32(h), as32(b), as32(d), a
+
+
+def trule_ground(graph, head, body, direction, anchors=None, scratch_bytes=RULE_SCRATCH_BYTES):
+    """The four counts of every temporal rule (head[i], (body[i], direction[i])) on the quadruple graph ``graph`` (rg_trule_ground;
+    include/redgnn.h has the definition): int64 [R, 4] on the device = (body_pairs, hits, pca_body_pairs, head_pairs) over the pairs
+    ((x, t), y) with (x, t) in ``anchors``, int [S, 2] = (entity, time id), distinct; None: graph.default_anchors().  Relation ids
+    are the graph's, 0..n_rela_rows-1; directions 0 past, 1 now, 2 future (of the edge's time against the anchor's, as the forward
+    forms it), 3 any.  Everything is validated on the host (ValueError).  The anchors are sorted by (time, entity) and the work is cut
+    into chunks of (rules x blocks of consecutive anchors, a multiple of 32) whose bitmaps fit ``scratch_bytes``, as rule_chunking
+    says; each block gets anchor_ptr = clip(ptr - s0, 0, s1 - s0), ptr being the first sorted anchor of every time id.  The scratch
+    is allocated once and the counts are integers added per chunk, so the result does not depend on the budget."""
+    if isinstance(scratch_bytes, (bool, np.bool_)) or not isinstance(scratch_bytes, (int, np.integer)) or scratch_bytes < 0:
+        raise ValueError("trule_ground: scratch_bytes must be a non-negative integer (got %r)" % (scratch_bytes,))
+    h, b, d, a = check_trules(graph, head, body, direction, anchors)
+    dev = _require_gpu(graph.device)
+    R, L, S = h.shape[0], b.shape[1], a.shape[0]
+    counts = torch.zeros((R, 4), dtype=torch.int64, device=dev)
+    if R == 0 or S == 0:
+        return counts
+    n_r, s_c = rule_chunking(graph.n_ent, R, S, int(scratch_bytes))
+    ptr = np.searchsorted(a[:, 1], np.arange(graph.n_time + 1))              # the first sorted anchor whose time is >= tau
+    starts = np.arange(0, S, s_c)
+    block_ptr = np.clip(ptr[None, :] - starts[:, None], 0, np.minimum(starts + s_c, S)[:, None] - starts[:, None])
+    h_d, b_d, d_d, e_d, p_d = (torch.from_numpy(np.ascontiguousarray(x, dtype=np.int32)).to(dev) for x in (h, b, d, a[:, 0], block_ptr))
+    p = _lib.ptr
+    with torch.cuda.device(dev):
+        scratch = torch.empty(trule_ground_scratch_bytes(graph.n_ent, min(n_r, R), min(s_c, S)), dtype=torch.uint8, device=dev)
+        for r0 in range(0, R, n_r):
+            r1 = min(r0 + n_r, R)
+            for k, s0 in enumerate(starts.tolist()):
+                s1 = min(s0 + s_c, S)
+                if TRULE_EVENTS is not None:
+                    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                    ev[0].record()
+                _lib.check(_lib.lib().rg_trule_ground(graph.handle, p(h_d[r0:r1]), p(b_d[r0:r1]), p(d_d[r0:r1]), r1 - r0, L,
+                                                      p(e_d[s0:s1]), p(p_d[k]), s1 - s0, p(scratch), p(counts[r0:r1]),
+                                                      _lib.stream_ptr()))
+                if TRULE_EVENTS is not None:
+                    ev[1].record()
+                    TRULE_EVENTS.append((ev[0], ev[1], r1 - r0, s1 - s0))
     return counts
 
 
@@ -1230,7 +1331,7 @@ def rule_apply(graph, head, body, weight, subs, rels, scratch_bytes=RULE_SCRATCH
     no bit of the result depends on the budget.  Memory: 16 bytes per (query, entity) cell plus the scratch."""
     if getattr(graph, "n_time", 0):
         raise ValueError("rule_apply: temporal graph: rules are grounded on static and inductive graphs only "
-                         "(a temporal rule would have to say what it does with time)")
+                         "(temporal rules are mined and grounded, trule_ground, but not applied to queries)")
     if isinstance(scratch_bytes, (bool, np.bool_)) or not isinstance(scratch_bytes, (int, np.integer)) or scratch_bytes < 0:
         raise ValueError("rule_apply: scratch_bytes must be a non-negative integer (got %r)" % (scratch_bytes,))
     h, b, w, s, r = check_rule_apply(graph.n_ent, graph.n_rel, head, body, weight, subs, rels)

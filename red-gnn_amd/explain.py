@@ -14,7 +14,9 @@ one backward marking pass per hop reads only the marked tails' CSR rows.  This m
 
 Temporal interpolation (T_RED_GNN.explain, rg_texplain_*): ``rd = model.explain(batch, objs)`` with the batch dict of forward; every
 edge also carries its time id (``rd.time``), ``rd.q_time`` is the rows' query time and ``rd.direction()`` the forward's past / now /
-future of each edge.
+future of each edge.  ``table = model.rules(batch, objs, k=2)`` counts the best paths as temporal rules, steps (relation, direction)
+with identity steps written as direction 3 = any (TemporalRuleTable), and ``model.rule_quality(table)`` counts how they hold in the
+quadruple graph per anchor (entity, query time id) (TemporalRuleQuality; engine.trule_ground, csrc/trule_ground.hip).
 
 Temporal extrapolation (extrapolation.T_RED_GNN.explain, rg_xexplain_*): ``rd = model.explain(X, objs)`` with the batch object of
 forward; ``rd.data_row`` names the past fact behind every edge (-1: a self-loop, relation id n_rel), ``rd.time`` its day and
@@ -275,27 +277,9 @@ class RuleTable:
         return out
 
 
-@dataclass
-class RuleQuality:
-    """How the rules of a RuleTable hold in a knowledge graph (engine.rule_ground; csrc/rule_ground.hip): exact counts over the pairs
-    (x, y) with x one of ``n_sources`` source entities, on the graph as built (inverse and identity rows included, a repeated fact
-    counted once).  body(x, y): the rule's relation sequence leads from x to y, identity steps being ordinary steps.
-
-    table           RuleTable  the rules, row by row
-    body_pairs      int64 [R]  pairs the body connects
-    hits            int64 [R]  ... that the head relation connects too (AMIE's support; ``table.support`` counts explained paths)
-    pca_body_pairs  int64 [R]  pairs the body connects whose x has some fact of the head relation
-    head_pairs      int64 [R]  pairs the head relation connects
-    n_sources       int        number of source entities
-
-    hits <= pca_body_pairs <= body_pairs and hits <= head_pairs.
-    """
-    table: RuleTable
-    body_pairs: torch.Tensor
-    hits: torch.Tensor
-    pca_body_pairs: torch.Tensor
-    head_pairs: torch.Tensor
-    n_sources: int
+class _Quality:
+    """What RuleQuality and TemporalRuleQuality share: the ratios of the four counts and the ordering of ``top``.  A subclass has the
+    fields table, body_pairs, hits, pca_body_pairs, head_pairs and the methods trivial(), cpu() and _tie_key()."""
 
     def _ratio(self, den):
         num, den = self.hits.double(), den.double()
@@ -313,15 +297,6 @@ class RuleQuality:
         """float64 [R]: hits / head_pairs, 0.0 where the head relation has no fact from a source."""
         return self._ratio(self.head_pairs)
 
-    def trivial(self):
-        """bool [R]: the body with its identity steps dropped is exactly [head]; such a rule has confidence 1 by construction."""
-        step = self.table.body != 2 * self.table.n_rel
-        return (step.sum(1) == 1) & ((self.table.body * step).sum(1) == self.table.head)
-
-    def cpu(self):
-        return RuleQuality(self.table.cpu(), self.body_pairs.cpu(), self.hits.cpu(), self.pca_body_pairs.cpu(), self.head_pairs.cpu(),
-                           self.n_sources)
-
     def top(self, q_rel, n, by="confidence", min_hits=1, drop_trivial=True):
         """Row indices (int64, at most n) of the best rules of query relation ``q_rel`` by "confidence", "pca_confidence" or "hits",
         among those with hits >= min_hits (and not trivial).  Ties go to the larger hits, then to the smaller body."""
@@ -331,7 +306,7 @@ class RuleQuality:
             raise ValueError("top: by must be 'confidence', 'pca_confidence' or 'hits' (got %r)" % (by,))
         q = self.cpu()                                   # a few thousand rows at most: ordered on the host
         score = (q.hits.double() if by == "hits" else getattr(q, by)()).numpy()
-        hits, body = q.hits.numpy(), q.table.body.numpy()
+        hits, body = q.hits.numpy(), q._tie_key().numpy()
         keep = (q.table.head == int(q_rel)) & (q.hits >= int(min_hits))
         if drop_trivial:
             keep = keep & ~q.trivial()
@@ -346,6 +321,149 @@ class RuleQuality:
         conf, pca = q.confidence().tolist(), q.pca_confidence().tolist()
         return ["%s  %d/%d conf=%.4f pca=%.4f" % (line, h, b, c, p)
                 for line, h, b, c, p in zip(q.table.format(id2rel), q.hits.tolist(), q.body_pairs.tolist(), conf, pca)]
+
+
+@dataclass
+class RuleQuality(_Quality):
+    """How the rules of a RuleTable hold in a knowledge graph (engine.rule_ground; csrc/rule_ground.hip): exact counts over the pairs
+    (x, y) with x one of ``n_sources`` source entities, on the graph as built (inverse and identity rows included, a repeated fact
+    counted once).  body(x, y): the rule's relation sequence leads from x to y, identity steps being ordinary steps.
+
+    table           RuleTable  the rules, row by row
+    body_pairs      int64 [R]  pairs the body connects
+    hits            int64 [R]  ... that the head relation connects too (AMIE's support; ``table.support`` counts explained paths)
+    pca_body_pairs  int64 [R]  pairs the body connects whose x has some fact of the head relation
+    head_pairs      int64 [R]  pairs the head relation connects
+    n_sources       int        number of source entities
+
+    hits <= pca_body_pairs <= body_pairs and hits <= head_pairs.  confidence(), pca_confidence(), head_coverage(), top() and format()
+    are _Quality's.
+    """
+    table: RuleTable
+    body_pairs: torch.Tensor
+    hits: torch.Tensor
+    pca_body_pairs: torch.Tensor
+    head_pairs: torch.Tensor
+    n_sources: int
+
+    def trivial(self):
+        """bool [R]: the body with its identity steps dropped is exactly [head]; such a rule has confidence 1 by construction."""
+        step = self.table.body != 2 * self.table.n_rel
+        return (step.sum(1) == 1) & ((self.table.body * step).sum(1) == self.table.head)
+
+    def _tie_key(self):
+        return self.table.body
+
+    def cpu(self):
+        return RuleQuality(self.table.cpu(), self.body_pairs.cpu(), self.hits.cpu(), self.pca_body_pairs.cpu(), self.head_pairs.cpu(),
+                           self.n_sources)
+
+
+DIRECTION_ANY = 3                                        # a step that matches every edge time (engine.TRULE_DIRECTIONS)
+
+
+@dataclass
+class TemporalRuleTable:
+    """Paths of the temporal interpolation model counted as rules: one row per distinct (query relation, (r_1, d_1), .., (r_L, d_L)),
+    sorted by that key.  d is the direction of the step's edge against the query time as the forward forms it (RDigraph.direction():
+    0 past, 1 now, 2 future); an identity step (relation id n_rel; the reference gives those rows the sentinel time n_time - 1) is
+    written with direction 3 = any, so a rule does not split by where its padding fell.
+
+    head       int64 [R]      the query relation
+    body       int64 [R, L]   the relations of the steps
+    direction  int64 [R, L]   their directions, 0..3
+    support    int64 [R]      paths counted
+    fixed      int64 [R]      the sum of their alpha products in units of 2^-32, each path rounded once: tables add exactly
+    n_rel      int            the model's n_rel: relation ids 0..n_rel-1 as the quadruples hold them, n_rel the identity
+    """
+    head: torch.Tensor
+    body: torch.Tensor
+    direction: torch.Tensor
+    support: torch.Tensor
+    fixed: torch.Tensor
+    n_rel: int
+
+    product_sum = RuleTable.product_sum
+    mean = RuleTable.mean
+
+    def _rows(self, rows):
+        return TemporalRuleTable(self.head[rows], self.body[rows], self.direction[rows], self.support[rows], self.fixed[rows], self.n_rel)
+
+    def key(self):
+        """int64 [R, 1 + 2L]: (head, r_1, d_1, .., r_L, d_L), the key the rows are sorted by."""
+        R, L = self.body.shape
+        return torch.cat([self.head[:, None], torch.stack([self.body, self.direction], 2).reshape(R, 2 * L)], 1)
+
+    def top(self, q_rel, n):
+        """The n rules of query relation ``q_rel`` with the largest support (ties: the smaller key), as a table in that order."""
+        if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or n < 1:
+            raise ValueError("top: n must be a positive integer (got %r)" % (n,))
+        rows = torch.nonzero(self.head == int(q_rel)).reshape(-1)                 # ascending: key order
+        return self._rows(rows[torch.argsort(-self.support[rows], stable=True)][:int(n)])
+
+    def __add__(self, other):
+        if not isinstance(other, TemporalRuleTable):
+            return NotImplemented
+        if other.n_rel != self.n_rel or other.body.shape[1] != self.body.shape[1]:
+            raise ValueError("rule tables of different relation count or path length do not add (n_rel %d / %d, L %d / %d)"
+                             % (self.n_rel, other.n_rel, self.body.shape[1], other.body.shape[1]))
+        return _temporal_table(torch.cat([self.key(), other.key()], 0), torch.cat([self.support, other.support]),
+                               torch.cat([self.fixed, other.fixed]), self.n_rel)
+
+    def cpu(self):
+        return TemporalRuleTable(self.head.cpu(), self.body.cpu(), self.direction.cpu(), self.support.cpu(), self.fixed.cpu(), self.n_rel)
+
+    def format(self, id2rel=None):
+        """One string per rule, ``r3[past](x,z1) ^ r1(z1,y) -> r0(x,y)``: every step with its direction in brackets (none for
+        "any"), identity steps dropped, the head - a "now" fact - without a tag; ``id2rel`` names the relation ids (a sequence or
+        dict), else r<id>."""
+        name = lambda r: str(id2rel[r]) if id2rel is not None else "r%d" % r
+        out = []
+        for h, b, d in zip(self.head.tolist(), self.body.tolist(), self.direction.tolist()):
+            steps = [(r, k) for r, k in zip(b, d) if r != self.n_rel]
+            var = ["x"] + ["z%d" % i for i in range(1, len(steps))] + ["y"]
+            tag = lambda k: "" if k == DIRECTION_ANY else "[%s]" % engine.TRULE_DIRECTIONS[k]
+            lhs = " ^ ".join("%s%s(%s,%s)" % (name(r), tag(k), var[i], var[i + 1]) for i, (r, k) in enumerate(steps)) if steps else "x=y"
+            out.append("%s -> %s(x,y)" % (lhs, name(h)))
+        return out
+
+
+@dataclass
+class TemporalRuleQuality(_Quality):
+    """How the rules of a TemporalRuleTable hold in the quadruple graph (engine.trule_ground; csrc/trule_ground.hip): exact counts over
+    the pairs ((x, t), y) with (x, t) one of ``n_anchors`` anchors - an entity and a query time id - on the graph as built, a repeated
+    row counted once.  body(x, y | t): the steps lead from x to y through rows whose time stands to t as each step's direction says;
+    head(x, y | t): the graph has the row (x, head, y, t).
+
+    table           TemporalRuleTable  the rules, row by row
+    body_pairs      int64 [R]  pairs the body connects
+    hits            int64 [R]  ... that are facts of the head relation at the anchor's time too
+    pca_body_pairs  int64 [R]  pairs the body connects whose anchor has some fact of the head relation at its time
+    head_pairs      int64 [R]  pairs the head relation connects at the anchors' times
+    n_anchors       int        number of anchors
+
+    hits <= pca_body_pairs <= body_pairs and hits <= head_pairs.  confidence(), pca_confidence(), head_coverage(), top() and format()
+    are _Quality's.
+    """
+    table: TemporalRuleTable
+    body_pairs: torch.Tensor
+    hits: torch.Tensor
+    pca_body_pairs: torch.Tensor
+    head_pairs: torch.Tensor
+    n_anchors: int
+
+    def trivial(self):
+        """bool [R]: the body with its identity steps dropped is exactly [(head, now)]; such a rule has confidence 1 by construction."""
+        t = self.table
+        step = t.body != t.n_rel
+        return (step.sum(1) == 1) & ((t.body * step).sum(1) == t.head) & ((t.direction * step).sum(1) == 1)
+
+    def _tie_key(self):
+        return self.table.key()[:, 1:]
+
+    def cpu(self):
+        return TemporalRuleQuality(self.table.cpu(), self.body_pairs.cpu(), self.hits.cpu(), self.pca_body_pairs.cpu(),
+                                   self.head_pairs.cpu(), self.n_anchors)
 
 
 def rule_quality(model, table, mode="test", sources=None, scratch_bytes=engine.RULE_SCRATCH_BYTES):
@@ -564,6 +682,33 @@ def rules_from_paths(paths, q_rel, n_rel):
     key = torch.cat([q[:, None, None].expand(B, k, 1), paths.rels()], -1)[have]              # [P, 1 + L]
     fixed = torch.floor(paths.product[have] * 2.0 ** FRACTION_BITS + 0.5).long()
     return _table(key, torch.ones_like(fixed), fixed, n_rel)
+
+
+def _temporal_table(key, support, fixed, n_rel):
+    """TemporalRuleTable of rows key int64 [P, 1 + 2L] = (head, r_1, d_1, .., r_L, d_L), equal keys merged: _table on the wide key."""
+    t = _table(key, support, fixed, n_rel)
+    return TemporalRuleTable(t.head, t.body[:, 0::2].contiguous(), t.body[:, 1::2].contiguous(), t.support, t.fixed, n_rel)
+
+
+def temporal_rules_from_paths(paths, q_rel, n_rel):
+    """The TemporalRuleTable of a PathSet of a temporal r-digraph: every present path of row b counts once for the rule (q_rel[b],
+    its steps' (relation, direction)), the directions read from paths.digraph.direction() and an identity step (relation ``n_rel``)
+    written as direction 3; products rounded as rules_from_paths rounds them.  ``q_rel``: one query relation per row."""
+    B, k, L = paths.edge.shape
+    dev = paths.edge.device
+    q = torch.as_tensor(_ids(q_rel, "q_rel")).to(dev)
+    if q.numel() != B:
+        raise ValueError("temporal_rules_from_paths: %d query relations for %d rows" % (q.numel(), B))
+    n_rel = int(n_rel)
+    if n_rel < 1 or (B > 0 and (int(q.min()) < 0 or int(q.max()) > n_rel)):
+        raise ValueError("temporal_rules_from_paths: query relation id out of range (n_rel+1=%d)" % (n_rel + 1))
+    rel = paths.rels()
+    d = paths._gather(paths.digraph.direction().long(), -1)
+    d = torch.where(rel == n_rel, torch.full_like(d, DIRECTION_ANY), d)
+    have = torch.arange(k, device=dev)[None, :] < paths.count.long()[:, None]                # [B, k]
+    key = torch.cat([q[:, None, None].expand(B, k, 1), torch.stack([rel, d], 3).reshape(B, k, 2 * L)], -1)[have]     # [P, 1 + 2L]
+    fixed = torch.floor(paths.product[have] * 2.0 ** FRACTION_BITS + 0.5).long()
+    return _temporal_table(key, torch.ones_like(fixed), fixed, n_rel)
 
 
 def rules(model, subs, rels, objs=None, k=1, mode="test", min_alpha=0.0):

@@ -410,8 +410,8 @@ class RED_GNN_trans(nn.Module):
         from them.  ``sources``: the distinct entity ids x the pairs (x, y) start from (None: every entity).  Exact integer counts from
         one HIP pass over the graph per chunk of rules (rg_rule_ground); they do not depend on ``scratch_bytes``, which bounds the
         bitmaps.  The counts are taken on that graph as built, so the facts of the split being scored are not in it.  ValueError if
-        ``table.n_rel`` is not the model's.  Returns an explain.RuleQuality (device tensors).  Static and inductive models only: a
-        temporal rule would have to say what it does with time."""
+        ``table.n_rel`` is not the model's.  Returns an explain.RuleQuality (device tensors).  Static and inductive models; the temporal
+        interpolation model has its own T_RED_GNN.rule_quality (temporal rules, rg_trule_ground)."""
         from . import explain as _explain
         return _explain.rule_quality(self, table, mode, sources, scratch_bytes)
 

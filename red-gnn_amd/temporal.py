@@ -12,7 +12,8 @@ attention_vis loop with .item() syncs (model_cuda.py:121-135,163-166,178-184) do
 device bitmap walk, and the per-edge work of a layer is one fused kernel (rg_tlayer_fwd) with the three direction linears
 hoisted per node / relation / |dt| (W(h + r + tau) = Wh + Wr + Wtau).  The attention_vis table itself - alpha sum and edge count per
 relation - is ``attention_profile`` (rg_tattn_profile; with the edge direction past / now / future as one more axis), the r-digraph the
-reference draws in model_cuda_rule_vis.py is ``explain`` (rg_texplain_*; every edge with its time id), and ``predict`` gives the
+reference draws in model_cuda_rule_vis.py is ``explain`` (rg_texplain_*; every edge with its time id), ``rules`` / ``rules_all`` count
+its best paths as temporal rules and ``rule_quality`` counts how those hold in the quadruple graph (rg_trule_ground), and ``predict`` gives the
 filtered top-k answers of (head, relation, time) queries (rg_topk).  The validation loop of main.py:125-183 is ``evaluate`` /
 ``rank_batch`` (evaluation.py, rg_segment_eval): loss, raw and filtered ranks from the visited pairs, without the [B, n_ent] matrix.
 Training: ``mode='train'`` drops the batch's own quadruples (``batch['example_idx']`` rows of ``params.graph``,
@@ -109,6 +110,51 @@ class T_RED_GNN(nn.Module):
         ``q_time`` set.  objs=None: the model's own top answer per row.  Edges with attention below min_alpha are left out."""
         from . import explain as _explain
         return _explain.explain_temporal(self, batch, objs, min_alpha)
+
+    def rules(self, batch, objs=None, k=1, min_alpha=0.0):
+        """The k best paths behind the answer of every query of ``batch`` counted as temporal rules: explain -> top_paths(k) ->
+        explain.TemporalRuleTable, one row per distinct (query relation, (relation, direction) of every step), the direction being
+        the forward's past / now / future of the step's edge against the query time and identity steps written as "any".  objs=None:
+        batch["tail"] where the batch has it, else the model's own top answer per row, as explain."""
+        from . import explain as _explain
+        if objs is None and "tail" in batch:
+            objs = batch["tail"]
+        rd = self.explain(batch, objs, min_alpha)
+        return _explain.temporal_rules_from_paths(rd.top_paths(k), batch["relation"], self.n_rel)
+
+    def rules_all(self, quads, k=1, batch_size=64):
+        """The rule tables of ``quads`` int [n, 4] = (head, rel, tail, time id), the layout of params.graph - each row a query with its
+        tail as the answer - walked in batches of ``batch_size`` rows and added (tables add exactly)."""
+        q = np.asarray(quads.detach().cpu().numpy() if torch.is_tensor(quads) else quads)
+        if q.ndim != 2 or q.shape[1] != 4 or len(q) == 0 or q.dtype == np.bool_ or not np.issubdtype(q.dtype, np.integer):
+            raise ValueError("rules_all: quads must be a non-empty integer array [n, 4] = (head, rel, tail, time id) (got %s %s)"
+                             % (q.dtype, q.shape))
+        if isinstance(batch_size, (bool, np.bool_)) or not isinstance(batch_size, (int, np.integer)) or batch_size < 1:
+            raise ValueError("rules_all: batch_size must be a positive integer (got %r)" % (batch_size,))
+        table = None
+        for lo in range(0, len(q), int(batch_size)):
+            part = q[lo:lo + int(batch_size)]
+            t = self.rules({"head": part[:, 0], "relation": part[:, 1], "time": part[:, 3]}, part[:, 2], k=k)
+            table = t if table is None else table + t
+        return table
+
+    def rule_quality(self, table, anchors=None, scratch_bytes=engine.RULE_SCRATCH_BYTES):
+        """How the rules of ``table`` (an explain.TemporalRuleTable) hold in the full quadruple graph, the one explain walks:
+        explain.TemporalRuleQuality with the exact counts body_pairs, hits, pca_body_pairs and head_pairs of every rule over the pairs
+        ((x, t), y), (x, t) an anchor - ``anchors`` int [S, 2] = (entity, time id), distinct; None: every (head, time) of the graph's
+        non-identity rows - counted in HIP (rg_trule_ground), independent of ``scratch_bytes``, which bounds the bitmaps of a chunk.
+
+        The counts are taken on the graph as built, so ``hits`` says how often a rule reproduces facts the graph already holds.  A
+        table mined from quadruples that are in the graph (the training set) contains, for each of them, the trivial rule "the fact
+        itself, now" with confidence 1 (``trivial()`` marks it): mine on held-out quadruples."""
+        from . import explain as _explain
+        if not isinstance(table, _explain.TemporalRuleTable):
+            raise ValueError("rule_quality: table must be an explain.TemporalRuleTable (got %s)" % type(table).__name__)
+        if table.n_rel != self.n_rel:
+            raise ValueError("rule_quality: the table has n_rel=%d, the model n_rel=%d" % (table.n_rel, self.n_rel))
+        counts = engine.trule_ground(self.graph, table.head, table.body, table.direction, anchors, scratch_bytes)
+        n_anchors = len(self.graph.default_anchors()) if anchors is None else int(len(anchors))
+        return _explain.TemporalRuleQuality(table, *(counts[:, c].contiguous() for c in range(4)), n_anchors)
 
     def attention_profile(self, batch, group="relation"):
         """Edge count and alpha sum per (query | query relation, hop, direction, edge relation) over the hop edges of the queries of
