@@ -502,6 +502,39 @@ int rg_rule_apply(const rg_graph* g, const int32_t* head, const int32_t* body, c
                   const int32_t* q_ptr, int32_t batch, const int64_t* slab, int64_t n_words, void* scratch, int32_t phases,
                   float* best, float* surv, int32_t* best_rule, int32_t* fired, void* stream);
 
+/* ---- temporal rule application: rg_rule_apply for the quadruple graph of the interpolation model (n_time != 0): which answers
+ * weighted temporal rules predict for queries (s, r, ?, t), and which rule is behind each; no counterpart in the reference.  The graph,
+ * the directions and body(x, y | t) are exactly those of rg_trule_ground: a step (r, d) admits a row (u, r, v, tau) for a query of time
+ * id t iff d == 3, or the forward's direction of tau - t is d (0 past, 1 now, 2 future); identity steps are ordinary steps.  The rules
+ * are (head[i], body[i][0..L-1], dir[i][0..L-1], weight[i]), i = 0..n_rules-1, head non-decreasing, weight fp32 in (0, 1] and miss[i] =
+ * fl32(1 - weight[i]) formed by the caller.  The queries are (sub[b], rel[b], time[b]), b = 0..batch-1, duplicates allowed.  Rule i
+ * fires for cell (b, y) iff head[i] == rel[b] and body_i(sub[b], y | time[b]).  The four outputs, fp32 / fp32 / int32 / int32
+ * [batch, n_ent] with row stride n_ent, are initialised by the caller (0 / 1 / -1 / 0) and folded exactly as in rg_rule_apply, in
+ * ascending i:
+ *   fired += 1;  surv = fl32(surv * miss[i]);  if (weight[i] > best) { best = weight[i]; best_rule = rule_base + i; }
+ * Every output is the same bit for bit in every run, for every grid and lane-group choice, and however the rules are cut into
+ * consecutive calls on one stream.
+ * The queries are given sorted stably by the key rel * n_time + time: q_sub int32 [batch] the subjects and q_row int32 [batch] the
+ * caller's row b, both in sorted order, and q_ptr int32 [n_rela_rows * n_time + 1], q_ptr[k] the first sorted position whose key is
+ * >= k (the last entry = batch).  Relation h owns the positions p0 = q_ptr[h * n_time] .. p1 = q_ptr[(h + 1) * n_time]: rule i of head
+ * h has S_i = p1 - p0 sources, W_i = ceil(S_i / 32) words per entity and two slabs of n_ent * W_i words at word slab[i] of the two
+ * halves of the scratch, slab int64 [n_rules + 1], n_words = slab[n_rules], scratch of rg_rule_apply_scratch_bytes(n_words) bytes -
+ * all as in rg_rule_apply.  Query times are never loaded: for an edge (u, v, tau) of the step's relation the columns it may move are
+ * now [q_ptr[h * n_time + tau] - p0, q_ptr[h * n_time + tau + 1] - p0), past from that upper bound to S_i, future from 0 to that lower
+ * bound, any [0, S_i); per hop |edges of r_l| * (words in range) words are read, masked at both ends and ORed with integer atomics
+ * (csrc/trule_apply.hip).  phases: 1 = zero the scratch, seed and hop, 2 = aggregate, 3 = both.  All arrays are DEVICE arrays; n_hops
+ * in 1..32, n_rules <= 65535.  Errors: a NULL graph, a static graph (n_time == 0: use rg_rule_apply), a graph without its CSR by
+ * relation and edge times, n_rules / n_hops / batch / phases / rule_base / n_words out of range; n_rules == 0 or batch == 0 does
+ * nothing.  A relation id outside 0..n_rela_rows-1 is tested before any load and reads nothing, a direction outside 0..3 makes the step
+ * empty, an edge end or subject outside 0..n_ent-1, an edge time outside 0..n_time-1 and a q_row outside 0..batch-1 are skipped, q_ptr
+ * is indexed in int64 and its entries are clamped to 0..batch, a slab outside 0..n_words is left out and an empty range moves nothing;
+ * an unsorted head makes the result unspecified: nothing outside the graph's arrays, the scratch or the four outputs is touched
+ * whatever the arrays hold; the caller validates them (engine.py).  Allocates nothing, asynchronous on `stream`. */
+int rg_trule_apply(const rg_graph* g, const int32_t* head, const int32_t* body, const int32_t* dir, const float* weight,
+                   const float* miss, int32_t n_rules, int32_t n_hops, int32_t rule_base, const int32_t* q_sub, const int32_t* q_row,
+                   const int32_t* q_ptr, int32_t batch, const int64_t* slab, int64_t n_words, void* scratch, int32_t phases,
+                   float* best, float* surv, int32_t* best_rule, int32_t* fired, void* stream);
+
 /* rg_dense_fwd with the node count read on the device (after rg_frontier_expand_async): n_cap = capacity of the row buffers,
  * n_dev = rg_frontier_count_ptr() of the frontier whose newest level the rows belong to, n_hint = the row count the caller expects
  * (0 = unknown): it only sizes the grid, every row count up to n_cap is processed correctly. */

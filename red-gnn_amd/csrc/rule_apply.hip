@@ -7,7 +7,8 @@
 // per entity, and bit j of its bitmaps is the query at sorted position q_ptr[h] + j.  Its bitmaps are slabs of n_ent * W_i words at
 // word slab[i] of two regions of the scratch:
 //   cur, next : uint32 [n_words]       n_words = slab[n_rules]; bit j of word slab[i] + y * W_i + j / 32: source j reaches y under rule i
-// A rule without queries has no slab and every kernel leaves it at once.  Word indices are int64 throughout.
+// A rule without queries has no slab and every kernel leaves it at once.  Word indices are int64 throughout.  The queries, the slabs,
+// the seed and the aggregate live in rule_slabs.h, shared with trule_apply.hip (there q_ptr has n_time entries per relation, here one).
 //
 //   fill       the whole scratch is zeroed by rg::zero_async (a kernel: common.h says why no memset node)
 //   seed       bit j of cur_i[q_sub[q_ptr[h] + j]]
@@ -27,57 +28,11 @@
 // Bounds.  A relation id outside 0..n_rela_rows-1 is tested before any load and reads nothing; an edge end or subject outside
 // 0..n_ent-1 and a q_row outside 0..batch-1 are skipped; q_ptr entries are clamped to 0..batch; a slab that does not lie inside
 // 0..n_words is left out.  Whatever the arrays hold, nothing outside the graph, the scratch or the four outputs is touched.
-#include <algorithm>
-
-#include "common.h"
+#include "rule_slabs.h"
 
 namespace {
 
-constexpr int AT = 256;                           // threads per workgroup
-constexpr int APPLY_MAX_HOPS = 32;
-constexpr int APPLY_MAX_RULES = 65535;            // the rule is blockIdx.y
-constexpr size_t APPLY_ALIGN = 256;
-constexpr int64_t APPLY_MAX_WORDS = (int64_t)1 << 40;   // per region (4 TiB): keeps every byte count far inside size_t
-
-inline size_t region_bytes(int64_t n_words) { return rg::align_up((size_t)n_words * 4, APPLY_ALIGN); }
-
-struct Queries {
-  const int32_t* sub;    // [batch] subjects in sorted order
-  const int32_t* row;    // [batch] the caller's row of each sorted position
-  const int32_t* ptr;    // [n_rela_rows + 1] sorted positions by relation
-  int32_t batch, n_rela_rows;
-};
-
-struct Slab {
-  int64_t base;          // first word
-  int32_t p0, S, W;      // first sorted position, sources, words per entity
-};
-
-__device__ __forceinline__ int32_t clamp_pos(int32_t p, int32_t batch) { return p < 0 ? 0 : (p > batch ? batch : p); }
-
-// the sources and slab of a rule with head h; false: no such relation, no query of it, or a slab outside the scratch
-__device__ __forceinline__ bool rule_slab(const Queries& q, int32_t h, const int64_t* __restrict__ slab, int64_t i, int32_t n_ent,
-                                          int64_t n_words, Slab* out) {
-  if (h < 0 || h >= q.n_rela_rows) return false;
-  const int32_t p0 = clamp_pos(q.ptr[h], q.batch), p1 = clamp_pos(q.ptr[h + 1], q.batch);
-  if (p1 <= p0) return false;
-  const int32_t W = (p1 - p0 + 31) >> 5;
-  const int64_t base = slab[i];
-  if (base < 0 || base > n_words || (int64_t)n_ent * W > n_words - base) return false;
-  out->base = base; out->p0 = p0; out->S = p1 - p0; out->W = W;
-  return true;
-}
-
-__global__ __launch_bounds__(AT) void apply_seed_kernel(Queries q, const int32_t* __restrict__ head, const int64_t* __restrict__ slab,
-                                                        int32_t n_ent, int64_t n_words, uint32_t* __restrict__ cur) {
-  const int64_t i = blockIdx.y;
-  Slab sl;
-  if (!rule_slab(q, head[i], slab, i, n_ent, n_words, &sl)) return;
-  for (int32_t j = blockIdx.x * AT + threadIdx.x; j < sl.S; j += gridDim.x * AT) {
-    const uint32_t s = (uint32_t)q.sub[sl.p0 + j];
-    if (s < (uint32_t)n_ent) atomicOr(&cur[sl.base + (int64_t)s * sl.W + (j >> 5)], 1u << (j & 31));
-  }
-}
+using namespace rgapply;       // Queries, Slab, rule_slab, the seed and the aggregate (rule_slabs.h: shared with trule_apply.hip)
 
 // step l of every rule: to_i[v] |= from_i[u] over the edges (u, v) of relation body[i][l].  No barrier: a workgroup whose rule has no
 // query, no such relation, or fewer edges than the grid covers, leaves.
@@ -108,70 +63,10 @@ __global__ __launch_bounds__(AT) void apply_hop_kernel(const int32_t* __restrict
   }
 }
 
-// blockIdx.y (strided) is the sorted position p, the threads run along y: p's relation, rule range and slabs are uniform in the
-// workgroup, the four stores of a wave are 256 contiguous bytes each and so are its bitmap loads where W = 1.
-__global__ __launch_bounds__(AT) void apply_aggregate_kernel(Queries q, const int32_t* __restrict__ head, const float* __restrict__ weight,
-                                                             const float* __restrict__ miss, int32_t n_rules, int32_t rule_base,
-                                                             const int64_t* __restrict__ slab, int32_t n_ent, int64_t n_words,
-                                                             const uint32_t* __restrict__ cur, float* __restrict__ best,
-                                                             float* __restrict__ surv, int32_t* __restrict__ best_rule,
-                                                             int32_t* __restrict__ fired) {
-  const int32_t y = blockIdx.x * AT + threadIdx.x;
-  for (int32_t p = blockIdx.y; p < q.batch; p += gridDim.y) {
-    const int32_t row = q.row[p];
-    if ((uint32_t)row >= (uint32_t)q.batch) continue;
-    int32_t lo = 0, hi = q.n_rela_rows;                   // the relation h with q_ptr[h] <= p < q_ptr[h + 1]: the last h with q_ptr[h] <= p
-    while (hi - lo > 1) {
-      const int32_t mid = (lo + hi) >> 1;
-      if (clamp_pos(q.ptr[mid], q.batch) <= p) lo = mid; else hi = mid;
-    }
-    const int32_t h = lo;
-    int32_t a = 0, b = n_rules;                           // first rule with head >= h
-    while (a < b) {
-      const int32_t mid = (a + b) >> 1;
-      if (head[mid] < h) a = mid + 1; else b = mid;
-    }
-    if (a >= n_rules || head[a] != h || y >= n_ent) continue;
-    const int64_t cell = (int64_t)row * n_ent + y;
-    float c_best = 0.f, c_surv = 1.f;
-    int32_t c_rule = -1, c_fired = 0;
-    bool loaded = false;
-    Slab sl;                                              // p0, S and W are the relation's: only the base changes with the rule
-    if (!rule_slab(q, h, slab, a, n_ent, n_words, &sl)) continue;
-    const int32_t j = p - sl.p0;
-    if (j < 0 || j >= sl.S) continue;
-    const int64_t word = (int64_t)y * sl.W + (j >> 5), span = (int64_t)n_ent * sl.W;
-    for (int32_t i = a; i < n_rules && head[i] == h; ++i) {
-      const int64_t base = slab[i];
-      if (base < 0 || base > n_words || span > n_words - base) continue;
-      const uint32_t x = cur[base + word];
-      if (!((x >> (j & 31)) & 1u)) continue;
-      if (!loaded) {
-        c_best = best[cell]; c_surv = surv[cell]; c_rule = best_rule[cell]; c_fired = fired[cell];
-        loaded = true;
-      }
-      const float w = weight[i];
-      c_fired += 1;
-      c_surv = __fmul_rn(c_surv, miss[i]);
-      if (w > c_best) { c_best = w; c_rule = rule_base + i; }
-    }
-    if (loaded) {
-      best[cell] = c_best; surv[cell] = c_surv; best_rule[cell] = c_rule; fired[cell] = c_fired;
-    }
-  }
-}
-
-// blocks along x for `items` units of work at `per_block` a pass, a few passes each, with the rules in y
-unsigned grid_x(int64_t items, int64_t per_block, int32_t n_rules) {
-  const int64_t want = rg::ceil_div(std::max<int64_t>(items, 1), per_block * 8);
-  return (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, std::max<int64_t>(1, std::min<int64_t>(1024, 65536 / n_rules))));
-}
-
 }  // namespace
 
 extern "C" size_t rg_rule_apply_scratch_bytes(int64_t n_words) {
-  if (n_words < 1 || n_words > APPLY_MAX_WORDS) return 0;
-  return 2 * region_bytes(n_words);
+  return rgapply::scratch_bytes(n_words);
 }
 
 extern "C" int rg_rule_apply(const rg_graph* g, const int32_t* head, const int32_t* body, const float* weight, const float* miss,
@@ -194,14 +89,13 @@ extern "C" int rg_rule_apply(const rg_graph* g, const int32_t* head, const int32
   RG_CHECK(bytes != 0, "rg_rule_apply: n_words=%lld is outside the bitmaps' range 1..2^40", (long long)n_words);
   const hipStream_t s = (hipStream_t)stream;
   const int32_t n_ent = g->n_ent;
-  const Queries q{q_sub, q_row, q_ptr, batch, g->n_rela_rows};
+  const Queries q{q_sub, q_row, q_ptr, batch, g->n_rela_rows, 1};
   uint32_t* cur = static_cast<uint32_t*>(scratch);
   uint32_t* next = reinterpret_cast<uint32_t*>(static_cast<unsigned char*>(scratch) + bytes / 2);
   const size_t map_bytes = (size_t)n_words * 4;
 
   if (phases & 1) {
-    int32_t g_shift = 0;                                  // of the widest rule there can be: sizes the grid only
-    while (g_shift < 6 && (1 << g_shift) < rg::ceil_div(batch, 32)) ++g_shift;
+    const int32_t g_shift = group_shift(rg::ceil_div(batch, 32));      // of the widest rule there can be: sizes the grid only
     const dim3 hop_grid(grid_x(g->n_fact, AT >> g_shift, n_rules), n_rules);
     if (rg::zero_async(scratch, bytes, s)) return 1;
     hipLaunchKernelGGL(apply_seed_kernel, dim3(grid_x(batch, AT, n_rules), n_rules), dim3(AT), 0, s, q, head, slab, n_ent, n_words,

@@ -1331,7 +1331,7 @@ def rule_apply(graph, head, body, weight, subs, rels, scratch_bytes=RULE_SCRATCH
     no bit of the result depends on the budget.  Memory: 16 bytes per (query, entity) cell plus the scratch."""
     if getattr(graph, "n_time", 0):
         raise ValueError("rule_apply: temporal graph: rules are grounded on static and inductive graphs only "
-                         "(temporal rules are mined and grounded, trule_ground, but not applied to queries)")
+                         "(temporal rules, whose steps carry a direction, are applied by trule_apply)")
     if isinstance(scratch_bytes, (bool, np.bool_)) or not isinstance(scratch_bytes, (int, np.integer)) or scratch_bytes < 0:
         raise ValueError("rule_apply: scratch_bytes must be a non-negative integer (got %r)" % (scratch_bytes,))
     h, b, w, s, r = check_rule_apply(graph.n_ent, graph.n_rel, head, body, weight, subs, rels)
@@ -1377,4 +1377,101 @@ def rule_apply(graph, head, body, weight, subs, rels, scratch_bytes=RULE_SCRATCH
                 call(2)
                 ev[2].record()
                 RULE_APPLY_EVENTS.append((ev[0], ev[1], ev[2], r1 - r0, int(slabs[c][-1])))
+    return best, surv, best_rule, fired
+
+
+# tools/probe_trule_apply.py sets this to a list to collect (start, after seed + hops, end events, n_rules, n_words) per call of trule_apply
+TRULE_APPLY_EVENTS = None
+
+
+def check_trule_apply(graph, head, body, direction, weight, subs, rels, times):
+    """The host validation of trule_apply: (head int32 [R], body int32 [R, L], direction int32 [R, L], weight fp32 [R], subs int32 [B],
+    rels int32 [B], times int32 [B]) as contiguous numpy arrays, or ValueError.  ``graph`` needs n_ent, n_rela_rows and n_time; no device
+    is touched."""
+    who = "trule_apply"
+    if not int(getattr(graph, "n_time", 0) or 0):
+        raise ValueError("%s: static graph (no time ids): static rules are applied by rule_apply" % who)
+    h, b, d, _ = check_trules(graph, head, body, direction, np.zeros((0, 2), np.int64), who=who)
+    if h.size > 1 and (np.diff(h) < 0).any():
+        at = int(np.argmax(np.diff(h) < 0))
+        raise ValueError("%s: head must be non-decreasing (rule %d has head %d after %d)" % (who, at + 1, h[at + 1], h[at]))
+    w = weight.detach().cpu().numpy() if torch.is_tensor(weight) else np.asarray(weight)
+    if w.dtype.kind != "f" or w.ndim != 1 or w.shape[0] != h.shape[0]:
+        raise ValueError("%s: weight must be a float array [R] (got %s %s for %d rules)" % (who, w.dtype, w.shape, h.shape[0]))
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    if w.size and not (np.isfinite(w).all() and (w > 0).all() and (w <= 1).all()):
+        bad = int(np.argmax(~(np.isfinite(w) & (w > 0) & (w <= 1))))
+        raise ValueError("%s: weights must be finite and in (0, 1] as float32 (rule %d has %r)" % (who, bad, float(w[bad])))
+    s, r, t = _int_array(subs, "subs", who), _int_array(rels, "rels", who), _int_array(times, "times", who)
+    if s.ndim != 1 or r.shape != s.shape or t.shape != s.shape:
+        raise ValueError("%s: need one relation and one time per subject (got subs %s, rels %s, times %s)" % (who, s.shape, r.shape, t.shape))
+    n_ent, n_rows, n_time = int(graph.n_ent), int(graph.n_rela_rows), int(graph.n_time)
+    if s.size and (s.min() < 0 or s.max() >= n_ent):
+        raise ValueError("%s: subject id out of range 0..%d (got %d..%d)" % (who, n_ent - 1, s.min(), s.max()))
+    if r.size and (r.min() < 0 or r.max() >= n_rows):
+        raise ValueError("%s: query relation id out of range 0..%d (got %d..%d)" % (who, n_rows - 1, r.min(), r.max()))
+    if t.size and (t.min() < 0 or t.max() >= n_time):
+        raise ValueError("%s: query time id out of range 0..%d (got %d..%d)" % (who, n_time - 1, t.min(), t.max()))
+    as32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+    return h, b, d, w, as32(s), as32(r), as32(t)
+
+
+def trule_apply(graph, head, body, direction, weight, subs, rels, times, scratch_bytes=RULE_SCRATCH_BYTES):
+    """The temporal rules (head[i], (body[i], direction[i]), weight[i]) applied to the queries (subs[b], rels[b], ?, times[b]) on the
+    quadruple graph ``graph`` (rg_trule_apply; include/redgnn.h has the definition): the four device tensors [B, n_ent] of rule_apply -
+    ``best`` fp32, ``surv`` fp32, ``best_rule`` int32 and ``fired`` int32 - over the rules whose head is the query relation and whose
+    steps lead from the subject to the entity through rows whose time stands to the query's as each step's direction says (0 past,
+    1 now, 2 future, 3 any).  ``head`` non-decreasing, weights in (0, 1], relation ids the graph's (0..n_rela_rows-1), duplicate
+    queries allowed; all validated on the host (ValueError).  The queries are sorted stably by (relation, time id), q_ptr holds the
+    first sorted position of every (relation, time id), and the rules are cut into consecutive ranges whose bitmaps fit
+    ``scratch_bytes`` (rule_apply_chunking; one rule at least per call); the calls run in rule order on the current stream and carry
+    the four tensors, so no bit of the result depends on the budget.  Memory: 16 bytes per (query, entity) cell plus the scratch."""
+    if isinstance(scratch_bytes, (bool, np.bool_)) or not isinstance(scratch_bytes, (int, np.integer)) or scratch_bytes < 0:
+        raise ValueError("trule_apply: scratch_bytes must be a non-negative integer (got %r)" % (scratch_bytes,))
+    h, b, d, w, s, r, t = check_trule_apply(graph, head, body, direction, weight, subs, rels, times)
+    dev = _require_gpu(graph.device)
+    R, L, B, n_ent = h.shape[0], b.shape[1], s.shape[0], int(graph.n_ent)
+    best = torch.zeros((B, n_ent), dtype=torch.float32, device=dev)
+    surv = torch.ones((B, n_ent), dtype=torch.float32, device=dev)
+    best_rule = torch.full((B, n_ent), -1, dtype=torch.int32, device=dev)
+    fired = torch.zeros((B, n_ent), dtype=torch.int32, device=dev)
+    if R == 0 or B == 0:
+        return best, surv, best_rule, fired
+    n_rows, n_time = int(graph.n_rela_rows), int(graph.n_time)
+    key = r.astype(np.int64) * n_time + t
+    order = np.argsort(key, kind="stable")
+    q_ptr = np.searchsorted(key[order], np.arange(n_rows * n_time + 1)).astype(np.int32)
+    per_rel = np.diff(q_ptr[::n_time].astype(np.int64))                            # queries per relation
+    words = n_ent * ((per_rel[h] + 31) // 32)                                      # per rule
+    chunks = [(r0, r1) for r0, r1 in rule_apply_chunking(words, int(scratch_bytes)) if words[r0:r1].sum() > 0]
+    if not chunks:
+        return best, surv, best_rule, fired
+    slabs = [np.concatenate([[0], np.cumsum(words[r0:r1])]).astype(np.int64) for r0, r1 in chunks]
+    need = [rule_apply_scratch_bytes(sl[-1]) for sl in slabs]
+    if min(need) == 0:
+        raise ValueError("trule_apply: a rule's bitmap of %d words is beyond the bitmaps' range (fewer queries per call)" % max(words))
+    miss = (np.float32(1.0) - w).astype(np.float32)
+    to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    h_d, b_d, d_d, w_d, m_d, qs_d, qr_d, qp_d = (to(a) for a in (h, b, d, w, miss, s[order], order.astype(np.int32), q_ptr))
+    slab_d = to(np.concatenate(slabs))
+    off = np.concatenate([[0], np.cumsum([len(sl) for sl in slabs])])
+    p = _lib.ptr
+    with torch.cuda.device(dev):
+        scratch = torch.empty(max(need), dtype=torch.uint8, device=dev)
+        for c, (r0, r1) in enumerate(chunks):
+            def call(phases):
+                _lib.check(_lib.lib().rg_trule_apply(graph.handle, p(h_d[r0:r1]), p(b_d[r0:r1]), p(d_d[r0:r1]), p(w_d[r0:r1]),
+                                                     p(m_d[r0:r1]), r1 - r0, L, r0, p(qs_d), p(qr_d), p(qp_d), B,
+                                                     p(slab_d[off[c]:off[c + 1]]), int(slabs[c][-1]), p(scratch), phases, p(best),
+                                                     p(surv), p(best_rule), p(fired), _lib.stream_ptr()))
+            if TRULE_APPLY_EVENTS is None:
+                call(3)
+            else:
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+                ev[0].record()
+                call(1)
+                ev[1].record()
+                call(2)
+                ev[2].record()
+                TRULE_APPLY_EVENTS.append((ev[0], ev[1], ev[2], r1 - r0, int(slabs[c][-1])))
     return best, surv, best_rule, fired

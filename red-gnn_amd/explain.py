@@ -554,8 +554,9 @@ class RulePrediction:
 def rule_weights(quality, by="confidence", laplace=0.0, min_hits=1, drop_trivial=True):
     """(rows int64 [K], weight float32 [K]) on the host: the rules of ``quality`` kept for scoring, in table order, and their weights
     float32(hits / (den + laplace)) formed in float64, den = body_pairs (by="confidence") or pca_body_pairs ("pca_confidence").  Kept:
-    hits >= min_hits, weight > 0, and not trivial() unless ``drop_trivial`` is False."""
-    if not isinstance(quality, RuleQuality):
+    hits >= min_hits, weight > 0, and not trivial() unless ``drop_trivial`` is False.  ``quality``: a RuleQuality or a
+    TemporalRuleQuality (the same counts and trivial(); the drivers check which of the two they take)."""
+    if not isinstance(quality, (RuleQuality, TemporalRuleQuality)):
         raise ValueError("rule_scores: quality must be an explain.RuleQuality (got %s)" % type(quality).__name__)
     if by not in ("confidence", "pca_confidence"):
         raise ValueError("rule_scores: by must be 'confidence' or 'pca_confidence' (got %r)" % (by,))
@@ -576,6 +577,8 @@ def rule_weights(quality, by="confidence", laplace=0.0, min_hits=1, drop_trivial
 def rule_scores(model, quality, subs, rels, by="confidence", laplace=0.0, min_hits=1, drop_trivial=True, mode="test",
                 scratch_bytes=engine.RULE_SCRATCH_BYTES):
     """RED_GNN_trans.rule_scores (see there)."""
+    if not isinstance(quality, RuleQuality):
+        raise ValueError("rule_scores: quality must be an explain.RuleQuality (got %s)" % type(quality).__name__)
     rows, weight = rule_weights(quality, by, laplace, min_hits, drop_trivial)
     table = quality.table
     if table.n_rel != model.n_rel:
@@ -654,6 +657,122 @@ def split_rule_evaluate(base, quality=None, data="test", mine="valid", k=1, agg=
     mrr, h1, h10 = cal_performance(ranks.cpu().numpy())
     n = int(ranks.numel())
     return dict(mrr=float(mrr), h1=float(h1), h10=float(h10), n=n, coverage=covered / n)
+
+
+def _temporal_quality(model, quality, who):
+    if not isinstance(quality, TemporalRuleQuality):
+        raise ValueError("%s: quality must be an explain.TemporalRuleQuality (got %s)" % (who, type(quality).__name__))
+    if quality.table.n_rel != model.n_rel:
+        raise ValueError("%s: the table has n_rel=%d, the model n_rel=%d" % (who, quality.table.n_rel, model.n_rel))
+
+
+def _temporal_queries(model, batch, who):
+    """temporal.batch_ids, and three empty arrays for a batch without rows (rule_scores and rule_predict take one)."""
+    from .temporal import batch_ids
+    if all(k in batch and len(batch[k]) == 0 for k in ("head", "relation", "time")):
+        z = np.zeros(0, np.int64)
+        return z, z.copy(), z.copy()
+    return batch_ids(model, batch, who)
+
+
+def temporal_rule_scores(model, quality, batch, by="confidence", laplace=0.0, min_hits=1, drop_trivial=True,
+                         scratch_bytes=engine.RULE_SCRATCH_BYTES, who="rule_scores"):
+    """T_RED_GNN.rule_scores (see there)."""
+    _temporal_quality(model, quality, who)
+    rows, weight = rule_weights(quality, by, laplace, min_hits, drop_trivial)
+    heads, rels, times = _temporal_queries(model, batch, who)
+    t = quality.table
+    head, body, direction = (x.cpu().numpy()[rows] for x in (t.head, t.body, t.direction))
+    best, surv, best_rule, fired = engine.trule_apply(model.graph, head, body, direction, weight, heads, rels, times, scratch_bytes)
+    rows_d = torch.as_tensor(rows).to(best.device)
+    if rows_d.numel():                                   # kept-rule index -> table row
+        best_rule = torch.where(best_rule >= 0, rows_d.int()[best_rule.clamp(min=0).long()], best_rule)
+    return RuleScores(best, surv, best_rule, fired, rows_d)
+
+
+def temporal_rule_predict(model, quality, batch, k=10, agg="noisy_or", known=None, **kw):
+    """T_RED_GNN.rule_predict (see there)."""
+    from .prediction import K_MAX
+    _check_agg(agg, "rule_predict")
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= k <= K_MAX:
+        raise ValueError("rule_predict: k must be an integer in 1..%d (got %r)" % (K_MAX, k))
+    if known is not None and (not isinstance(known, (tuple, list)) or len(known) != 3):
+        raise ValueError("rule_predict: known must be the (keys, ptr, idx) triple of temporal_known_index")
+    rs = temporal_rule_scores(model, quality, batch, who="rule_predict", **kw)
+    heads, rels, times = _temporal_queries(model, batch, "rule_predict")
+    device = rs.best.device
+    B = rs.best.shape[0]
+    if B == 0:
+        z = lambda dt, fill: torch.full((0, int(k)), fill, dtype=dt, device=device)
+        return RulePrediction(z(torch.int64, -1), z(torch.float32, 0.0), z(torch.int64, -1), z(torch.int32, 0), quality.table)
+    q_key = None
+    if known is not None:
+        known = tuple(torch.as_tensor(x).to(device=device, dtype=dt).contiguous()
+                      for x, dt in zip(known, (torch.int64, torch.int64, torch.int32)))
+        q_key = torch.as_tensor((heads * (model.n_rel + 1) + rels) * model.n_time + times, dtype=torch.int64).to(device)
+    idx, val = engine.topk(rs.score(agg).contiguous(), int(k), q_key, known)
+    ids = idx.long()
+    at = ids.clamp(min=0)
+    rule = torch.where(ids >= 0, rs.best_rule.gather(1, at).long(), torch.full_like(ids, -1))
+    fired = torch.where(ids >= 0, rs.fired.gather(1, at), torch.zeros_like(idx))
+    return RulePrediction(ids, val, rule, fired, quality.table)
+
+
+def temporal_filter_lists(keys_of, tails, known):
+    """(ptr int32 [B + 1], idx int32) of the filter sets rg_rank takes: per query the sorted union of its tail and the tails the index
+    ``known`` = (keys, ptr, idx) numpy arrays (None: nothing) lists for its key.  A set that contains the answer."""
+    lists = []
+    for key, tail in zip(keys_of.tolist(), tails.tolist()):
+        mine = [tail]
+        if known is not None:
+            at = int(np.searchsorted(known[0], key))
+            if at < len(known[0]) and known[0][at] == key:
+                mine = np.union1d(known[2][known[1][at]:known[1][at + 1]], mine)
+        lists.append(np.asarray(mine, np.int32))
+    ptr = np.concatenate([[0], np.cumsum([len(x) for x in lists])]).astype(np.int32)
+    return ptr, np.concatenate(lists).astype(np.int32)
+
+
+def temporal_rule_evaluate(model, quads, quality=None, mine=None, k=1, agg="noisy_or", known=None, known_static=None, batch_size=256,
+                           **kw):
+    """T_RED_GNN.rule_evaluate (see there)."""
+    from .evaluation import KINDS, _check_known, check_quads
+    from .utils import cal_ranks_csr
+    who = "rule_evaluate"
+    _check_agg(agg, who)
+    if (quality is None) == (mine is None):
+        raise ValueError("%s: give exactly one of quality (a TemporalRuleQuality) and mine (quadruples to mine the rules from)" % who)
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= k <= engine.PATHS_MAX_K:
+        raise ValueError("%s: k must be an integer in 1..%d (got %r)" % (who, engine.PATHS_MAX_K, k))
+    q = check_quads(model, quads, batch_size, who)
+    _check_known(known, who, "known")
+    _check_known(known_static, who, "known_static")
+    if quality is None:
+        quality = model.rule_quality(model.rules_all(check_quads(model, mine, 1, who + " (mine)"), k))
+    _temporal_quality(model, quality, who)
+    host = lambda kn: None if kn is None else tuple(np.asarray(x.detach().cpu().numpy() if torch.is_tensor(x) else x) for x in kn)
+    known, known_static = host(known), host(known_static)
+    device = model.linear_classifier.weight.device
+    to = lambda a: torch.as_tensor(a).to(device)
+    ranks, covered = {sfx: [] for sfx in KINDS.values()}, 0
+    for lo in range(0, len(q), int(batch_size)):
+        b = q[lo:lo + int(batch_size)]
+        rs = temporal_rule_scores(model, quality, {"head": b[:, 0], "relation": b[:, 1], "time": b[:, 3]}, who=who, **kw)
+        score = rs.score(agg).contiguous()
+        tails = to(b[:, 2].astype(np.int32))
+        ans_ptr = torch.arange(len(b) + 1, dtype=torch.int32, device=device)
+        key_hr = b[:, 0] * (model.n_rel + 1) + b[:, 1]
+        for sfx, keys_of, index in (("", key_hr, None), ("_fil_t", key_hr * model.n_time + b[:, 3], known), ("_fil", key_hr, known_static)):
+            filt_ptr, filt_idx = temporal_filter_lists(keys_of, b[:, 2], index)
+            ranks[sfx].append(cal_ranks_csr(score, ans_ptr, tails, to(filt_ptr), to(filt_idx)).double())
+        covered += int((rs.fired.gather(1, tails.long()[:, None]) > 0).sum())
+    n = len(q)
+    out = {"n": n, "coverage": covered / n}
+    for sfx in KINDS.values():
+        rank = torch.cat(ranks[sfx]).cpu().numpy()
+        out["hits1" + sfx], out["hits3" + sfx], out["hits10" + sfx] = (float(np.sum(rank <= c) / n) for c in (1, 3, 10))
+        out["mrr" + sfx], out["mr" + sfx] = float(np.sum(1.0 / rank) / n), float(np.sum(rank) / n)
+    return out
 
 
 def _table(key, support, fixed, n_rel):

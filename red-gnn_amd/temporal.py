@@ -13,7 +13,8 @@ device bitmap walk, and the per-edge work of a layer is one fused kernel (rg_tla
 hoisted per node / relation / |dt| (W(h + r + tau) = Wh + Wr + Wtau).  The attention_vis table itself - alpha sum and edge count per
 relation - is ``attention_profile`` (rg_tattn_profile; with the edge direction past / now / future as one more axis), the r-digraph the
 reference draws in model_cuda_rule_vis.py is ``explain`` (rg_texplain_*; every edge with its time id), ``rules`` / ``rules_all`` count
-its best paths as temporal rules and ``rule_quality`` counts how those hold in the quadruple graph (rg_trule_ground), and ``predict`` gives the
+its best paths as temporal rules, ``rule_quality`` counts how those hold in the quadruple graph (rg_trule_ground), ``rule_scores`` /
+``rule_predict`` / ``rule_evaluate`` apply them to queries (rg_trule_apply: what the rules alone predict, and how well), and ``predict`` gives the
 filtered top-k answers of (head, relation, time) queries (rg_topk).  The validation loop of main.py:125-183 is ``evaluate`` /
 ``rank_batch`` (evaluation.py, rg_segment_eval): loss, raw and filtered ranks from the visited pairs, without the [B, n_ent] matrix.
 Training: ``mode='train'`` drops the batch's own quadruples (``batch['example_idx']`` rows of ``params.graph``,
@@ -155,6 +156,44 @@ class T_RED_GNN(nn.Module):
         counts = engine.trule_ground(self.graph, table.head, table.body, table.direction, anchors, scratch_bytes)
         n_anchors = len(self.graph.default_anchors()) if anchors is None else int(len(anchors))
         return _explain.TemporalRuleQuality(table, *(counts[:, c].contiguous() for c in range(4)), n_anchors)
+
+    def rule_scores(self, quality, batch, by="confidence", laplace=0.0, min_hits=1, drop_trivial=True,
+                    scratch_bytes=engine.RULE_SCRATCH_BYTES):
+        """What the rules of ``quality`` (an explain.TemporalRuleQuality, from rule_quality) predict for the queries (head, relation,
+        ?, time) of ``batch`` (the dict forward takes) on the full quadruple graph, in HIP (rg_trule_apply): explain.RuleScores with
+        best / surv / best_rule / fired [B, n_ent].  A rule fires for (b, y) iff its head is the query relation and its steps lead
+        from the head to y through rows whose time stands to the query's as each step's direction says.  The rules kept and their
+        weights are explain.rule_weights(quality, by, laplace, min_hits, drop_trivial); ``best_rule`` holds table rows.  No bit
+        depends on ``scratch_bytes``, which bounds the bitmaps of one call."""
+        from . import explain as _explain
+        return _explain.temporal_rule_scores(self, quality, batch, by, laplace, min_hits, drop_trivial, scratch_bytes)
+
+    def rule_predict(self, quality, batch, k=10, agg="noisy_or", known=None, **weights):
+        """The k best answers of every query of ``batch`` by rule score alone (agg "noisy_or": 1 - the product of the firing rules'
+        1 - weight; "max": the largest weight), selected in HIP (rg_topk): explain.RulePrediction, score descending then entity id
+        ascending, -1 / -inf / -1 / 0 past the end, ``rule`` the table row of each answer's best rule and ``table`` the
+        TemporalRuleTable, so format() prints the rule with its [past] / [now] / [future] tags.  ``known`` =
+        prediction.temporal_known_index(...): the tails it lists for a query's (head, relation, time) are left out.  ``weights``:
+        by, laplace, min_hits, drop_trivial, scratch_bytes of rule_scores.  A batch without rows gives [0, k] tensors."""
+        from . import explain as _explain
+        return _explain.temporal_rule_predict(self, quality, batch, k, agg, known, **weights)
+
+    def rule_evaluate(self, quads, quality=None, mine=None, k=1, agg="noisy_or", known=None, known_static=None, batch_size=256,
+                      **weights):
+        """Ranking metrics of the rules alone on ``quads`` int [n, 4] = (head, rel, tail, time id), next to evaluate: exactly one of
+        ``quality`` (a TemporalRuleQuality) and ``mine`` (int [m, 4] quadruples, e.g. the valid split: rules_all(mine, k) ->
+        rule_quality) is given.  Per batch of ``batch_size`` queries the rule scores (rule_scores, ``agg``) are ranked by rg_rank three
+        times - raw, with the time-aware filter ``known`` = prediction.temporal_known_index(...) and with the static filter
+        ``known_static`` = prediction.temporal_static_known_index(...); a query's filter set is its tail and the tails the index
+        lists for its key.  Returns a dict: n, coverage (the share of tails some rule reaches) and hits1 / hits3 / hits10 / mrr / mr
+        with the suffixes "" / _fil_t / _fil of evaluate, sums in float64.
+
+        One difference from evaluate: rg_rank's tie term counts every entity that scores exactly as the tail, filtered ones
+        included, where rg_segment_eval's eq_fil leaves the filtered ones out.  Every entity no rule reaches scores 0, so the
+        filtered rank of an unreached tail is larger here by half the number of filtered entities that are unreached too.  The
+        convention is BaseModel.rule_evaluate's."""
+        from . import explain as _explain
+        return _explain.temporal_rule_evaluate(self, quads, quality, mine, k, agg, known, known_static, batch_size, **weights)
 
     def attention_profile(self, batch, group="relation"):
         """Edge count and alpha sum per (query | query relation, hop, direction, edge relation) over the hop edges of the queries of
