@@ -473,6 +473,45 @@ int rg_trule_ground(const rg_graph* g, const int32_t* head, const int32_t* body,
                     const int32_t* anchor_ent, const int32_t* anchor_ptr, int32_t n_anchors, void* scratch, int64_t* counts,
                     void* stream);
 
+/* ---- extrapolation rule quality: rg_rule_ground for the one-graph layout of the forecasting model (extrapolation.T_RED_GNN); no
+ * counterpart in the reference.  The model's data: data[j] = (s, r, o, ts), j = 0..n_data-1, sorted by time; row_day[j] = ts //
+ * time_granularity; off = the model's time_offset_list, n_day = len(off); a query day t has the forward's row window [win_lo[t],
+ * win_hi[t]) = [off[max(t - 120, 0)], off[t]).  The window keeps the reference's quirks: off[t] is the index of the LAST row of day
+ * t - 1, so that row is left out, and off[t] is 0 after a day without rows, so a window is empty or reaches back to row 0.  The windows
+ * are therefore NOT monotone in t, and rows with a lag far above 120 occur.
+ * An extrapolation rule is a head relation h and L steps (r_l, [lag_lo_l, lag_hi_l)): every edge of the forecasting model lies in the
+ * past, so what tells one step from another is how far back the fact lies.  An anchor is a pair (x, t) of an entity and a query day.
+ * The graph is used as T_RED_GNN builds it: the self-loops first, relation id n_rel_true and time field n_data, then the data rows, each
+ * with its own row index as time field (g->n_time == n_data + 1).  A step (r, [lo, hi)) admits the data row j = (u, r, v) at day t iff
+ * win_lo[t] <= j < win_hi[t] and lo <= t - row_day[j] < hi; it admits the self-loop (u, n_rel_true, u) at day t iff lo <=
+ * min(t, loop_window) < hi, the lag the forward gives the self-loop (loop_window = 120).  "Any lag" is [0, INT32_MAX): every self-loop
+ * and every data row of the window.  body(x, y | t) holds iff there are z_0 = x, .., z_L = y with an admitted row (z_{l-1}, r_l, z_l)
+ * for every l (a repeated row counts once: the products are boolean); head(x, y | t) iff some data row (x, h, y) has row_day == t -
+ * the fact on the query day itself, which no window holds; a self-loop is never a head.  counts int64 [n_rules, 4] is ADDED to
+ * (caller-zeroed; calls over disjoint anchor sets sum), its columns body_pairs, hits, pca_body_pairs, head_pairs over ((x, t), y)
+ * exactly as rg_trule_ground defines them, so hits <= pca_body_pairs <= body_pairs and hits <= head_pairs.
+ * head int32 [n_rules]; body, lag_lo and lag_hi int32 [n_rules, n_hops]; row_day int32 [n_data]; win_lo and win_hi int32 [n_day]; the
+ * anchors are j = 0..n_anchors-1, distinct and sorted by day: anchor_ent int32 [n_anchors] holds their entities and anchor_ptr int32
+ * [n_day + 1] the first j whose day is >= t.  All arrays are DEVICE arrays; n_hops in 1..32, n_rules <= 65535.  The bitmaps of
+ * rg_rule_ground with anchors for columns (csrc/xrule_ground.hip): an edge walks its step's candidate days, [row_day[j] + lag_lo,
+ * min(row_day[j] + lag_hi, n_day)) for a data row (each day tested against its window), one range of days for a self-loop, and every
+ * run of consecutive passing days [a, b) moves the columns [anchor_ptr[a], anchor_ptr[b]), masked at both end words and ORed with
+ * integer atomics; the head pass moves the columns of day row_day[j] without a window test; then one counting pass.  OR and integer
+ * adds are order-independent, so every count is exact, the same in every run and the same however the rules and the sorted anchors
+ * are cut into calls.  scratch holds rg_rule_ground_scratch_bytes(n_ent, n_rules, n_anchors) bytes (that layout), 4-B aligned, and is
+ * zeroed by the call.  Errors: a NULL graph, a graph that is not the extrapolation layout (n_time != n_data + 1, or no CSR by relation
+ * with edge times), n_hops outside 1..32, n_rules > 65535, n_anchors < 0, n_day < 1, loop_window < 0; n_rules == 0 or n_anchors == 0
+ * does nothing.  A relation id outside 0..n_rela_rows-1 is tested before any load and reads nothing, lag_lo >= lag_hi makes the step
+ * empty, an edge end or anchor entity outside 0..n_ent-1, a row index outside 0..n_data and a row_day outside 0..n_day-1 are skipped,
+ * the days are formed in 64 bits and clamped to 0..n_day, anchor_ptr entries are clamped to 0..n_anchors and an empty range moves
+ * nothing: nothing outside the graph's arrays, row_day[0..n_data), win_lo / win_hi[0..n_day), the anchor arrays, the scratch and
+ * counts is touched whatever the id arrays hold; the caller validates them (engine.py).  Allocates nothing, asynchronous on `stream`. */
+int rg_xrule_ground(const rg_graph* g, const int32_t* head, const int32_t* body, const int32_t* lag_lo, const int32_t* lag_hi,
+                    int32_t n_rules, int32_t n_hops, const int32_t* row_day, int32_t n_data,
+                    const int32_t* win_lo, const int32_t* win_hi, int32_t n_day, int32_t loop_window,
+                    const int32_t* anchor_ent, const int32_t* anchor_ptr, int32_t n_anchors,
+                    void* scratch, int64_t* counts, void* stream);
+
 /* ---- rule application: which answers weighted rules predict for queries (s, r, ?), and which rule is behind each; no counterpart in
  * the reference.  The graph, A_r(x, y) and body(x, y) are exactly those of rg_rule_ground.  The rules are (head[i], body[i][0..L-1],
  * weight[i]), i = 0..n_rules-1, head non-decreasing, weight fp32 in (0, 1] and miss[i] = fl32(1 - weight[i]) formed by the caller (in

@@ -30,6 +30,7 @@ SYMBOLS = [
     "rg_rule_apply_scratch_bytes", "rg_rule_apply",
     "rg_trule_ground_scratch_bytes", "rg_trule_ground",
     "rg_trule_apply",
+    "rg_xrule_ground",
 ]
 
 _lib = None
@@ -150,6 +151,7 @@ def lib():
     L.rg_trule_ground_scratch_bytes.argtypes = [i32, i32, i32]
     L.rg_trule_ground_scratch_bytes.restype = sz
     L.rg_trule_ground.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, i32, vp, vp, vp]
+    L.rg_xrule_ground.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, vp, i32, i32, vp, vp, i32, vp, vp, vp]
     L.rg_trule_apply.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, i64, vp, i32, vp, vp, vp, vp, vp]
     _lib = L
     return L

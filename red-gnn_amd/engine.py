@@ -1262,6 +1262,122 @@ def trule_ground(graph, head, body, direction, anchors=None, scratch_bytes=RULE_
     return counts
 
 
+# tools/probe_xrule_quality.py sets this to a list to collect (start_event, end_event, n_rules, n_anchors) per chunk of xrule_ground
+XRULE_EVENTS = None
+XRULE_LOOP_WINDOW = 120              # extrapolation.WINDOW: the lag the forward gives the self-loop of a full window
+XRULE_ANY_HI = 2 ** 31 - 1           # the open end of a lag range: [0, XRULE_ANY_HI) is "any lag"
+
+
+def xrule_default_anchors(graph, row_day):
+    """int64 [S, 2] = (entity, day) sorted by (day, entity): the distinct (subject, day) pairs of the data rows of an extrapolation
+    graph (the rows whose time field, their data-row index, is below n_data = len(row_day)), read from the rows the graph was built
+    from - the anchors xrule_ground counts over when given none."""
+    rows = getattr(graph, "_rows", None)
+    if rows is None or rows[1] is not None:
+        raise ValueError("xrule_ground: the graph no longer holds its rows: pass anchors")
+    q, day = rows[0], np.asarray(row_day, dtype=np.int64).reshape(-1)
+    q = q[(q[:, 3] >= 0) & (q[:, 3] < len(day))]
+    key = np.unique(day[q[:, 3]] * int(graph.n_ent) + q[:, 0])
+    return np.stack([key % int(graph.n_ent), key // int(graph.n_ent)], 1)
+
+
+def check_xrules(graph, head, body, lag_lo, lag_hi, row_day, win_lo, win_hi, anchors=None, loop_window=XRULE_LOOP_WINDOW,
+                 who="xrule_ground"):
+    """The host validation of xrule_ground: (head int32 [R], body, lag_lo, lag_hi int32 [R, L], row_day int32 [n_data], win_lo, win_hi
+    int32 [n_day], anchors int64 [S, 2] = (entity, day) sorted by (day, entity)) as contiguous numpy arrays, or ValueError.  ``graph``
+    needs n_ent, n_rela_rows and n_time = n_data + 1 (and its rows where ``anchors`` is None); no device is touched."""
+    n_ent, n_rows, n_time = int(graph.n_ent), int(graph.n_rela_rows), int(getattr(graph, "n_time", 0) or 0)
+    h, b = _int_array(head, "head", who), _int_array(body, "body", who)
+    lo, hi = _int_array(lag_lo, "lag_lo", who), _int_array(lag_hi, "lag_hi", who)
+    day, w_lo, w_hi = _int_array(row_day, "row_day", who), _int_array(win_lo, "win_lo", who), _int_array(win_hi, "win_hi", who)
+    if h.ndim != 1 or b.ndim != 2 or b.shape[0] != h.shape[0] or lo.shape != b.shape or hi.shape != b.shape:
+        raise ValueError("%s: head must be [R], body, lag_lo and lag_hi [R, L] (got %s, %s, %s and %s)"
+                         % (who, h.shape, b.shape, lo.shape, hi.shape))
+    if not 1 <= b.shape[1] <= RULE_MAX_HOPS:
+        raise ValueError("%s: the body length %d is not in 1..%d" % (who, b.shape[1], RULE_MAX_HOPS))
+    if day.ndim != 1 or n_time != day.shape[0] + 1:
+        raise ValueError("%s: not the extrapolation layout: row_day must be [n_data] and the graph's n_time n_data + 1 (got %s and "
+                         "n_time=%d)" % (who, day.shape, n_time))
+    if w_lo.ndim != 1 or w_lo.shape != w_hi.shape or w_lo.shape[0] < 1:
+        raise ValueError("%s: win_lo and win_hi must be [n_day], n_day >= 1 (got %s and %s)" % (who, w_lo.shape, w_hi.shape))
+    n_day = w_lo.shape[0]
+    if isinstance(loop_window, (bool, np.bool_)) or not isinstance(loop_window, (int, np.integer)) or not 0 <= loop_window < 2 ** 31:
+        raise ValueError("%s: loop_window must be a non-negative integer (got %r)" % (who, loop_window))
+    if h.size and (min(h.min(), b.min()) < 0 or max(h.max(), b.max()) >= n_rows):
+        raise ValueError("%s: relation id out of range 0..%d (got %d..%d)"
+                         % (who, n_rows - 1, min(h.min(), b.min()), max(h.max(), b.max())))
+    if lo.size and (lo.min() < 0 or hi.max() > XRULE_ANY_HI or (lo >= hi).any()):
+        raise ValueError("%s: lag range out of order: need 0 <= lag_lo < lag_hi <= %d for every step (got lag_lo %d..%d, lag_hi %d..%d)"
+                         % (who, XRULE_ANY_HI, lo.min(), lo.max(), hi.min(), hi.max()))
+    if day.size and (day.min() < 0 or day.max() >= n_day):
+        raise ValueError("%s: row_day out of range 0..%d (got %d..%d)" % (who, n_day - 1, day.min(), day.max()))
+    if anchors is None:
+        a = xrule_default_anchors(graph, day)
+    else:
+        a = _int_array(anchors, "anchors", who)
+        if a.ndim != 2 or a.shape[1] != 2:
+            raise ValueError("%s: anchors must be [S, 2] = (entity, day) (got %s)" % (who, a.shape))
+        a = a.astype(np.int64)
+        if a.size and (a[:, 0].min() < 0 or a[:, 0].max() >= n_ent or a[:, 1].min() < 0 or a[:, 1].max() >= n_day):
+            raise ValueError("%s: anchor out of range (entity 0..%d, day 0..%d; got %d..%d and %d..%d)"
+                             % (who, n_ent - 1, n_day - 1, a[:, 0].min(), a[:, 0].max(), a[:, 1].min(), a[:, 1].max()))
+        key = np.sort(a[:, 1] * n_ent + a[:, 0])
+        if np.unique(key).size != key.size:
+            raise ValueError("%s: duplicate anchors (%d pairs, %d distinct)" % (who, key.size, np.unique(key).size))
+        a = np.stack([key % n_ent, key // n_ent], 1)
+    as32 = lambda x: np.ascontiguousarray(x, dtype=np.int32)
+    if w_lo.size and (min(w_lo.min(), w_hi.min()) < 0 or max(w_lo.max(), w_hi.max()) > day.shape[0]):
+        raise ValueError("%s: window bound out of range 0..%d (got %d..%d)"
+                         % (who, day.shape[0], min(w_lo.min(), w_hi.min()), max(w_lo.max(), w_hi.max())))
+    return as32(h), as32(b), as32(lo), as32(hi), as32(day), as32(w_lo), as32(w_hi), a
+
+
+def xrule_ground(graph, head, body, lag_lo, lag_hi, row_day, win_lo, win_hi, anchors=None, loop_window=XRULE_LOOP_WINDOW,
+                 scratch_bytes=RULE_SCRATCH_BYTES):
+    """The four counts of every extrapolation rule (head[i], (body[i], [lag_lo[i], lag_hi[i]))) on the one-graph layout ``graph`` of
+    extrapolation.T_RED_GNN (rg_xrule_ground; include/redgnn.h has the definition): int64 [R, 4] on the device = (body_pairs, hits,
+    pca_body_pairs, head_pairs) over the pairs ((x, t), y) with (x, t) in ``anchors``, int [S, 2] = (entity, query day), distinct;
+    None: xrule_default_anchors.  ``row_day`` [n_data] is the day of every data row, ``win_lo`` / ``win_hi`` [n_day] the forward's row
+    window of every query day, ``loop_window`` the lag a full window gives a self-loop.  A step admits a fact of its relation whose lag
+    against the query day lies in [lag_lo, lag_hi) and whose row lies in the day's window; [0, 2^31 - 1) is any lag.  Everything is
+    validated on the host (ValueError).  The anchors are sorted by (day, entity) and the work is cut into chunks of (rules x blocks of
+    consecutive anchors, a multiple of 32) whose bitmaps fit ``scratch_bytes``, as rule_chunking says; each block gets anchor_ptr =
+    clip(ptr - s0, 0, s1 - s0), ptr being the first sorted anchor of every day.  The scratch is allocated once and the counts are
+    integers added per chunk, so the result does not depend on the budget."""
+    if isinstance(scratch_bytes, (bool, np.bool_)) or not isinstance(scratch_bytes, (int, np.integer)) or scratch_bytes < 0:
+        raise ValueError("xrule_ground: scratch_bytes must be a non-negative integer (got %r)" % (scratch_bytes,))
+    h, b, lo, hi, day, w_lo, w_hi, a = check_xrules(graph, head, body, lag_lo, lag_hi, row_day, win_lo, win_hi, anchors, loop_window)
+    dev = _require_gpu(graph.device)
+    R, L, S, n_data, n_day = h.shape[0], b.shape[1], a.shape[0], day.shape[0], w_lo.shape[0]
+    counts = torch.zeros((R, 4), dtype=torch.int64, device=dev)
+    if R == 0 or S == 0:
+        return counts
+    n_r, s_c = rule_chunking(graph.n_ent, R, S, int(scratch_bytes))
+    ptr = np.searchsorted(a[:, 1], np.arange(n_day + 1))                     # the first sorted anchor whose day is >= t
+    starts = np.arange(0, S, s_c)
+    block_ptr = np.clip(ptr[None, :] - starts[:, None], 0, np.minimum(starts + s_c, S)[:, None] - starts[:, None])
+    h_d, b_d, lo_d, hi_d, day_d, wl_d, wh_d, e_d, p_d = (torch.from_numpy(np.ascontiguousarray(x, dtype=np.int32)).to(dev)
+                                                         for x in (h, b, lo, hi, day, w_lo, w_hi, a[:, 0], block_ptr))
+    p = _lib.ptr
+    with torch.cuda.device(dev):
+        scratch = torch.empty(rule_ground_scratch_bytes(graph.n_ent, min(n_r, R), min(s_c, S)), dtype=torch.uint8, device=dev)
+        for r0 in range(0, R, n_r):
+            r1 = min(r0 + n_r, R)
+            for k, s0 in enumerate(starts.tolist()):
+                s1 = min(s0 + s_c, S)
+                if XRULE_EVENTS is not None:
+                    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                    ev[0].record()
+                _lib.check(_lib.lib().rg_xrule_ground(graph.handle, p(h_d[r0:r1]), p(b_d[r0:r1]), p(lo_d[r0:r1]), p(hi_d[r0:r1]),
+                                                      r1 - r0, L, p(day_d), n_data, p(wl_d), p(wh_d), n_day, int(loop_window),
+                                                      p(e_d[s0:s1]), p(p_d[k]), s1 - s0, p(scratch), p(counts[r0:r1]),
+                                                      _lib.stream_ptr()))
+                if XRULE_EVENTS is not None:
+                    ev[1].record()
+                    XRULE_EVENTS.append((ev[0], ev[1], r1 - r0, s1 - s0))
+    return counts
+
+
 RULE_APPLY_ALIGN = 256               # csrc/rule_apply.hip: APPLY_ALIGN
 RULE_APPLY_MAX_WORDS = 1 << 40       # ... APPLY_MAX_WORDS (words of one bitmap region)
 # tools/probe_rule_apply.py sets this to a list to collect (start, after seed + hops, end events, n_rules, n_words) per call of rule_apply

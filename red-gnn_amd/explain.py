@@ -20,7 +20,10 @@ quadruple graph per anchor (entity, query time id) (TemporalRuleQuality; engine.
 
 Temporal extrapolation (extrapolation.T_RED_GNN.explain, rg_xexplain_*): ``rd = model.explain(X, objs)`` with the batch object of
 forward; ``rd.data_row`` names the past fact behind every edge (-1: a self-loop, relation id n_rel), ``rd.time`` its day and
-``rd.lag()`` how many days before the query it lies.
+``rd.lag()`` how many days before the query it lies.  ``table = model.rules(X, objs, k=2)`` counts the best paths as lag-binned rules,
+steps (relation, lag bin) under the ``lag_edges`` of attention_profile with identity steps written as ANY (LagRuleTable), and
+``model.rule_quality(table)`` counts how they hold in the model's own data per anchor (entity, query day) under the forward's row
+windows (LagRuleQuality; engine.xrule_ground, csrc/xrule_ground.hip).
 """
 from dataclasses import dataclass
 
@@ -30,6 +33,7 @@ import torch
 from . import engine
 from .models import _pad4, pad_attn
 from .profile import FRACTION_BITS                       # sums in units of 2^-32, as the attention profile's
+from .profile import check_lag_edges, lag_labels
 
 
 @dataclass
@@ -466,6 +470,131 @@ class TemporalRuleQuality(_Quality):
                                    self.head_pairs.cpu(), self.n_anchors)
 
 
+@dataclass
+class LagRuleTable:
+    """Paths of the extrapolation model counted as rules: one row per distinct (query relation, (r_1, b_1), .., (r_L, b_L)), sorted
+    by that key.  Every edge of the forecasting model lies in the past, so a step is told apart by how far back its fact lies: b is the
+    bin of the edge's lag in days (RDigraph.lag(): query day minus the edge's day) under ``lag_edges``, the bins of profile.lag_bins
+    and of attention_profile; bin len(lag_edges) + 1 is ANY.  An identity step (relation id n_rel) is always written as ANY, so a rule
+    does not split by where its padding fell.
+
+    head       int64 [R]      the query relation
+    body       int64 [R, L]   the relations of the steps
+    lag_bin    int64 [R, L]   their lag bins, 0..len(lag_edges) + 1
+    support    int64 [R]      paths counted
+    fixed      int64 [R]      the sum of their alpha products in units of 2^-32, each path rounded once: tables add exactly
+    lag_edges  tuple          the first day of every lag bin but the first (profile.check_lag_edges)
+    n_rel      int            the identity's relation id: the model's n_rel_true (extrapolation.T_RED_GNN.n_rel is one more)
+    """
+    head: torch.Tensor
+    body: torch.Tensor
+    lag_bin: torch.Tensor
+    support: torch.Tensor
+    fixed: torch.Tensor
+    lag_edges: tuple
+    n_rel: int
+
+    product_sum = RuleTable.product_sum
+    mean = RuleTable.mean
+
+    def __post_init__(self):
+        self.lag_edges = check_lag_edges(self.lag_edges)
+
+    @property
+    def any_bin(self):
+        """The bin id that stands for any lag: len(lag_edges) + 1."""
+        return len(self.lag_edges) + 1
+
+    def _rows(self, rows):
+        return LagRuleTable(self.head[rows], self.body[rows], self.lag_bin[rows], self.support[rows], self.fixed[rows], self.lag_edges,
+                            self.n_rel)
+
+    def key(self):
+        """int64 [R, 1 + 2L]: (head, r_1, b_1, .., r_L, b_L), the key the rows are sorted by."""
+        R, L = self.body.shape
+        return torch.cat([self.head[:, None], torch.stack([self.body, self.lag_bin], 2).reshape(R, 2 * L)], 1)
+
+    def top(self, q_rel, n):
+        """The n rules of query relation ``q_rel`` with the largest support (ties: the smaller key), as a table in that order."""
+        if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or n < 1:
+            raise ValueError("top: n must be a positive integer (got %r)" % (n,))
+        rows = torch.nonzero(self.head == int(q_rel)).reshape(-1)                 # ascending: key order
+        return self._rows(rows[torch.argsort(-self.support[rows], stable=True)][:int(n)])
+
+    def __add__(self, other):
+        if not isinstance(other, LagRuleTable):
+            return NotImplemented
+        if other.n_rel != self.n_rel or other.body.shape[1] != self.body.shape[1] or other.lag_edges != self.lag_edges:
+            raise ValueError("rule tables of different relation count, path length or lag edges do not add (n_rel %d / %d, L %d / %d, "
+                             "lag_edges %r / %r)" % (self.n_rel, other.n_rel, self.body.shape[1], other.body.shape[1], self.lag_edges,
+                                                     other.lag_edges))
+        return _lag_table(torch.cat([self.key(), other.key()], 0), torch.cat([self.support, other.support]),
+                          torch.cat([self.fixed, other.fixed]), self.lag_edges, self.n_rel)
+
+    def cpu(self):
+        return LagRuleTable(self.head.cpu(), self.body.cpu(), self.lag_bin.cpu(), self.support.cpu(), self.fixed.cpu(), self.lag_edges,
+                            self.n_rel)
+
+    def lag_ranges(self):
+        """(lag_lo, lag_hi) int64 [R, L]: the days [lag_lo, lag_hi) of every step's bin, as engine.xrule_ground takes them.  The
+        last bin's hi and ANY's hi are 2^31 - 1; ANY starts at 0."""
+        first = torch.tensor((0,) + self.lag_edges + (0,), dtype=torch.int64, device=self.lag_bin.device)
+        last = torch.tensor(self.lag_edges + (engine.XRULE_ANY_HI, engine.XRULE_ANY_HI), dtype=torch.int64, device=self.lag_bin.device)
+        return first[self.lag_bin], last[self.lag_bin]
+
+    def format(self, id2rel=None):
+        """One string per rule, ``r3[2-3d](x,z1) ^ r7[61-120d](z1,y) -> r1(x,y)``: every step with the days of its lag bin in
+        brackets, as AttentionProfile.lag_labels() names them (``[121+d]`` for the open last bin, none for ANY), identity steps
+        dropped, the head - a fact of the query day - without a tag; ``id2rel`` names the relation ids (a sequence or dict), else
+        r<id>."""
+        name = lambda r: str(id2rel[r]) if id2rel is not None else "r%d" % r
+        labels = ["[%d+d]" % a if b is None else ("[%dd]" % a if a == b else "[%d-%dd]" % (a, b)) for a, b in lag_labels(self.lag_edges)]
+        labels.append("")
+        out = []
+        for h, b, d in zip(self.head.tolist(), self.body.tolist(), self.lag_bin.tolist()):
+            steps = [(r, k) for r, k in zip(b, d) if r != self.n_rel]
+            var = ["x"] + ["z%d" % i for i in range(1, len(steps))] + ["y"]
+            lhs = " ^ ".join("%s%s(%s,%s)" % (name(r), labels[k], var[i], var[i + 1]) for i, (r, k) in enumerate(steps)) if steps else "x=y"
+            out.append("%s -> %s(x,y)" % (lhs, name(h)))
+        return out
+
+
+@dataclass
+class LagRuleQuality(_Quality):
+    """How the rules of a LagRuleTable hold in the forecasting model's own data (engine.xrule_ground; csrc/xrule_ground.hip): exact
+    counts over the pairs ((x, t), y) with (x, t) one of ``n_anchors`` anchors - an entity and a query day - a repeated row counted
+    once.  body(x, y | t): the steps lead from x to y through rows of day t's window whose lag lies in each step's bin; head(x, y | t):
+    the data hold a row (x, head, y) of day t itself.
+
+    table           LagRuleTable  the rules, row by row
+    body_pairs      int64 [R]  pairs the body connects
+    hits            int64 [R]  ... that are facts of the head relation on the anchor's day too
+    pca_body_pairs  int64 [R]  pairs the body connects whose anchor has some fact of the head relation on its day
+    head_pairs      int64 [R]  pairs the head relation connects on the anchors' days
+    n_anchors       int        number of anchors
+
+    hits <= pca_body_pairs <= body_pairs and hits <= head_pairs.  confidence(), pca_confidence(), head_coverage(), top() and format()
+    are _Quality's.
+    """
+    table: LagRuleTable
+    body_pairs: torch.Tensor
+    hits: torch.Tensor
+    pca_body_pairs: torch.Tensor
+    head_pairs: torch.Tensor
+    n_anchors: int
+
+    def trivial(self):
+        """bool [R]: all False - no window holds a fact of the query day, so no body restates its head."""
+        return torch.zeros(self.hits.shape[0], dtype=torch.bool, device=self.hits.device)
+
+    def _tie_key(self):
+        return self.table.key()[:, 1:]
+
+    def cpu(self):
+        return LagRuleQuality(self.table.cpu(), self.body_pairs.cpu(), self.hits.cpu(), self.pca_body_pairs.cpu(), self.head_pairs.cpu(),
+                              self.n_anchors)
+
+
 def rule_quality(model, table, mode="test", sources=None, scratch_bytes=engine.RULE_SCRATCH_BYTES):
     """RED_GNN_trans.rule_quality (see there)."""
     if not isinstance(table, RuleTable):
@@ -828,6 +957,36 @@ def temporal_rules_from_paths(paths, q_rel, n_rel):
     key = torch.cat([q[:, None, None].expand(B, k, 1), torch.stack([rel, d], 3).reshape(B, k, 2 * L)], -1)[have]     # [P, 1 + 2L]
     fixed = torch.floor(paths.product[have] * 2.0 ** FRACTION_BITS + 0.5).long()
     return _temporal_table(key, torch.ones_like(fixed), fixed, n_rel)
+
+
+def _lag_table(key, support, fixed, lag_edges, n_rel):
+    """LagRuleTable of rows key int64 [P, 1 + 2L] = (head, r_1, b_1, .., r_L, b_L), equal keys merged: _table on the wide key."""
+    t = _table(key, support, fixed, n_rel)
+    return LagRuleTable(t.head, t.body[:, 0::2].contiguous(), t.body[:, 1::2].contiguous(), t.support, t.fixed, lag_edges, n_rel)
+
+
+def lag_rules_from_paths(paths, q_rel, n_rel, lag_edges):
+    """The LagRuleTable of a PathSet of an extrapolation r-digraph: every present path of row b counts once for the rule (q_rel[b],
+    its steps' (relation, lag bin)), the lags read from paths.digraph.lag() and binned as profile.lag_bins bins them, an identity step
+    (relation ``n_rel``, the model's n_rel_true) written as ANY; products rounded as rules_from_paths rounds them.  ``q_rel``: one
+    query relation per row."""
+    B, k, L = paths.edge.shape
+    dev = paths.edge.device
+    edges = check_lag_edges(lag_edges)
+    q = torch.as_tensor(_ids(q_rel, "q_rel")).to(dev)
+    if q.numel() != B:
+        raise ValueError("lag_rules_from_paths: %d query relations for %d rows" % (q.numel(), B))
+    n_rel = int(n_rel)
+    if n_rel < 1 or (B > 0 and (int(q.min()) < 0 or int(q.max()) > n_rel)):
+        raise ValueError("lag_rules_from_paths: query relation id out of range (n_rel+1=%d)" % (n_rel + 1))
+    rel = paths.rels()
+    lag = paths._gather(paths.digraph.lag().long(), 0)
+    b = torch.bucketize(lag, torch.tensor(edges, dtype=torch.int64, device=dev), right=True)      # profile.lag_bins: side="right"
+    b = torch.where(rel == n_rel, torch.full_like(b, len(edges) + 1), b)
+    have = torch.arange(k, device=dev)[None, :] < paths.count.long()[:, None]                # [B, k]
+    key = torch.cat([q[:, None, None].expand(B, k, 1), torch.stack([rel, b], 3).reshape(B, k, 2 * L)], -1)[have]     # [P, 1 + 2L]
+    fixed = torch.floor(paths.product[have] * 2.0 ** FRACTION_BITS + 0.5).long()
+    return _lag_table(key, torch.ones_like(fixed), fixed, edges, n_rel)
 
 
 def rules(model, subs, rels, objs=None, k=1, mode="test", min_alpha=0.0):

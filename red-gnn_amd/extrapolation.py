@@ -22,7 +22,9 @@ reaches, known objects excluded, in one HIP launch on the forward's pairs (csrc/
 ``T_RED_GNN.explain(X, objs)`` the r-digraph of past facts behind a forecast, every edge with its attention and data row
 (csrc/explain.hip, rg_xexplain_count / rg_xexplain_emit; the driver is explain.explain_extrapolation).  ``T_RED_GNN.attention_profile``
 sums the attention of a batch's edges per hop, edge relation and lag bin (csrc/profile.hip, rg_xattn_profile; the driver is
-profile.attention_profile_extrapolation), ``attention_profile_all`` over a split.
+profile.attention_profile_extrapolation), ``attention_profile_all`` over a split.  ``T_RED_GNN.rules`` / ``rules_all`` count the k
+best paths behind forecasts as lag-binned rules (explain.LagRuleTable) and ``rule_quality`` counts how those hold in the model's own
+data, per (entity, query day) anchor under the forward's row windows (csrc/xrule_ground.hip, rg_xrule_ground).
 Without gradients the per-row products of the forward (attention inputs, W_past products, time table, classifier) run through
 rg_rows_linear (csrc/rows_linear.hip), whose rows do not depend on the row count: a query computes the same bits in every batch.
 
@@ -156,6 +158,7 @@ class T_RED_GNN(nn.Module):
         self._row_time_host = data[:, 3] // self.time_granularity
         self.register_buffer("row_time", torch.as_tensor(self._row_time_host, dtype=torch.int32), persistent=False)
         self._frontiers = engine.FrontierPool()
+        self._anchors = None                                   # default_anchors(), formed on first use
         self.last_stats = None
 
     def forward(self, X):
@@ -347,6 +350,64 @@ class T_RED_GNN(nn.Module):
             part = self.attention_profile(_Batch(b[:, 0], b[:, 1], b[:, 3]), "relation", lag_edges)
             prof = part if prof is None else prof + part
         return prof
+
+    def rules(self, X, objs=None, k=1, lag_edges=DEFAULT_LAG_EDGES, min_alpha=0.0):
+        """The k best paths behind the forecast of every row of X (as forward's) counted as lag-binned rules: explain -> top_paths(k)
+        -> explain.LagRuleTable, one row per distinct (query relation, (relation, lag bin) of every step).  The lag of a step is the
+        query day minus the day of its fact, binned by ``lag_edges`` as attention_profile bins it; identity steps are written as
+        ANY.  objs=None: each row's own top forecast, as explain."""
+        from . import explain as _explain
+        edges = _explain.check_lag_edges(lag_edges)
+        rd = self.explain(X, objs, min_alpha)
+        return _explain.lag_rules_from_paths(rd.top_paths(k), np.asarray(X.rel_idx), self.n_rel_true, edges)
+
+    def rules_all(self, queries, k=1, batch_size=64, lag_edges=DEFAULT_LAG_EDGES):
+        """The rule tables of ``queries`` int [n, 4] = (s, p, o, ts) (checked as evaluate's) - each row a query with its object as
+        the answer - walked in batches of ``batch_size`` rows and added (tables add exactly)."""
+        q = check_queries(self, queries, batch_size, "rules_all")
+        table = None
+        for lo in range(0, len(q), int(batch_size)):
+            b = q[lo:lo + int(batch_size)]
+            t = self.rules(_Batch(b[:, 0], b[:, 1], b[:, 3]), b[:, 2], k=k, lag_edges=lag_edges)
+            table = t if table is None else table + t
+        return table
+
+    def windows(self):
+        """(win_lo, win_hi) int64 [n_day]: the forward's row window [off[max(t - 120, 0)], off[t]) of every query day t, off being
+        time_offset_list (as _run forms it per query)."""
+        off = self.time_offset_list
+        t = np.arange(len(off))
+        return off[np.maximum(t - WINDOW, 0)], off[t]
+
+    def default_anchors(self):
+        """int64 [S, 2] = (entity, day) sorted by (day, entity): the distinct (subject, day) pairs of the data rows."""
+        if self._anchors is None:
+            self._anchors = engine.xrule_default_anchors(self.graph, self._row_time_host)
+        return self._anchors
+
+    def rule_quality(self, table, anchors=None, scratch_bytes=engine.RULE_SCRATCH_BYTES):
+        """How the rules of ``table`` (an explain.LagRuleTable) hold in the model's own data: explain.LagRuleQuality with the exact
+        counts body_pairs, hits, pca_body_pairs and head_pairs of every rule over the pairs ((x, t), y), (x, t) an anchor -
+        ``anchors`` int [S, 2] = (entity, query day), distinct; None: every (subject, day) of the data rows - counted in HIP
+        (rg_xrule_ground), independent of ``scratch_bytes``, which bounds the bitmaps of a chunk.
+
+        body_pairs: the (anchor, y) pairs the body connects through rows of day t's window - the forward's, with the reference's
+        offsets as they are - whose lag lies in each step's bin.  hits: those with a row (x, head, y) on day t itself.
+        pca_body_pairs: the body's pairs whose anchor has some head fact on day t.  head_pairs: the head facts of the anchors' days.
+        The counts are taken on the model's own data, so ``hits`` says how often a rule reproduces known facts of the query day, not
+        held-out ones.  No window holds a row of the query day, so no rule is trivial."""
+        from . import explain as _explain
+        if not isinstance(table, _explain.LagRuleTable):
+            raise ValueError("rule_quality: table must be an explain.LagRuleTable (got %s)" % type(table).__name__)
+        if table.n_rel != self.n_rel_true:
+            raise ValueError("rule_quality: the table has n_rel=%d, the model n_rel=%d" % (table.n_rel, self.n_rel_true))
+        if anchors is None:
+            anchors = self.default_anchors()
+        lag_lo, lag_hi = table.lag_ranges()
+        win_lo, win_hi = self.windows()
+        counts = engine.xrule_ground(self.graph, table.head, table.body, lag_lo, lag_hi, self._row_time_host, win_lo, win_hi, anchors,
+                                     WINDOW, scratch_bytes)
+        return _explain.LagRuleQuality(table, *(counts[:, c].contiguous() for c in range(4)), int(len(anchors)))
 
     def evaluate(self, queries, sp_index=None, spt_index=None, batch_size=64, return_ranks=False):
         """The validation loop of main.py:353-472 for a split: ``queries`` int [n, 4] = (s, p, o, ts), in batches of ``batch_size``

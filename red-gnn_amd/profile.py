@@ -59,6 +59,13 @@ def lag_bins(lag, edges):
     return np.searchsorted(np.asarray(edges, dtype=np.int64), lag, side="right")
 
 
+def lag_labels(edges):
+    """The lag bins of ``edges`` as (first day, last day) pairs, the last one (first day, None): open-ended.  (A first edge of 0
+    leaves bin 0 empty: (0, -1).)"""
+    first = (0,) + tuple(edges)
+    return [(a, b - 1) for a, b in zip(first, first[1:])] + [(first[-1], None)]
+
+
 @dataclass
 class AttentionProfile:
     """count int64 [G, L, 2R+1] and fixed int64 [G, L, 2R+1] (the sums of alpha in units of 2^-32), on the device that computed them.
@@ -156,8 +163,7 @@ class AttentionProfile:
         empty: (0, -1).)"""
         if "lag" not in self.axes or self.lag_edges is None:
             raise ValueError("lag_labels: this profile has no lag axis (axes %r)" % (self.axes,))
-        first = (0,) + tuple(self.lag_edges)
-        return [(a, b - 1) for a, b in zip(first, first[1:])] + [(first[-1], None)]
+        return lag_labels(self.lag_edges)
 
     def lag_share(self, row):
         """float64 [L, n_bins]: the share of each hop's attention mass (the sum of alpha over the edge relations) that row ``row`` gives
