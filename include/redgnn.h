@@ -80,6 +80,17 @@ int rg_graph_export_out_by_tail(const rg_graph* g, int32_t* rel_tail_host, int32
  * int32 [n_fact] beside in_head_rel (either may be NULL).  With them a test can name the CSR position of an edge whose (head, rel,
  * tail) repeats at several times.  An error on static graphs. */
 int rg_graph_export_time(const rg_graph* g, int32_t* out_time_host, int32_t* in_time_host);
+/* copy any other array of the graph back by name (tests), and its scalars.  Arrays, all of 32-bit words, as [rows, cols]:
+ *   rel_ptr [n_rela_rows+1], rel_ht [n_fact, 2] = {head, tail}, rel_tm [n_fact]       the CSR by relation (rel_tm: temporal graphs)
+ *   time_ptr [n_time+1], time_ht [n_fact, 2] = {head, tail}, time_rel [n_fact]         the CSR by time id (temporal graphs)
+ *   in_pk, out_pk, out_bt_pk uint32 [n_fact]          the packed entries beside in_head_rel, out_rel_tail and the out-list by tail
+ *   in_vr_rows, out_vr_rows, rel_vr_rows, time_vr_rows [n, 4] = {row id, first entry, length, slot or -1}: the virtual rows of the CSR by
+ *       tail, by head, by relation and by time id, sorted by length descending; *_vr_split [n_split, 4] = {row id, first slot, segments, 0}
+ * Sizes first: dims_out int64 [2] = {rows, cols} (may be NULL); an array this graph does not have (packed entries of a wide graph, the
+ * time arrays of a static one) gives rows = -1 and is no error, a name not in the list is one.  out_host (may be NULL) receives rows *
+ * cols words.  scalars_out int64 [15] (may be NULL) = n_fact, max_in_deg, max_out_deg, then n, n_split, n_slots of in_vr, out_vr, rel_vr
+ * and time_vr.  name may be NULL (scalars only). */
+int rg_graph_export_array(const rg_graph* g, const char* name, int64_t* dims_out, void* out_host, int64_t* scalars_out);
 
 /* ---- frontier expansion: replaces DataLoader.get_neighbors, load_data.py:106-131 ------------
  * A frontier keeps `n_levels` visited-set snapshots: level 0 = the query nodes, level k = after

@@ -20,7 +20,7 @@ SYMBOLS = [
     "rg_explain_scratch_bytes", "rg_explain_seed", "rg_explain_count", "rg_explain_emit", "rg_explain_gather",
     "rg_topk",
     "rg_attn_profile",
-    "rg_graph_export_time", "rg_texplain_count", "rg_texplain_emit", "rg_tattn_profile",
+    "rg_graph_export_time", "rg_graph_export_array", "rg_texplain_count", "rg_texplain_emit", "rg_tattn_profile",
     "rg_segment_rank", "rg_segment_topk",
     "rg_xexplain_count", "rg_xexplain_emit",
     "rg_xattn_profile", "rg_rows_linear",
@@ -129,6 +129,7 @@ def lib():
     L.rg_explain_gather.argtypes = [i64, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp]
     L.rg_attn_profile.argtypes = [vp, vp, i32, i32, i32, i64, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp]
     L.rg_graph_export_time.argtypes = [vp, vp, vp]
+    L.rg_graph_export_array.argtypes = [vp, C.c_char_p, vp, vp, vp]
     L.rg_texplain_count.argtypes = L.rg_explain_count.argtypes
     L.rg_texplain_emit.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, i32, C.c_float, vp, vp, vp, vp, vp]
     L.rg_tattn_profile.argtypes = [vp, vp, i32, i32, i32, i64, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp]

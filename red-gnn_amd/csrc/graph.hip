@@ -544,4 +544,34 @@ int rg_graph_export_packs(const rg_graph* g, int32_t* n_packs, int32_t* n_vrows,
   return 0;
 }
 
+int rg_graph_export_array(const rg_graph* g, const char* name, int64_t* dims, void* out, int64_t* scalars) {
+  RG_CHECK(g != nullptr, "rg_graph_export_array: graph is NULL");
+  if (scalars) {
+    const rg_vrows* vr[4] = {&g->in_vr, &g->out_vr, &g->rel_vr, &g->time_vr};
+    scalars[0] = g->n_fact; scalars[1] = g->max_in_deg; scalars[2] = g->max_out_deg;
+    for (int i = 0; i < 4; ++i) { scalars[3 + 3 * i] = vr[i]->n; scalars[4 + 3 * i] = vr[i]->n_split; scalars[5 + 3 * i] = vr[i]->n_slots; }
+  }
+  if (!name) return 0;
+  struct Entry { const char* name; const void* p; int64_t rows, cols; };
+  const int64_t nf = g->n_fact;
+  const Entry table[] = {
+      {"rel_ptr", g->rel_ptr, (int64_t)g->n_rela_rows + 1, 1}, {"rel_ht", g->rel_ht, nf, 2}, {"rel_tm", g->rel_tm, nf, 1},
+      {"time_ptr", g->time_ptr, (int64_t)g->n_time + 1, 1},     {"time_ht", g->time_ht, nf, 2}, {"time_rel", g->time_rel, nf, 1},
+      {"in_pk", g->in_pk, nf, 1},                               {"out_pk", g->out_pk, nf, 1},   {"out_bt_pk", g->out_bt_pk, nf, 1},
+      {"in_vr_rows", g->in_vr.rows, g->in_vr.n, 4},             {"in_vr_split", g->in_vr.split, g->in_vr.n_split, 4},
+      {"out_vr_rows", g->out_vr.rows, g->out_vr.n, 4},          {"out_vr_split", g->out_vr.split, g->out_vr.n_split, 4},
+      {"rel_vr_rows", g->rel_vr.rows, g->rel_vr.n, 4},          {"rel_vr_split", g->rel_vr.split, g->rel_vr.n_split, 4},
+      {"time_vr_rows", g->time_vr.rows, g->time_vr.n, 4},       {"time_vr_split", g->time_vr.split, g->time_vr.n_split, 4},
+  };
+  for (const Entry& e : table) {
+    if (strcmp(name, e.name) != 0) continue;
+    const bool present = e.p != nullptr;
+    if (dims) { dims[0] = present ? e.rows : -1; dims[1] = e.cols; }
+    if (out && present && e.rows > 0) RG_HIP(hipMemcpy(out, e.p, (size_t)(e.rows * e.cols) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return 0;
+  }
+  rg::set_error("rg_graph_export_array: the graph has no array named '%s'", name);
+  return 1;
+}
+
 }  // extern "C"

@@ -3,8 +3,10 @@
 // re-split 3:1, load_graph :76-81) without copying the triples to the host and back: rows (triples, inverses, identity), the
 // three CSRs (by tail in fact order; by head ordered by relation then fact order; by relation), packed entries, length-sorted
 // virtual rows and the word-parallel walk's packs are produced by stable radix sorts (hipCUB), scans and a few kernels; one
-// small read-back per CSR returns the counts that size the arena.  Every array equals the host builder's bit for bit (test:
-// test_device_graph_build_equals_host_build), including the packs: their best-fit placement is inherently sequential, so the 16-byte
+// small read-back per CSR returns the counts that size the arena.  Every array equals the host builder's bit for bit: tests/test_graph_gpu.py
+// compares every array and scalar of either builder (Graph.export_all) with the numpy reference of tests/graph_ref.py and checks the
+// packs against the definition of a correct packing; test_device_graph_build_equals_host_build compares the two builders' CSRs, in-row
+// virtual rows and packs directly.  The packs' best-fit placement is inherently sequential, so the 16-byte
 // descriptors of the length-sorted rows (0.6 MB for 40 k rows) visit the host for it - the triples and the CSR arrays never do.
 #include <hipcub/hipcub.hpp>
 

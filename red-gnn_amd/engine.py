@@ -111,6 +111,37 @@ class Graph:
         _lib.check(_lib.lib().rg_graph_export_out_by_tail(self.handle, _lib.ptr(rt), _lib.ptr(pos), None))
         return rt, pos
 
+    EXPORT_SCALARS = ("n_fact", "max_in_deg", "max_out_deg") + tuple("%s_vr_%s" % (d, f) for d in ("in", "out", "rel", "time")
+                                                                    for f in ("n", "n_split", "n_slots"))
+    EXPORT_ARRAYS = ("rel_ptr", "rel_ht", "rel_tm", "time_ptr", "time_ht", "time_rel", "in_pk", "out_pk", "out_bt_pk") + \
+        tuple("%s_vr_%s" % (d, f) for d in ("in", "out", "rel", "time") for f in ("rows", "split"))
+
+    def export_all(self):
+        """Every array and scalar of the graph as a dict of numpy arrays and ints — for tests.  What export (out_ptr, out_rel_tail,
+        in_ptr, in_head_rel), export_out_by_tail (out_bt_rel_tail, out_bt_pos), export_time (out_time, in_time) and export_packs
+        (pack_ent, pack, pack_rows; its vrows are in_vr_rows) give, the EXPORT_ARRAYS of rg_graph_export_array and its EXPORT_SCALARS.
+        An array the graph does not have (the out-list by tail of a temporal graph, the time arrays of a static one, packed entries
+        of a wide one) is None; a graph without packs has pack arrays of length 0."""
+        L = _lib.lib()
+        d = dict(zip(("out_ptr", "out_rel_tail", "in_ptr", "in_head_rel"), self.export()))
+        temporal = bool(getattr(self, "n_time", 0))
+        d["out_bt_rel_tail"], d["out_bt_pos"] = (None, None) if temporal else self.export_out_by_tail()
+        d["out_time"], d["in_time"] = self.export_time() if temporal else (None, None)
+        _, d["pack_ent"], d["pack"], d["pack_rows"] = self.export_packs()
+        scalars = np.zeros(len(self.EXPORT_SCALARS), np.int64)
+        _lib.check(L.rg_graph_export_array(self.handle, None, None, None, _lib.ptr(scalars)))
+        d.update((k, int(v)) for k, v in zip(self.EXPORT_SCALARS, scalars))
+        for name in self.EXPORT_ARRAYS:
+            dims = np.zeros(2, np.int64)
+            _lib.check(L.rg_graph_export_array(self.handle, name.encode(), _lib.ptr(dims), None, None))
+            if dims[0] < 0:
+                d[name] = None
+                continue
+            a = np.empty((int(dims[0]), int(dims[1])), np.uint32 if name.endswith("_pk") else np.int32)
+            _lib.check(L.rg_graph_export_array(self.handle, name.encode(), None, _lib.ptr(a), None))
+            d[name] = a.reshape(-1) if dims[1] == 1 else a
+        return d
+
     def close(self):
         if getattr(self, "handle", None) is not None and _lib._lib is not None:
             _lib.lib().rg_graph_destroy(self.handle)
