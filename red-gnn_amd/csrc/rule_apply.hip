@@ -20,10 +20,10 @@
 //              end: a cell no rule of the call reaches costs no output traffic.  No atomics: a cell has one thread, and the calls that
 //              carry the arrays from one range of rules to the next are ordered by the stream.
 //
-// The hop's inner loop is rule_ground.hip's rule_hop_kernel written once more (that kernel takes one W per call and collects `any`;
-// here W, the slab and the lane group follow the rule): the rule is blockIdx.y, a group of G lanes owns one edge and runs along w,
-// G the power of two >= W_i capped at 64, uniform within the workgroup.  OR is order-independent and the fold's order is the rule
-// order, so every output is the same bit for bit in every run and however the rules are cut into calls.
+// The hop's inner loop is the whole-row move of rule_bits.h, the one rule_ground.hip's rule_hop_kernel runs (that kernel takes one W per
+// call and collects `any`; here W, the slab and the lane group follow the rule): the rule is blockIdx.y, a group of G lanes owns one edge
+// and runs along w, G the power of two >= W_i capped at 64, uniform within the workgroup.  OR is order-independent and the fold's
+// order is the rule order, so every output is the same bit for bit in every run and however the rules are cut into calls.
 //
 // Bounds.  A relation id outside 0..n_rela_rows-1 is tested before any load and reads nothing; an edge end or subject outside
 // 0..n_ent-1 and a q_row outside 0..batch-1 are skipped; q_ptr entries are clamped to 0..batch; a slab that does not lie inside
@@ -36,7 +36,7 @@ using namespace rgapply;       // Queries, Slab, rule_slab, the seed and the agg
 
 // step l of every rule: to_i[v] |= from_i[u] over the edges (u, v) of relation body[i][l].  No barrier: a workgroup whose rule has no
 // query, no such relation, or fewer edges than the grid covers, leaves.
-__global__ __launch_bounds__(AT) void apply_hop_kernel(const int32_t* __restrict__ rel_ptr, const int2* __restrict__ rel_ht, Queries q,
+__global__ __launch_bounds__(RT) void apply_hop_kernel(const int32_t* __restrict__ rel_ptr, const int2* __restrict__ rel_ht, Queries q,
                                                        const int32_t* __restrict__ head, const int32_t* __restrict__ body,
                                                        int32_t n_hops, int32_t l, const int64_t* __restrict__ slab, int32_t n_ent,
                                                        int64_t n_words, const uint32_t* __restrict__ from, uint32_t* __restrict__ to) {
@@ -46,20 +46,12 @@ __global__ __launch_bounds__(AT) void apply_hop_kernel(const int32_t* __restrict
   Slab sl;
   if (!rule_slab(q, head[i], slab, i, n_ent, n_words, &sl)) return;
   const int32_t W = sl.W;
-  int32_t g_shift = 0;
-  while (g_shift < 6 && (1 << g_shift) < W) ++g_shift;
   const int64_t e0 = rel_ptr[r], e1 = rel_ptr[r + 1];
-  const int32_t G = 1 << g_shift, w0 = threadIdx.x & (G - 1);
-  const int64_t per_block = AT >> g_shift;
-  for (int64_t e = e0 + blockIdx.x * per_block + (threadIdx.x >> g_shift); e < e1; e += gridDim.x * per_block) {
+  const Lanes ln = hop_lanes(group_shift(W));
+  for (int64_t e = e0 + ln.first; e < e1; e += ln.step) {
     const int2 ht = rel_ht[e];
     if ((uint32_t)ht.x >= (uint32_t)n_ent || (uint32_t)ht.y >= (uint32_t)n_ent) continue;
-    const uint32_t* __restrict__ src = from + sl.base + (int64_t)ht.x * W;
-    uint32_t* dst = to + sl.base + (int64_t)ht.y * W;
-    for (int32_t w = w0; w < W; w += G) {
-      const uint32_t x = src[w];
-      if (x != 0) atomicOr(&dst[w], x);
-    }
+    move_row(from + sl.base + (int64_t)ht.x * W, to + sl.base + (int64_t)ht.y * W, nullptr, W, ln);
   }
 }
 
@@ -77,45 +69,15 @@ extern "C" int rg_rule_apply(const rg_graph* g, const int32_t* head, const int32
   RG_CHECK(g->n_time == 0, "rg_rule_apply: temporal graph (n_time=%d): rules are grounded on static and inductive graphs only",
            g->n_time);
   RG_CHECK(g->rel_ptr && g->rel_ht, "rg_rule_apply: the graph has no CSR by relation (rel_ptr is NULL)");
-  RG_CHECK(n_rules >= 0 && n_rules <= APPLY_MAX_RULES, "rg_rule_apply: n_rules=%d not in 0..%d", n_rules, APPLY_MAX_RULES);
-  RG_CHECK(n_hops >= 1 && n_hops <= APPLY_MAX_HOPS, "rg_rule_apply: n_hops=%d not in 1..%d", n_hops, APPLY_MAX_HOPS);
-  RG_CHECK(batch >= 0, "rg_rule_apply: batch=%d", batch);
-  RG_CHECK(phases >= 1 && phases <= 3, "rg_rule_apply: phases=%d not in 1..3 (1: seed and hops, 2: aggregate)", phases);
-  RG_CHECK(rule_base >= 0 && rule_base <= INT32_MAX - APPLY_MAX_RULES, "rg_rule_apply: rule_base=%d", rule_base);
+  if (apply_check("rg_rule_apply", n_rules, n_hops, batch, phases, rule_base)) return 1;
   if (n_rules == 0 || batch == 0) return 0;
-  RG_CHECK(head && body && weight && miss && q_sub && q_row && q_ptr && slab && scratch && best && surv && best_rule && fired,
-           "rg_rule_apply: NULL argument");
-  const size_t bytes = rg_rule_apply_scratch_bytes(n_words);
-  RG_CHECK(bytes != 0, "rg_rule_apply: n_words=%lld is outside the bitmaps' range 1..2^40", (long long)n_words);
-  const hipStream_t s = (hipStream_t)stream;
-  const int32_t n_ent = g->n_ent;
   const Queries q{q_sub, q_row, q_ptr, batch, g->n_rela_rows, 1};
-  uint32_t* cur = static_cast<uint32_t*>(scratch);
-  uint32_t* next = reinterpret_cast<uint32_t*>(static_cast<unsigned char*>(scratch) + bytes / 2);
-  const size_t map_bytes = (size_t)n_words * 4;
-
-  if (phases & 1) {
-    const int32_t g_shift = group_shift(rg::ceil_div(batch, 32));      // of the widest rule there can be: sizes the grid only
-    const dim3 hop_grid(grid_x(g->n_fact, AT >> g_shift, n_rules), n_rules);
-    if (rg::zero_async(scratch, bytes, s)) return 1;
-    hipLaunchKernelGGL(apply_seed_kernel, dim3(grid_x(batch, AT, n_rules), n_rules), dim3(AT), 0, s, q, head, slab, n_ent, n_words,
-                       cur);
-    RG_LAUNCH_CHECK();
-    for (int32_t l = 0; l < n_hops; ++l) {
-      hipLaunchKernelGGL(apply_hop_kernel, hop_grid, dim3(AT), 0, s, g->rel_ptr, g->rel_ht, q, head, body, n_hops, l, slab, n_ent,
-                         n_words, cur, next);
-      RG_LAUNCH_CHECK();
-      std::swap(cur, next);
-      if (l + 1 < n_hops && rg::zero_async(next, map_bytes, s)) return 1;
-    }
-  } else if (n_hops & 1) {
-    std::swap(cur, next);                                 // where phase 1 left the result: one swap per hop
-  }
-  if (phases & 2) {
-    const dim3 grid((unsigned)rg::ceil_div(n_ent, AT), (unsigned)std::min<int32_t>(batch, 65535));
-    hipLaunchKernelGGL(apply_aggregate_kernel, grid, dim3(AT), 0, s, q, head, weight, miss, n_rules, rule_base, slab, n_ent, n_words,
-                       cur, best, surv, best_rule, fired);
-    RG_LAUNCH_CHECK();
-  }
-  return 0;
+  const Rules r{head, weight, miss, n_rules, n_hops, rule_base, slab, n_words, best, surv, best_rule, fired};
+  const auto hop = [&](int32_t l, dim3 grid, hipStream_t s, const uint32_t* from, uint32_t* to) {
+    hipLaunchKernelGGL(apply_hop_kernel, grid, dim3(RT), 0, s, g->rel_ptr, g->rel_ht, q, head, body, n_hops, l, slab, g->n_ent, n_words,
+                       from, to);
+  };
+  return apply_chain("rg_rule_apply", g, q, r,
+                     head && body && weight && miss && q_sub && q_row && q_ptr && slab && scratch && best && surv && best_rule && fired,
+                     scratch, phases, stream, hop);
 }

@@ -27,7 +27,7 @@
 
 namespace {
 
-using namespace rgrule;      // the scratch layout, the seed and count kernels and the grid rule, shared with trule_ground.hip
+using namespace rgrule;      // the scratch layout, the seed and count kernels and the chain: shared with trule_ / xrule_ground.hip
 
 // one step of every rule: to[i][v] |= from[i][u] over the edges (u, v) of relation rel_of[i * rel_stride]; `any` (or NULL) collects
 // per word the bits that moved.  No barrier: a workgroup whose rule has no such relation, or fewer edges than the grid covers, leaves.
@@ -39,23 +39,13 @@ __global__ __launch_bounds__(RT) void rule_hop_kernel(const int32_t* __restrict_
   const int32_t r = rel_of[i * rel_stride];
   if (r < 0 || r >= n_rela_rows) return;
   const int64_t e0 = rel_ptr[r], e1 = rel_ptr[r + 1];
-  const int32_t G = 1 << g_shift, w0 = threadIdx.x & (G - 1);
-  const int64_t per_block = RT >> g_shift;
+  const Lanes ln = hop_lanes(g_shift);
   const int64_t base = i * n_ent * W;
   uint32_t* any_i = any ? any + i * W : nullptr;
-  for (int64_t e = e0 + blockIdx.x * per_block + (threadIdx.x >> g_shift); e < e1; e += gridDim.x * per_block) {
+  for (int64_t e = e0 + ln.first; e < e1; e += ln.step) {
     const int2 ht = rel_ht[e];
     if ((uint32_t)ht.x >= (uint32_t)n_ent || (uint32_t)ht.y >= (uint32_t)n_ent) continue;
-    const uint32_t* __restrict__ src = from + base + (int64_t)ht.x * W;
-    uint32_t* dst = to + base + (int64_t)ht.y * W;
-    for (int32_t w = w0; w < W; w += G) {
-      const uint32_t x = src[w];
-      if (x != 0) {
-        atomicOr(&dst[w], x);
-        // the plain read may be stale: bits only ever appear, so a stale word costs an atomic and never drops one
-        if (any_i && (any_i[w] & x) != x) atomicOr(&any_i[w], x);
-      }
-    }
+    move_row(from + base + (int64_t)ht.x * W, to + base + (int64_t)ht.y * W, any_i, W, ln);
   }
 }
 
@@ -71,38 +61,12 @@ extern "C" int rg_rule_ground(const rg_graph* g, const int32_t* head, const int3
   RG_CHECK(g->n_time == 0, "rg_rule_ground: temporal graph (n_time=%d): rules are grounded on static and inductive graphs only",
            g->n_time);
   RG_CHECK(g->rel_ptr && g->rel_ht, "rg_rule_ground: the graph has no CSR by relation (rel_ptr is NULL)");
-  RG_CHECK(n_rules >= 0 && n_rules <= RULE_MAX_RULES, "rg_rule_ground: n_rules=%d not in 0..%d", n_rules, RULE_MAX_RULES);
-  RG_CHECK(n_hops >= 1 && n_hops <= RULE_MAX_HOPS, "rg_rule_ground: n_hops=%d not in 1..%d", n_hops, RULE_MAX_HOPS);
-  RG_CHECK(n_sources >= 0, "rg_rule_ground: n_sources=%d", n_sources);
+  if (ground_check("rg_rule_ground", "sources", n_rules, n_hops, n_sources)) return 1;
   if (n_rules == 0 || n_sources == 0) return 0;
-  RG_CHECK(head && body && sources && scratch && counts, "rg_rule_ground: NULL argument");
-  const size_t bytes = rg_rule_ground_scratch_bytes(g->n_ent, n_rules, n_sources);
-  RG_CHECK(bytes != 0, "rg_rule_ground: %d rules x %d entities x %d sources is beyond the bitmaps' range", n_rules, g->n_ent,
-           n_sources);
-  const hipStream_t s = (hipStream_t)stream;
-  const int32_t n_ent = g->n_ent, W = (int32_t)rg::ceil_div(n_sources, 32);
-  const int32_t g_shift = group_shift(W);
-  Maps m;
-  carve(scratch, n_ent, n_rules, W, &m);
-  const size_t map_bytes = (size_t)((int64_t)n_rules * n_ent * W) * 4;
-  const dim3 hop_grid(grid_x(g->n_fact, RT >> g_shift, n_rules), n_rules);
-
-  if (rg::zero_async(scratch, bytes, s)) return 1;
-  hipLaunchKernelGGL(rule_seed_kernel, dim3(grid_x(n_sources, RT, n_rules), n_rules), dim3(RT), 0, s, sources, n_sources, n_ent, W,
-                     m.cur);
-  RG_LAUNCH_CHECK();
-  hipLaunchKernelGGL(rule_hop_kernel, hop_grid, dim3(RT), 0, s, g->rel_ptr, g->rel_ht, g->n_rela_rows, n_ent, head, 1, W, g_shift,
-                     m.cur, m.head, m.any);
-  RG_LAUNCH_CHECK();
-  for (int32_t l = 0; l < n_hops; ++l) {
-    hipLaunchKernelGGL(rule_hop_kernel, hop_grid, dim3(RT), 0, s, g->rel_ptr, g->rel_ht, g->n_rela_rows, n_ent, body + l, n_hops, W,
-                       g_shift, m.cur, m.next, (uint32_t*)nullptr);
-    RG_LAUNCH_CHECK();
-    std::swap(m.cur, m.next);
-    if (l + 1 < n_hops && rg::zero_async(m.next, map_bytes, s)) return 1;
-  }
-  hipLaunchKernelGGL(rule_count_kernel, dim3(grid_x((int64_t)n_ent * W, RT, n_rules), n_rules), dim3(RT), 0, s, n_ent, W, m.cur,
-                     m.head, m.any, reinterpret_cast<unsigned long long*>(counts));
-  RG_LAUNCH_CHECK();
-  return 0;
+  const auto hop = [&](const Step& t) {
+    hipLaunchKernelGGL(rule_hop_kernel, t.grid, dim3(RT), 0, t.s, g->rel_ptr, g->rel_ht, g->n_rela_rows, g->n_ent,
+                       t.l < 0 ? head : body + t.l, t.l < 0 ? 1 : n_hops, t.W, t.g_max, t.from, t.to, t.any);
+  };
+  return ground_chain("rg_rule_ground", "sources", g, n_rules, n_hops, sources, n_sources, head && body && sources && scratch && counts,
+                      scratch, counts, stream, hop);
 }

@@ -3,21 +3,14 @@
 // products on entity-major bitmaps; a call covers n_r rules and S columns, W = ceil(S / 32) words per entity, and the scratch holds
 //   cur, next, head : uint32 [n_r][n_ent][W]      bit j of word (i, y, j / 32): column j reaches y under rule i
 //   any             : uint32 [n_r][W]             bit j: column j has some fact of the rule's head relation
-// Word indices are int64 throughout (n_r * n_ent * W passes 2^31 on a mid-sized graph with all entities as sources).  Only the hop
-// kernels differ, and each file keeps its own.
+// Word indices are int64 throughout (n_r * n_ent * W passes 2^31 on a mid-sized graph with all entities as sources).  The chain itself
+// (ground_chain) is here too: a file adds its hop kernel - the step of its family around the moves of rule_bits.h - and the launch of it.
 #pragma once
-#include <algorithm>
-
-#include "common.h"
+#include "rule_bits.h"
 
 namespace rgrule {
+using namespace rgbits;      // the limits, grid_x, group_shift, the lane group and the moves, shared with rule_slabs.h
 namespace {
-
-constexpr int RT = 256;                           // threads per workgroup
-constexpr int RULE_MAX_HOPS = 32;
-constexpr int RULE_MAX_RULES = 65535;             // the rule is blockIdx.y
-constexpr size_t RULE_ALIGN = 256;
-constexpr int64_t RULE_MAX_WORDS = (int64_t)1 << 40;   // per bitmap (4 TiB): keeps every byte count far inside size_t
 
 struct Maps {
   uint32_t* cur;
@@ -100,17 +93,55 @@ __global__ __launch_bounds__(RT) void rule_count_kernel(int32_t n_ent, int32_t W
   }
 }
 
-// blocks along x for `items` units of work at `per_block` a pass, a few passes each, with the rules in y
-inline unsigned grid_x(int64_t items, int64_t per_block, int32_t n_rules) {
-  const int64_t want = rg::ceil_div(std::max<int64_t>(items, 1), per_block * 8);
-  return (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, std::max<int64_t>(1, std::min<int64_t>(1024, 65536 / n_rules))));
+// the argument checks every grounding entry point (`fn`: its name) makes alike, its columns being `cols` ("sources", "anchors"); 0 = fine
+inline int ground_check(const char* fn, const char* cols, int32_t n_rules, int32_t n_hops, int32_t n_cols) {
+  if (check_rule_counts(fn, n_rules, n_hops)) return 1;
+  RG_CHECK(n_cols >= 0, "%s: n_%s=%d", fn, cols, n_cols);
+  return 0;
 }
 
-// the power of two >= words, at most 64 (a wave), as a shift: the lanes that own one edge in a hop
-inline int32_t group_shift(int64_t words) {
-  int32_t s = 0;
-  while (s < 6 && (1 << s) < words) ++s;
-  return s;
+// what ground_chain hands a family's hop launch: one step of every rule of the call
+struct Step {
+  int32_t l;                 // the step, 0..n_hops-1; -1: the head pass, which collects `any`
+  int32_t W, g_max;          // words per entity, and the row-wide lane group group_shift(W) the grid is sized for
+  dim3 grid;
+  hipStream_t s;
+  const uint32_t* from;
+  uint32_t* to;
+  uint32_t* any;             // NULL in the body's steps
+};
+
+// A grounding call of n_rules >= 1 rules over S >= 1 columns, `col_ent` their entities: zero, seed, the head pass, the hops with swap
+// and re-zero, count.  `all_given`: none of the entry point's pointers is NULL.  hop(step) launches the family's hop kernel.
+template <class Hop>
+int ground_chain(const char* fn, const char* cols, const rg_graph* g, int32_t n_rules, int32_t n_hops, const int32_t* col_ent, int32_t S,
+                 bool all_given, void* scratch, int64_t* counts, void* stream, Hop hop) {
+  RG_CHECK(all_given, "%s: NULL argument", fn);
+  const size_t bytes = scratch_bytes(g->n_ent, n_rules, S);
+  RG_CHECK(bytes != 0, "%s: %d rules x %d entities x %d %s is beyond the bitmaps' range", fn, n_rules, g->n_ent, S, cols);
+  const hipStream_t s = (hipStream_t)stream;
+  const int32_t n_ent = g->n_ent, W = (int32_t)rg::ceil_div(S, 32);
+  const int32_t g_max = group_shift(W);
+  Maps m;
+  carve(scratch, n_ent, n_rules, W, &m);
+  const size_t map_bytes = (size_t)((int64_t)n_rules * n_ent * W) * 4;
+  const dim3 hop_grid(grid_x(g->n_fact, RT >> g_max, n_rules), n_rules);
+
+  if (rg::zero_async(scratch, bytes, s)) return 1;
+  hipLaunchKernelGGL(rule_seed_kernel, dim3(grid_x(S, RT, n_rules), n_rules), dim3(RT), 0, s, col_ent, S, n_ent, W, m.cur);
+  RG_LAUNCH_CHECK();
+  hop(Step{-1, W, g_max, hop_grid, s, m.cur, m.head, m.any});
+  RG_LAUNCH_CHECK();
+  for (int32_t l = 0; l < n_hops; ++l) {
+    hop(Step{l, W, g_max, hop_grid, s, m.cur, m.next, nullptr});
+    RG_LAUNCH_CHECK();
+    std::swap(m.cur, m.next);
+    if (l + 1 < n_hops && rg::zero_async(m.next, map_bytes, s)) return 1;
+  }
+  hipLaunchKernelGGL(rule_count_kernel, dim3(grid_x((int64_t)n_ent * W, RT, n_rules), n_rules), dim3(RT), 0, s, n_ent, W, m.cur,
+                     m.head, m.any, reinterpret_cast<unsigned long long*>(counts));
+  RG_LAUNCH_CHECK();
+  return 0;
 }
 
 }  // namespace

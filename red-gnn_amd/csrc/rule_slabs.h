@@ -1,7 +1,7 @@
 // What rule_apply.hip (static rules) and trule_apply.hip (temporal rules) share: the sorted queries, the per-rule slabs of the scratch,
 // the seed kernel, the aggregate kernel - the one place where the fold over the firing rules is written - and the grid rule.  Both apply
-// a rule as a chain of boolean products on entity-major bitmaps whose columns are only the queries of the rule's head relation; only the
-// hop kernels differ, and each file keeps its own.
+// a rule as a chain of boolean products on entity-major bitmaps whose columns are only the queries of the rule's head relation.  The chain
+// itself (apply_chain) is here too: a file adds its hop kernel - the step of its family around the moves of rule_bits.h - and the launch of it.
 //
 // The host sorts the queries (q_sub, q_row in sorted order) and gives q_ptr with `stride` entries per relation: relation h owns the
 // sorted positions q_ptr[h * stride] .. q_ptr[(h + 1) * stride].  stride = 1: sorted by relation (rg_rule_apply); stride = n_time: sorted
@@ -11,20 +11,13 @@
 //   cur, next : uint32 [n_words]       n_words = slab[n_rules]; bit j of word slab[i] + y * W_i + j / 32: source j reaches y under rule i
 // A rule without queries has no slab and every kernel leaves it at once.  Word indices are int64 throughout.
 #pragma once
-#include <algorithm>
-
-#include "common.h"
+#include "rule_bits.h"
 
 namespace rgapply {
+using namespace rgbits;      // the limits, grid_x, group_shift, the lane group and the moves, shared with rule_maps.h
 namespace {
 
-constexpr int AT = 256;                           // threads per workgroup
-constexpr int APPLY_MAX_HOPS = 32;
-constexpr int APPLY_MAX_RULES = 65535;            // the rule is blockIdx.y
-constexpr size_t APPLY_ALIGN = 256;
-constexpr int64_t APPLY_MAX_WORDS = (int64_t)1 << 40;   // per region (4 TiB): keeps every byte count far inside size_t
-
-inline size_t region_bytes(int64_t n_words) { return rg::align_up((size_t)n_words * 4, APPLY_ALIGN); }
+inline size_t region_bytes(int64_t n_words) { return rg::align_up((size_t)n_words * 4, RULE_ALIGN); }
 
 struct Queries {
   const int32_t* sub;    // [batch] subjects in sorted order
@@ -57,12 +50,12 @@ __device__ __forceinline__ bool rule_slab(const Queries& q, int32_t h, const int
   return true;
 }
 
-__global__ __launch_bounds__(AT) void apply_seed_kernel(Queries q, const int32_t* __restrict__ head, const int64_t* __restrict__ slab,
+__global__ __launch_bounds__(RT) void apply_seed_kernel(Queries q, const int32_t* __restrict__ head, const int64_t* __restrict__ slab,
                                                         int32_t n_ent, int64_t n_words, uint32_t* __restrict__ cur) {
   const int64_t i = blockIdx.y;
   Slab sl;
   if (!rule_slab(q, head[i], slab, i, n_ent, n_words, &sl)) return;
-  for (int32_t j = blockIdx.x * AT + threadIdx.x; j < sl.S; j += gridDim.x * AT) {
+  for (int32_t j = blockIdx.x * RT + threadIdx.x; j < sl.S; j += gridDim.x * RT) {
     const uint32_t s = (uint32_t)q.sub[sl.p0 + j];
     if (s < (uint32_t)n_ent) atomicOr(&cur[sl.base + (int64_t)s * sl.W + (j >> 5)], 1u << (j & 31));
   }
@@ -70,13 +63,13 @@ __global__ __launch_bounds__(AT) void apply_seed_kernel(Queries q, const int32_t
 
 // blockIdx.y (strided) is the sorted position p, the threads run along y: p's relation, rule range and slabs are uniform in the
 // workgroup, the four stores of a wave are 256 contiguous bytes each and so are its bitmap loads where W = 1.
-__global__ __launch_bounds__(AT) void apply_aggregate_kernel(Queries q, const int32_t* __restrict__ head, const float* __restrict__ weight,
+__global__ __launch_bounds__(RT) void apply_aggregate_kernel(Queries q, const int32_t* __restrict__ head, const float* __restrict__ weight,
                                                              const float* __restrict__ miss, int32_t n_rules, int32_t rule_base,
                                                              const int64_t* __restrict__ slab, int32_t n_ent, int64_t n_words,
                                                              const uint32_t* __restrict__ cur, float* __restrict__ best,
                                                              float* __restrict__ surv, int32_t* __restrict__ best_rule,
                                                              int32_t* __restrict__ fired) {
-  const int32_t y = blockIdx.x * AT + threadIdx.x;
+  const int32_t y = blockIdx.x * RT + threadIdx.x;
   for (int32_t p = blockIdx.y; p < q.batch; p += gridDim.y) {
     const int32_t row = q.row[p];
     if ((uint32_t)row >= (uint32_t)q.batch) continue;
@@ -121,23 +114,73 @@ __global__ __launch_bounds__(AT) void apply_aggregate_kernel(Queries q, const in
   }
 }
 
-// blocks along x for `items` units of work at `per_block` a pass, a few passes each, with the rules in y
-inline unsigned grid_x(int64_t items, int64_t per_block, int32_t n_rules) {
-  const int64_t want = rg::ceil_div(std::max<int64_t>(items, 1), per_block * 8);
-  return (unsigned)std::max<int64_t>(1, std::min<int64_t>(want, std::max<int64_t>(1, std::min<int64_t>(1024, 65536 / n_rules))));
-}
-
-// the power of two >= words, at most 64 (a wave), as a shift: the lanes that own one edge in a hop
-__host__ __device__ __forceinline__ int32_t group_shift(int64_t words) {
-  int32_t s = 0;
-  while (s < 6 && ((int64_t)1 << s) < words) ++s;
-  return s;
-}
-
 // the scratch of both entry points: two regions of n_words words; 0 where n_words is outside 1..2^40
 inline size_t scratch_bytes(int64_t n_words) {
-  if (n_words < 1 || n_words > APPLY_MAX_WORDS) return 0;
+  if (n_words < 1 || n_words > RULE_MAX_WORDS) return 0;
   return 2 * region_bytes(n_words);
+}
+
+// the argument checks both entry points (`fn`: its name) make alike; 0 = fine
+inline int apply_check(const char* fn, int32_t n_rules, int32_t n_hops, int32_t batch, int32_t phases, int32_t rule_base) {
+  if (check_rule_counts(fn, n_rules, n_hops)) return 1;
+  RG_CHECK(batch >= 0, "%s: batch=%d", fn, batch);
+  RG_CHECK(phases >= 1 && phases <= 3, "%s: phases=%d not in 1..3 (1: seed and hops, 2: aggregate)", fn, phases);
+  RG_CHECK(rule_base >= 0 && rule_base <= INT32_MAX - RULE_MAX_RULES, "%s: rule_base=%d", fn, rule_base);
+  return 0;
+}
+
+// what apply_chain needs beyond the queries: the rules of the call, their slabs and the four outputs
+struct Rules {
+  const int32_t* head;
+  const float* weight;
+  const float* miss;
+  int32_t n_rules, n_hops, rule_base;
+  const int64_t* slab;
+  int64_t n_words;
+  float* best;
+  float* surv;
+  int32_t* best_rule;
+  int32_t* fired;
+};
+
+// An application call of n_rules >= 1 rules to batch >= 1 queries.  Phase 1: zero, seed, the hops with swap and re-zero; phase 2: the
+// aggregate, which finds phase 1's result where the hops' swaps left it.  `all_given`: none of the entry point's pointers is NULL.
+// hop(l, grid, s, from, to) launches step l of the family's hop kernel on `grid`, sized from the widest rule there can be.
+template <class Hop>
+int apply_chain(const char* fn, const rg_graph* g, const Queries& q, const Rules& r, bool all_given, void* scratch, int32_t phases,
+                void* stream, Hop hop) {
+  RG_CHECK(all_given, "%s: NULL argument", fn);
+  const size_t bytes = scratch_bytes(r.n_words);
+  RG_CHECK(bytes != 0, "%s: n_words=%lld is outside the bitmaps' range 1..2^40", fn, (long long)r.n_words);
+  const hipStream_t s = (hipStream_t)stream;
+  const int32_t n_ent = g->n_ent, n_rules = r.n_rules;
+  uint32_t* cur = static_cast<uint32_t*>(scratch);
+  uint32_t* next = reinterpret_cast<uint32_t*>(static_cast<unsigned char*>(scratch) + bytes / 2);
+  const size_t map_bytes = (size_t)r.n_words * 4;
+
+  if (phases & 1) {
+    const int32_t g_shift = group_shift(rg::ceil_div(q.batch, 32));      // of the widest rule there can be: sizes the grid only
+    const dim3 hop_grid(grid_x(g->n_fact, RT >> g_shift, n_rules), n_rules);
+    if (rg::zero_async(scratch, bytes, s)) return 1;
+    hipLaunchKernelGGL(apply_seed_kernel, dim3(grid_x(q.batch, RT, n_rules), n_rules), dim3(RT), 0, s, q, r.head, r.slab, n_ent,
+                       r.n_words, cur);
+    RG_LAUNCH_CHECK();
+    for (int32_t l = 0; l < r.n_hops; ++l) {
+      hop(l, hop_grid, s, cur, next);
+      RG_LAUNCH_CHECK();
+      std::swap(cur, next);
+      if (l + 1 < r.n_hops && rg::zero_async(next, map_bytes, s)) return 1;
+    }
+  } else if (r.n_hops & 1) {
+    std::swap(cur, next);                                 // where phase 1 left the result: one swap per hop
+  }
+  if (phases & 2) {
+    const dim3 grid((unsigned)rg::ceil_div(n_ent, RT), (unsigned)std::min<int32_t>(q.batch, 65535));
+    hipLaunchKernelGGL(apply_aggregate_kernel, grid, dim3(RT), 0, s, q, r.head, r.weight, r.miss, n_rules, r.rule_base, r.slab, n_ent,
+                       r.n_words, cur, r.best, r.surv, r.best_rule, r.fired);
+    RG_LAUNCH_CHECK();
+  }
+  return 0;
 }
 
 }  // namespace

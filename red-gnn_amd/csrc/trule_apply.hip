@@ -42,7 +42,7 @@ using namespace rgapply;
 
 // step l of every rule: to_i[v] |= from_i[u] & range(tau, d) over the edges (u, v, tau) of relation body[i][l] under direction
 // dir[i][l].  No barrier: a workgroup whose rule has no query, no such relation or direction, or fewer edges than the grid covers, leaves.
-__global__ __launch_bounds__(AT) void tapply_hop_kernel(const int32_t* __restrict__ rel_ptr, const int2* __restrict__ rel_ht,
+__global__ __launch_bounds__(RT) void tapply_hop_kernel(const int32_t* __restrict__ rel_ptr, const int2* __restrict__ rel_ht,
                                                         const int32_t* __restrict__ rel_tm, Queries q, int32_t n_time,
                                                         const int32_t* __restrict__ head, const int32_t* __restrict__ body,
                                                         const int32_t* __restrict__ dir, int32_t n_hops, int32_t l,
@@ -64,9 +64,8 @@ __global__ __launch_bounds__(AT) void tapply_hop_kernel(const int32_t* __restric
 #endif
   const int32_t* __restrict__ t_ptr = q.ptr + (int64_t)h * n_time;     // [n_time + 1] entries of q_ptr belong to h
   const int64_t e0 = rel_ptr[r], e1 = rel_ptr[r + 1];
-  const int32_t G = 1 << g_shift, w0 = threadIdx.x & (G - 1);
-  const int64_t per_block = AT >> g_shift;
-  for (int64_t e = e0 + blockIdx.x * per_block + (threadIdx.x >> g_shift); e < e1; e += gridDim.x * per_block) {
+  const Lanes ln = hop_lanes(g_shift);
+  for (int64_t e = e0 + ln.first; e < e1; e += ln.step) {
     const int2 ht = rel_ht[e];
     const int32_t tau = rel_tm[e];
     if ((uint32_t)ht.x >= (uint32_t)n_ent || (uint32_t)ht.y >= (uint32_t)n_ent || (uint32_t)tau >= (uint32_t)n_time) continue;
@@ -78,17 +77,7 @@ __global__ __launch_bounds__(AT) void tapply_hop_kernel(const int32_t* __restric
       else if (d == 1) { lo = c0; hi = c1; }
       else hi = c0;
     }
-    if (lo >= hi) continue;
-    const int32_t w_lo = lo >> 5, w_hi = (hi - 1) >> 5;           // 0 <= w_lo <= w_hi < W: hi <= S
-    const uint32_t m_lo = 0xffffffffu << (lo & 31), m_hi = 0xffffffffu >> (31 - ((hi - 1) & 31));
-    const uint32_t* __restrict__ src = from + sl.base + (int64_t)ht.x * W;
-    uint32_t* dst = to + sl.base + (int64_t)ht.y * W;
-    for (int32_t w = w_lo + w0; w <= w_hi; w += G) {
-      uint32_t x = src[w];
-      if (w == w_lo) x &= m_lo;
-      if (w == w_hi) x &= m_hi;
-      if (x != 0) atomicOr(&dst[w], x);
-    }
+    if (lo < hi) move_range(from + sl.base + (int64_t)ht.x * W, to + sl.base + (int64_t)ht.y * W, nullptr, lo, hi, ln);
   }
 }
 
@@ -103,45 +92,16 @@ extern "C" int rg_trule_apply(const rg_graph* g, const int32_t* head, const int3
   RG_CHECK(g->n_time != 0, "rg_trule_apply: static graph (n_time=0): use rg_rule_apply");
   RG_CHECK(g->rel_ptr && g->rel_ht && g->rel_tm,
            "rg_trule_apply: the graph has no CSR by relation with edge times (rel_ptr / rel_ht / rel_tm is NULL)");
-  RG_CHECK(n_rules >= 0 && n_rules <= APPLY_MAX_RULES, "rg_trule_apply: n_rules=%d not in 0..%d", n_rules, APPLY_MAX_RULES);
-  RG_CHECK(n_hops >= 1 && n_hops <= APPLY_MAX_HOPS, "rg_trule_apply: n_hops=%d not in 1..%d", n_hops, APPLY_MAX_HOPS);
-  RG_CHECK(batch >= 0, "rg_trule_apply: batch=%d", batch);
-  RG_CHECK(phases >= 1 && phases <= 3, "rg_trule_apply: phases=%d not in 1..3 (1: seed and hops, 2: aggregate)", phases);
-  RG_CHECK(rule_base >= 0 && rule_base <= INT32_MAX - APPLY_MAX_RULES, "rg_trule_apply: rule_base=%d", rule_base);
+  if (apply_check("rg_trule_apply", n_rules, n_hops, batch, phases, rule_base)) return 1;
   if (n_rules == 0 || batch == 0) return 0;
-  RG_CHECK(head && body && dir && weight && miss && q_sub && q_row && q_ptr && slab && scratch && best && surv && best_rule && fired,
-           "rg_trule_apply: NULL argument");
-  const size_t bytes = rgapply::scratch_bytes(n_words);
-  RG_CHECK(bytes != 0, "rg_trule_apply: n_words=%lld is outside the bitmaps' range 1..2^40", (long long)n_words);
-  const hipStream_t s = (hipStream_t)stream;
-  const int32_t n_ent = g->n_ent, n_time = g->n_time;
-  const Queries q{q_sub, q_row, q_ptr, batch, g->n_rela_rows, n_time};
-  uint32_t* cur = static_cast<uint32_t*>(scratch);
-  uint32_t* next = reinterpret_cast<uint32_t*>(static_cast<unsigned char*>(scratch) + bytes / 2);
-  const size_t map_bytes = (size_t)n_words * 4;
-
-  if (phases & 1) {
-    const int32_t g_shift = group_shift(rg::ceil_div(batch, 32));      // of the widest rule there can be: sizes the grid only
-    const dim3 hop_grid(grid_x(g->n_fact, AT >> g_shift, n_rules), n_rules);
-    if (rg::zero_async(scratch, bytes, s)) return 1;
-    hipLaunchKernelGGL(apply_seed_kernel, dim3(grid_x(batch, AT, n_rules), n_rules), dim3(AT), 0, s, q, head, slab, n_ent, n_words,
-                       cur);
-    RG_LAUNCH_CHECK();
-    for (int32_t l = 0; l < n_hops; ++l) {
-      hipLaunchKernelGGL(tapply_hop_kernel, hop_grid, dim3(AT), 0, s, g->rel_ptr, g->rel_ht, g->rel_tm, q, n_time, head, body, dir,
-                         n_hops, l, slab, n_ent, n_words, cur, next);
-      RG_LAUNCH_CHECK();
-      std::swap(cur, next);
-      if (l + 1 < n_hops && rg::zero_async(next, map_bytes, s)) return 1;
-    }
-  } else if (n_hops & 1) {
-    std::swap(cur, next);                                 // where phase 1 left the result: one swap per hop
-  }
-  if (phases & 2) {
-    const dim3 grid((unsigned)rg::ceil_div(n_ent, AT), (unsigned)std::min<int32_t>(batch, 65535));
-    hipLaunchKernelGGL(apply_aggregate_kernel, grid, dim3(AT), 0, s, q, head, weight, miss, n_rules, rule_base, slab, n_ent, n_words,
-                       cur, best, surv, best_rule, fired);
-    RG_LAUNCH_CHECK();
-  }
-  return 0;
+  const Queries q{q_sub, q_row, q_ptr, batch, g->n_rela_rows, g->n_time};
+  const Rules r{head, weight, miss, n_rules, n_hops, rule_base, slab, n_words, best, surv, best_rule, fired};
+  const auto hop = [&](int32_t l, dim3 grid, hipStream_t s, const uint32_t* from, uint32_t* to) {
+    hipLaunchKernelGGL(tapply_hop_kernel, grid, dim3(RT), 0, s, g->rel_ptr, g->rel_ht, g->rel_tm, q, g->n_time, head, body, dir, n_hops, l,
+                       slab, g->n_ent, n_words, from, to);
+  };
+  return apply_chain("rg_trule_apply", g, q, r,
+                     head && body && dir && weight && miss && q_sub && q_row && q_ptr && slab && scratch && best && surv && best_rule &&
+                         fired,
+                     scratch, phases, stream, hop);
 }

@@ -57,11 +57,10 @@ __global__ __launch_bounds__(RT) void trule_hop_kernel(const int32_t* __restrict
   if (d < 0 || d > 3) return;
   const int64_t e0 = rel_ptr[r], e1 = rel_ptr[r + 1];
   const int32_t g_shift = d == 1 ? g_now : g_wide;
-  const int32_t G = 1 << g_shift, w0 = threadIdx.x & (G - 1);
-  const int64_t per_block = RT >> g_shift;
+  const Lanes ln = hop_lanes(g_shift);
   const int64_t base = i * n_ent * W;
   uint32_t* any_i = any ? any + i * W : nullptr;
-  for (int64_t e = e0 + blockIdx.x * per_block + (threadIdx.x >> g_shift); e < e1; e += gridDim.x * per_block) {
+  for (int64_t e = e0 + ln.first; e < e1; e += ln.step) {
     const int2 ht = rel_ht[e];
     const int32_t tau = rel_tm[e];
     if ((uint32_t)ht.x >= (uint32_t)n_ent || (uint32_t)ht.y >= (uint32_t)n_ent || (uint32_t)tau >= (uint32_t)n_time) continue;
@@ -72,21 +71,7 @@ __global__ __launch_bounds__(RT) void trule_hop_kernel(const int32_t* __restrict
       else if (d == 1) { lo = p0; hi = p1; }
       else hi = p0;
     }
-    if (lo >= hi) continue;
-    const int32_t w_lo = lo >> 5, w_hi = (hi - 1) >> 5;           // 0 <= w_lo <= w_hi < W: hi <= S
-    const uint32_t m_lo = 0xffffffffu << (lo & 31), m_hi = 0xffffffffu >> (31 - ((hi - 1) & 31));
-    const uint32_t* __restrict__ src = from + base + (int64_t)ht.x * W;
-    uint32_t* dst = to + base + (int64_t)ht.y * W;
-    for (int32_t w = w_lo + w0; w <= w_hi; w += G) {
-      uint32_t x = src[w];
-      if (w == w_lo) x &= m_lo;
-      if (w == w_hi) x &= m_hi;
-      if (x != 0) {
-        atomicOr(&dst[w], x);
-        // the plain read may be stale: bits only ever appear, so a stale word costs an atomic and never drops one
-        if (any_i && (any_i[w] & x) != x) atomicOr(&any_i[w], x);
-      }
-    }
+    if (lo < hi) move_range(from + base + (int64_t)ht.x * W, to + base + (int64_t)ht.y * W, any_i, lo, hi, ln);
   }
 }
 
@@ -102,41 +87,19 @@ extern "C" int rg_trule_ground(const rg_graph* g, const int32_t* head, const int
   RG_CHECK(g, "rg_trule_ground: NULL graph");
   RG_CHECK(g->n_time != 0, "rg_trule_ground: static graph (n_time=0): use rg_rule_ground");
   RG_CHECK(g->rel_ptr && g->rel_ht && g->rel_tm, "rg_trule_ground: the graph has no CSR by relation with edge times (rel_ptr / rel_tm is NULL)");
-  RG_CHECK(n_rules >= 0 && n_rules <= RULE_MAX_RULES, "rg_trule_ground: n_rules=%d not in 0..%d", n_rules, RULE_MAX_RULES);
-  RG_CHECK(n_hops >= 1 && n_hops <= RULE_MAX_HOPS, "rg_trule_ground: n_hops=%d not in 1..%d", n_hops, RULE_MAX_HOPS);
-  RG_CHECK(n_anchors >= 0, "rg_trule_ground: n_anchors=%d", n_anchors);
+  if (ground_check("rg_trule_ground", "anchors", n_rules, n_hops, n_anchors)) return 1;
   if (n_rules == 0 || n_anchors == 0) return 0;
-  RG_CHECK(head && body && dir && anchor_ent && anchor_ptr && scratch && counts, "rg_trule_ground: NULL argument");
-  const size_t bytes = rg_trule_ground_scratch_bytes(g->n_ent, n_rules, n_anchors);
-  RG_CHECK(bytes != 0, "rg_trule_ground: %d rules x %d entities x %d anchors is beyond the bitmaps' range", n_rules, g->n_ent,
-           n_anchors);
-  const hipStream_t s = (hipStream_t)stream;
-  const int32_t n_ent = g->n_ent, n_time = g->n_time, S = n_anchors, W = (int32_t)rg::ceil_div(S, 32);
+  const auto hop = [&](const Step& t) {
 #ifdef RG_TRULE_ONE_G      // A/B build (tools/build_variant.sh): the row-wide group for every direction
-  const int32_t g_wide = group_shift(W), g_now = g_wide;
+    const int32_t g_now = t.g_max;
 #else
-  const int32_t g_wide = group_shift(W), g_now = group_shift(std::min<int64_t>(W, W / n_time + 1));
+    const int32_t g_now = group_shift(std::min<int64_t>(t.W, t.W / g->n_time + 1));
 #endif
-  Maps m;
-  carve(scratch, n_ent, n_rules, W, &m);
-  const size_t map_bytes = (size_t)((int64_t)n_rules * n_ent * W) * 4;
-  const dim3 hop_grid(grid_x(g->n_fact, RT >> g_wide, n_rules), n_rules);
-
-  if (rg::zero_async(scratch, bytes, s)) return 1;
-  hipLaunchKernelGGL(rule_seed_kernel, dim3(grid_x(S, RT, n_rules), n_rules), dim3(RT), 0, s, anchor_ent, S, n_ent, W, m.cur);
-  RG_LAUNCH_CHECK();
-  hipLaunchKernelGGL(trule_hop_kernel, hop_grid, dim3(RT), 0, s, g->rel_ptr, g->rel_ht, g->rel_tm, g->n_rela_rows, n_ent, n_time, head,
-                     (const int32_t*)nullptr, 1, anchor_ptr, S, W, g_now, g_wide, m.cur, m.head, m.any);
-  RG_LAUNCH_CHECK();
-  for (int32_t l = 0; l < n_hops; ++l) {
-    hipLaunchKernelGGL(trule_hop_kernel, hop_grid, dim3(RT), 0, s, g->rel_ptr, g->rel_ht, g->rel_tm, g->n_rela_rows, n_ent, n_time,
-                       body + l, dir + l, n_hops, anchor_ptr, S, W, g_now, g_wide, m.cur, m.next, (uint32_t*)nullptr);
-    RG_LAUNCH_CHECK();
-    std::swap(m.cur, m.next);
-    if (l + 1 < n_hops && rg::zero_async(m.next, map_bytes, s)) return 1;
-  }
-  hipLaunchKernelGGL(rule_count_kernel, dim3(grid_x((int64_t)n_ent * W, RT, n_rules), n_rules), dim3(RT), 0, s, n_ent, W, m.cur,
-                     m.head, m.any, reinterpret_cast<unsigned long long*>(counts));
-  RG_LAUNCH_CHECK();
-  return 0;
+    const bool is_head = t.l < 0;      // a "now" step: the kernel takes NULL directions for it
+    hipLaunchKernelGGL(trule_hop_kernel, t.grid, dim3(RT), 0, t.s, g->rel_ptr, g->rel_ht, g->rel_tm, g->n_rela_rows, g->n_ent, g->n_time,
+                       is_head ? head : body + t.l, is_head ? (const int32_t*)nullptr : dir + t.l, is_head ? 1 : n_hops, anchor_ptr,
+                       n_anchors, t.W, g_now, t.g_max, t.from, t.to, t.any);
+  };
+  return ground_chain("rg_trule_ground", "anchors", g, n_rules, n_hops, anchor_ent, n_anchors,
+                      head && body && dir && anchor_ent && anchor_ptr && scratch && counts, scratch, counts, stream, hop);
 }

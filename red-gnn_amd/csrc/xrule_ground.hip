@@ -17,8 +17,8 @@
 //   data row j     t in [row_day[j] + lo, min(row_day[j] + hi, n_day)), each tested against its window
 //   self-loop      the days that pass are one range: [lo, hi) where hi <= loop_window, [lo, n_day) where lo <= loop_window < hi
 // and merges every run of consecutive passing days [a, b) into the one column range [ptr[a], ptr[b]), which it moves with the both-end
-// masks and the integer atomicOr of trule_hop_kernel.  Merging changes no bit: the runs are disjoint and their union is the set of
-// passing days.  Nothing bounds the candidate days from above but n_day: an "any" step or the open last bin tests every later day of
+// masks and the integer atomicOr of move_range (rule_bits.h), as trule_hop_kernel does.  Merging changes no bit: the runs are
+// disjoint and their union is the set of passing days.  Nothing bounds the candidate days from above but n_day: an "any" step or the open last bin tests every later day of
 // the row (two loads from the window arrays, n_day entries each, per day).
 //
 //   fill    the whole scratch is zeroed by rg::zero_async
@@ -43,30 +43,12 @@
 // Bounds.  A relation id outside 0..n_rela_rows-1 is tested before any load and reads nothing; lag_lo >= lag_hi makes the step empty;
 // an edge end or anchor entity outside 0..n_ent-1, a row index outside 0..n_data and a row_day outside 0..n_day-1 are skipped; the
 // candidate days are formed in int64 and clamped to 0..n_day before any window entry is read; anchor_ptr entries are clamped to 0..S
-// and a range with lo >= hi moves nothing.  The masks are those of trule_hop_kernel (both shifts in 0..31).
+// and a range with lo >= hi moves nothing.  The masks are move_range's (rule_bits.h: both shifts in 0..31).
 #include "rule_maps.h"
 
 namespace {
 
 using namespace rgrule;
-
-// to[v] |= from[u] & columns [lo, hi), 0 <= lo < hi <= S, by the G lanes of a group (w0 = the lane's index in it); `any_i` (or NULL)
-// collects per word the bits that moved
-__device__ __forceinline__ void move_range(const uint32_t* __restrict__ src, uint32_t* dst, uint32_t* any_i, int32_t lo, int32_t hi,
-                                           int32_t w0, int32_t G) {
-  const int32_t w_lo = lo >> 5, w_hi = (hi - 1) >> 5;           // 0 <= w_lo <= w_hi < W: hi <= S
-  const uint32_t m_lo = 0xffffffffu << (lo & 31), m_hi = 0xffffffffu >> (31 - ((hi - 1) & 31));
-  for (int32_t w = w_lo + w0; w <= w_hi; w += G) {
-    uint32_t x = src[w];
-    if (w == w_lo) x &= m_lo;
-    if (w == w_hi) x &= m_hi;
-    if (x != 0) {
-      atomicOr(&dst[w], x);
-      // the plain read may be stale: bits only ever appear, so a stale word costs an atomic and never drops one
-      if (any_i && (any_i[w] & x) != x) atomicOr(&any_i[w], x);
-    }
-  }
-}
 
 // one step of every rule: to[i][v] |= from[i][u] & columns(days the step admits the edge at) over the edges (u, v, j) of relation
 // rel_of[i * stride] under the lags [lo_of[i * stride], hi_of[i * stride]).  lo_of NULL: the head pass - row j moves the columns of day
@@ -102,12 +84,11 @@ __global__ __launch_bounds__(RT) void xrule_hop_kernel(const int32_t* __restrict
     while (g_shift < g_max && ((int64_t)1 << g_shift) < words) ++g_shift;
   }
 #endif
-  const int32_t G = 1 << g_shift, w0 = threadIdx.x & (G - 1);
-  const int64_t per_block = RT >> g_shift;
+  const Lanes ln = hop_lanes(g_shift);
   const int64_t base = i * n_ent * W;
   uint32_t* any_i = any ? any + i * W : nullptr;
   const auto ptr_at = [&](int32_t t) { return min(max(anchor_ptr[t], 0), S); };      // t in 0..n_day
-  for (int64_t e = e0 + blockIdx.x * per_block + (threadIdx.x >> g_shift); e < e1; e += gridDim.x * per_block) {
+  for (int64_t e = e0 + ln.first; e < e1; e += ln.step) {
     const int2 ht = rel_ht[e];
     const int32_t j = rel_tm[e];
     if ((uint32_t)ht.x >= (uint32_t)n_ent || (uint32_t)ht.y >= (uint32_t)n_ent || (uint32_t)j > (uint32_t)n_data) continue;
@@ -119,14 +100,14 @@ __global__ __launch_bounds__(RT) void xrule_hop_kernel(const int32_t* __restrict
       const int32_t b = lag_hi > loop_window ? n_day : (int32_t)std::min<int64_t>(lag_hi, n_day);      // (lag_hi <= 0: a >= b)
       if (a >= b) continue;
       const int32_t lo = ptr_at(a), hi = ptr_at(b);
-      if (lo < hi) move_range(src, dst, any_i, lo, hi, w0, G);
+      if (lo < hi) move_range(src, dst, any_i, lo, hi, ln);
       continue;
     }
     const int32_t d = row_day[j];
     if ((uint32_t)d >= (uint32_t)n_day) continue;
     if (is_head) {
       const int32_t lo = ptr_at(d), hi = ptr_at(d + 1);
-      if (lo < hi) move_range(src, dst, any_i, lo, hi, w0, G);
+      if (lo < hi) move_range(src, dst, any_i, lo, hi, ln);
       continue;
     }
     const int32_t t0 = (int32_t)std::min<int64_t>(std::max<int64_t>(d + lag_lo, 0), n_day);
@@ -138,13 +119,13 @@ __global__ __launch_bounds__(RT) void xrule_hop_kernel(const int32_t* __restrict
         if (run < 0) run = t;
       } else if (run >= 0) {
         const int32_t lo = ptr_at(run), hi = ptr_at(t);
-        if (lo < hi) move_range(src, dst, any_i, lo, hi, w0, G);
+        if (lo < hi) move_range(src, dst, any_i, lo, hi, ln);
         run = -1;
       }
     }
     if (run >= 0) {
       const int32_t lo = ptr_at(run), hi = ptr_at(t1);
-      if (lo < hi) move_range(src, dst, any_i, lo, hi, w0, G);
+      if (lo < hi) move_range(src, dst, any_i, lo, hi, ln);
     }
   }
 }
@@ -160,42 +141,19 @@ extern "C" int rg_xrule_ground(const rg_graph* g, const int32_t* head, const int
            "rg_xrule_ground: not the extrapolation layout (n_time=%d, n_data=%d: every edge's time field is its data row, n_time = n_data + 1)",
            g->n_time, n_data);
   RG_CHECK(g->rel_ptr && g->rel_ht && g->rel_tm, "rg_xrule_ground: the graph has no CSR by relation with edge times (rel_ptr / rel_tm is NULL)");
-  RG_CHECK(n_rules >= 0 && n_rules <= RULE_MAX_RULES, "rg_xrule_ground: n_rules=%d not in 0..%d", n_rules, RULE_MAX_RULES);
-  RG_CHECK(n_hops >= 1 && n_hops <= RULE_MAX_HOPS, "rg_xrule_ground: n_hops=%d not in 1..%d", n_hops, RULE_MAX_HOPS);
-  RG_CHECK(n_anchors >= 0, "rg_xrule_ground: n_anchors=%d", n_anchors);
+  if (ground_check("rg_xrule_ground", "anchors", n_rules, n_hops, n_anchors)) return 1;
   RG_CHECK(n_day >= 1, "rg_xrule_ground: n_day=%d", n_day);
   RG_CHECK(loop_window >= 0, "rg_xrule_ground: loop_window=%d", loop_window);
   if (n_rules == 0 || n_anchors == 0) return 0;
-  RG_CHECK(head && body && lag_lo && lag_hi && (row_day || n_data == 0) && win_lo && win_hi && anchor_ent && anchor_ptr && scratch && counts,
-           "rg_xrule_ground: NULL argument");
-  const size_t bytes = scratch_bytes(g->n_ent, n_rules, n_anchors);
-  RG_CHECK(bytes != 0, "rg_xrule_ground: %d rules x %d entities x %d anchors is beyond the bitmaps' range", n_rules, g->n_ent,
-           n_anchors);
-  const hipStream_t s = (hipStream_t)stream;
-  const int32_t n_ent = g->n_ent, S = n_anchors, W = (int32_t)rg::ceil_div(S, 32);
-  const int32_t g_max = group_shift(W);
-  Maps m;
-  carve(scratch, n_ent, n_rules, W, &m);
-  const size_t map_bytes = (size_t)((int64_t)n_rules * n_ent * W) * 4;
-  const dim3 hop_grid(grid_x(g->n_fact, RT >> g_max, n_rules), n_rules);
-
-  if (rg::zero_async(scratch, bytes, s)) return 1;
-  hipLaunchKernelGGL(rule_seed_kernel, dim3(grid_x(S, RT, n_rules), n_rules), dim3(RT), 0, s, anchor_ent, S, n_ent, W, m.cur);
-  RG_LAUNCH_CHECK();
-  hipLaunchKernelGGL(xrule_hop_kernel, hop_grid, dim3(RT), 0, s, g->rel_ptr, g->rel_ht, g->rel_tm, g->n_rela_rows, n_ent, n_data, head,
-                     (const int32_t*)nullptr, (const int32_t*)nullptr, 1, row_day, win_lo, win_hi, n_day, loop_window, anchor_ptr, S, W,
-                     g_max, m.cur, m.head, m.any);
-  RG_LAUNCH_CHECK();
-  for (int32_t l = 0; l < n_hops; ++l) {
-    hipLaunchKernelGGL(xrule_hop_kernel, hop_grid, dim3(RT), 0, s, g->rel_ptr, g->rel_ht, g->rel_tm, g->n_rela_rows, n_ent, n_data,
-                       body + l, lag_lo + l, lag_hi + l, n_hops, row_day, win_lo, win_hi, n_day, loop_window, anchor_ptr, S, W, g_max,
-                       m.cur, m.next, (uint32_t*)nullptr);
-    RG_LAUNCH_CHECK();
-    std::swap(m.cur, m.next);
-    if (l + 1 < n_hops && rg::zero_async(m.next, map_bytes, s)) return 1;
-  }
-  hipLaunchKernelGGL(rule_count_kernel, dim3(grid_x((int64_t)n_ent * W, RT, n_rules), n_rules), dim3(RT), 0, s, n_ent, W, m.cur,
-                     m.head, m.any, reinterpret_cast<unsigned long long*>(counts));
-  RG_LAUNCH_CHECK();
-  return 0;
+  const auto hop = [&](const Step& t) {
+    const bool is_head = t.l < 0;      // the kernel knows the head pass by its NULL lags
+    hipLaunchKernelGGL(xrule_hop_kernel, t.grid, dim3(RT), 0, t.s, g->rel_ptr, g->rel_ht, g->rel_tm, g->n_rela_rows, g->n_ent, n_data,
+                       is_head ? head : body + t.l, is_head ? (const int32_t*)nullptr : lag_lo + t.l,
+                       is_head ? (const int32_t*)nullptr : lag_hi + t.l, is_head ? 1 : n_hops, row_day, win_lo, win_hi, n_day, loop_window,
+                       anchor_ptr, n_anchors, t.W, t.g_max, t.from, t.to, t.any);
+  };
+  return ground_chain("rg_xrule_ground", "anchors", g, n_rules, n_hops, anchor_ent, n_anchors,
+                      head && body && lag_lo && lag_hi && (row_day || n_data == 0) && win_lo && win_hi && anchor_ent && anchor_ptr &&
+                          scratch && counts,
+                      scratch, counts, stream, hop);
 }

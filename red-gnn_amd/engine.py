@@ -1106,7 +1106,7 @@ def paths_topk(edges, alpha, offsets, n_hops, k, scratch_bytes=PATHS_SCRATCH_BYT
     return path_edge, path_prod, path_count
 
 
-RULE_MAX_HOPS = 32                   # csrc/rule_ground.hip: RULE_MAX_HOPS
+RULE_MAX_HOPS = 32                   # csrc/rule_bits.h: RULE_MAX_HOPS
 RULE_MAX_RULES = 65535               # ... RULE_MAX_RULES (rules of one call)
 RULE_SCRATCH_BYTES = 1 << 30         # default scratch budget of rule_ground
 # tools/probe_rule_quality.py sets this to a list to collect (start_event, end_event, n_rules, n_sources) per chunk of rule_ground
@@ -1124,18 +1124,70 @@ def _int_array(x, name, who):
     return a
 
 
+def _as32(a):
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _check_scratch_bytes(scratch_bytes, who):
+    if isinstance(scratch_bytes, (bool, np.bool_)) or not isinstance(scratch_bytes, (int, np.integer)) or scratch_bytes < 0:
+        raise ValueError("%s: scratch_bytes must be a non-negative integer (got %r)" % (who, scratch_bytes))
+    return int(scratch_bytes)
+
+
+def _check_rule_shapes(who, h, b, **steps):
+    """head [R], body and every array of ``steps`` (named as the caller's arguments) [R, L] with 1 <= L <= RULE_MAX_HOPS, or ValueError."""
+    if h.ndim != 1 or b.ndim != 2 or b.shape[0] != h.shape[0] or any(x.shape != b.shape for x in steps.values()):
+        names, shapes = ["body"] + list(steps), [str(x.shape) for x in (h, b) + tuple(steps.values())]
+        want = "head must be [R], %s and %s [R, L]" % (", ".join(names[:-1]), names[-1]) if steps else "head must be [R] and body [R, L]"
+        raise ValueError("%s: %s (got %s and %s)" % (who, want, ", ".join(shapes[:-1]), shapes[-1]))
+    if not 1 <= b.shape[1] <= RULE_MAX_HOPS:
+        raise ValueError("%s: the body length %d is not in 1..%d" % (who, b.shape[1], RULE_MAX_HOPS))
+
+
+def _check_rel_range(who, h, b, top, note=""):
+    """Every relation id of head and body in 0..top, or ValueError (``note``: what top is, inside the bracket)."""
+    if h.size and (min(h.min(), b.min()) < 0 or max(h.max(), b.max()) > top):
+        raise ValueError("%s: relation id out of range 0..%d (%sgot %d..%d)"
+                         % (who, top, note, min(h.min(), b.min()), max(h.max(), b.max())))
+
+
+def _check_anchors(who, anchors, n_ent, n_unit, unit):
+    """int64 [S, 2] = (entity, ``unit``: "time id" or "day", in 0..n_unit-1), distinct, sorted by (unit, entity), or ValueError."""
+    a = _int_array(anchors, "anchors", who)
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError("%s: anchors must be [S, 2] = (entity, %s) (got %s)" % (who, unit, a.shape))
+    a = a.astype(np.int64)
+    if a.size and (a[:, 0].min() < 0 or a[:, 0].max() >= n_ent or a[:, 1].min() < 0 or a[:, 1].max() >= n_unit):
+        raise ValueError("%s: anchor out of range (entity 0..%d, %s 0..%d; got %d..%d and %d..%d)"
+                         % (who, n_ent - 1, unit, n_unit - 1, a[:, 0].min(), a[:, 0].max(), a[:, 1].min(), a[:, 1].max()))
+    key = np.sort(a[:, 1] * n_ent + a[:, 0])
+    if np.unique(key).size != key.size:
+        raise ValueError("%s: duplicate anchors (%d pairs, %d distinct)" % (who, key.size, np.unique(key).size))
+    return np.stack([key % n_ent, key // n_ent], 1)
+
+
+def _check_heads_and_weights(who, h, weight):
+    """weight as float32 [R], finite and in (0, 1], for rules whose heads ``h`` do not decrease, or ValueError."""
+    if h.size > 1 and (np.diff(h) < 0).any():
+        at = int(np.argmax(np.diff(h) < 0))
+        raise ValueError("%s: head must be non-decreasing (rule %d has head %d after %d)" % (who, at + 1, h[at + 1], h[at]))
+    w = weight.detach().cpu().numpy() if torch.is_tensor(weight) else np.asarray(weight)
+    if w.dtype.kind != "f" or w.ndim != 1 or w.shape[0] != h.shape[0]:
+        raise ValueError("%s: weight must be a float array [R] (got %s %s for %d rules)" % (who, w.dtype, w.shape, h.shape[0]))
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    if w.size and not (np.isfinite(w).all() and (w > 0).all() and (w <= 1).all()):
+        bad = int(np.argmax(~(np.isfinite(w) & (w > 0) & (w <= 1))))
+        raise ValueError("%s: weights must be finite and in (0, 1] as float32 (rule %d has %r)" % (who, bad, float(w[bad])))
+    return w
+
+
 def check_rules(n_ent, n_rel, head, body, sources=None, who="rule_ground"):
     """The host validation of rule_ground: (head int32 [R], body int32 [R, L], sources int32 [S]) as contiguous numpy arrays, or
     ValueError.  ``sources=None``: every entity."""
     h, b = _int_array(head, "head", who), _int_array(body, "body", who)
-    if h.ndim != 1 or b.ndim != 2 or b.shape[0] != h.shape[0]:
-        raise ValueError("%s: head must be [R] and body [R, L] (got %s and %s)" % (who, h.shape, b.shape))
-    if not 1 <= b.shape[1] <= RULE_MAX_HOPS:
-        raise ValueError("%s: the body length %d is not in 1..%d" % (who, b.shape[1], RULE_MAX_HOPS))
+    _check_rule_shapes(who, h, b)
     n_ent, n_rel = int(n_ent), int(n_rel)
-    if h.size and (min(h.min(), b.min()) < 0 or max(h.max(), b.max()) > 2 * n_rel):
-        raise ValueError("%s: relation id out of range 0..%d (2*n_rel; got %d..%d)"
-                         % (who, 2 * n_rel, min(h.min(), b.min()), max(h.max(), b.max())))
+    _check_rel_range(who, h, b, 2 * n_rel, "2*n_rel; ")
     if sources is None:
         s = np.arange(n_ent, dtype=np.int32)
     else:
@@ -1146,8 +1198,7 @@ def check_rules(n_ent, n_rel, head, body, sources=None, who="rule_ground"):
             raise ValueError("%s: source id out of range 0..%d (got %d..%d)" % (who, n_ent - 1, s.min(), s.max()))
         if np.unique(s).size != s.size:
             raise ValueError("%s: duplicate sources (%d ids, %d distinct)" % (who, s.size, np.unique(s).size))
-    as32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
-    return as32(h), as32(b), as32(s)
+    return _as32(h), _as32(b), _as32(s)
 
 
 def rule_chunking(n_ent, n_rules, n_sources, scratch_bytes):
@@ -1179,32 +1230,53 @@ def rule_ground(graph, head, body, sources=None, scratch_bytes=RULE_SCRATCH_BYTE
     if getattr(graph, "n_time", 0):
         raise ValueError("rule_ground: temporal graph: rules are grounded on static and inductive graphs only "
                          "(temporal rules, whose steps carry a direction, are grounded by trule_ground)")
-    if isinstance(scratch_bytes, (bool, np.bool_)) or not isinstance(scratch_bytes, (int, np.integer)) or scratch_bytes < 0:
-        raise ValueError("rule_ground: scratch_bytes must be a non-negative integer (got %r)" % (scratch_bytes,))
+    scratch_bytes = _check_scratch_bytes(scratch_bytes, "rule_ground")
     h, b, s = check_rules(graph.n_ent, graph.n_rel, head, body, sources)
+    L, p = b.shape[1], _lib.ptr
+
+    def upload(dev, s_c):
+        h_d, b_d, s_d = (torch.from_numpy(a).to(dev) for a in (h, b, s))
+        return lambda r0, r1, k, s0, s1, scratch, counts: _lib.check(_lib.lib().rg_rule_ground(
+            graph.handle, p(h_d[r0:r1]), p(b_d[r0:r1]), r1 - r0, L, p(s_d[s0:s1]), s1 - s0, p(scratch), p(counts), _lib.stream_ptr()))
+    return _ground_chunks("RULE_EVENTS", graph, h.shape[0], s.shape[0], scratch_bytes, upload)
+
+
+def _ground_chunks(events, graph, R, S, scratch_bytes, upload):
+    """What rule_ground, trule_ground and xrule_ground do once their arguments are valid: int64 [R, 4] counts of R rules over S
+    columns, the work cut as rule_chunking says.  ``upload(dev, s_c)`` puts the family's arrays on the device, knowing the columns of a
+    block, and returns ``call(r0, r1, k, s0, s1, scratch, counts)``: the entry point on the rules r0..r1 and block k = columns s0..s1,
+    adding into ``counts`` [r1 - r0, 4].  The scratch is allocated once, for the largest chunk.  ``events`` names the module attribute
+    (RULE_EVENTS, ...) that collects a pair of events, the rules and the columns of every chunk where a probe has set it to a list."""
     dev = _require_gpu(graph.device)
-    R, L, S = h.shape[0], b.shape[1], s.shape[0]
     counts = torch.zeros((R, 4), dtype=torch.int64, device=dev)
     if R == 0 or S == 0:
         return counts
-    n_r, s_c = rule_chunking(graph.n_ent, R, S, int(scratch_bytes))
-    h_d, b_d, s_d = (torch.from_numpy(a).to(dev) for a in (h, b, s))
-    p = _lib.ptr
+    n_r, s_c = rule_chunking(graph.n_ent, R, S, scratch_bytes)
+    call = upload(dev, s_c)
     with torch.cuda.device(dev):
         scratch = torch.empty(rule_ground_scratch_bytes(graph.n_ent, min(n_r, R), min(s_c, S)), dtype=torch.uint8, device=dev)
         for r0 in range(0, R, n_r):
             r1 = min(r0 + n_r, R)
-            for s0 in range(0, S, s_c):
+            for k, s0 in enumerate(range(0, S, s_c)):
                 s1 = min(s0 + s_c, S)
-                if RULE_EVENTS is not None:
+                log = globals()[events]                  # read at call time: a test or probe assigns the attribute
+                if log is not None:
                     ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                     ev[0].record()
-                _lib.check(_lib.lib().rg_rule_ground(graph.handle, p(h_d[r0:r1]), p(b_d[r0:r1]), r1 - r0, L, p(s_d[s0:s1]), s1 - s0,
-                                                     p(scratch), p(counts[r0:r1]), _lib.stream_ptr()))
-                if RULE_EVENTS is not None:
+                call(r0, r1, k, s0, s1, scratch, counts[r0:r1])
+                if log is not None:
                     ev[1].record()
-                    RULE_EVENTS.append((ev[0], ev[1], r1 - r0, s1 - s0))
+                    log.append((ev[0], ev[1], r1 - r0, s1 - s0))
     return counts
+
+
+def _block_anchor_ptr(unit_of, n_unit, s_c):
+    """int [blocks, n_unit + 1]: anchor_ptr of every block of ``s_c`` consecutive anchors, ``unit_of`` [S] being their sorted time ids
+    (days): clip(ptr - s0, 0, s1 - s0), ptr[tau] the first anchor whose time is >= tau."""
+    S = unit_of.shape[0]
+    ptr = np.searchsorted(unit_of, np.arange(n_unit + 1))
+    starts = np.arange(0, S, s_c)
+    return np.clip(ptr[None, :] - starts[:, None], 0, np.minimum(starts + s_c, S)[:, None] - starts[:, None])
 
 
 # tools/probe_trule_quality.py sets this to a list to collect (start_event, end_event, n_rules, n_anchors) per chunk of trule_ground
@@ -1225,31 +1297,12 @@ def check_trules(graph, head, body, direction, anchors=None, who="trule_ground")
         raise ValueError("%s: static graph (no time ids): static rules are grounded by rule_ground" % who)
     n_ent, n_rows = int(graph.n_ent), int(graph.n_rela_rows)
     h, b, d = _int_array(head, "head", who), _int_array(body, "body", who), _int_array(direction, "direction", who)
-    if h.ndim != 1 or b.ndim != 2 or b.shape[0] != h.shape[0] or d.shape != b.shape:
-        raise ValueError("%s: head must be [R], body and direction [R, L] (got %s, %s and %s)" % (who, h.shape, b.shape, d.shape))
-    if not 1 <= b.shape[1] <= RULE_MAX_HOPS:
-        raise ValueError("%s: the body length %d is not in 1..%d" % (who, b.shape[1], RULE_MAX_HOPS))
-    if h.size and (min(h.min(), b.min()) < 0 or max(h.max(), b.max()) >= n_rows):
-        raise ValueError("%s: relation id out of range 0..%d (got %d..%d)"
-                         % (who, n_rows - 1, min(h.min(), b.min()), max(h.max(), b.max())))
+    _check_rule_shapes(who, h, b, direction=d)
+    _check_rel_range(who, h, b, n_rows - 1)
     if d.size and (d.min() < 0 or d.max() > 3):
         raise ValueError("%s: direction out of range 0..3 (past, now, future, any; got %d..%d)" % (who, d.min(), d.max()))
-    if anchors is None:
-        a = graph.default_anchors()
-    else:
-        a = _int_array(anchors, "anchors", who)
-        if a.ndim != 2 or a.shape[1] != 2:
-            raise ValueError("%s: anchors must be [S, 2] = (entity, time id) (got %s)" % (who, a.shape))
-        a = a.astype(np.int64)
-        if a.size and (a[:, 0].min() < 0 or a[:, 0].max() >= n_ent or a[:, 1].min() < 0 or a[:, 1].max() >= n_time):
-            raise ValueError("%s: anchor out of range (entity 0..%d, time id 0..%d; got %d..%d and %d..%d)"
-                             % (who, n_ent - 1, n_time - 1, a[:, 0].min(), a[:, 0].max(), a[:, 1].min(), a[:, 1].max()))
-        key = np.sort(a[:, 1] * n_ent + a[:, 0])
-        if np.unique(key).size != key.size:
-            raise ValueError("%s: duplicate anchors (%d pairs, %d distinct)" % (who, key.size, np.unique(key).size))
-        a = np.stack([key % n_ent, key // n_ent], 1)
-    as32 = lambda x: np.ascontiguousarray(x, dtype=np.int32)
-    return as32(h), as32(b), as32(d), a
+    a = graph.default_anchors() if anchors is None else _check_anchors(who, anchors, n_ent, n_time, "time id")
+    return _as32(h), _as32(b), _as32(d), a
 
 
 def trule_ground(graph, head, body, direction, anchors=None, scratch_bytes=RULE_SCRATCH_BYTES):
@@ -1261,36 +1314,17 @@ def trule_ground(graph, head, body, direction, anchors=None, scratch_bytes=RULE_
     into chunks of (rules x blocks of consecutive anchors, a multiple of 32) whose bitmaps fit ``scratch_bytes``, as rule_chunking
     says; each block gets anchor_ptr = clip(ptr - s0, 0, s1 - s0), ptr being the first sorted anchor of every time id.  The scratch
     is allocated once and the counts are integers added per chunk, so the result does not depend on the budget."""
-    if isinstance(scratch_bytes, (bool, np.bool_)) or not isinstance(scratch_bytes, (int, np.integer)) or scratch_bytes < 0:
-        raise ValueError("trule_ground: scratch_bytes must be a non-negative integer (got %r)" % (scratch_bytes,))
+    scratch_bytes = _check_scratch_bytes(scratch_bytes, "trule_ground")
     h, b, d, a = check_trules(graph, head, body, direction, anchors)
-    dev = _require_gpu(graph.device)
-    R, L, S = h.shape[0], b.shape[1], a.shape[0]
-    counts = torch.zeros((R, 4), dtype=torch.int64, device=dev)
-    if R == 0 or S == 0:
-        return counts
-    n_r, s_c = rule_chunking(graph.n_ent, R, S, int(scratch_bytes))
-    ptr = np.searchsorted(a[:, 1], np.arange(graph.n_time + 1))              # the first sorted anchor whose time is >= tau
-    starts = np.arange(0, S, s_c)
-    block_ptr = np.clip(ptr[None, :] - starts[:, None], 0, np.minimum(starts + s_c, S)[:, None] - starts[:, None])
-    h_d, b_d, d_d, e_d, p_d = (torch.from_numpy(np.ascontiguousarray(x, dtype=np.int32)).to(dev) for x in (h, b, d, a[:, 0], block_ptr))
-    p = _lib.ptr
-    with torch.cuda.device(dev):
-        scratch = torch.empty(trule_ground_scratch_bytes(graph.n_ent, min(n_r, R), min(s_c, S)), dtype=torch.uint8, device=dev)
-        for r0 in range(0, R, n_r):
-            r1 = min(r0 + n_r, R)
-            for k, s0 in enumerate(starts.tolist()):
-                s1 = min(s0 + s_c, S)
-                if TRULE_EVENTS is not None:
-                    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                    ev[0].record()
-                _lib.check(_lib.lib().rg_trule_ground(graph.handle, p(h_d[r0:r1]), p(b_d[r0:r1]), p(d_d[r0:r1]), r1 - r0, L,
-                                                      p(e_d[s0:s1]), p(p_d[k]), s1 - s0, p(scratch), p(counts[r0:r1]),
-                                                      _lib.stream_ptr()))
-                if TRULE_EVENTS is not None:
-                    ev[1].record()
-                    TRULE_EVENTS.append((ev[0], ev[1], r1 - r0, s1 - s0))
-    return counts
+    L, p = b.shape[1], _lib.ptr
+
+    def upload(dev, s_c):
+        h_d, b_d, d_d, e_d, p_d = (torch.from_numpy(_as32(x)).to(dev)
+                                   for x in (h, b, d, a[:, 0], _block_anchor_ptr(a[:, 1], graph.n_time, s_c)))
+        return lambda r0, r1, k, s0, s1, scratch, counts: _lib.check(_lib.lib().rg_trule_ground(
+            graph.handle, p(h_d[r0:r1]), p(b_d[r0:r1]), p(d_d[r0:r1]), r1 - r0, L, p(e_d[s0:s1]), p(p_d[k]), s1 - s0, p(scratch),
+            p(counts), _lib.stream_ptr()))
+    return _ground_chunks("TRULE_EVENTS", graph, h.shape[0], a.shape[0], scratch_bytes, upload)
 
 
 # tools/probe_xrule_quality.py sets this to a list to collect (start_event, end_event, n_rules, n_anchors) per chunk of xrule_ground
@@ -1321,11 +1355,7 @@ def check_xrules(graph, head, body, lag_lo, lag_hi, row_day, win_lo, win_hi, anc
     h, b = _int_array(head, "head", who), _int_array(body, "body", who)
     lo, hi = _int_array(lag_lo, "lag_lo", who), _int_array(lag_hi, "lag_hi", who)
     day, w_lo, w_hi = _int_array(row_day, "row_day", who), _int_array(win_lo, "win_lo", who), _int_array(win_hi, "win_hi", who)
-    if h.ndim != 1 or b.ndim != 2 or b.shape[0] != h.shape[0] or lo.shape != b.shape or hi.shape != b.shape:
-        raise ValueError("%s: head must be [R], body, lag_lo and lag_hi [R, L] (got %s, %s, %s and %s)"
-                         % (who, h.shape, b.shape, lo.shape, hi.shape))
-    if not 1 <= b.shape[1] <= RULE_MAX_HOPS:
-        raise ValueError("%s: the body length %d is not in 1..%d" % (who, b.shape[1], RULE_MAX_HOPS))
+    _check_rule_shapes(who, h, b, lag_lo=lo, lag_hi=hi)
     if day.ndim != 1 or n_time != day.shape[0] + 1:
         raise ValueError("%s: not the extrapolation layout: row_day must be [n_data] and the graph's n_time n_data + 1 (got %s and "
                          "n_time=%d)" % (who, day.shape, n_time))
@@ -1334,33 +1364,17 @@ def check_xrules(graph, head, body, lag_lo, lag_hi, row_day, win_lo, win_hi, anc
     n_day = w_lo.shape[0]
     if isinstance(loop_window, (bool, np.bool_)) or not isinstance(loop_window, (int, np.integer)) or not 0 <= loop_window < 2 ** 31:
         raise ValueError("%s: loop_window must be a non-negative integer (got %r)" % (who, loop_window))
-    if h.size and (min(h.min(), b.min()) < 0 or max(h.max(), b.max()) >= n_rows):
-        raise ValueError("%s: relation id out of range 0..%d (got %d..%d)"
-                         % (who, n_rows - 1, min(h.min(), b.min()), max(h.max(), b.max())))
+    _check_rel_range(who, h, b, n_rows - 1)
     if lo.size and (lo.min() < 0 or hi.max() > XRULE_ANY_HI or (lo >= hi).any()):
         raise ValueError("%s: lag range out of order: need 0 <= lag_lo < lag_hi <= %d for every step (got lag_lo %d..%d, lag_hi %d..%d)"
                          % (who, XRULE_ANY_HI, lo.min(), lo.max(), hi.min(), hi.max()))
     if day.size and (day.min() < 0 or day.max() >= n_day):
         raise ValueError("%s: row_day out of range 0..%d (got %d..%d)" % (who, n_day - 1, day.min(), day.max()))
-    if anchors is None:
-        a = xrule_default_anchors(graph, day)
-    else:
-        a = _int_array(anchors, "anchors", who)
-        if a.ndim != 2 or a.shape[1] != 2:
-            raise ValueError("%s: anchors must be [S, 2] = (entity, day) (got %s)" % (who, a.shape))
-        a = a.astype(np.int64)
-        if a.size and (a[:, 0].min() < 0 or a[:, 0].max() >= n_ent or a[:, 1].min() < 0 or a[:, 1].max() >= n_day):
-            raise ValueError("%s: anchor out of range (entity 0..%d, day 0..%d; got %d..%d and %d..%d)"
-                             % (who, n_ent - 1, n_day - 1, a[:, 0].min(), a[:, 0].max(), a[:, 1].min(), a[:, 1].max()))
-        key = np.sort(a[:, 1] * n_ent + a[:, 0])
-        if np.unique(key).size != key.size:
-            raise ValueError("%s: duplicate anchors (%d pairs, %d distinct)" % (who, key.size, np.unique(key).size))
-        a = np.stack([key % n_ent, key // n_ent], 1)
-    as32 = lambda x: np.ascontiguousarray(x, dtype=np.int32)
+    a = xrule_default_anchors(graph, day) if anchors is None else _check_anchors(who, anchors, n_ent, n_day, "day")
     if w_lo.size and (min(w_lo.min(), w_hi.min()) < 0 or max(w_lo.max(), w_hi.max()) > day.shape[0]):
         raise ValueError("%s: window bound out of range 0..%d (got %d..%d)"
                          % (who, day.shape[0], min(w_lo.min(), w_hi.min()), max(w_lo.max(), w_hi.max())))
-    return as32(h), as32(b), as32(lo), as32(hi), as32(day), as32(w_lo), as32(w_hi), a
+    return _as32(h), _as32(b), _as32(lo), _as32(hi), _as32(day), _as32(w_lo), _as32(w_hi), a
 
 
 def xrule_ground(graph, head, body, lag_lo, lag_hi, row_day, win_lo, win_hi, anchors=None, loop_window=XRULE_LOOP_WINDOW,
@@ -1375,42 +1389,21 @@ def xrule_ground(graph, head, body, lag_lo, lag_hi, row_day, win_lo, win_hi, anc
     consecutive anchors, a multiple of 32) whose bitmaps fit ``scratch_bytes``, as rule_chunking says; each block gets anchor_ptr =
     clip(ptr - s0, 0, s1 - s0), ptr being the first sorted anchor of every day.  The scratch is allocated once and the counts are
     integers added per chunk, so the result does not depend on the budget."""
-    if isinstance(scratch_bytes, (bool, np.bool_)) or not isinstance(scratch_bytes, (int, np.integer)) or scratch_bytes < 0:
-        raise ValueError("xrule_ground: scratch_bytes must be a non-negative integer (got %r)" % (scratch_bytes,))
+    scratch_bytes = _check_scratch_bytes(scratch_bytes, "xrule_ground")
     h, b, lo, hi, day, w_lo, w_hi, a = check_xrules(graph, head, body, lag_lo, lag_hi, row_day, win_lo, win_hi, anchors, loop_window)
-    dev = _require_gpu(graph.device)
-    R, L, S, n_data, n_day = h.shape[0], b.shape[1], a.shape[0], day.shape[0], w_lo.shape[0]
-    counts = torch.zeros((R, 4), dtype=torch.int64, device=dev)
-    if R == 0 or S == 0:
-        return counts
-    n_r, s_c = rule_chunking(graph.n_ent, R, S, int(scratch_bytes))
-    ptr = np.searchsorted(a[:, 1], np.arange(n_day + 1))                     # the first sorted anchor whose day is >= t
-    starts = np.arange(0, S, s_c)
-    block_ptr = np.clip(ptr[None, :] - starts[:, None], 0, np.minimum(starts + s_c, S)[:, None] - starts[:, None])
-    h_d, b_d, lo_d, hi_d, day_d, wl_d, wh_d, e_d, p_d = (torch.from_numpy(np.ascontiguousarray(x, dtype=np.int32)).to(dev)
-                                                         for x in (h, b, lo, hi, day, w_lo, w_hi, a[:, 0], block_ptr))
-    p = _lib.ptr
-    with torch.cuda.device(dev):
-        scratch = torch.empty(rule_ground_scratch_bytes(graph.n_ent, min(n_r, R), min(s_c, S)), dtype=torch.uint8, device=dev)
-        for r0 in range(0, R, n_r):
-            r1 = min(r0 + n_r, R)
-            for k, s0 in enumerate(starts.tolist()):
-                s1 = min(s0 + s_c, S)
-                if XRULE_EVENTS is not None:
-                    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                    ev[0].record()
-                _lib.check(_lib.lib().rg_xrule_ground(graph.handle, p(h_d[r0:r1]), p(b_d[r0:r1]), p(lo_d[r0:r1]), p(hi_d[r0:r1]),
-                                                      r1 - r0, L, p(day_d), n_data, p(wl_d), p(wh_d), n_day, int(loop_window),
-                                                      p(e_d[s0:s1]), p(p_d[k]), s1 - s0, p(scratch), p(counts[r0:r1]),
-                                                      _lib.stream_ptr()))
-                if XRULE_EVENTS is not None:
-                    ev[1].record()
-                    XRULE_EVENTS.append((ev[0], ev[1], r1 - r0, s1 - s0))
-    return counts
+    L, n_data, n_day, p = b.shape[1], day.shape[0], w_lo.shape[0], _lib.ptr
+
+    def upload(dev, s_c):
+        h_d, b_d, lo_d, hi_d, day_d, wl_d, wh_d, e_d, p_d = (
+            torch.from_numpy(_as32(x)).to(dev) for x in (h, b, lo, hi, day, w_lo, w_hi, a[:, 0], _block_anchor_ptr(a[:, 1], n_day, s_c)))
+        return lambda r0, r1, k, s0, s1, scratch, counts: _lib.check(_lib.lib().rg_xrule_ground(
+            graph.handle, p(h_d[r0:r1]), p(b_d[r0:r1]), p(lo_d[r0:r1]), p(hi_d[r0:r1]), r1 - r0, L, p(day_d), n_data, p(wl_d), p(wh_d),
+            n_day, int(loop_window), p(e_d[s0:s1]), p(p_d[k]), s1 - s0, p(scratch), p(counts), _lib.stream_ptr()))
+    return _ground_chunks("XRULE_EVENTS", graph, h.shape[0], a.shape[0], scratch_bytes, upload)
 
 
-RULE_APPLY_ALIGN = 256               # csrc/rule_apply.hip: APPLY_ALIGN
-RULE_APPLY_MAX_WORDS = 1 << 40       # ... APPLY_MAX_WORDS (words of one bitmap region)
+RULE_APPLY_ALIGN = 256               # csrc/rule_bits.h: RULE_ALIGN
+RULE_APPLY_MAX_WORDS = 1 << 40       # ... RULE_MAX_WORDS (words of one bitmap region)
 # tools/probe_rule_apply.py sets this to a list to collect (start, after seed + hops, end events, n_rules, n_words) per call of rule_apply
 RULE_APPLY_EVENTS = None
 
@@ -1446,16 +1439,7 @@ def check_rule_apply(n_ent, n_rel, head, body, weight, subs, rels):
     contiguous numpy arrays, or ValueError."""
     who = "rule_apply"
     h, b, _ = check_rules(n_ent, n_rel, head, body, np.zeros(0, np.int32), who=who)
-    if h.size > 1 and (np.diff(h) < 0).any():
-        at = int(np.argmax(np.diff(h) < 0))
-        raise ValueError("%s: head must be non-decreasing (rule %d has head %d after %d)" % (who, at + 1, h[at + 1], h[at]))
-    w = weight.detach().cpu().numpy() if torch.is_tensor(weight) else np.asarray(weight)
-    if w.dtype.kind != "f" or w.ndim != 1 or w.shape[0] != h.shape[0]:
-        raise ValueError("%s: weight must be a float array [R] (got %s %s for %d rules)" % (who, w.dtype, w.shape, h.shape[0]))
-    w = np.ascontiguousarray(w, dtype=np.float32)
-    if w.size and not (np.isfinite(w).all() and (w > 0).all() and (w <= 1).all()):
-        bad = int(np.argmax(~(np.isfinite(w) & (w > 0) & (w <= 1))))
-        raise ValueError("%s: weights must be finite and in (0, 1] as float32 (rule %d has %r)" % (who, bad, float(w[bad])))
+    w = _check_heads_and_weights(who, h, weight)
     s, r = _int_array(subs, "subs", who), _int_array(rels, "rels", who)
     if s.ndim != 1 or r.ndim != 1 or s.shape[0] != r.shape[0]:
         raise ValueError("%s: need one relation per subject (got subs %s, rels %s)" % (who, s.shape, r.shape))
@@ -1464,8 +1448,7 @@ def check_rule_apply(n_ent, n_rel, head, body, weight, subs, rels):
         raise ValueError("%s: subject id out of range 0..%d (got %d..%d)" % (who, n_ent - 1, s.min(), s.max()))
     if r.size and (r.min() < 0 or r.max() > 2 * n_rel):
         raise ValueError("%s: query relation id out of range 0..%d (2*n_rel; got %d..%d)" % (who, 2 * n_rel, r.min(), r.max()))
-    as32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
-    return h, b, w, as32(s), as32(r)
+    return h, b, w, _as32(s), _as32(r)
 
 
 def rule_apply(graph, head, body, weight, subs, rels, scratch_bytes=RULE_SCRATCH_BYTES):
@@ -1479,31 +1462,39 @@ def rule_apply(graph, head, body, weight, subs, rels, scratch_bytes=RULE_SCRATCH
     if getattr(graph, "n_time", 0):
         raise ValueError("rule_apply: temporal graph: rules are grounded on static and inductive graphs only "
                          "(temporal rules, whose steps carry a direction, are applied by trule_apply)")
-    if isinstance(scratch_bytes, (bool, np.bool_)) or not isinstance(scratch_bytes, (int, np.integer)) or scratch_bytes < 0:
-        raise ValueError("rule_apply: scratch_bytes must be a non-negative integer (got %r)" % (scratch_bytes,))
+    scratch_bytes = _check_scratch_bytes(scratch_bytes, "rule_apply")
     h, b, w, s, r = check_rule_apply(graph.n_ent, graph.n_rel, head, body, weight, subs, rels)
+    order = np.argsort(r, kind="stable")
+    q_ptr = np.searchsorted(r[order], np.arange(2 * int(graph.n_rel) + 2)).astype(np.int32)
+    words = int(graph.n_ent) * ((np.diff(q_ptr).astype(np.int64)[h] + 31) // 32)     # per rule
+    return _apply_chunks("rule_apply", "RULE_APPLY_EVENTS", graph, (h, b), w, s[order], order, q_ptr, words, scratch_bytes,
+                         lambda *args: _lib.lib().rg_rule_apply(graph.handle, *args))
+
+
+def _apply_chunks(who, events, graph, rules, w, q_sub, q_row, q_ptr, words, scratch_bytes, entry):
+    """What rule_apply and trule_apply do once the queries are sorted: the four outputs [B, n_ent], the rules cut into consecutive
+    calls as rule_apply_chunking says, every call's slabs, and the calls in rule order.  ``rules``: the per-rule int32 arrays in the
+    entry point's order, (head, body) or (head, body, direction); ``w`` their weights; ``q_sub`` [B] the subjects in sorted order,
+    ``q_row`` [B] the caller's row of every sorted position, ``q_ptr`` as the entry point takes it; ``words`` [R] the words of every
+    rule's slab; ``entry(*args)``: the entry point after its graph.  ``events`` names the module attribute (RULE_APPLY_EVENTS, ...):
+    where a probe has set it to a list a call is split into its two phases and the three events around them, the rules and the words
+    of the call are collected."""
     dev = _require_gpu(graph.device)
-    R, L, B, n_ent = h.shape[0], b.shape[1], s.shape[0], int(graph.n_ent)
+    R, L, B, n_ent = rules[0].shape[0], rules[1].shape[1], q_sub.shape[0], int(graph.n_ent)
     best = torch.zeros((B, n_ent), dtype=torch.float32, device=dev)
     surv = torch.ones((B, n_ent), dtype=torch.float32, device=dev)
     best_rule = torch.full((B, n_ent), -1, dtype=torch.int32, device=dev)
     fired = torch.zeros((B, n_ent), dtype=torch.int32, device=dev)
-    if R == 0 or B == 0:
-        return best, surv, best_rule, fired
-    n_rows = 2 * int(graph.n_rel) + 1
-    order = np.argsort(r, kind="stable")
-    q_ptr = np.searchsorted(r[order], np.arange(n_rows + 1)).astype(np.int32)
-    words = n_ent * ((np.diff(q_ptr).astype(np.int64)[h] + 31) // 32)             # per rule
-    chunks = [(r0, r1) for r0, r1 in rule_apply_chunking(words, int(scratch_bytes)) if words[r0:r1].sum() > 0]
-    if not chunks:
+    chunks = [(r0, r1) for r0, r1 in rule_apply_chunking(words, scratch_bytes) if words[r0:r1].sum() > 0]
+    if R == 0 or B == 0 or not chunks:
         return best, surv, best_rule, fired
     slabs = [np.concatenate([[0], np.cumsum(words[r0:r1])]).astype(np.int64) for r0, r1 in chunks]
     need = [rule_apply_scratch_bytes(sl[-1]) for sl in slabs]
     if min(need) == 0:
-        raise ValueError("rule_apply: a rule's bitmap of %d words is beyond the bitmaps' range (fewer queries per call)" % max(words))
-    miss = (np.float32(1.0) - w).astype(np.float32)
+        raise ValueError("%s: a rule's bitmap of %d words is beyond the bitmaps' range (fewer queries per call)" % (who, max(words)))
     to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    h_d, b_d, w_d, m_d, qs_d, qr_d, qp_d = (to(a) for a in (h, b, w, miss, s[order], order.astype(np.int32), q_ptr))
+    rules_d = [to(a) for a in rules]
+    w_d, m_d, qs_d, qr_d, qp_d = (to(a) for a in (w, (np.float32(1.0) - w).astype(np.float32), q_sub, q_row.astype(np.int32), q_ptr))
     slab_d = to(np.concatenate(slabs))
     off = np.concatenate([[0], np.cumsum([len(sl) for sl in slabs])])
     p = _lib.ptr
@@ -1511,10 +1502,11 @@ def rule_apply(graph, head, body, weight, subs, rels, scratch_bytes=RULE_SCRATCH
         scratch = torch.empty(max(need), dtype=torch.uint8, device=dev)
         for c, (r0, r1) in enumerate(chunks):
             def call(phases):
-                _lib.check(_lib.lib().rg_rule_apply(graph.handle, p(h_d[r0:r1]), p(b_d[r0:r1]), p(w_d[r0:r1]), p(m_d[r0:r1]), r1 - r0, L,
-                                                    r0, p(qs_d), p(qr_d), p(qp_d), B, p(slab_d[off[c]:off[c + 1]]), int(slabs[c][-1]),
-                                                    p(scratch), phases, p(best), p(surv), p(best_rule), p(fired), _lib.stream_ptr()))
-            if RULE_APPLY_EVENTS is None:
+                _lib.check(entry(*(p(a[r0:r1]) for a in rules_d), p(w_d[r0:r1]), p(m_d[r0:r1]), r1 - r0, L, r0, p(qs_d), p(qr_d), p(qp_d),
+                                 B, p(slab_d[off[c]:off[c + 1]]), int(slabs[c][-1]), p(scratch), phases, p(best), p(surv), p(best_rule),
+                                 p(fired), _lib.stream_ptr()))
+            log = globals()[events]                      # read at call time: a test or probe assigns the attribute
+            if log is None:
                 call(3)
             else:
                 ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
@@ -1523,7 +1515,7 @@ def rule_apply(graph, head, body, weight, subs, rels, scratch_bytes=RULE_SCRATCH
                 ev[1].record()
                 call(2)
                 ev[2].record()
-                RULE_APPLY_EVENTS.append((ev[0], ev[1], ev[2], r1 - r0, int(slabs[c][-1])))
+                log.append((ev[0], ev[1], ev[2], r1 - r0, int(slabs[c][-1])))
     return best, surv, best_rule, fired
 
 
@@ -1539,16 +1531,7 @@ def check_trule_apply(graph, head, body, direction, weight, subs, rels, times):
     if not int(getattr(graph, "n_time", 0) or 0):
         raise ValueError("%s: static graph (no time ids): static rules are applied by rule_apply" % who)
     h, b, d, _ = check_trules(graph, head, body, direction, np.zeros((0, 2), np.int64), who=who)
-    if h.size > 1 and (np.diff(h) < 0).any():
-        at = int(np.argmax(np.diff(h) < 0))
-        raise ValueError("%s: head must be non-decreasing (rule %d has head %d after %d)" % (who, at + 1, h[at + 1], h[at]))
-    w = weight.detach().cpu().numpy() if torch.is_tensor(weight) else np.asarray(weight)
-    if w.dtype.kind != "f" or w.ndim != 1 or w.shape[0] != h.shape[0]:
-        raise ValueError("%s: weight must be a float array [R] (got %s %s for %d rules)" % (who, w.dtype, w.shape, h.shape[0]))
-    w = np.ascontiguousarray(w, dtype=np.float32)
-    if w.size and not (np.isfinite(w).all() and (w > 0).all() and (w <= 1).all()):
-        bad = int(np.argmax(~(np.isfinite(w) & (w > 0) & (w <= 1))))
-        raise ValueError("%s: weights must be finite and in (0, 1] as float32 (rule %d has %r)" % (who, bad, float(w[bad])))
+    w = _check_heads_and_weights(who, h, weight)
     s, r, t = _int_array(subs, "subs", who), _int_array(rels, "rels", who), _int_array(times, "times", who)
     if s.ndim != 1 or r.shape != s.shape or t.shape != s.shape:
         raise ValueError("%s: need one relation and one time per subject (got subs %s, rels %s, times %s)" % (who, s.shape, r.shape, t.shape))
@@ -1559,8 +1542,7 @@ def check_trule_apply(graph, head, body, direction, weight, subs, rels, times):
         raise ValueError("%s: query relation id out of range 0..%d (got %d..%d)" % (who, n_rows - 1, r.min(), r.max()))
     if t.size and (t.min() < 0 or t.max() >= n_time):
         raise ValueError("%s: query time id out of range 0..%d (got %d..%d)" % (who, n_time - 1, t.min(), t.max()))
-    as32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
-    return h, b, d, w, as32(s), as32(r), as32(t)
+    return h, b, d, w, _as32(s), _as32(r), _as32(t)
 
 
 def trule_apply(graph, head, body, direction, weight, subs, rels, times, scratch_bytes=RULE_SCRATCH_BYTES):
@@ -1573,52 +1555,13 @@ def trule_apply(graph, head, body, direction, weight, subs, rels, times, scratch
     first sorted position of every (relation, time id), and the rules are cut into consecutive ranges whose bitmaps fit
     ``scratch_bytes`` (rule_apply_chunking; one rule at least per call); the calls run in rule order on the current stream and carry
     the four tensors, so no bit of the result depends on the budget.  Memory: 16 bytes per (query, entity) cell plus the scratch."""
-    if isinstance(scratch_bytes, (bool, np.bool_)) or not isinstance(scratch_bytes, (int, np.integer)) or scratch_bytes < 0:
-        raise ValueError("trule_apply: scratch_bytes must be a non-negative integer (got %r)" % (scratch_bytes,))
+    scratch_bytes = _check_scratch_bytes(scratch_bytes, "trule_apply")
     h, b, d, w, s, r, t = check_trule_apply(graph, head, body, direction, weight, subs, rels, times)
-    dev = _require_gpu(graph.device)
-    R, L, B, n_ent = h.shape[0], b.shape[1], s.shape[0], int(graph.n_ent)
-    best = torch.zeros((B, n_ent), dtype=torch.float32, device=dev)
-    surv = torch.ones((B, n_ent), dtype=torch.float32, device=dev)
-    best_rule = torch.full((B, n_ent), -1, dtype=torch.int32, device=dev)
-    fired = torch.zeros((B, n_ent), dtype=torch.int32, device=dev)
-    if R == 0 or B == 0:
-        return best, surv, best_rule, fired
     n_rows, n_time = int(graph.n_rela_rows), int(graph.n_time)
     key = r.astype(np.int64) * n_time + t
     order = np.argsort(key, kind="stable")
     q_ptr = np.searchsorted(key[order], np.arange(n_rows * n_time + 1)).astype(np.int32)
     per_rel = np.diff(q_ptr[::n_time].astype(np.int64))                            # queries per relation
-    words = n_ent * ((per_rel[h] + 31) // 32)                                      # per rule
-    chunks = [(r0, r1) for r0, r1 in rule_apply_chunking(words, int(scratch_bytes)) if words[r0:r1].sum() > 0]
-    if not chunks:
-        return best, surv, best_rule, fired
-    slabs = [np.concatenate([[0], np.cumsum(words[r0:r1])]).astype(np.int64) for r0, r1 in chunks]
-    need = [rule_apply_scratch_bytes(sl[-1]) for sl in slabs]
-    if min(need) == 0:
-        raise ValueError("trule_apply: a rule's bitmap of %d words is beyond the bitmaps' range (fewer queries per call)" % max(words))
-    miss = (np.float32(1.0) - w).astype(np.float32)
-    to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    h_d, b_d, d_d, w_d, m_d, qs_d, qr_d, qp_d = (to(a) for a in (h, b, d, w, miss, s[order], order.astype(np.int32), q_ptr))
-    slab_d = to(np.concatenate(slabs))
-    off = np.concatenate([[0], np.cumsum([len(sl) for sl in slabs])])
-    p = _lib.ptr
-    with torch.cuda.device(dev):
-        scratch = torch.empty(max(need), dtype=torch.uint8, device=dev)
-        for c, (r0, r1) in enumerate(chunks):
-            def call(phases):
-                _lib.check(_lib.lib().rg_trule_apply(graph.handle, p(h_d[r0:r1]), p(b_d[r0:r1]), p(d_d[r0:r1]), p(w_d[r0:r1]),
-                                                     p(m_d[r0:r1]), r1 - r0, L, r0, p(qs_d), p(qr_d), p(qp_d), B,
-                                                     p(slab_d[off[c]:off[c + 1]]), int(slabs[c][-1]), p(scratch), phases, p(best),
-                                                     p(surv), p(best_rule), p(fired), _lib.stream_ptr()))
-            if TRULE_APPLY_EVENTS is None:
-                call(3)
-            else:
-                ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-                ev[0].record()
-                call(1)
-                ev[1].record()
-                call(2)
-                ev[2].record()
-                TRULE_APPLY_EVENTS.append((ev[0], ev[1], ev[2], r1 - r0, int(slabs[c][-1])))
-    return best, surv, best_rule, fired
+    words = int(graph.n_ent) * ((per_rel[h] + 31) // 32)                           # per rule
+    return _apply_chunks("trule_apply", "TRULE_APPLY_EVENTS", graph, (h, b, d), w, s[order], order, q_ptr, words, scratch_bytes,
+                         lambda *args: _lib.lib().rg_trule_apply(graph.handle, *args))

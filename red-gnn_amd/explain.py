@@ -25,7 +25,7 @@ steps (relation, lag bin) under the ``lag_edges`` of attention_profile with iden
 ``model.rule_quality(table)`` counts how they hold in the model's own data per anchor (entity, query day) under the forward's row
 windows (LagRuleQuality; engine.xrule_ground, csrc/xrule_ground.hip).
 """
-from dataclasses import dataclass
+from dataclasses import dataclass, fields, replace
 
 import numpy as np
 import torch
@@ -219,8 +219,49 @@ class PathSet:
         return self._gather(self.digraph.data_row, -1)
 
 
+def _check_count(x, who, name, most=None):
+    """``x`` is an integer >= 1 (and <= ``most``), or ValueError."""
+    if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)) or x < 1 or (most is not None and x > most):
+        want = "a positive integer" if most is None else "an integer in 1..%d" % most
+        raise ValueError("%s: %s must be %s (got %r)" % (who, name, want, x))
+
+
+def _cpu(x):
+    """A dataclass with every tensor of it, and every table in it, on the host."""
+    return replace(x, **{f.name: getattr(x, f.name).cpu() for f in fields(x) if hasattr(getattr(x, f.name), "cpu")})
+
+
+class _Rules:
+    """What the three rule tables share: a subclass is a dataclass with the tensors head [R], support [R], fixed [R] and body [R, L]
+    among its fields, rows sorted by its key, and the int n_rel."""
+
+    cpu = _cpu
+
+    def product_sum(self):
+        """float64 [R]: the sum of the alpha products of each rule's paths."""
+        return self.fixed.double() * 2.0 ** -FRACTION_BITS
+
+    def mean(self):
+        """float64 [R]: the mean alpha product of each rule's paths."""
+        return self.product_sum() / self.support.double()
+
+    def _rows(self, rows):
+        return replace(self, **{f.name: getattr(self, f.name)[rows] for f in fields(self) if torch.is_tensor(getattr(self, f.name))})
+
+    def top(self, q_rel, n):
+        """The n rules of query relation ``q_rel`` with the largest support (ties: the smaller body, or key), as a table in that order."""
+        _check_count(n, "top", "n")
+        rows = torch.nonzero(self.head == int(q_rel)).reshape(-1)                 # ascending: key order
+        return self._rows(rows[torch.argsort(-self.support[rows], stable=True)][:int(n)])
+
+    def _check_add(self, other):
+        if other.n_rel != self.n_rel or other.body.shape[1] != self.body.shape[1]:
+            raise ValueError("rule tables of different relation count or path length do not add (n_rel %d / %d, L %d / %d)"
+                             % (self.n_rel, other.n_rel, self.body.shape[1], other.body.shape[1]))
+
+
 @dataclass
-class RuleTable:
+class RuleTable(_Rules):
     """Paths counted as rules: one row per distinct (query relation, relation sequence r_1..r_L), sorted by (head, body).
 
     head     int64 [R]      the query relation
@@ -235,33 +276,12 @@ class RuleTable:
     fixed: torch.Tensor
     n_rel: int
 
-    def product_sum(self):
-        """float64 [R]: the sum of the alpha products of each rule's paths."""
-        return self.fixed.double() * 2.0 ** -FRACTION_BITS
-
-    def mean(self):
-        """float64 [R]: the mean alpha product of each rule's paths."""
-        return self.product_sum() / self.support.double()
-
-    def top(self, q_rel, n):
-        """The n rules of query relation ``q_rel`` with the largest support (ties: the smaller body), as a RuleTable in that order."""
-        if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or n < 1:
-            raise ValueError("top: n must be a positive integer (got %r)" % (n,))
-        rows = torch.nonzero(self.head == int(q_rel)).reshape(-1)                 # ascending: body order
-        rows = rows[torch.argsort(-self.support[rows], stable=True)][:int(n)]
-        return RuleTable(self.head[rows], self.body[rows], self.support[rows], self.fixed[rows], self.n_rel)
-
     def __add__(self, other):
         if not isinstance(other, RuleTable):
             return NotImplemented
-        if other.n_rel != self.n_rel or other.body.shape[1] != self.body.shape[1]:
-            raise ValueError("rule tables of different relation count or path length do not add (n_rel %d / %d, L %d / %d)"
-                             % (self.n_rel, other.n_rel, self.body.shape[1], other.body.shape[1]))
+        self._check_add(other)
         key = torch.cat([torch.cat([self.head[:, None], self.body], 1), torch.cat([other.head[:, None], other.body], 1)], 0)
         return _table(key, torch.cat([self.support, other.support]), torch.cat([self.fixed, other.fixed]), self.n_rel)
-
-    def cpu(self):
-        return RuleTable(self.head.cpu(), self.body.cpu(), self.support.cpu(), self.fixed.cpu(), self.n_rel)
 
     def format(self, id2rel=None):
         """One string per rule, ``r1(x,z1) ^ r2^-1(z1,y) -> q(x,y)``: identity steps dropped, ids >= n_rel printed as inverses of
@@ -281,9 +301,53 @@ class RuleTable:
         return out
 
 
+class _StepRules(_Rules):
+    """What TemporalRuleTable and LagRuleTable share: a step is a relation and a second id, held in the field ``_step`` names
+    ("direction", "lag_bin"); the fields are head, body, that one, support, fixed and then what does not change with the rows."""
+
+    def key(self):
+        """int64 [R, 1 + 2L]: (head, r_1, s_1, .., r_L, s_L), s the direction or lag bin of the step: the key the rows are sorted by."""
+        R, L = self.body.shape
+        return torch.cat([self.head[:, None], torch.stack([self.body, getattr(self, self._step)], 2).reshape(R, 2 * L)], 1)
+
+    @classmethod
+    def _merged(cls, key, support, fixed, *rest):
+        """The table of rows key int64 [P, 1 + 2L] = (head, r_1, s_1, .., r_L, s_L), equal keys merged: _table on the wide key.
+        ``rest``: the fields after ``fixed``, n_rel last."""
+        t = _table(key, support, fixed, rest[-1])
+        return cls(t.head, t.body[:, 0::2].contiguous(), t.body[:, 1::2].contiguous(), t.support, t.fixed, *rest)
+
+    def __add__(self, other):
+        if not isinstance(other, type(self)):
+            return NotImplemented
+        self._check_add(other)
+        return self._merged(torch.cat([self.key(), other.key()], 0), torch.cat([self.support, other.support]),
+                            torch.cat([self.fixed, other.fixed]), *(getattr(self, f.name) for f in fields(self)[5:]))
+
+    def _format(self, id2rel, tag):
+        """One string per rule, ``r3<tag>(x,z1) ^ r1<tag>(z1,y) -> r0(x,y)``, ``tag(s)`` the text after a step's relation; identity
+        steps dropped, the head without a tag."""
+        name = lambda r: str(id2rel[r]) if id2rel is not None else "r%d" % r
+        out = []
+        for h, b, d in zip(self.head.tolist(), self.body.tolist(), getattr(self, self._step).tolist()):
+            steps = [(r, k) for r, k in zip(b, d) if r != self.n_rel]
+            var = ["x"] + ["z%d" % i for i in range(1, len(steps))] + ["y"]
+            lhs = " ^ ".join("%s%s(%s,%s)" % (name(r), tag(k), var[i], var[i + 1]) for i, (r, k) in enumerate(steps)) if steps else "x=y"
+            out.append("%s -> %s(x,y)" % (lhs, name(h)))
+        return out
+
+
+@dataclass
 class _Quality:
-    """What RuleQuality and TemporalRuleQuality share: the ratios of the four counts and the ordering of ``top``.  A subclass has the
-    fields table, body_pairs, hits, pca_body_pairs, head_pairs and the methods trivial(), cpu() and _tie_key()."""
+    """What RuleQuality, TemporalRuleQuality and LagRuleQuality share: the rules and their four counts, the ratios of the counts and
+    the ordering of ``top``.  A subclass adds its last field (n_sources, n_anchors) and the methods trivial() and _tie_key()."""
+    table: _Rules
+    body_pairs: torch.Tensor
+    hits: torch.Tensor
+    pca_body_pairs: torch.Tensor
+    head_pairs: torch.Tensor
+
+    cpu = _cpu
 
     def _ratio(self, den):
         num, den = self.hits.double(), den.double()
@@ -304,8 +368,7 @@ class _Quality:
     def top(self, q_rel, n, by="confidence", min_hits=1, drop_trivial=True):
         """Row indices (int64, at most n) of the best rules of query relation ``q_rel`` by "confidence", "pca_confidence" or "hits",
         among those with hits >= min_hits (and not trivial).  Ties go to the larger hits, then to the smaller body."""
-        if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or n < 1:
-            raise ValueError("top: n must be a positive integer (got %r)" % (n,))
+        _check_count(n, "top", "n")
         if by not in ("confidence", "pca_confidence", "hits"):
             raise ValueError("top: by must be 'confidence', 'pca_confidence' or 'hits' (got %r)" % (by,))
         q = self.cpu()                                   # a few thousand rows at most: ordered on the host
@@ -341,13 +404,8 @@ class RuleQuality(_Quality):
     n_sources       int        number of source entities
 
     hits <= pca_body_pairs <= body_pairs and hits <= head_pairs.  confidence(), pca_confidence(), head_coverage(), top() and format()
-    are _Quality's.
+    and cpu() are _Quality's, and so are the first five fields.
     """
-    table: RuleTable
-    body_pairs: torch.Tensor
-    hits: torch.Tensor
-    pca_body_pairs: torch.Tensor
-    head_pairs: torch.Tensor
     n_sources: int
 
     def trivial(self):
@@ -358,16 +416,12 @@ class RuleQuality(_Quality):
     def _tie_key(self):
         return self.table.body
 
-    def cpu(self):
-        return RuleQuality(self.table.cpu(), self.body_pairs.cpu(), self.hits.cpu(), self.pca_body_pairs.cpu(), self.head_pairs.cpu(),
-                           self.n_sources)
-
 
 DIRECTION_ANY = 3                                        # a step that matches every edge time (engine.TRULE_DIRECTIONS)
 
 
 @dataclass
-class TemporalRuleTable:
+class TemporalRuleTable(_StepRules):
     """Paths of the temporal interpolation model counted as rules: one row per distinct (query relation, (r_1, d_1), .., (r_L, d_L)),
     sorted by that key.  d is the direction of the step's edge against the query time as the forward forms it (RDigraph.direction():
     0 past, 1 now, 2 future); an identity step (relation id n_rel; the reference gives those rows the sentinel time n_time - 1) is
@@ -386,50 +440,13 @@ class TemporalRuleTable:
     support: torch.Tensor
     fixed: torch.Tensor
     n_rel: int
-
-    product_sum = RuleTable.product_sum
-    mean = RuleTable.mean
-
-    def _rows(self, rows):
-        return TemporalRuleTable(self.head[rows], self.body[rows], self.direction[rows], self.support[rows], self.fixed[rows], self.n_rel)
-
-    def key(self):
-        """int64 [R, 1 + 2L]: (head, r_1, d_1, .., r_L, d_L), the key the rows are sorted by."""
-        R, L = self.body.shape
-        return torch.cat([self.head[:, None], torch.stack([self.body, self.direction], 2).reshape(R, 2 * L)], 1)
-
-    def top(self, q_rel, n):
-        """The n rules of query relation ``q_rel`` with the largest support (ties: the smaller key), as a table in that order."""
-        if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or n < 1:
-            raise ValueError("top: n must be a positive integer (got %r)" % (n,))
-        rows = torch.nonzero(self.head == int(q_rel)).reshape(-1)                 # ascending: key order
-        return self._rows(rows[torch.argsort(-self.support[rows], stable=True)][:int(n)])
-
-    def __add__(self, other):
-        if not isinstance(other, TemporalRuleTable):
-            return NotImplemented
-        if other.n_rel != self.n_rel or other.body.shape[1] != self.body.shape[1]:
-            raise ValueError("rule tables of different relation count or path length do not add (n_rel %d / %d, L %d / %d)"
-                             % (self.n_rel, other.n_rel, self.body.shape[1], other.body.shape[1]))
-        return _temporal_table(torch.cat([self.key(), other.key()], 0), torch.cat([self.support, other.support]),
-                               torch.cat([self.fixed, other.fixed]), self.n_rel)
-
-    def cpu(self):
-        return TemporalRuleTable(self.head.cpu(), self.body.cpu(), self.direction.cpu(), self.support.cpu(), self.fixed.cpu(), self.n_rel)
+    _step = "direction"
 
     def format(self, id2rel=None):
         """One string per rule, ``r3[past](x,z1) ^ r1(z1,y) -> r0(x,y)``: every step with its direction in brackets (none for
         "any"), identity steps dropped, the head - a "now" fact - without a tag; ``id2rel`` names the relation ids (a sequence or
         dict), else r<id>."""
-        name = lambda r: str(id2rel[r]) if id2rel is not None else "r%d" % r
-        out = []
-        for h, b, d in zip(self.head.tolist(), self.body.tolist(), self.direction.tolist()):
-            steps = [(r, k) for r, k in zip(b, d) if r != self.n_rel]
-            var = ["x"] + ["z%d" % i for i in range(1, len(steps))] + ["y"]
-            tag = lambda k: "" if k == DIRECTION_ANY else "[%s]" % engine.TRULE_DIRECTIONS[k]
-            lhs = " ^ ".join("%s%s(%s,%s)" % (name(r), tag(k), var[i], var[i + 1]) for i, (r, k) in enumerate(steps)) if steps else "x=y"
-            out.append("%s -> %s(x,y)" % (lhs, name(h)))
-        return out
+        return self._format(id2rel, lambda k: "" if k == DIRECTION_ANY else "[%s]" % engine.TRULE_DIRECTIONS[k])
 
 
 @dataclass
@@ -447,13 +464,8 @@ class TemporalRuleQuality(_Quality):
     n_anchors       int        number of anchors
 
     hits <= pca_body_pairs <= body_pairs and hits <= head_pairs.  confidence(), pca_confidence(), head_coverage(), top() and format()
-    are _Quality's.
+    and cpu() are _Quality's, and so are the first five fields.
     """
-    table: TemporalRuleTable
-    body_pairs: torch.Tensor
-    hits: torch.Tensor
-    pca_body_pairs: torch.Tensor
-    head_pairs: torch.Tensor
     n_anchors: int
 
     def trivial(self):
@@ -465,13 +477,9 @@ class TemporalRuleQuality(_Quality):
     def _tie_key(self):
         return self.table.key()[:, 1:]
 
-    def cpu(self):
-        return TemporalRuleQuality(self.table.cpu(), self.body_pairs.cpu(), self.hits.cpu(), self.pca_body_pairs.cpu(),
-                                   self.head_pairs.cpu(), self.n_anchors)
-
 
 @dataclass
-class LagRuleTable:
+class LagRuleTable(_StepRules):
     """Paths of the extrapolation model counted as rules: one row per distinct (query relation, (r_1, b_1), .., (r_L, b_L)), sorted
     by that key.  Every edge of the forecasting model lies in the past, so a step is told apart by how far back its fact lies: b is the
     bin of the edge's lag in days (RDigraph.lag(): query day minus the edge's day) under ``lag_edges``, the bins of profile.lag_bins
@@ -493,9 +501,7 @@ class LagRuleTable:
     fixed: torch.Tensor
     lag_edges: tuple
     n_rel: int
-
-    product_sum = RuleTable.product_sum
-    mean = RuleTable.mean
+    _step = "lag_bin"
 
     def __post_init__(self):
         self.lag_edges = check_lag_edges(self.lag_edges)
@@ -505,35 +511,11 @@ class LagRuleTable:
         """The bin id that stands for any lag: len(lag_edges) + 1."""
         return len(self.lag_edges) + 1
 
-    def _rows(self, rows):
-        return LagRuleTable(self.head[rows], self.body[rows], self.lag_bin[rows], self.support[rows], self.fixed[rows], self.lag_edges,
-                            self.n_rel)
-
-    def key(self):
-        """int64 [R, 1 + 2L]: (head, r_1, b_1, .., r_L, b_L), the key the rows are sorted by."""
-        R, L = self.body.shape
-        return torch.cat([self.head[:, None], torch.stack([self.body, self.lag_bin], 2).reshape(R, 2 * L)], 1)
-
-    def top(self, q_rel, n):
-        """The n rules of query relation ``q_rel`` with the largest support (ties: the smaller key), as a table in that order."""
-        if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or n < 1:
-            raise ValueError("top: n must be a positive integer (got %r)" % (n,))
-        rows = torch.nonzero(self.head == int(q_rel)).reshape(-1)                 # ascending: key order
-        return self._rows(rows[torch.argsort(-self.support[rows], stable=True)][:int(n)])
-
-    def __add__(self, other):
-        if not isinstance(other, LagRuleTable):
-            return NotImplemented
+    def _check_add(self, other):
         if other.n_rel != self.n_rel or other.body.shape[1] != self.body.shape[1] or other.lag_edges != self.lag_edges:
             raise ValueError("rule tables of different relation count, path length or lag edges do not add (n_rel %d / %d, L %d / %d, "
                              "lag_edges %r / %r)" % (self.n_rel, other.n_rel, self.body.shape[1], other.body.shape[1], self.lag_edges,
                                                      other.lag_edges))
-        return _lag_table(torch.cat([self.key(), other.key()], 0), torch.cat([self.support, other.support]),
-                          torch.cat([self.fixed, other.fixed]), self.lag_edges, self.n_rel)
-
-    def cpu(self):
-        return LagRuleTable(self.head.cpu(), self.body.cpu(), self.lag_bin.cpu(), self.support.cpu(), self.fixed.cpu(), self.lag_edges,
-                            self.n_rel)
 
     def lag_ranges(self):
         """(lag_lo, lag_hi) int64 [R, L]: the days [lag_lo, lag_hi) of every step's bin, as engine.xrule_ground takes them.  The
@@ -547,16 +529,9 @@ class LagRuleTable:
         brackets, as AttentionProfile.lag_labels() names them (``[121+d]`` for the open last bin, none for ANY), identity steps
         dropped, the head - a fact of the query day - without a tag; ``id2rel`` names the relation ids (a sequence or dict), else
         r<id>."""
-        name = lambda r: str(id2rel[r]) if id2rel is not None else "r%d" % r
         labels = ["[%d+d]" % a if b is None else ("[%dd]" % a if a == b else "[%d-%dd]" % (a, b)) for a, b in lag_labels(self.lag_edges)]
         labels.append("")
-        out = []
-        for h, b, d in zip(self.head.tolist(), self.body.tolist(), self.lag_bin.tolist()):
-            steps = [(r, k) for r, k in zip(b, d) if r != self.n_rel]
-            var = ["x"] + ["z%d" % i for i in range(1, len(steps))] + ["y"]
-            lhs = " ^ ".join("%s%s(%s,%s)" % (name(r), labels[k], var[i], var[i + 1]) for i, (r, k) in enumerate(steps)) if steps else "x=y"
-            out.append("%s -> %s(x,y)" % (lhs, name(h)))
-        return out
+        return self._format(id2rel, labels.__getitem__)
 
 
 @dataclass
@@ -574,13 +549,8 @@ class LagRuleQuality(_Quality):
     n_anchors       int        number of anchors
 
     hits <= pca_body_pairs <= body_pairs and hits <= head_pairs.  confidence(), pca_confidence(), head_coverage(), top() and format()
-    are _Quality's.
+    and cpu() are _Quality's, and so are the first five fields.
     """
-    table: LagRuleTable
-    body_pairs: torch.Tensor
-    hits: torch.Tensor
-    pca_body_pairs: torch.Tensor
-    head_pairs: torch.Tensor
     n_anchors: int
 
     def trivial(self):
@@ -589,10 +559,6 @@ class LagRuleQuality(_Quality):
 
     def _tie_key(self):
         return self.table.key()[:, 1:]
-
-    def cpu(self):
-        return LagRuleQuality(self.table.cpu(), self.body_pairs.cpu(), self.hits.cpu(), self.pca_body_pairs.cpu(), self.head_pairs.cpu(),
-                              self.n_anchors)
 
 
 def rule_quality(model, table, mode="test", sources=None, scratch_bytes=engine.RULE_SCRATCH_BYTES):
@@ -703,6 +669,30 @@ def rule_weights(quality, by="confidence", laplace=0.0, min_hits=1, drop_trivial
     return rows, weight[rows]
 
 
+def _rule_scores(best, surv, best_rule, fired, rows):
+    """RuleScores of the four outputs of engine.rule_apply / trule_apply on the rules ``rows`` of a table (int64 on the host):
+    best_rule goes from kept-rule index to table row."""
+    rows_d = torch.as_tensor(rows).to(best.device)
+    if rows_d.numel():
+        best_rule = torch.where(best_rule >= 0, rows_d.int()[best_rule.clamp(min=0).long()], best_rule)
+    return RuleScores(best, surv, best_rule, fired, rows_d)
+
+
+def _rule_prediction(rs, k, agg, q_key, known, table):
+    """RulePrediction of the k best entities of every row of the RuleScores ``rs`` under ``agg`` (engine.topk with its filter
+    ``q_key``, ``known``), each with its best rule and how many fired; empty tensors for a batch without rows."""
+    device = rs.best.device
+    if rs.best.shape[0] == 0:
+        z = lambda dt, fill: torch.full((0, int(k)), fill, dtype=dt, device=device)
+        return RulePrediction(z(torch.int64, -1), z(torch.float32, 0.0), z(torch.int64, -1), z(torch.int32, 0), table)
+    idx, val = engine.topk(rs.score(agg).contiguous(), int(k), q_key, known)
+    ids = idx.long()
+    at = ids.clamp(min=0)
+    rule = torch.where(ids >= 0, rs.best_rule.gather(1, at).long(), torch.full_like(ids, -1))
+    fired = torch.where(ids >= 0, rs.fired.gather(1, at), torch.zeros_like(idx))
+    return RulePrediction(ids, val, rule, fired, table)
+
+
 def rule_scores(model, quality, subs, rels, by="confidence", laplace=0.0, min_hits=1, drop_trivial=True, mode="test",
                 scratch_bytes=engine.RULE_SCRATCH_BYTES):
     """RED_GNN_trans.rule_scores (see there)."""
@@ -715,35 +705,22 @@ def rule_scores(model, quality, subs, rels, by="confidence", laplace=0.0, min_hi
     graph = model.loader.graph_for(mode)
     head, body = table.head.cpu().numpy()[rows], table.body.cpu().numpy()[rows]
     best, surv, best_rule, fired = engine.rule_apply(graph, head, body, weight, _ids(subs, "subs"), _ids(rels, "rels"), scratch_bytes)
-    rows_d = torch.as_tensor(rows).to(best.device)
-    if rows_d.numel():                                   # kept-rule index -> table row
-        best_rule = torch.where(best_rule >= 0, rows_d.int()[best_rule.clamp(min=0).long()], best_rule)
-    return RuleScores(best, surv, best_rule, fired, rows_d)
+    return _rule_scores(best, surv, best_rule, fired, rows)
 
 
 def rule_predict(model, quality, subs, rels, k=10, agg="noisy_or", exclude_known=True, mode="test", **kw):
     """RED_GNN_trans.rule_predict (see there)."""
     from .prediction import K_MAX, _known_on_device
     _check_agg(agg, "rule_predict")
-    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= k <= K_MAX:
-        raise ValueError("rule_predict: k must be an integer in 1..%d (got %r)" % (K_MAX, k))
+    _check_count(k, "rule_predict", "k", K_MAX)
     subs_h, rels_h = _ids(subs, "subs"), _ids(rels, "rels")
     rs = rule_scores(model, quality, subs_h, rels_h, mode=mode, **kw)
     device = rs.best.device
-    B = rs.best.shape[0]
     known, q_key = None, None
     if exclude_known:
         known = _known_on_device(model.loader, mode, device)
         q_key = torch.as_tensor(subs_h * (2 * model.n_rel + 1) + rels_h, dtype=torch.int64).to(device)
-    if B == 0:
-        z = lambda dt, fill: torch.full((0, int(k)), fill, dtype=dt, device=device)
-        return RulePrediction(z(torch.int64, -1), z(torch.float32, 0.0), z(torch.int64, -1), z(torch.int32, 0), quality.table)
-    idx, val = engine.topk(rs.score(agg).contiguous(), int(k), q_key, known)
-    ids = idx.long()
-    at = ids.clamp(min=0)
-    rule = torch.where(ids >= 0, rs.best_rule.gather(1, at).long(), torch.full_like(ids, -1))
-    fired = torch.where(ids >= 0, rs.fired.gather(1, at), torch.zeros_like(idx))
-    return RulePrediction(ids, val, rule, fired, quality.table)
+    return _rule_prediction(rs, k, agg, q_key, known, quality.table)
 
 
 def split_rule_ranks(base, quality, data="test", agg="noisy_or", batch=256, max_queries=None, **kw):
@@ -753,8 +730,7 @@ def split_rule_ranks(base, quality, data="test", agg="noisy_or", batch=256, max_
     if data not in ("valid", "test"):
         raise ValueError("rule_evaluate: data must be 'valid' or 'test' (got %r)" % (data,))
     _check_agg(agg, "rule_evaluate")
-    if isinstance(batch, (bool, np.bool_)) or not isinstance(batch, (int, np.integer)) or batch < 1:
-        raise ValueError("rule_evaluate: batch must be a positive integer (got %r)" % (batch,))
+    _check_count(batch, "rule_evaluate", "batch")
     loader = base.loader
     n_all = len(loader.valid_q if data == "valid" else loader.test_q)
     n = n_all if max_queries is None else min(n_all, int(max_queries))
@@ -813,38 +789,25 @@ def temporal_rule_scores(model, quality, batch, by="confidence", laplace=0.0, mi
     t = quality.table
     head, body, direction = (x.cpu().numpy()[rows] for x in (t.head, t.body, t.direction))
     best, surv, best_rule, fired = engine.trule_apply(model.graph, head, body, direction, weight, heads, rels, times, scratch_bytes)
-    rows_d = torch.as_tensor(rows).to(best.device)
-    if rows_d.numel():                                   # kept-rule index -> table row
-        best_rule = torch.where(best_rule >= 0, rows_d.int()[best_rule.clamp(min=0).long()], best_rule)
-    return RuleScores(best, surv, best_rule, fired, rows_d)
+    return _rule_scores(best, surv, best_rule, fired, rows)
 
 
 def temporal_rule_predict(model, quality, batch, k=10, agg="noisy_or", known=None, **kw):
     """T_RED_GNN.rule_predict (see there)."""
     from .prediction import K_MAX
     _check_agg(agg, "rule_predict")
-    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= k <= K_MAX:
-        raise ValueError("rule_predict: k must be an integer in 1..%d (got %r)" % (K_MAX, k))
+    _check_count(k, "rule_predict", "k", K_MAX)
     if known is not None and (not isinstance(known, (tuple, list)) or len(known) != 3):
         raise ValueError("rule_predict: known must be the (keys, ptr, idx) triple of temporal_known_index")
     rs = temporal_rule_scores(model, quality, batch, who="rule_predict", **kw)
     heads, rels, times = _temporal_queries(model, batch, "rule_predict")
     device = rs.best.device
-    B = rs.best.shape[0]
-    if B == 0:
-        z = lambda dt, fill: torch.full((0, int(k)), fill, dtype=dt, device=device)
-        return RulePrediction(z(torch.int64, -1), z(torch.float32, 0.0), z(torch.int64, -1), z(torch.int32, 0), quality.table)
     q_key = None
-    if known is not None:
+    if known is not None and rs.best.shape[0]:
         known = tuple(torch.as_tensor(x).to(device=device, dtype=dt).contiguous()
                       for x, dt in zip(known, (torch.int64, torch.int64, torch.int32)))
         q_key = torch.as_tensor((heads * (model.n_rel + 1) + rels) * model.n_time + times, dtype=torch.int64).to(device)
-    idx, val = engine.topk(rs.score(agg).contiguous(), int(k), q_key, known)
-    ids = idx.long()
-    at = ids.clamp(min=0)
-    rule = torch.where(ids >= 0, rs.best_rule.gather(1, at).long(), torch.full_like(ids, -1))
-    fired = torch.where(ids >= 0, rs.fired.gather(1, at), torch.zeros_like(idx))
-    return RulePrediction(ids, val, rule, fired, quality.table)
+    return _rule_prediction(rs, k, agg, q_key, known, quality.table)
 
 
 def temporal_filter_lists(keys_of, tails, known):
@@ -871,8 +834,7 @@ def temporal_rule_evaluate(model, quads, quality=None, mine=None, k=1, agg="nois
     _check_agg(agg, who)
     if (quality is None) == (mine is None):
         raise ValueError("%s: give exactly one of quality (a TemporalRuleQuality) and mine (quadruples to mine the rules from)" % who)
-    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= k <= engine.PATHS_MAX_K:
-        raise ValueError("%s: k must be an integer in 1..%d (got %r)" % (who, engine.PATHS_MAX_K, k))
+    _check_count(k, who, "k", engine.PATHS_MAX_K)
     q = check_quads(model, quads, batch_size, who)
     _check_known(known, who, "known")
     _check_known(known_static, who, "known_static")
@@ -915,54 +877,49 @@ def _table(key, support, fixed, n_rel):
                      n_rel)
 
 
+def _path_query_rels(who, paths, q_rel, n_rel, n_ids, n_ids_text):
+    """(q int64 [B] on the paths' device, n_rel as int): one query relation in 0..n_ids-1 per row of a PathSet, or ValueError."""
+    B = paths.edge.shape[0]
+    q = torch.as_tensor(_ids(q_rel, "q_rel")).to(paths.edge.device)
+    if q.numel() != B:
+        raise ValueError("%s: %d query relations for %d rows" % (who, q.numel(), B))
+    if int(n_rel) < 1 or (B > 0 and (int(q.min()) < 0 or int(q.max()) >= n_ids)):
+        raise ValueError("%s: query relation id out of range (%s=%d)" % (who, n_ids_text, n_ids))
+    return q, int(n_rel)
+
+
+def _path_rules(paths, q, steps):
+    """(key int64 [P, 1 + W], support, fixed int64 [P]) of the P present paths of a PathSet: row b's paths have the key (q[b],
+    steps[b, j]), ``steps`` int64 [B, k, W]; every path counts once, with its product rounded once, in float64, to
+    floor(p * 2^32 + 0.5) units of 2^-32."""
+    B, k = paths.edge.shape[:2]
+    have = torch.arange(k, device=q.device)[None, :] < paths.count.long()[:, None]          # [B, k]
+    key = torch.cat([q[:, None, None].expand(B, k, 1), steps], -1)[have]
+    fixed = torch.floor(paths.product[have] * 2.0 ** FRACTION_BITS + 0.5).long()
+    return key, torch.ones_like(fixed), fixed
+
+
+def _step_keys(rel, step):
+    """int64 [B, k, 2L]: (r_1, s_1, .., r_L, s_L) of every path, from its relations and second ids [B, k, L] each."""
+    return torch.stack([rel, step], 3).reshape(*rel.shape[:2], 2 * rel.shape[2])
+
+
 def rules_from_paths(paths, q_rel, n_rel):
     """The RuleTable of a PathSet: every present path of row b counts once for the rule (q_rel[b], its relation sequence), with its
     product rounded once, in float64, to floor(p * 2^32 + 0.5) units of 2^-32.  ``q_rel``: one query relation per row."""
-    B, k, L = paths.edge.shape
-    dev = paths.edge.device
-    q = torch.as_tensor(_ids(q_rel, "q_rel")).to(dev)
-    if q.numel() != B:
-        raise ValueError("rules_from_paths: %d query relations for %d rows" % (q.numel(), B))
-    n_rel = int(n_rel)
-    if n_rel < 1 or (B > 0 and (int(q.min()) < 0 or int(q.max()) > 2 * n_rel)):
-        raise ValueError("rules_from_paths: query relation id out of range (2*n_rel+1=%d)" % (2 * n_rel + 1))
-    have = torch.arange(k, device=dev)[None, :] < paths.count.long()[:, None]                # [B, k]
-    key = torch.cat([q[:, None, None].expand(B, k, 1), paths.rels()], -1)[have]              # [P, 1 + L]
-    fixed = torch.floor(paths.product[have] * 2.0 ** FRACTION_BITS + 0.5).long()
-    return _table(key, torch.ones_like(fixed), fixed, n_rel)
-
-
-def _temporal_table(key, support, fixed, n_rel):
-    """TemporalRuleTable of rows key int64 [P, 1 + 2L] = (head, r_1, d_1, .., r_L, d_L), equal keys merged: _table on the wide key."""
-    t = _table(key, support, fixed, n_rel)
-    return TemporalRuleTable(t.head, t.body[:, 0::2].contiguous(), t.body[:, 1::2].contiguous(), t.support, t.fixed, n_rel)
+    q, n_rel = _path_query_rels("rules_from_paths", paths, q_rel, n_rel, 2 * int(n_rel) + 1, "2*n_rel+1")
+    return _table(*_path_rules(paths, q, paths.rels()), n_rel)
 
 
 def temporal_rules_from_paths(paths, q_rel, n_rel):
     """The TemporalRuleTable of a PathSet of a temporal r-digraph: every present path of row b counts once for the rule (q_rel[b],
     its steps' (relation, direction)), the directions read from paths.digraph.direction() and an identity step (relation ``n_rel``)
     written as direction 3; products rounded as rules_from_paths rounds them.  ``q_rel``: one query relation per row."""
-    B, k, L = paths.edge.shape
-    dev = paths.edge.device
-    q = torch.as_tensor(_ids(q_rel, "q_rel")).to(dev)
-    if q.numel() != B:
-        raise ValueError("temporal_rules_from_paths: %d query relations for %d rows" % (q.numel(), B))
-    n_rel = int(n_rel)
-    if n_rel < 1 or (B > 0 and (int(q.min()) < 0 or int(q.max()) > n_rel)):
-        raise ValueError("temporal_rules_from_paths: query relation id out of range (n_rel+1=%d)" % (n_rel + 1))
+    q, n_rel = _path_query_rels("temporal_rules_from_paths", paths, q_rel, n_rel, int(n_rel) + 1, "n_rel+1")
     rel = paths.rels()
     d = paths._gather(paths.digraph.direction().long(), -1)
     d = torch.where(rel == n_rel, torch.full_like(d, DIRECTION_ANY), d)
-    have = torch.arange(k, device=dev)[None, :] < paths.count.long()[:, None]                # [B, k]
-    key = torch.cat([q[:, None, None].expand(B, k, 1), torch.stack([rel, d], 3).reshape(B, k, 2 * L)], -1)[have]     # [P, 1 + 2L]
-    fixed = torch.floor(paths.product[have] * 2.0 ** FRACTION_BITS + 0.5).long()
-    return _temporal_table(key, torch.ones_like(fixed), fixed, n_rel)
-
-
-def _lag_table(key, support, fixed, lag_edges, n_rel):
-    """LagRuleTable of rows key int64 [P, 1 + 2L] = (head, r_1, b_1, .., r_L, b_L), equal keys merged: _table on the wide key."""
-    t = _table(key, support, fixed, n_rel)
-    return LagRuleTable(t.head, t.body[:, 0::2].contiguous(), t.body[:, 1::2].contiguous(), t.support, t.fixed, lag_edges, n_rel)
+    return TemporalRuleTable._merged(*_path_rules(paths, q, _step_keys(rel, d)), n_rel)
 
 
 def lag_rules_from_paths(paths, q_rel, n_rel, lag_edges):
@@ -970,23 +927,13 @@ def lag_rules_from_paths(paths, q_rel, n_rel, lag_edges):
     its steps' (relation, lag bin)), the lags read from paths.digraph.lag() and binned as profile.lag_bins bins them, an identity step
     (relation ``n_rel``, the model's n_rel_true) written as ANY; products rounded as rules_from_paths rounds them.  ``q_rel``: one
     query relation per row."""
-    B, k, L = paths.edge.shape
-    dev = paths.edge.device
     edges = check_lag_edges(lag_edges)
-    q = torch.as_tensor(_ids(q_rel, "q_rel")).to(dev)
-    if q.numel() != B:
-        raise ValueError("lag_rules_from_paths: %d query relations for %d rows" % (q.numel(), B))
-    n_rel = int(n_rel)
-    if n_rel < 1 or (B > 0 and (int(q.min()) < 0 or int(q.max()) > n_rel)):
-        raise ValueError("lag_rules_from_paths: query relation id out of range (n_rel+1=%d)" % (n_rel + 1))
+    q, n_rel = _path_query_rels("lag_rules_from_paths", paths, q_rel, n_rel, int(n_rel) + 1, "n_rel+1")
     rel = paths.rels()
     lag = paths._gather(paths.digraph.lag().long(), 0)
-    b = torch.bucketize(lag, torch.tensor(edges, dtype=torch.int64, device=dev), right=True)      # profile.lag_bins: side="right"
+    b = torch.bucketize(lag, torch.tensor(edges, dtype=torch.int64, device=q.device), right=True)      # profile.lag_bins: side="right"
     b = torch.where(rel == n_rel, torch.full_like(b, len(edges) + 1), b)
-    have = torch.arange(k, device=dev)[None, :] < paths.count.long()[:, None]                # [B, k]
-    key = torch.cat([q[:, None, None].expand(B, k, 1), torch.stack([rel, b], 3).reshape(B, k, 2 * L)], -1)[have]     # [P, 1 + 2L]
-    fixed = torch.floor(paths.product[have] * 2.0 ** FRACTION_BITS + 0.5).long()
-    return _lag_table(key, torch.ones_like(fixed), fixed, edges, n_rel)
+    return LagRuleTable._merged(*_path_rules(paths, q, _step_keys(rel, b)), edges, n_rel)
 
 
 def rules(model, subs, rels, objs=None, k=1, mode="test", min_alpha=0.0):
