@@ -585,6 +585,49 @@ int rg_trule_apply(const rg_graph* g, const int32_t* head, const int32_t* body, 
                    const int32_t* q_ptr, int32_t batch, const int64_t* slab, int64_t n_words, void* scratch, int32_t phases,
                    float* best, float* surv, int32_t* best_rule, int32_t* fired, void* stream);
 
+/* ---- extrapolation rule application: rg_rule_apply for the one-graph layout of the forecasting model (extrapolation.T_RED_GNN): which
+ * answers weighted extrapolation rules forecast for queries (s, r, ?, day t), and which rule is behind each; no counterpart in the
+ * reference.  The graph, row_day, the windows and loop_window are exactly those of rg_xrule_ground, and a step admits an edge for a
+ * query of day t exactly as rg_xrule_ground admits it for an anchor of day t: a step (r, [lo, hi)) admits the data row j = (u, r, v)
+ * iff win_lo[t] <= j < win_hi[t] and lo <= t - row_day[j] < hi, and the self-loop (u, n_rel_true, u) iff lo <= min(t, loop_window) <
+ * hi.  The rules are (head[i], (body[i][l], [lag_lo[i][l], lag_hi[i][l])), weight[i]), i = 0..n_rules-1, l = 0..n_hops-1, head
+ * non-decreasing, weight fp32 in (0, 1] and miss[i] = fl32(1 - weight[i]) formed by the caller.  The queries are (sub[b], rel[b],
+ * day[b]), b = 0..batch-1, duplicates allowed.  Rule i fires for cell (b, y) iff head[i] == rel[b] and there are z_0 = sub[b], ..,
+ * z_L = y with a row (z_{l-1}, body[i][l], z_l) that step l admits for day[b], for every l (a repeated row counts once: the products
+ * are boolean).  There is no head pass.  The four outputs, fp32 / fp32 / int32 / int32 [batch, n_ent] with row stride n_ent, are
+ * initialised by the caller (0 / 1 / -1 / 0) and folded exactly as in rg_rule_apply, in ascending i:
+ *   fired += 1;  surv = fl32(surv * miss[i]);  if (weight[i] > best) { best = weight[i]; best_rule = rule_base + i; }
+ * Every output is the same bit for bit in every run, for every grid and lane-group choice, and however the rules are cut into
+ * consecutive calls on one stream.
+ * The queries are given sorted stably by (rel, day): q_sub int32 [batch] the subjects and q_row int32 [batch] the caller's row b, both
+ * in sorted order, and q_ptr int32 [n_rela_rows + 1] with the sorted positions of relation h = q_ptr[h]..q_ptr[h + 1], one entry per
+ * relation as in rg_rule_apply; S_i, W_i, slab int64 [n_rules + 1], n_words = slab[n_rules] and the scratch of
+ * rg_rule_apply_scratch_bytes(n_words) bytes are that function's too.  The distinct query days of every relation are the "entries":
+ * day_ptr int32 [n_rela_rows + 1] - relation h owns the entries day_ptr[h]..day_ptr[h + 1] -, day_of int32 [n_qdays] the day of every
+ * entry, ascending inside a relation, and day_pos int32 [n_qdays + 1] the first sorted position of every entry, day_pos[n_qdays] =
+ * batch.  Entry k of relation h owns the columns [day_pos[k] - q_ptr[h], day_pos[k + 1] - q_ptr[h]) of the rule's slab.  For a data
+ * row j the hop finds the first entry whose day is >= row_day[j] + lag_lo by binary search, walks the entries while their day is below
+ * min(row_day[j] + lag_hi, n_day), tests each entry's day against its window and moves every run of consecutive passing entries as one
+ * column range, masked at both end words and ORed with integer atomics; a self-loop's days are one range found by two binary searches
+ * (csrc/xrule_apply.hip).  Per edge that is O(log entries + entries in range), whatever n_day is.  phases: 1 = zero the scratch, seed
+ * and hop, 2 = aggregate, 3 = both.  All arrays are DEVICE arrays; n_hops in 1..32, n_rules <= 65535.  Errors: a NULL graph, a graph
+ * that is not the extrapolation layout (n_time != n_data + 1, or no CSR by relation with edge times), n_rules / n_hops / batch / phases
+ * / rule_base / n_words out of range, n_day < 1, loop_window < 0, n_qdays < 0, a NULL array; n_rules == 0 or batch == 0 does nothing.
+ * A relation id outside 0..n_rela_rows-1 is tested before any load and reads nothing, lag_lo >= lag_hi makes the step empty, an edge
+ * end or subject outside 0..n_ent-1, a row index outside 0..n_data, a row_day or day_of value outside 0..n_day-1 and a q_row outside
+ * 0..batch-1 are skipped, the candidate days are formed in 64 bits and clamped to 0..n_day, day_ptr entries are clamped to 0..n_qdays,
+ * day_pos and q_ptr entries to 0..batch and every range to 0..S_i, an empty range moves nothing and a slab outside 0..n_words is left
+ * out; an unsorted head or day_of makes the result of the rules concerned unspecified: nothing outside the graph's arrays,
+ * row_day[0..n_data), win_lo / win_hi[0..n_day), the query arrays, the scratch or the four outputs is touched whatever the arrays
+ * hold; the caller validates them (engine.py).  Allocates nothing, asynchronous on `stream`. */
+int rg_xrule_apply(const rg_graph* g, const int32_t* head, const int32_t* body, const int32_t* lag_lo, const int32_t* lag_hi,
+                   const float* weight, const float* miss, int32_t n_rules, int32_t n_hops, int32_t rule_base,
+                   const int32_t* row_day, int32_t n_data, const int32_t* win_lo, const int32_t* win_hi, int32_t n_day,
+                   int32_t loop_window, const int32_t* q_sub, const int32_t* q_row, const int32_t* q_ptr,
+                   const int32_t* day_ptr, const int32_t* day_of, const int32_t* day_pos, int32_t n_qdays, int32_t batch,
+                   const int64_t* slab, int64_t n_words, void* scratch, int32_t phases,
+                   float* best, float* surv, int32_t* best_rule, int32_t* fired, void* stream);
+
 /* rg_dense_fwd with the node count read on the device (after rg_frontier_expand_async): n_cap = capacity of the row buffers,
  * n_dev = rg_frontier_count_ptr() of the frontier whose newest level the rows belong to, n_hint = the row count the caller expects
  * (0 = unknown): it only sizes the grid, every row count up to n_cap is processed correctly. */

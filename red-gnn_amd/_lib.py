@@ -31,6 +31,7 @@ SYMBOLS = [
     "rg_trule_ground_scratch_bytes", "rg_trule_ground",
     "rg_trule_apply",
     "rg_xrule_ground",
+    "rg_xrule_apply",
 ]
 
 _lib = None
@@ -154,6 +155,8 @@ def lib():
     L.rg_trule_ground.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, i32, vp, vp, vp]
     L.rg_xrule_ground.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, vp, i32, i32, vp, vp, i32, vp, vp, vp]
     L.rg_trule_apply.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, i64, vp, i32, vp, vp, vp, vp, vp]
+    L.rg_xrule_apply.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32,
+                                 vp, i64, vp, i32, vp, vp, vp, vp, vp]
     _lib = L
     return L
 

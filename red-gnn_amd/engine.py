@@ -1472,11 +1472,11 @@ def rule_apply(graph, head, body, weight, subs, rels, scratch_bytes=RULE_SCRATCH
 
 
 def _apply_chunks(who, events, graph, rules, w, q_sub, q_row, q_ptr, words, scratch_bytes, entry):
-    """What rule_apply and trule_apply do once the queries are sorted: the four outputs [B, n_ent], the rules cut into consecutive
-    calls as rule_apply_chunking says, every call's slabs, and the calls in rule order.  ``rules``: the per-rule int32 arrays in the
-    entry point's order, (head, body) or (head, body, direction); ``w`` their weights; ``q_sub`` [B] the subjects in sorted order,
-    ``q_row`` [B] the caller's row of every sorted position, ``q_ptr`` as the entry point takes it; ``words`` [R] the words of every
-    rule's slab; ``entry(*args)``: the entry point after its graph.  ``events`` names the module attribute (RULE_APPLY_EVENTS, ...):
+    """What rule_apply, trule_apply and xrule_apply do once the queries are sorted: the four outputs [B, n_ent], the rules cut into
+    consecutive calls as rule_apply_chunking says, every call's slabs, and the calls in rule order.  ``rules``: the per-rule int32
+    arrays in the entry point's order, (head, body), (head, body, direction) or (head, body, lag_lo, lag_hi); ``w`` their weights;
+    ``q_sub`` [B] the subjects in sorted order, ``q_row`` [B] the caller's row of every sorted position, ``q_ptr`` as the entry point
+    takes it; ``words`` [R] the words of every rule's slab; ``entry(*args)``: the entry point after its graph.  ``events`` names the module attribute (RULE_APPLY_EVENTS, ...):
     where a probe has set it to a list a call is split into its two phases and the three events around them, the rules and the words
     of the call are collected."""
     dev = _require_gpu(graph.device)
@@ -1565,3 +1565,75 @@ def trule_apply(graph, head, body, direction, weight, subs, rels, times, scratch
     words = int(graph.n_ent) * ((per_rel[h] + 31) // 32)                           # per rule
     return _apply_chunks("trule_apply", "TRULE_APPLY_EVENTS", graph, (h, b, d), w, s[order], order, q_ptr, words, scratch_bytes,
                          lambda *args: _lib.lib().rg_trule_apply(graph.handle, *args))
+
+
+# tools/probe_xrule_apply.py sets this to a list to collect (start, after seed + hops, end events, n_rules, n_words) per call of xrule_apply
+XRULE_APPLY_EVENTS = None
+
+
+def check_xrule_apply(graph, head, body, lag_lo, lag_hi, weight, subs, rels, days, row_day, win_lo, win_hi,
+                      loop_window=XRULE_LOOP_WINDOW):
+    """The host validation of xrule_apply: (head int32 [R], body, lag_lo, lag_hi int32 [R, L], weight fp32 [R], subs, rels, days int32
+    [B], row_day int32 [n_data], win_lo, win_hi int32 [n_day]) as contiguous numpy arrays, or ValueError.  ``graph`` needs n_ent,
+    n_rela_rows and n_time = n_data + 1; no device is touched."""
+    who = "xrule_apply"
+    h, b, lo, hi, day, w_lo, w_hi, _ = check_xrules(graph, head, body, lag_lo, lag_hi, row_day, win_lo, win_hi, np.zeros((0, 2), np.int64),
+                                                    loop_window, who=who)
+    w = _check_heads_and_weights(who, h, weight)
+    s, r, t = _int_array(subs, "subs", who), _int_array(rels, "rels", who), _int_array(days, "days", who)
+    if s.ndim != 1 or r.shape != s.shape or t.shape != s.shape:
+        raise ValueError("%s: need one relation and one day per subject (got subs %s, rels %s, days %s)" % (who, s.shape, r.shape, t.shape))
+    n_ent, n_rows, n_day = int(graph.n_ent), int(graph.n_rela_rows), w_lo.shape[0]
+    if s.size and (s.min() < 0 or s.max() >= n_ent):
+        raise ValueError("%s: subject id out of range 0..%d (got %d..%d)" % (who, n_ent - 1, s.min(), s.max()))
+    if r.size and (r.min() < 0 or r.max() >= n_rows):
+        raise ValueError("%s: query relation id out of range 0..%d (got %d..%d)" % (who, n_rows - 1, r.min(), r.max()))
+    if t.size and (t.min() < 0 or t.max() >= n_day):
+        raise ValueError("%s: query day out of range 0..%d (got %d..%d)" % (who, n_day - 1, t.min(), t.max()))
+    return h, b, lo, hi, w, _as32(s), _as32(r), _as32(t), day, w_lo, w_hi
+
+
+def xrule_query_layout(rels, days, n_rows, n_day):
+    """The query layout of rg_xrule_apply for the queries (rels[b], days[b]), relations 0..n_rows-1 and days 0..n_day-1: (order, q_ptr,
+    day_ptr, day_of, day_pos).  ``order`` [B] sorts the queries stably by (relation, day); q_ptr int32 [n_rows + 1] holds the first
+    sorted position of every relation; the entries are the distinct (relation, day) pairs in sorted order: day_ptr int32 [n_rows + 1]
+    the entries of every relation, day_of int32 [D] their days, day_pos int32 [D + 1] their first sorted positions, day_pos[D] = B."""
+    r, t = np.asarray(rels, np.int64).reshape(-1), np.asarray(days, np.int64).reshape(-1)
+    key = r * int(n_day) + t
+    order = np.argsort(key, kind="stable")
+    entries, first = np.unique(key[order], return_index=True)
+    q_ptr = np.searchsorted(r[order], np.arange(n_rows + 1)).astype(np.int32)
+    day_ptr = np.searchsorted(entries // int(n_day), np.arange(n_rows + 1)).astype(np.int32)
+    day_pos = np.concatenate([first, [len(r)]]).astype(np.int32)
+    return order, q_ptr, day_ptr, (entries % int(n_day)).astype(np.int32), day_pos
+
+
+def xrule_apply(graph, head, body, lag_lo, lag_hi, weight, subs, rels, days, row_day, win_lo, win_hi, loop_window=XRULE_LOOP_WINDOW,
+                scratch_bytes=RULE_SCRATCH_BYTES):
+    """The extrapolation rules (head[i], (body[i], [lag_lo[i], lag_hi[i])), weight[i]) applied to the queries (subs[b], rels[b], ?,
+    days[b]) on the one-graph layout ``graph`` of extrapolation.T_RED_GNN (rg_xrule_apply; include/redgnn.h has the definition): the
+    four device tensors [B, n_ent] of rule_apply - ``best`` fp32, ``surv`` fp32, ``best_rule`` int32 and ``fired`` int32 - over the
+    rules whose head is the query relation and whose steps lead from the subject to the entity through rows that each step admits for
+    the query day, exactly as xrule_ground admits them for an anchor of that day (``row_day``, ``win_lo`` / ``win_hi`` and
+    ``loop_window`` as there).  ``head`` non-decreasing, weights in (0, 1], relation ids the graph's (0..n_rela_rows-1), days in
+    0..n_day-1, duplicate queries allowed; all validated on the host (ValueError).  The queries are sorted stably by (relation, day)
+    and the distinct days of every relation are listed (xrule_query_layout); the rules are cut into consecutive ranges whose bitmaps
+    fit ``scratch_bytes`` (rule_apply_chunking; one rule at least per call); the calls run in rule order on the current stream and
+    carry the four tensors, so no bit of the result depends on the budget.  Memory: 16 bytes per (query, entity) cell plus the
+    scratch."""
+    scratch_bytes = _check_scratch_bytes(scratch_bytes, "xrule_apply")
+    h, b, lo, hi, w, s, r, t, day, w_lo, w_hi = check_xrule_apply(graph, head, body, lag_lo, lag_hi, weight, subs, rels, days, row_day,
+                                                                  win_lo, win_hi, loop_window)
+    n_data, n_day, p = day.shape[0], w_lo.shape[0], _lib.ptr
+    order, q_ptr, day_ptr, day_of, day_pos = xrule_query_layout(r, t, int(graph.n_rela_rows), n_day)
+    words = int(graph.n_ent) * ((np.diff(q_ptr).astype(np.int64)[h] + 31) // 32)     # per rule
+    bound = []                       # the device arrays beyond _apply_chunks' own, uploaded by the first call
+
+    def entry(*a):                   # a: head, body, lag_lo, lag_hi, weight, miss, n_rules, L, rule_base | q_sub, q_row, q_ptr | the rest
+        if not bound:
+            dev = _require_gpu(graph.device)
+            bound.extend(torch.from_numpy(x).to(dev) for x in (day, w_lo, w_hi, day_ptr, day_of, day_pos))
+        day_d, wl_d, wh_d, dp_d, do_d, ds_d = bound
+        return _lib.lib().rg_xrule_apply(graph.handle, *a[:9], p(day_d), n_data, p(wl_d), p(wh_d), n_day, int(loop_window), *a[9:12],
+                                         p(dp_d), p(do_d), p(ds_d), day_of.shape[0], *a[12:])
+    return _apply_chunks("xrule_apply", "XRULE_APPLY_EVENTS", graph, (h, b, lo, hi), w, s[order], order, q_ptr, words, scratch_bytes, entry)

@@ -23,7 +23,8 @@ forward; ``rd.data_row`` names the past fact behind every edge (-1: a self-loop,
 ``rd.lag()`` how many days before the query it lies.  ``table = model.rules(X, objs, k=2)`` counts the best paths as lag-binned rules,
 steps (relation, lag bin) under the ``lag_edges`` of attention_profile with identity steps written as ANY (LagRuleTable), and
 ``model.rule_quality(table)`` counts how they hold in the model's own data per anchor (entity, query day) under the forward's row
-windows (LagRuleQuality; engine.xrule_ground, csrc/xrule_ground.hip).
+windows (LagRuleQuality; engine.xrule_ground, csrc/xrule_ground.hip); ``model.rule_scores(quality, X)`` / ``rule_predict`` /
+``rule_evaluate`` apply the weighted rules to queries (engine.xrule_apply, csrc/xrule_apply.hip).
 """
 from dataclasses import dataclass, fields, replace
 
@@ -33,7 +34,7 @@ import torch
 from . import engine
 from .models import _pad4, pad_attn
 from .profile import FRACTION_BITS                       # sums in units of 2^-32, as the attention profile's
-from .profile import check_lag_edges, lag_labels
+from .profile import DEFAULT_LAG_EDGES, check_lag_edges, lag_labels
 
 
 @dataclass
@@ -649,9 +650,10 @@ class RulePrediction:
 def rule_weights(quality, by="confidence", laplace=0.0, min_hits=1, drop_trivial=True):
     """(rows int64 [K], weight float32 [K]) on the host: the rules of ``quality`` kept for scoring, in table order, and their weights
     float32(hits / (den + laplace)) formed in float64, den = body_pairs (by="confidence") or pca_body_pairs ("pca_confidence").  Kept:
-    hits >= min_hits, weight > 0, and not trivial() unless ``drop_trivial`` is False.  ``quality``: a RuleQuality or a
-    TemporalRuleQuality (the same counts and trivial(); the drivers check which of the two they take)."""
-    if not isinstance(quality, (RuleQuality, TemporalRuleQuality)):
+    hits >= min_hits, weight > 0, and not trivial() unless ``drop_trivial`` is False.  ``quality``: a RuleQuality, a
+    TemporalRuleQuality or a LagRuleQuality (the same counts and trivial(), which is all False for the last; the drivers check which
+    of the three they take)."""
+    if not isinstance(quality, (RuleQuality, TemporalRuleQuality, LagRuleQuality)):
         raise ValueError("rule_scores: quality must be an explain.RuleQuality (got %s)" % type(quality).__name__)
     if by not in ("confidence", "pca_confidence"):
         raise ValueError("rule_scores: by must be 'confidence' or 'pca_confidence' (got %r)" % (by,))
@@ -825,6 +827,17 @@ def temporal_filter_lists(keys_of, tails, known):
     return ptr, np.concatenate(lists).astype(np.int32)
 
 
+def _rule_metrics(ranks, covered, n):
+    """The dict temporal_rule_evaluate and lag_rule_evaluate return: n, coverage = covered / n and hits1 / hits3 / hits10 / mrr / mr
+    of ``ranks`` = {suffix: list of float64 rank tensors, n ranks in all} for every suffix of evaluation.KINDS; sums in float64."""
+    out = {"n": n, "coverage": covered / n}
+    for sfx, parts in ranks.items():
+        rank = torch.cat(parts).cpu().numpy()
+        out["hits1" + sfx], out["hits3" + sfx], out["hits10" + sfx] = (float(np.sum(rank <= c) / n) for c in (1, 3, 10))
+        out["mrr" + sfx], out["mr" + sfx] = float(np.sum(1.0 / rank) / n), float(np.sum(rank) / n)
+    return out
+
+
 def temporal_rule_evaluate(model, quads, quality=None, mine=None, k=1, agg="noisy_or", known=None, known_static=None, batch_size=256,
                            **kw):
     """T_RED_GNN.rule_evaluate (see there)."""
@@ -857,13 +870,103 @@ def temporal_rule_evaluate(model, quads, quality=None, mine=None, k=1, agg="nois
             filt_ptr, filt_idx = temporal_filter_lists(keys_of, b[:, 2], index)
             ranks[sfx].append(cal_ranks_csr(score, ans_ptr, tails, to(filt_ptr), to(filt_idx)).double())
         covered += int((rs.fired.gather(1, tails.long()[:, None]) > 0).sum())
-    n = len(q)
-    out = {"n": n, "coverage": covered / n}
-    for sfx in KINDS.values():
-        rank = torch.cat(ranks[sfx]).cpu().numpy()
-        out["hits1" + sfx], out["hits3" + sfx], out["hits10" + sfx] = (float(np.sum(rank <= c) / n) for c in (1, 3, 10))
-        out["mrr" + sfx], out["mr" + sfx] = float(np.sum(1.0 / rank) / n), float(np.sum(rank) / n)
-    return out
+    return _rule_metrics(ranks, covered, len(q))
+
+
+def _lag_quality(model, quality, who):
+    if not isinstance(quality, LagRuleQuality):
+        raise ValueError("%s: quality must be an explain.LagRuleQuality (got %s)" % (who, type(quality).__name__))
+    if quality.table.n_rel != model.n_rel_true:
+        raise ValueError("%s: the table has n_rel=%d, the model n_rel=%d" % (who, quality.table.n_rel, model.n_rel_true))
+
+
+def _lag_queries(model, X, who):
+    """extrapolation.check_batch, and three empty arrays for a batch without rows (rule_scores and rule_predict take one)."""
+    from .extrapolation import check_batch
+    if all(len(x) == 0 for x in (X.src_idx, X.rel_idx, X.ts)):
+        z = np.zeros(0, np.int64)
+        return z, z.copy(), z.copy()
+    return check_batch(model, X, who)
+
+
+def lag_rule_scores(model, quality, X, by="confidence", laplace=0.0, min_hits=1, scratch_bytes=engine.RULE_SCRATCH_BYTES,
+                    who="rule_scores"):
+    """extrapolation.T_RED_GNN.rule_scores (see there)."""
+    from .extrapolation import WINDOW
+    _lag_quality(model, quality, who)
+    rows, weight = rule_weights(quality, by, laplace, min_hits)          # (no rule of this family is trivial)
+    src, rel, ts = _lag_queries(model, X, who)
+    t = quality.table
+    head, body, lag_lo, lag_hi = (x.cpu().numpy()[rows] for x in (t.head, t.body) + tuple(t.lag_ranges()))
+    win_lo, win_hi = model.windows()
+    best, surv, best_rule, fired = engine.xrule_apply(model.graph, head, body, lag_lo, lag_hi, weight, src, rel, ts // model.time_granularity,
+                                                      model._row_time_host, win_lo, win_hi, WINDOW, scratch_bytes)
+    return _rule_scores(best, surv, best_rule, fired, rows)
+
+
+def lag_rule_predict(model, quality, X, k=10, agg="noisy_or", known=None, **kw):
+    """extrapolation.T_RED_GNN.rule_predict (see there)."""
+    from .extrapolation import KnownObjects
+    from .prediction import K_MAX
+    _check_agg(agg, "rule_predict")
+    _check_count(k, "rule_predict", "k", K_MAX)
+    if known is not None and not isinstance(known, KnownObjects):
+        raise ValueError("rule_predict: known must be a KnownObjects index (extrapolation.known_objects_index)")
+    rs = lag_rule_scores(model, quality, X, who="rule_predict", **kw)
+    src, rel, ts = _lag_queries(model, X, "rule_predict")
+    device = rs.best.device
+    q_key = known_dev = None
+    if known is not None and rs.best.shape[0]:
+        q_key = torch.as_tensor(known.query_keys(src, rel, ts)).to(device)
+        known_dev = model._index_on_device(known, device)
+    return _rule_prediction(rs, k, agg, q_key, known_dev, quality.table)
+
+
+def anchors_before(anchors, day, who="rule_evaluate"):
+    """The rows of ``anchors`` int [S, 2] = (entity, day) whose day is below ``day``; ValueError where none is."""
+    a = np.asarray(anchors, np.int64).reshape(-1, 2)
+    a = a[a[:, 1] < int(day)]
+    if len(a) == 0:
+        raise ValueError("%s: no anchor lies before the earliest query day %d: pass anchors, or a quality" % (who, int(day)))
+    return a
+
+
+def lag_rule_evaluate(model, queries, quality=None, mine=None, k=1, agg="noisy_or", sp_index=None, spt_index=None, batch_size=256,
+                      lag_edges=DEFAULT_LAG_EDGES, anchors=None, **kw):
+    """extrapolation.T_RED_GNN.rule_evaluate (see there)."""
+    from .evaluation import KINDS
+    from .extrapolation import KnownObjects, _Batch, check_queries
+    from .utils import cal_ranks_csr
+    who = "rule_evaluate"
+    _check_agg(agg, who)
+    if (quality is None) == (mine is None):
+        raise ValueError("%s: give exactly one of quality (a LagRuleQuality) and mine (queries to mine the rules from)" % who)
+    _check_count(k, who, "k", engine.PATHS_MAX_K)
+    q = check_queries(model, queries, batch_size, who)
+    for name, index in (("sp_index", sp_index), ("spt_index", spt_index)):
+        if index is not None and not isinstance(index, KnownObjects):
+            raise ValueError("%s: %s must be a KnownObjects index (extrapolation.known_objects_index)" % (who, name))
+    if quality is None:
+        table = model.rules_all(check_queries(model, mine, 1, who + " (mine)"), k, lag_edges=lag_edges)
+        if anchors is None:
+            anchors = anchors_before(model.default_anchors(), (q[:, 3] // model.time_granularity).min(), who)
+        quality = model.rule_quality(table, anchors)
+    _lag_quality(model, quality, who)
+    device = model.linear_classifier.weight.device
+    to = lambda a: torch.as_tensor(a).to(device)
+    ranks, covered = {sfx: [] for sfx in KINDS.values()}, 0
+    for lo in range(0, len(q), int(batch_size)):
+        b = q[lo:lo + int(batch_size)]
+        rs = lag_rule_scores(model, quality, _Batch(b[:, 0], b[:, 1], b[:, 3]), who=who, **kw)
+        score = rs.score(agg).contiguous()
+        tails = to(b[:, 2].astype(np.int32))
+        ans_ptr = torch.arange(len(b) + 1, dtype=torch.int32, device=device)
+        for sfx, index in (("", None), ("_fil_t", spt_index), ("_fil", sp_index)):
+            keys_of = b[:, 0] if index is None else index.query_keys(b[:, 0], b[:, 1], b[:, 3])
+            filt_ptr, filt_idx = temporal_filter_lists(keys_of, b[:, 2], index)
+            ranks[sfx].append(cal_ranks_csr(score, ans_ptr, tails, to(filt_ptr), to(filt_idx)).double())
+        covered += int((rs.fired.gather(1, tails.long()[:, None]) > 0).sum())
+    return _rule_metrics(ranks, covered, len(q))
 
 
 def _table(key, support, fixed, n_rel):

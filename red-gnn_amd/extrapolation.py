@@ -24,7 +24,9 @@ reaches, known objects excluded, in one HIP launch on the forward's pairs (csrc/
 sums the attention of a batch's edges per hop, edge relation and lag bin (csrc/profile.hip, rg_xattn_profile; the driver is
 profile.attention_profile_extrapolation), ``attention_profile_all`` over a split.  ``T_RED_GNN.rules`` / ``rules_all`` count the k
 best paths behind forecasts as lag-binned rules (explain.LagRuleTable) and ``rule_quality`` counts how those hold in the model's own
-data, per (entity, query day) anchor under the forward's row windows (csrc/xrule_ground.hip, rg_xrule_ground).
+data, per (entity, query day) anchor under the forward's row windows (csrc/xrule_ground.hip, rg_xrule_ground);
+``rule_scores`` / ``rule_predict`` / ``rule_evaluate`` apply the weighted rules to queries (s, p, ?, t) under the same windows
+(csrc/xrule_apply.hip, rg_xrule_apply; the drivers are explain.lag_rule_scores / lag_rule_predict / lag_rule_evaluate).
 Without gradients the per-row products of the forward (attention inputs, W_past products, time table, classifier) run through
 rg_rows_linear (csrc/rows_linear.hip), whose rows do not depend on the row count: a query computes the same bits in every batch.
 
@@ -408,6 +410,48 @@ class T_RED_GNN(nn.Module):
         counts = engine.xrule_ground(self.graph, table.head, table.body, lag_lo, lag_hi, self._row_time_host, win_lo, win_hi, anchors,
                                      WINDOW, scratch_bytes)
         return _explain.LagRuleQuality(table, *(counts[:, c].contiguous() for c in range(4)), int(len(anchors)))
+
+    def rule_scores(self, quality, X, by="confidence", laplace=0.0, min_hits=1, scratch_bytes=engine.RULE_SCRATCH_BYTES):
+        """What the rules of ``quality`` (an explain.LagRuleQuality, from rule_quality) forecast for the queries (s, p, ?, t) of X (as
+        forward's; day = ts // time_granularity; a batch without rows is allowed) on the model's own data, in HIP (rg_xrule_apply):
+        explain.RuleScores with best / surv / best_rule / fired [B, n_ent].  A rule fires for (b, y) iff its head is the query
+        relation and its steps lead from the subject to y through rows of the query day's window - the forward's, windows() - whose
+        lag lies in each step's bin, exactly as rule_quality counts a body for an anchor of that day; a self-loop has the lag
+        min(day, 120).  The rules kept and their weights are explain.rule_weights(quality, by, laplace, min_hits); ``best_rule`` holds
+        table rows.  No bit depends on ``scratch_bytes``, which bounds the bitmaps of one call."""
+        from . import explain as _explain
+        return _explain.lag_rule_scores(self, quality, X, by, laplace, min_hits, scratch_bytes)
+
+    def rule_predict(self, quality, X, k=10, agg="noisy_or", known=None, **weights):
+        """The k best forecasts of every query of X by rule score alone (agg "noisy_or": 1 - the product of the firing rules'
+        1 - weight; "max": the largest weight), selected in HIP (rg_topk) over all entities: explain.RulePrediction, score descending
+        then entity id ascending, -1 / -inf / -1 / 0 past the end, ``rule`` the table row of each answer's best rule and ``table`` the
+        LagRuleTable, so format() prints the rule with its lag tags.  ``known``: a KnownObjects index of the (s, p) or the (s, p, t)
+        kind (known_objects_index); the objects it lists for a query are left out.  ``weights``: by, laplace, min_hits, scratch_bytes
+        of rule_scores.  A batch without rows gives [0, k] tensors."""
+        from . import explain as _explain
+        return _explain.lag_rule_predict(self, quality, X, k, agg, known, **weights)
+
+    def rule_evaluate(self, queries, quality=None, mine=None, k=1, agg="noisy_or", sp_index=None, spt_index=None, batch_size=256,
+                      lag_edges=DEFAULT_LAG_EDGES, anchors=None, **weights):
+        """Ranking metrics of the rules alone on ``queries`` int [n, 4] = (s, p, o, ts) (checked as evaluate's), next to evaluate:
+        exactly one of ``quality`` (a LagRuleQuality) and ``mine`` (int [m, 4] queries: rules_all(mine, k, lag_edges=lag_edges) ->
+        rule_quality(table, anchors)) is given.  Per batch of ``batch_size`` queries the rule scores (rule_scores, ``agg``) are ranked
+        over all n_ent entities by rg_rank three times - raw, filtered by the other known objects of (s, p) (``sp_index``) and of
+        (s, p, ts) (``spt_index``), both from known_objects_index; a query's filter set is its object and the objects the index
+        lists for it.  Returns a dict: n, coverage (the share of objects some rule reaches) and hits1 / hits3 / hits10 / mrr / mr with
+        the suffixes "" / _fil / _fil_t, sums in float64.  ``weights``: by, laplace, min_hits, scratch_bytes of rule_scores.
+
+        When it mines (``mine``) and ``anchors`` is None, the confidences are counted on the default anchors whose day is BELOW THE
+        EARLIEST QUERY DAY, not on all of them: the model's data may hold the evaluated rows themselves, and a rule must not be
+        weighted by the facts it is then scored on.  ValueError if that leaves no anchor.  Given anchors are used as they are.
+
+        Two differences from evaluate: the ranks are over every entity, not over the ones the query's window reaches, and rg_rank's
+        tie term counts every entity that scores exactly as the object, filtered ones included (the convention of
+        BaseModel.rule_evaluate): every entity no rule reaches scores 0."""
+        from . import explain as _explain
+        return _explain.lag_rule_evaluate(self, queries, quality, mine, k, agg, sp_index, spt_index, batch_size, lag_edges, anchors,
+                                          **weights)
 
     def evaluate(self, queries, sp_index=None, spt_index=None, batch_size=64, return_ranks=False):
         """The validation loop of main.py:353-472 for a split: ``queries`` int [n, 4] = (s, p, o, ts), in batches of ``batch_size``
