@@ -275,7 +275,12 @@ int rg_xlayer_bwd(const rg_frontier* f, const rg_graph* g, int32_t level, int64_
  * W_final [d] or NULL.  agg [n,ld], hidden_prev [n_old,ld], prev_idx int32 [n] (-1 = new node; NULL = all
  * new), a_s_out [n,ap], nodes int32 [n,2], scores_all [B*n_ent] (pre-zeroed; only visited entries are
  * written), hidden_out [n,ld] - or NULL on the last layer (W_final given, Ws_next NULL), when nobody reads the new state: the kernels then
- * skip its stores and the scores are bit for bit the same; NULL in any other call is an error.  act: 0 identity, 1 relu, 2 tanh.  Supported: d <= 64 or d == 128, attn_dim <= 16
+ * skip its stores and the scores are bit for bit the same; NULL in any other call is an error.  Rows are written whole up to the
+ * kernels' padded width (32 columns for d <= 32, 64 for d <= 64, 128; columns of a wider ld are left alone): with zero pad columns
+ * d .. ld - 1 in agg and hidden_prev, the pad columns of hidden_out are exactly 0 (the padded weights and biases are zero, so a pad
+ * element is 0.5 tanh(0) + 0.5 h0_pad), and a_s_out columns attn_dim .. ap - 1 are exactly 0.  The new state does not depend on
+ * which of Ws_next / W_final a call carries, nor on n_hint of rg_dense_fwd_dev (bit for bit, at every precision).
+ * act: 0 identity, 1 relu, 2 tanh.  Supported: d <= 64 or d == 128, attn_dim <= 16
  * (rg_dense_fwd_supported); other shapes return an error and the caller keeps its own dense path. */
 int rg_dense_fwd_supported(int32_t d, int32_t attn_dim);
 int rg_dense_fwd(int64_t n, int32_t d, int32_t ld, const float* agg, const float* hidden_prev,

@@ -2,9 +2,9 @@
 // Same operator as dense.hip (Static/transductive/models.py :41 W_h + act, :81-84 the gathered single-step GRU, the next layer's :36
 // Ws_attn(hs), :86-88 the readout), same transposed data flow (node = lane, accumulators feed the next product), but every fp32
 // operand v is carried as   v = s * (hi + lo),   hi = fp16(v / s),  lo = fp16(v / s - hi)
-// with s a power of two - per node row for the activations (the row's largest magnitude goes to [2^14, 2^15)), one for all the
-// weights of the launch (their largest magnitude to at most 2^15) - so that hi + lo carries 22 significant bits of the row's /
-// the weights' largest entries and lo stays a normal f16.  A product W X is three v_mfma_f32_16x16x32_f16 into one fp32 accumulator:
+// with s a power of two - per node row for the activations (the row's largest magnitude goes to [2^14, 2^15)), one for the layer's
+// seven weight matrices and one for the projections (their largest magnitude to at most 2^15) - so that hi + lo carries 22 significant
+// bits of the row's / the weights' largest entries and lo stays a normal f16.  A product W X is three v_mfma_f32_16x16x32_f16 into one fp32 accumulator:
 //   acc += W_hi X_hi + W_hi X_lo + W_lo X_hi            (the dropped W_lo X_lo is 2^-22 of a product)
 // and W X = s_w^-1 s_x^-1 acc.  A 64-term dot product comes out within a few 1e-7 of its largest terms (fp32 FMA chains: about 1e-7);
 // measured against fp64 the layer's outputs are as close as the exact kernel's (tools/probe_dense_precision.py: both are set by the
@@ -46,12 +46,13 @@ __global__ __launch_bounds__(DENSE_T, 2) void dense_split_kernel(DenseArgs A) {
   uint32_t* wmax_bits = reinterpret_cast<uint32_t*>(stash + NW * NB * 64);
 
   const int d = A.d;
-  // ---- weights -> split f16 images, all under one power-of-two scale ----------------------------------------------------------
-  // 2^12 suits weights of magnitude 2^-8 .. 8 (initialised or trained layers); the staging pass finds the true maximum on its way
-  // and is repeated with a fitted scale when that guess would overflow f16 or leave the lo halves denormal.
+  // ---- weights -> split f16 images under power-of-two scales: one for the layer's seven matrices, one for the projections (Ws, W_final),
+  // so that the new state does not depend on which of them a launch carries (as in dense_split3.hip and the d = 128 images, split3.h).
+  // 2^12 suits weights of magnitude 2^-8 .. 8 (initialised or trained layers); the staging pass finds the true maxima on its way
+  // and is repeated with fitted scales when a guess would overflow f16 or leave the lo halves denormal.
   const bool vec4 = (d & 3) == 0;
-  float sw = 4096.0f, wm = 0.0f;
-  auto load_w = [&](h8* hi_img, h8* lo_img, const float* src, int rows_src, int row0_dst, int rows_dst) {
+  float sw = 4096.0f, sw_e = 4096.0f;
+  auto load_w = [&](h8* hi_img, h8* lo_img, const float* src, int rows_src, int row0_dst, int rows_dst, float sc, float& wm) {
     const bool v4 = vec4 && ((uintptr_t)src & 15) == 0;
     for (int i = threadIdx.x; i < rows_dst * S; i += DENSE_T) {
       const int r = i / S, ch = i - r * S;         // ch: 4-float chunk = (block ob, quarter hq)
@@ -71,36 +72,43 @@ __global__ __launch_bounds__(DENSE_T, 2) void dense_split_kernel(DenseArgs A) {
       }
       wm = fmaxf(fmaxf(wm, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
       h4 hi, lo;
-      split4(v[0] * sw, v[1] * sw, v[2] * sw, v[3] * sw, hi, lo);
+      split4(v[0] * sc, v[1] * sc, v[2] * sc, v[3] * sc, hi, lo);
       const int ob = ch >> 2, hq = ch & 3, row = row0_dst + r;
       const int slot = G::at(row, 4 * (ob >> 1) + hq);
       reinterpret_cast<h4*>(hi_img + slot)[ob & 1] = hi;
       reinterpret_cast<h4*>(lo_img + slot)[ob & 1] = lo;
     }
   };
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    if (threadIdx.x == 0) *wmax_bits = 0u;
-    __syncthreads();
-    wm = 0.0f;
-    load_w(Wh_hi, Wh_lo, A.W_h, d, 0, DP);
-    for (int g = 0; g < 3; ++g) {
-      load_w(Wih_hi, Wih_lo, A.w_ih + (int64_t)g * d * d, d, g * DP, DP);
-      load_w(Whh_hi, Whh_lo, A.w_hh + (int64_t)g * d * d, d, g * DP, DP);
-    }
-    load_w(E_hi, E_lo, A.Ws, A.Ws ? A.attn : 0, 0, 16);
-    load_w(E_hi, E_lo, A.W_final, A.W_final ? 1 : 0, 16, 16);
-    atomicMax(wmax_bits, __float_as_uint(wm));      // non-negative floats order like their bit patterns
-    __syncthreads();
-    const float wmax = __uint_as_float(*wmax_bits);
-    if (wmax == 0.0f || (wmax * sw <= 32768.0f && wmax * sw >= 16.0f)) break;
-    // (fit_weight_scale of split3.h without its test for zero, which the line above has made: with the call in its place the whole
-    // kernel is allocated differently)
+  // a scale suits its largest weight when that neither overflows f16 nor leaves the lo halves denormal
+  auto suits = [](float wmax, float sc) { return wmax == 0.0f || (wmax * sc <= 32768.0f && wmax * sc >= 16.0f); };
+  // (fit_weight_scale of split3.h without its test for zero, which `suits` has made)
+  auto refit = [](float wmax) {
     uint32_t eb = (__float_as_uint(wmax) >> 23) & 0xffu;
     eb = eb < 15u ? 15u : (eb > 254u ? 254u : eb);
-    sw = __uint_as_float((267u - eb) << 23);        // largest magnitude to [2^13, 2^14)
+    return __uint_as_float((267u - eb) << 23);        // largest magnitude to [2^13, 2^14)
+  };
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    if (threadIdx.x < 2) wmax_bits[threadIdx.x] = 0u;
+    __syncthreads();
+    float wm = 0.0f, wm_e = 0.0f;
+    load_w(Wh_hi, Wh_lo, A.W_h, d, 0, DP, sw, wm);
+    for (int g = 0; g < 3; ++g) {
+      load_w(Wih_hi, Wih_lo, A.w_ih + (int64_t)g * d * d, d, g * DP, DP, sw, wm);
+      load_w(Whh_hi, Whh_lo, A.w_hh + (int64_t)g * d * d, d, g * DP, DP, sw, wm);
+    }
+    load_w(E_hi, E_lo, A.Ws, A.Ws ? A.attn : 0, 0, 16, sw_e, wm_e);
+    load_w(E_hi, E_lo, A.W_final, A.W_final ? 1 : 0, 16, 16, sw_e, wm_e);
+    atomicMax(wmax_bits, __float_as_uint(wm));      // non-negative floats order like their bit patterns
+    atomicMax(wmax_bits + 1, __float_as_uint(wm_e));
+    __syncthreads();
+    const float wmax = __uint_as_float(wmax_bits[0]), wmax_e = __uint_as_float(wmax_bits[1]);
+    const bool ok = suits(wmax, sw), ok_e = suits(wmax_e, sw_e);
+    if (ok && ok_e) break;
+    if (!ok) sw = refit(wmax);
+    if (!ok_e) sw_e = refit(wmax_e);
     __syncthreads();
   }
-  const float inv_w = 1.0f / sw;                     // exact: a power of two
+  const float inv_w = 1.0f / sw, inv_we = 1.0f / sw_e;      // exact: powers of two
   fill_gru_bias<DENSE_T, DP, true, true>(bias_l, A, d);
   __syncthreads();
 
@@ -303,12 +311,12 @@ __global__ __launch_bounds__(DENSE_T, 2) void dense_split_kernel(DenseArgs A) {
       f32x4 acc = zero4;
       mma(O_E, O_E + P_E, 0, nh, nl, acc);
       if (node_ok && 4 * hq < A.ap)
-        reinterpret_cast<float4*>(A.a_s_out + node * A.ap)[hq] = make_float4(acc[0] * inv_w, acc[1] * inv_w, acc[2] * inv_w, acc[3] * inv_w);
+        reinterpret_cast<float4*>(A.a_s_out + node * A.ap)[hq] = make_float4(acc[0] * inv_we, acc[1] * inv_we, acc[2] * inv_we, acc[3] * inv_we);
     }
     if (A.W_final) {  // row 16 = register 0 of quarter 0 of block 1
       f32x4 acc = zero4;
       mma(O_E, O_E + P_E, 16, nh, nl, acc);
-      if (node_ok && hq == 0) A.scores[(int64_t)qe.x * A.n_ent + qe.y] = acc[0] * inv_w;
+      if (node_ok && hq == 0) A.scores[(int64_t)qe.x * A.n_ent + qe.y] = acc[0] * inv_we;
     }
   }
 }

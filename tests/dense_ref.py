@@ -6,6 +6,8 @@ rg_dense_train_bwd / _bwd2, rg_rows_addmm and rg_attn_tables), plus the case tab
                r = sigmoid(W_ir x + b_ir + W_hr h0 + b_hr);  z = sigmoid(W_iz x + b_iz + W_hz h0 + b_hz)
                hn = W_hn h0 + b_hn;  n = tanh(W_in x + b_in + r hn);  hidden = (1 - z) n + z h0;  a_s = hidden Ws_next^T
                workspace ws [rows, 5, d] = {r, z, n, h0, hn}
+               score = hidden . W_final, scattered to scores_all[nodes[:, 0] * n_ent + nodes[:, 1]]   (inference: rg_dense_fwd; its
+               contract, its case table and precision 1's two-term emulation are at the end of the file)
     backward   from g = grad_hidden and the SAVED ws / x (inputs, exactly as the kernels take them):
                dn = g (1 - z) (1 - n^2);  dr = dn hn r (1 - r);  dz = g (h0 - n) z (1 - z)
                dgi = (dr, dz, dn);  dgh = (dr, dz, dn r);  dgh_n = dn r
@@ -95,12 +97,27 @@ def _gather(hidden_prev, prev_idx, n, d, dt):
     return h0
 
 
-def _fwd_values(dt, agg, hidden_prev, prev_idx, W_h, act, w_ih, w_hh, b_ih, b_hh, mask, Ws_next, fault=None):
-    agg, hidden_prev, W_h, w_ih, w_hh, b_ih, b_hh, mask, Ws_next = (_c(dt, t) for t in (agg, hidden_prev, W_h, w_ih, w_hh, b_ih, b_hh, mask,
-                                                                                       Ws_next))
+def _stale_all_new(h0, prev_idx):
+    """fault: a 16-row tile without an old row keeps the h0 of the last tile that had one (negative tests only)."""
+    if prev_idx is None:
+        return h0
+    old, last, h0 = np.asarray(prev_idx) >= 0, None, h0.copy()
+    for t in range(0, len(h0), 16):
+        if old[t:t + 16].any():
+            last = h0[t:t + 16].copy()
+        elif last is not None:
+            h0[t:t + 16] = last[:len(h0[t:t + 16])]
+    return h0
+
+
+def _fwd_values(dt, agg, hidden_prev, prev_idx, W_h, act, w_ih, w_hh, b_ih, b_hh, mask, Ws_next, W_final=None, fault=None):
+    agg, hidden_prev, W_h, w_ih, w_hh, b_ih, b_hh, mask, Ws_next, W_final = (_c(dt, t) for t in (agg, hidden_prev, W_h, w_ih, w_hh, b_ih, b_hh,
+                                                                                                mask, Ws_next, W_final))
     n, d = agg.shape
     one = dt.type(1)
     h0 = _gather(hidden_prev, prev_idx, n, d, dt)
+    if fault == "stale_all_new":
+        h0 = _stale_all_new(h0, prev_idx)
     pre = agg @ W_h.T
     a = pre if act == 0 else np.maximum(pre, dt.type(0)) if act == 1 else np.tanh(pre)
     x = a if mask is None else a * mask
@@ -114,14 +131,18 @@ def _fwd_values(dt, agg, hidden_prev, prev_idx, W_h, act, w_ih, w_hh, b_ih, b_hh
     ng = np.tanh(npre)
     hidden = (one - z) * ng + z * h0
     a_s = None if Ws_next is None else hidden @ Ws_next.T
-    return dict(h0=h0, pre=pre, a=a, x=x, r=r, z=z, hn=hn, ng=ng, hidden=hidden, a_s=a_s)
+    # fault: the readout reads the old state instead of the new one (negative tests only)
+    score = None if W_final is None else (h0 if fault == "readout_h0" else hidden) @ W_final
+    return dict(h0=h0, pre=pre, a=a, x=x, r=r, z=z, hn=hn, ng=ng, hidden=hidden, a_s=a_s, score=score)
 
 
-def forward(agg, hidden_prev, prev_idx, W_h, act, w_ih, w_hh, b_ih, b_hh, mask=None, Ws_next=None, ap=None, dtype=np.float64, fault=None):
-    """hidden [n, d], x [n, d], ws [n, 5, d] = {r, z, n, h0, hn}, a_s [n, ap] (None without Ws_next; columns attn_dim .. ap - 1 zero) in
-    ``dtype``; .S / .n per output name in fp64 (include/redgnn.h, rg_dense_train_fwd / rg_dense_train_fwd_as)."""
+def forward(agg, hidden_prev, prev_idx, W_h, act, w_ih, w_hh, b_ih, b_hh, mask=None, Ws_next=None, ap=None, dtype=np.float64, fault=None,
+            W_final=None):
+    """hidden [n, d], x [n, d], ws [n, 5, d] = {r, z, n, h0, hn}, a_s [n, ap] (None without Ws_next; columns attn_dim .. ap - 1 zero),
+    score [n] = hidden . W_final (None without W_final: the readout of rg_dense_fwd, before its scatter) in ``dtype``; .S / .n per output
+    name in fp64 (include/redgnn.h, rg_dense_train_fwd / rg_dense_train_fwd_as / rg_dense_fwd)."""
     act = ACT.get(act, act)
-    args = (agg, hidden_prev, prev_idx, W_h, act, w_ih, w_hh, b_ih, b_hh, mask, Ws_next)
+    args = (agg, hidden_prev, prev_idx, W_h, act, w_ih, w_hh, b_ih, b_hh, mask, Ws_next, W_final)
     v = _fwd_values(np.dtype(dtype), *args, fault=fault)
     w = _fwd_values(np.dtype(np.float64), *args)
     A = lambda t: np.abs(np.asarray(t, np.float64))
@@ -150,8 +171,19 @@ def forward(agg, hidden_prev, prev_idx, W_h, act, w_ih, w_hh, b_ih, b_hh, mask=N
         S["a_s"] = np.zeros((n_rows, ap))
         S["a_s"][:, :attn] = S_h @ A(Ws_next).T
         n["a_s"] = n_n + d
+    if W_final is not None:
+        S["score"] = S_h @ A(W_final)
+        n["score"] = n_n + d
     ws = np.stack([v["r"], v["z"], v["ng"], v["h0"], v["hn"]], 1)
-    return types.SimpleNamespace(hidden=v["hidden"], x=v["x"], ws=ws, a_s=a_s, S=S, n=n)
+    return types.SimpleNamespace(hidden=v["hidden"], x=v["x"], ws=ws, a_s=a_s, score=v["score"], S=S, n=n)
+
+
+def scatter_scores(score, nodes, n_ent, size, fill=np.nan):
+    """scores_all [size] as rg_dense_fwd leaves it: ``score`` at nodes[:, 0] * n_ent + nodes[:, 1], ``fill`` everywhere else."""
+    out = np.full(size, fill, np.asarray(score).dtype)
+    nodes = np.asarray(nodes, np.int64)
+    out[nodes[:, 0] * n_ent + nodes[:, 1]] = score
+    return out
 
 
 # ---- backward -----------------------------------------------------------------------------------------------------------------------
@@ -366,3 +398,244 @@ def saved(case, x):
 def step_backward(case, x, x_saved, ws_saved, dtype=np.float64, fault=None):
     return backward(x["grad_hidden"], ws_saved, x_saved, x["mask"], case.keep, case.act, x["W_h"], x["w_ih"], x["w_hh"], x["prev_idx"],
                     x["n_old"], dtype=dtype, fault=fault)
+
+
+# ---- the inference contract (rg_dense_fwd / rg_dense_fwd_dev, precisions 0, 1, 2) ------------------------------------------------------
+# Outputs: hidden [n, d], a_s [n, ap] (with Ws_next), score [n] scattered by nodes (with W_final).  Precisions 0 (f32 MFMA) and 2 (exact
+# three-term f16 split: "fp32 arithmetic", include/redgnn.h) are held to ``bound`` with C_BOUND, like the training kernels.  Precision 1
+# carries every operand of a matrix product to 22 bits and gets one added term
+#
+#     |gpu - ref64| <= C_BOUND (n + n0) u S  +  C2_F16X2 p 2^-22 S  +  tiny
+#
+# with p = the number of matrix products chained into the element (P_CHAIN).  C2_F16X2 is 2 x the worst ratio
+# |emul - ref64| / (p 2^-22 S) of ``forward_f16x2`` below - the two-term operand form of csrc/split3.h in numpy, everything else in fp64 -
+# over the inference table.  2 rather than 4: the operand roundings are deterministic and the same in the kernel and in the emulation;
+# only their inputs differ, by the fp32 error the first term pays for.
+INFER_OUTPUTS = ("hidden", "a_s", "score")
+P_CHAIN = dict(x=1, hidden=2, a_s=3, score=3)
+U22 = 2.0 ** -22
+# measured: max over the inference table, outputs and elements of |forward_f16x2 - ref64| / (p 2^-22 S), rounded up
+# (test_dense_ref.py::test_f16x2_emulation_ratio_is_the_recorded_one keeps it honest)
+REF_F16X2_WORST_RATIO = 0.125      # spike_d20_ld32's hidden: 0.124
+C2_F16X2 = 2.0 * REF_F16X2_WORST_RATIO
+
+
+def bound_f16x2(S, n, n0, p):
+    return bound(S, n, n0, C_BOUND) + C2_F16X2 * p * U22 * np.asarray(S, np.float64)
+
+
+def infer_bound(precision, S, n, out):
+    """The allowance of output ``out`` at ``precision`` (0 f32, 1 f16x2, 2 f16x3)."""
+    return bound_f16x2(S, n, N0_STEP, P_CHAIN[out]) if precision == 1 else bound(S, n, N0_STEP, C_BOUND)
+
+
+def _pow2_scale(m, top):
+    """The power of two that takes m (>= 0) into [2^(top - 1), 2^top); 1 for m = 0."""
+    m = np.asarray(m, np.float64)
+    _, e = np.frexp(m)      # m = f 2^e, f in [1/2, 1)
+    return np.where(m > 0, np.ldexp(1.0, top - e), 1.0)
+
+
+def _split2(v, s):
+    """hi = f16(v s), lo = f16(v s - hi) (numpy's float16: round to nearest even, subnormals kept), as fp64."""
+    vs = np.asarray(v, np.float64) * s
+    hi = vs.astype(np.float16).astype(np.float64)
+    lo = (vs - hi).astype(np.float16).astype(np.float64)
+    return hi, lo
+
+
+def _prod2(X, sx, W, sw, fault=None):
+    """X W^T with both operands as two-term splits: (W_hi X_hi + W_hi X_lo + W_lo X_hi) / (sx sw), the sums in fp64.
+    fault "no_lo_hi": the W_lo X_hi term dropped; "one_term": hi halves only (negative tests only)."""
+    xh, xl = _split2(X, sx)
+    wh, wl = _split2(W, sw)
+    acc = xh @ wh.T
+    if fault != "one_term":
+        acc = acc + xl @ wh.T
+        if fault != "no_lo_hi":
+            acc = acc + xh @ wl.T
+    return acc / (sx * sw)
+
+
+def forward_f16x2(agg, hidden_prev, prev_idx, W_h, act, w_ih, w_hh, b_ih, b_hh, Ws_next=None, ap=None, W_final=None, fault=None):
+    """The step with the operands of every matrix product in the two-term f16 form csrc/split3.h documents - a power-of-two scale per
+    node row that takes the row's largest magnitude into [2^14, 2^15) (x and h0 of a row share one, so that W_ih x and W_hh h0 add in
+    one accumulator), one per launch that takes the largest weight of the layer's seven matrices into [2^13, 2^14) and one of their own
+    for the projections (split3.h:149-158, dense_split.hip, dense_split3.hip:82), hi = f16(v s), lo = f16(v s - hi), products hi hi + hi lo + lo hi - and everything
+    else (sums, biases, sigmoid, tanh, the state update) in fp64.  hidden, x, a_s, score as ``forward``."""
+    act = ACT.get(act, act)
+    f = lambda t: None if t is None else np.asarray(t, np.float64)
+    agg, hidden_prev, W_h, w_ih, w_hh, b_ih, b_hh, Ws_next, W_final = (f(t) for t in (agg, hidden_prev, W_h, w_ih, w_hh, b_ih, b_hh, Ws_next,
+                                                                                    W_final))
+    n, d = agg.shape
+    amax = lambda *ts: max([float(np.abs(t).max()) for t in ts if t is not None and t.size] + [0.0])
+    sw_g, sw_e = float(_pow2_scale(amax(W_h, w_ih, w_hh), 14)), float(_pow2_scale(amax(Ws_next, W_final), 14))
+    rows = lambda *ts: _pow2_scale(np.max([np.abs(t).max(1) for t in ts], 0), 15)[:, None]
+    h0 = _gather(hidden_prev, prev_idx, n, d, np.dtype(np.float64))
+    pre = _prod2(agg, rows(agg), W_h, sw_g, fault)
+    x = pre if act == 0 else np.maximum(pre, 0.0) if act == 1 else np.tanh(pre)
+    s = rows(x, h0)
+    gi = _prod2(x, s, w_ih, sw_g, fault) + b_ih
+    hh = _prod2(h0, s, w_hh, sw_g, fault)
+    r = _sigmoid(gi[:, :d] + hh[:, :d] + b_hh[:d])
+    z = _sigmoid(gi[:, d:2 * d] + hh[:, d:2 * d] + b_hh[d:2 * d])
+    ng = np.tanh(gi[:, 2 * d:] + r * (hh[:, 2 * d:] + b_hh[2 * d:]))
+    hidden = (1.0 - z) * ng + z * h0
+    sh = rows(hidden)
+    a_s = None
+    if Ws_next is not None:
+        attn = Ws_next.shape[0]
+        a_s = np.zeros((n, (attn + 3) // 4 * 4 if ap is None else ap))
+        a_s[:, :attn] = _prod2(hidden, sh, Ws_next, sw_e, fault)
+    score = None if W_final is None else _prod2(hidden, sh, W_final[None], sw_e, fault)[:, 0]
+    return types.SimpleNamespace(hidden=hidden, x=x, a_s=a_s, score=score)
+
+
+# The inference table: one entry per dispatch condition of the six fused kernels (csrc/dense.hip, dense_split.hip, dense_split3.hip for
+# d <= 64; dense128.hip, dense128_split.hip, dense128_split3.hip for d = 128); ``why`` cites the line the case flips.  Every case runs at
+# the precisions in ``precisions`` (all three unless the case says otherwise).  agg / hidden_prev come with their true d columns: padding
+# the rows to ld (zero pad columns) is the test's business.
+def _infer(name, d, n, ld=None, act="relu", prev="third", attn_dim=0, readout=False, no_hidden=False, rows="plain", ws_scale=1.0,
+           precisions=(0, 1, 2), seed=0, why=""):
+    return types.SimpleNamespace(name=name, kind="infer", d=d, ld=d if ld is None else ld, n=n, act=ACT[act], prev=prev, attn_dim=attn_dim,
+                                 ap=(attn_dim + 3) // 4 * 4, readout=readout, no_hidden=no_hidden, rows=rows, ws_scale=ws_scale,
+                                 precisions=precisions, seed=seed, why=why)
+
+
+# rows per pass of the persistent grid: 256 workgroups x NW waves x 16 rows (dense_common.h:67 dense_grid).  NW = 8 in dense.hip:42,
+# dense_split.hip:32, dense_split3.hip:35, dense128.hip:19, dense128_split.hip:19; NW = 4 in dense128_split3.hip:25
+ROWS_PER_PASS = {8: 256 * 8 * 16, 4: 256 * 4 * 16}
+
+_INFER_LIST = [
+    # ---- width and stride: DP = 32 for d <= 32, 64 above (dense.hip:366, dense_split.hip:342, dense_split3.hip launch_act); the weight
+    # staging's `c < d` guards (dense.hip:69, dense_split.hip:69, dense_split3.hip:100) on rows of stride ld4, the state store's `sl < ld4`
+    _infer("w_d1_ld4", 1, 1000, 4, "tanh", "runs", 1, True, seed=1, why="dense.hip:69 scalar staging, one column; one float4 per row (ld4 = 1)"),
+    _infer("w_d3_ld4", 3, 1000, 4, "relu", "third", 5, True, seed=2, why="d % 4 != 0 and d < 16: one pad column inside the only float4"),
+    _infer("w_d20", 20, 1000, 20, "idd", "runs", 5, True, seed=3, why="ld4 = 5: block 1 holds one float4 of four (col_ok, dense_split.hip:165)"),
+    _infer("w_d20_ld32", 20, 1000, 32, "relu", "all", 8, True, seed=4, why="ld > d with d % 4 == 0: vector staging, three pad float4 stored"),
+    _infer("w_d30_ld32", 30, 1000, 32, "tanh", "runs", 5, True, seed=5, why="dense_split3.hip:100 scalar staging, two pad columns in the last float4"),
+    _infer("w_d32", 32, 1000, 32, "idd", "third", 16, True, seed=6, why="DP = 32 at its upper edge"),
+    _infer("w_d33_ld36", 33, 1000, 36, "relu", "runs", 5, True, seed=7, why="d > 32 -> DP = 64 by one column; scalar staging; ld4 = 9"),
+    _infer("w_d48_ld64", 48, 1000, 64, "tanh", "third", 8, True, seed=8, why="DP = 64, block 3 all pad and stored"),
+    _infer("w_d63_ld64", 63, 1000, 64, "idd", "runs", 5, True, seed=9, why="scalar staging at DP = 64, one pad column"),
+    _infer("w_d64", 64, 1000, 64, "relu", "runs", 5, True, seed=10, why="DP = 64, full blocks"),
+    _infer("w_d128", 128, 1000, 128, "tanh", "runs", 5, True, seed=11, why="dense.hip:361 d == 128 -> the streamed-weight kernels"),
+    # ---- rows around the 16-row tile (n_tiles = ceil(n / 16); node_ok / rows_valid guards, dense_split3.hip:307)
+    _infer("n1_d64", 64, 1, act="relu", prev="all", attn_dim=5, readout=True, seed=12, why="one row of one tile"),
+    _infer("n15_d64", 64, 15, act="tanh", prev="third", attn_dim=8, readout=True, seed=13, why="tile short of one row"),
+    _infer("n16_d64", 64, 16, act="idd", prev="third", attn_dim=5, readout=True, seed=14, why="exactly one tile"),
+    _infer("n17_d64", 64, 17, act="relu", prev="all", attn_dim=16, readout=True, seed=15, why="one row into the second tile"),
+    _infer("n1_d128", 128, 1, act="tanh", prev="all", attn_dim=5, readout=True, seed=16, why="d = 128: one row of one tile"),
+    _infer("n15_d128", 128, 15, act="relu", prev="third", attn_dim=8, readout=True, seed=17, why="d = 128: tile short of one row"),
+    _infer("n16_d128", 128, 16, act="idd", prev="third", attn_dim=5, readout=True, seed=18, why="d = 128: exactly one tile"),
+    _infer("n17_d128", 128, 17, act="relu", prev="all", attn_dim=16, readout=True, seed=19, why="d = 128: one row into the second tile"),
+    # ---- the persistent grid's second pass (t += gridDim.x * NW: dense.hip:184, dense_split.hip:195, dense_split3.hip:243)
+    _infer("n32769_d64", 64, ROWS_PER_PASS[8] + 1, act="relu", prev="runs", attn_dim=5, readout=True, seed=20,
+           why="NW = 8: 32768 rows per pass, the second pass one row"),
+    _infer("n32769_d20", 20, ROWS_PER_PASS[8] + 1, act="tanh", prev="third", attn_dim=8, readout=True, seed=21,
+           why="the same at DP = 32 with a partly filled block"),
+    _infer("n32769_d128", 128, ROWS_PER_PASS[8] + 1, act="idd", prev="runs", attn_dim=5, readout=True, precisions=(0, 1), seed=22,
+           why="dense128.hip:19 / dense128_split.hip:19 NW = 8"),
+    _infer("n16385_d128", 128, ROWS_PER_PASS[4] + 1, act="relu", prev="runs", attn_dim=5, readout=True, precisions=(2,), seed=23,
+           why="dense128_split3.hip:25 NW = 4: 16384 rows per pass"),
+    # ---- prev_idx: NULL, all -1, every row old, a third at random, and runs of 1 .. 40 old / new rows (whole tiles all new, all old and
+    # mixed next to one another: any_old, dense.hip:263, dense_split.hip:307, dense_split3.hip:251/544)
+    _infer("prev_null", 48, 1000, act="relu", prev="null", attn_dim=5, seed=24, why="prev_idx NULL: no gather at all"),
+    _infer("prev_none", 64, 1000, act="tanh", prev="none", attn_dim=5, seed=25, why="prev_idx given, every entry -1: any_old false in every tile"),
+    _infer("prev_all", 32, 1000, act="idd", prev="all", attn_dim=5, seed=26, why="any_old true in every tile, no new row"),
+    _infer("prev_third", 64, 1000, act="relu", prev="third", attn_dim=5, seed=27, why="every tile mixed"),
+    _infer("prev_runs_d64", 64, 2000, act="tanh", prev="runs", attn_dim=5, seed=28, why="any_old true and false inside one call, DP = 64"),
+    _infer("prev_runs_d20", 20, 2000, act="relu", prev="runs", attn_dim=5, seed=29, why="any_old true and false inside one call, DP = 32"),
+    _infer("prev_runs_d128", 128, 2000, act="idd", prev="runs", attn_dim=5, seed=30, why="d = 128: old and new tiles in one call"),
+    # ---- projection and readout: attn_dim 1, 5, 8, 16 (ap 4, 8, 8, 16: `4 * hq < A.ap`), W_final scattered by sorted distinct
+    # (query, entity) pairs with gaps, neither, hidden_out = NULL on a readout
+    _infer("as1", 64, 1000, act="relu", prev="third", attn_dim=1, seed=31, why="dense.hip:290 ap = 4: one lane quarter stores"),
+    _infer("as5", 48, 1000, act="tanh", prev="runs", attn_dim=5, seed=32, why="ap = 8, three pad columns"),
+    _infer("as8", 32, 1000, act="idd", prev="all", attn_dim=8, seed=33, why="ap = 8, no pad"),
+    _infer("as16", 20, 1000, act="relu", prev="third", attn_dim=16, seed=34, why="ap = 16: all four lane quarters store"),
+    _infer("as16_d128", 128, 1000, act="tanh", prev="third", attn_dim=16, seed=35, why="d = 128 a_s store, block 56 of the image"),
+    _infer("readout", 64, 1000, act="relu", prev="runs", readout=True, seed=36, why="dense.hip:293 W_final only: row 16 of E, scatter by nodes"),
+    _infer("readout_d128", 128, 1000, act="idd", prev="third", readout=True, seed=37, why="d = 128: block 57 of the image"),
+    _infer("neither", 48, 1000, act="tanh", prev="third", seed=38, why="neither Ws_next nor W_final: the state alone"),
+    _infer("neither_d128", 128, 1000, act="relu", prev="runs", seed=39, why="d = 128: the state alone"),
+    _infer("no_hidden", 64, 1000, act="tanh", prev="runs", readout=True, no_hidden=True, seed=40,
+           why="dense.hip:312 / dense_split.hip:295 / dense_split3.hip:310 hidden_out = NULL: no state store"),
+    _infer("no_hidden_d20_ld32", 20, 1000, 32, act="relu", prev="third", readout=True, no_hidden=True, seed=41, why="the same at DP = 32, ld > d"),
+    _infer("no_hidden_d128", 128, 1000, act="idd", prev="runs", readout=True, no_hidden=True, seed=42, why="d = 128 without the state store"),
+    # ---- row scales of the split kernels: row_scale(row_abs_max(..)) per node row (dense_common.h:111, split3.h:121), shared by x and h0 in
+    # the GRU (dense_split.hip:258, dense_split3.hip:321)
+    _infer("spike_d64", 64, 1000, act="idd", prev="runs", attn_dim=5, readout=True, rows="spike", seed=43,
+           why="the row's largest element in every column in turn, 8 x the rest: a maximum the quarter-wave shuffles miss overflows f16"),
+    _infer("spike_d20_ld32", 20, 1000, 32, act="relu", prev="third", attn_dim=5, readout=True, rows="spike", seed=44, why="the same at DP = 32, ld > d"),
+    _infer("spike_d128", 128, 1000, act="idd", prev="runs", attn_dim=5, readout=True, rows="spike", seed=45, why="the same at d = 128"),
+    _infer("x_over_h_d64", 64, 1000, act="idd", prev="runs", attn_dim=5, readout=True, rows="x_over_h", seed=46,
+           why="agg x 100: |x| >> |h0| under the shared GRU scale"),
+    _infer("x_over_h_d128", 128, 1000, act="idd", prev="third", attn_dim=5, readout=True, rows="x_over_h", seed=47, why="the same at d = 128"),
+    _infer("h_over_x_d64", 64, 1000, act="idd", prev="runs", attn_dim=5, readout=True, rows="h_over_x", seed=48,
+           why="agg x 1e-3: |h0| >> |x| under the shared GRU scale"),
+    _infer("h_over_x_d128", 128, 1000, act="idd", prev="third", attn_dim=5, readout=True, rows="h_over_x", seed=49, why="the same at d = 128"),
+    # ---- weight scale: Ws_next x 300 with the gate weights at unit scale
+    _infer("ws300_d64", 64, 1000, act="relu", prev="runs", attn_dim=5, ws_scale=300.0, seed=50,
+           why="dense_split.hip the projections' scale refitted, the layer's kept; dense_split3.hip:82 the projections' own"),
+    _infer("ws300_d128", 128, 1000, act="tanh", prev="third", attn_dim=5, ws_scale=300.0, seed=51, why="split3.h:149-158 the projections' own scale"),
+]
+INFER_CASES = {c.name: c for c in _INFER_LIST}
+
+
+def _prev_runs(rng, n):
+    """Old and new rows in alternating runs of 1 .. 40 rows (seeded lengths): (prev_idx, n_old)."""
+    old = np.zeros(n, bool)
+    at, state = 0, bool(rng.integers(0, 2))
+    while at < n:
+        length = int(rng.integers(1, 41))
+        old[at:at + length] = state
+        at, state = at + length, not state
+    n_old = int(old.sum())
+    p = np.full(n, -1, np.int32)
+    p[old] = rng.permutation(n_old).astype(np.int32)
+    return p, n_old
+
+
+def tile_census(prev_idx, n):
+    """(all new, all old, mixed): how many 16-row tiles of the call have no old row, only old rows, both."""
+    old = np.zeros(n, bool) if prev_idx is None else np.asarray(prev_idx) >= 0
+    kinds = [(bool(old[t:t + 16].any()), bool(old[t:t + 16].all())) for t in range(0, n, 16)]
+    return sum(not a for a, _ in kinds), sum(b for _, b in kinds), sum(a and not b for a, b in kinds)
+
+
+def infer_inputs(case):
+    """Seeded inputs of an inference case: float32 arrays with the true d columns (prev_idx int32 [n] or None, nodes int32 [n, 2] sorted
+    distinct (query, entity) pairs with gaps), n_old, n_ent, n_scores (the size of scores_all the pairs need)."""
+    rng = np.random.default_rng(900 + case.seed)
+    f = lambda *shape, scale=1.0: (rng.standard_normal(shape) * scale).astype(np.float32)
+    d, n = case.d, case.n
+    prev_idx, n_old = _prev_runs(rng, n) if case.prev == "runs" else _prev(rng, case.prev, n)
+    agg = f(n, d)
+    if case.rows == "spike":
+        a = agg.astype(np.float64) * 10.0 ** rng.uniform(-3, 2, (n, 1))
+        r = np.arange(n)
+        a[r, r % d] = 8.0 * np.abs(a).max(1) * np.where(rng.random(n) < 0.5, -1.0, 1.0)
+        agg = a.astype(np.float32)
+    elif case.rows == "x_over_h":
+        agg = agg * np.float32(100.0)
+    elif case.rows == "h_over_x":
+        agg = agg * np.float32(1e-3)
+    n_ent = 37
+    flat = np.sort(rng.choice(3 * n + 5, n, replace=False)).astype(np.int64)
+    nodes = np.stack([flat // n_ent, flat % n_ent], 1).astype(np.int32)
+    return dict(agg=agg, prev_idx=prev_idx, n_old=n_old,
+                hidden_prev=None if prev_idx is None else np.clip(f(max(n_old, 1), d, scale=0.5), -1, 1),
+                W_h=f(d, d, scale=d ** -0.5), w_ih=f(3 * d, d, scale=d ** -0.5), w_hh=f(3 * d, d, scale=d ** -0.5),
+                b_ih=f(3 * d, scale=0.3), b_hh=f(3 * d, scale=0.3),
+                Ws_next=f(case.attn_dim, d, scale=case.ws_scale * d ** -0.5) if case.attn_dim else None,
+                W_final=f(d, scale=d ** -0.5) if case.readout else None, nodes=nodes, n_ent=n_ent, n_scores=3 * n + 5)
+
+
+def infer_forward(case, x, dtype=np.float64, fault=None):
+    return forward(x["agg"], x["hidden_prev"], x["prev_idx"], x["W_h"], case.act, x["w_ih"], x["w_hh"], x["b_ih"], x["b_hh"], None,
+                   x["Ws_next"], case.ap if case.attn_dim else None, dtype=dtype, fault=fault, W_final=x["W_final"])
+
+
+def infer_forward_f16x2(case, x, fault=None):
+    return forward_f16x2(x["agg"], x["hidden_prev"], x["prev_idx"], x["W_h"], case.act, x["w_ih"], x["w_hh"], x["b_ih"], x["b_hh"],
+                         x["Ws_next"], case.ap if case.attn_dim else None, x["W_final"], fault=fault)

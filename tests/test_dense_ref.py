@@ -2,6 +2,7 @@
 fp32 evaluation against the bound the GPU tests use (so the bound is known to be satisfiable by a correct fp32 implementation before a
 GPU is involved), and the bound against three deliberately wrong copies of the operation (so it is known to reject a subtly wrong
 kernel)."""
+import functools
 import math
 import types
 
@@ -182,9 +183,28 @@ def test_table_covers_what_it_names():
     assert all(c.why for c in C)
 
 
+@functools.lru_cache(maxsize=2)
+def _infer_ref(name):
+    """(inputs, fp64 reference) of an inference case, shared by the tests that follow one another on it."""
+    case = dr.INFER_CASES[name]
+    x = dr.infer_inputs(case)
+    return x, dr.infer_forward(case, x)
+
+
+def _outputs(f64):
+    return [o for o in dr.INFER_OUTPUTS if getattr(f64, o) is not None]
+
+
 def _ratios(case):
-    x = dr.inputs(case)
     r = {}
+    if case.kind == "infer":
+        x, f64 = _infer_ref(case.name)
+        f32 = dr.infer_forward(case, x, dtype=np.float32)
+        assert f32.hidden.dtype == np.float32 and (f32.score is None or f32.score.dtype == np.float32)
+        for o in _outputs(f64):
+            r[o] = dr.worst_ratio(getattr(f32, o), getattr(f64, o), f64.S[o], f64.n[o], dr.N0_STEP)
+        return r
+    x = dr.inputs(case)
     if case.kind == "step":
         f64, f32 = dr.step_forward(case, x), dr.step_forward(case, x, dtype=np.float32)
         assert f32.hidden.dtype == f32.ws.dtype == np.float32
@@ -210,15 +230,19 @@ def _ratios(case):
     return r
 
 
-@pytest.mark.parametrize("name", list(dr.CASES))
-def test_fp32_reference_within_its_bound(name):
-    """The reference evaluated in np.float32 (same code, same order) against its fp64 self on every case of the table: the ratio
-    |ref32 - ref64| / ((n + n0) u S) stays below the recorded constant for every element of every output, i.e. the GPU's bound
-    (4 x that) is one a correct fp32 implementation meets with a factor 4 to spare.  Prints the ratios."""
-    case = dr.CASES[name]
+_BOTH_TABLES = [pytest.param(c, id=c.name) for c in dr.CASES.values()] + [pytest.param(c, id="infer-" + c.name) for c in dr.INFER_CASES.values()]
+
+
+@pytest.mark.parametrize("case", _BOTH_TABLES)
+def test_fp32_reference_within_its_bound(case):
+    """The reference evaluated in np.float32 (same code, same order) against its fp64 self on every case of both tables (the inference
+    table: hidden, a_s and score): the ratio |ref32 - ref64| / ((n + n0) u S) stays below the recorded constant for every element of
+    every output, i.e. the GPU's bound (4 x that) is one a correct fp32 implementation meets with a factor 4 to spare.  Prints the
+    ratios."""
+    name = case.name
     r = _ratios(case)
     print("%s: %s" % (name, " ".join("%s=%.3g" % kv for kv in r.items())))
-    limit = dr.REF32_WORST_RATIO if case.kind == "step" else dr.REF32_WORST_RATIO_ROWS
+    limit = dr.REF32_WORST_RATIO if case.kind in ("step", "infer") else dr.REF32_WORST_RATIO_ROWS
     for o, v in r.items():
         assert v <= limit, (name, o, v)
 
@@ -229,16 +253,73 @@ def test_recorded_ratios_are_the_measured_ones():
     step = max(_ratios(dr.CASES["n70001_d64"]).values())
     rows = max(_ratios(dr.CASES["am16_k1"]).values())
     assert step <= dr.REF32_WORST_RATIO <= 1.25 * step and rows <= dr.REF32_WORST_RATIO_ROWS <= 1.25 * rows, (step, rows)
+    # the inference table's worst fp32 figure (w_d1_ld4's hidden, 0.049; its worst score 0.040) lies below the step's: the table shares
+    # REF32_WORST_RATIO and needs no constant of its own
+    infer = _ratios(dr.INFER_CASES["w_d1_ld4"])
+    assert max(infer.values()) <= dr.REF32_WORST_RATIO and 0 < infer["score"] <= dr.REF32_WORST_RATIO, infer
+    # the two-term emulation's constant: spike_d20_ld32's hidden
+    f16x2 = max(_f16x2_ratios(dr.INFER_CASES["spike_d20_ld32"]).values())
+    assert f16x2 <= dr.REF_F16X2_WORST_RATIO <= 1.25 * f16x2 and dr.C2_F16X2 == 2.0 * dr.REF_F16X2_WORST_RATIO, f16x2
+
+
+def _f16x2_ratios(case, fault=None):
+    """|forward_f16x2 - ref64| / (p 2^-22 S), the worst element per output."""
+    x, f64 = _infer_ref(case.name)
+    e = dr.infer_forward_f16x2(case, x, fault=fault)
+    r = {}
+    for o in _outputs(f64):
+        err = np.abs(getattr(e, o) - getattr(f64, o))
+        den = dr.P_CHAIN[o] * dr.U22 * f64.S[o]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r[o] = float(np.where(den > 0, err / den, np.where(err > dr.TINY, np.inf, 0.0)).max())
+    return r
+
+
+@pytest.mark.parametrize("name", list(dr.INFER_CASES))
+def test_f16x2_emulation_within_its_recorded_ratio(name):
+    """The two-term operand form emulated in numpy (dr.forward_f16x2) against the fp64 reference on every inference case: the ratio
+    |emul - ref64| / (p 2^-22 S) stays below REF_F16X2_WORST_RATIO for every element of every output; precision 1's added allowance is
+    2 x that.  Prints the ratios."""
+    r = _f16x2_ratios(dr.INFER_CASES[name])
+    print("%s: %s" % (name, " ".join("%s=%.3g" % kv for kv in r.items())))
+    for o, v in r.items():
+        assert v <= dr.REF_F16X2_WORST_RATIO, (name, o, v)
 
 
 @pytest.mark.parametrize("fault,case_name,outputs", [("no_b_hn", "d48_tanh", ("ws", "hidden")), ("no_b_hn", "d20_tanh_mask", ("ws", "hidden")),
                                                      ("dgh_n_no_r", "d64_relu_mask", ("dgh", "dgh_n", "dh0", "grad_prev")),
                                                      ("dgh_n_no_r", "d16_relu", ("dgh", "dgh_n", "dh0", "grad_prev")),
-                                                     ("col_shift", "d36_relu_mask", ("dgi", "dgh", "dpre", "dagg", "dh0"))])
+                                                     ("col_shift", "d36_relu_mask", ("dgi", "dgh", "dpre", "dagg", "dh0")),
+                                                     ("no_lo_hi", "w_d20", ("hidden", "a_s", "score")),
+                                                     ("no_lo_hi", "w_d3_ld4", ("hidden", "a_s", "score")),
+                                                     ("one_term", "w_d20", ("hidden", "a_s", "score")),
+                                                     ("stale_all_new", "prev_runs_d64", ("hidden", "a_s")),
+                                                     ("stale_all_new", "w_d128", ("hidden", "a_s", "score")),
+                                                     ("readout_h0", "readout", ("score",)),
+                                                     ("readout_h0", "w_d1_ld4", ("score",))])
 def test_bound_rejects_a_wrong_kernel(fault, case_name, outputs):
     """The tests can fail: the reference's own fp32 copy of the operation with one thing wrong - one gate bias (b_hn) dropped; dgh's n
     block missing its * r; at d = 36 the partly filled column block reading z one column to the right - is rejected by the GPU's bound
-    on each output the fault reaches (on more than 1 % of its elements, not on a stray one); the outputs upstream of the fault still pass."""
+    on each output the fault reaches (on more than 1 % of its elements, not on a stray one); the outputs upstream of the fault still pass.
+    The inference table: the two-term emulation with its W_lo X_hi term dropped, and with a single f16 term, fails PRECISION 1's bound
+    (the added 2^-22 term has not swallowed what the bound is for; at d = 128 the common term alone is wider than an 11-bit operand's
+    error, which is why the bit-for-bit product test of tests/test_dense_infer_gpu.py exists); an fp32 evaluation whose all-new tiles
+    keep the last mixed tile's h0, and one whose readout reads h0 instead of the new state, fail the common bound."""
+    if fault in ("no_lo_hi", "one_term", "stale_all_new", "readout_h0"):
+        case = dr.INFER_CASES[case_name]
+        x, ref = _infer_ref(case_name)
+        two_term = fault in ("no_lo_hi", "one_term")
+        bad = dr.infer_forward_f16x2(case, x, fault=fault) if two_term else dr.infer_forward(case, x, dtype=np.float32, fault=fault)
+        if fault == "stale_all_new":
+            assert min(dr.tile_census(x["prev_idx"], case.n)) > 0
+        for o in _outputs(ref):
+            within = np.abs(np.asarray(getattr(bad, o), np.float64) - getattr(ref, o)) <= dr.infer_bound(1 if two_term else 0, ref.S[o],
+                                                                                                         ref.n[o], o)
+            if o in outputs:
+                assert (~within).mean() > 0.01, (o, (~within).mean())
+            elif fault == "readout_h0":
+                assert within.all(), o      # the state and a_s are upstream of the readout
+        return
     case = dr.CASES[case_name]
     x = dr.inputs(case)
     if fault == "no_b_hn":
@@ -256,3 +337,109 @@ def test_bound_rejects_a_wrong_kernel(fault, case_name, outputs):
             assert (~within).mean() > 0.01, (o, (~within).mean())      # col_shift reaches 4 of dgi's 108 columns: 3.7 %
         elif o in clean:
             assert within.all(), o
+
+
+# ---- the inference table ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["w_d3_ld4", "w_d20", "w_d33_ld36", "prev_runs_d64", "readout", "prev_null", "n1_d128"])
+def test_inference_reference_equals_torch(name):
+    """The extended forward == torch.gru_cell around the same W_h / carry in fp64, a_s == hidden Ws^T, score == hidden . W_final with
+    S_score = S_hidden |W_final| and n_score = n_hidden + d, and the scatter helper puts score m at nodes[m, 0] * n_ent + nodes[m, 1]."""
+    case = dr.INFER_CASES[name]
+    x, f = _infer_ref(name)
+    d, n = case.d, case.n
+    step = types.SimpleNamespace(d=d, n=n, act=case.act)
+    T = _torch_step(step, dict(x, mask=None), None)
+    tol = dict(rtol=1e-11, atol=1e-12)
+    hidden = T["cell"].detach().numpy()
+    np.testing.assert_allclose(f.hidden, hidden, **tol)
+    if case.attn_dim:
+        np.testing.assert_allclose(f.a_s[:, :case.attn_dim], hidden @ np.asarray(x["Ws_next"], np.float64).T, **tol)
+        assert f.a_s.shape == (n, case.ap) and not f.a_s[:, case.attn_dim:].any() and not f.S["a_s"][:, case.attn_dim:].any()
+    else:
+        assert f.a_s is None and "a_s" not in f.S
+    if not case.readout:
+        assert f.score is None and "score" not in f.S
+        return
+    w = np.asarray(x["W_final"], np.float64)
+    np.testing.assert_allclose(f.score, torch.as_tensor(hidden) @ torch.as_tensor(w), **tol)
+    np.testing.assert_allclose(f.S["score"], f.S["hidden"] @ np.abs(w), rtol=1e-14)
+    assert f.n["score"] == f.n["hidden"] + d == f.n.get("a_s", f.n["score"]) and f.score.shape == (n,)
+    nodes, n_ent, size = x["nodes"], x["n_ent"], x["n_scores"]
+    all_ = dr.scatter_scores(f.score, nodes, n_ent, size)
+    at = nodes[:, 0].astype(np.int64) * n_ent + nodes[:, 1]
+    assert np.array_equal(all_[at], f.score) and np.isnan(all_).sum() == size - n
+    # sorted distinct pairs with gaps: not an arange
+    assert (np.diff(at) > 0).all() and at.max() < size and (n < 16 or (np.diff(at) > 1).any()) and (nodes[:, 1] < n_ent).all()
+
+
+def test_runs_mode_has_every_kind_of_tile():
+    """prev_idx of every `runs` case really holds 16-row tiles without an old row, tiles of old rows only and mixed tiles (the all-new
+    branch of any_old next to mixed tiles inside one call); a third at random has (almost) only mixed ones."""
+    runs = [c for c in dr.INFER_CASES.values() if c.prev == "runs"]
+    assert {c.d for c in runs} >= {1, 20, 30, 33, 63, 64, 128}
+    for c in runs:
+        x = dr.infer_inputs(c)
+        p = x["prev_idx"]
+        new, old, mixed = dr.tile_census(p, c.n)
+        assert new >= 5 and old >= 5 and mixed >= 5 and new + old + mixed == (c.n + 15) // 16, (c.name, new, old, mixed)
+        # somewhere an all-new tile sits right behind a tile with old rows (a stale h0 would have something to be stale with)
+        has_old = np.array([(p[t:t + 16] >= 0).any() for t in range(0, c.n, 16)])
+        assert (has_old[:-1] & ~has_old[1:]).any() and (~has_old[:-1] & has_old[1:]).any()
+        sel = np.sort(p[p >= 0])
+        assert x["n_old"] == len(sel) and np.array_equal(sel, np.arange(len(sel))) and x["hidden_prev"].shape == (max(len(sel), 1), c.d)
+        runs_len = np.diff(np.flatnonzero(np.diff(np.r_[-1, (p >= 0).astype(int), -1]) != 0))
+        assert 1 <= runs_len.min() and runs_len.max() <= 40
+    c = dr.INFER_CASES["prev_third"]
+    assert dr.tile_census(dr.infer_inputs(c)["prev_idx"], c.n)[0] == 0
+    assert dr.tile_census(None, 33) == (3, 0, 0) and dr.tile_census(np.zeros(33, np.int32), 33) == (0, 3, 0)
+
+
+def test_inference_table_covers_what_it_names():
+    C = list(dr.INFER_CASES.values())
+    assert all(c.why and c.kind == "infer" for c in C) and not set(dr.INFER_CASES) - {c.name for c in C}
+    wide = {(c.d, c.ld) for c in C if c.n == 1000 and c.rows == "plain" and c.attn_dim and c.readout}
+    assert wide >= {(1, 4), (3, 4), (20, 20), (20, 32), (30, 32), (32, 32), (33, 36), (48, 64), (63, 64), (64, 64), (128, 128)}
+    assert all(c.ld >= c.d and c.ld % 4 == 0 and c.ld <= 128 and c.ap == (c.attn_dim + 3) // 4 * 4 for c in C)
+    for d in (64, 128):
+        assert {c.n for c in C if c.d == d} >= {1, 15, 16, 17}
+    # a second pass of the persistent grid, per kernel: rows per pass from its NW
+    assert dr.ROWS_PER_PASS == {8: 32768, 4: 16384}
+    big = {(c.d, c.n, c.precisions) for c in C if c.n > 16384}
+    assert big == {(64, 32769, (0, 1, 2)), (20, 32769, (0, 1, 2)), (128, 32769, (0, 1)), (128, 16385, (2,))}
+    assert all(c.precisions == (0, 1, 2) for c in C if c.n <= 16384)
+    assert {c.prev for c in C} == {"null", "none", "all", "third", "runs"}
+    assert {c.attn_dim for c in C} == {0, 1, 5, 8, 16} and {c.ap for c in C} == {0, 4, 8, 16}
+    for d128 in (True, False):
+        sub = [c for c in C if (c.d == 128) == d128]
+        assert {c.act for c in sub} == {0, 1, 2} and {c.prev for c in sub} >= {"runs", "third", "all"}
+        assert any(c.readout and not c.attn_dim for c in sub) and any(not c.readout and not c.attn_dim for c in sub)
+        assert any(c.no_hidden for c in sub) and any(c.attn_dim == 16 for c in sub) and any(c.ws_scale == 300.0 for c in sub)
+        assert {c.rows for c in sub} == {"plain", "spike", "x_over_h", "h_over_x"}
+    assert all(c.readout and not c.attn_dim for c in C if c.no_hidden)
+    assert all(c.act == 0 and c.prev in ("runs", "third") for c in C if c.rows in ("x_over_h", "h_over_x"))
+    # the spike: one element 8 x the row's largest other one, its column cycling over all d; rows spread over five decades
+    c = dr.INFER_CASES["spike_d64"]
+    a = np.abs(dr.infer_inputs(c)["agg"].astype(np.float64))
+    col = a.argmax(1)
+    assert np.array_equal(col, np.arange(c.n) % c.d)
+    rest = np.where(np.arange(c.d)[None] == col[:, None], 0.0, a).max(1)
+    ratio = a.max(1) / rest      # 8 x the noise row's largest; more where that largest sat in the spike's own column
+    assert (ratio > 8.0 * (1 - 1e-6)).all() and (np.abs(ratio - 8.0) < 1e-5).mean() > 0.95
+    assert a.max(1).max() / a.max(1).min() > 1e4 and a.max() * 2.0 ** 14 / 2.0 ** np.floor(np.log2(a.max())) < 65504
+    x = dr.infer_inputs(dr.INFER_CASES["x_over_h_d64"])
+    assert np.abs(x["agg"]).mean() > 50 * np.abs(x["hidden_prev"]).mean()
+    x = dr.infer_inputs(dr.INFER_CASES["h_over_x_d64"])
+    assert np.abs(x["agg"]).mean() * 50 < np.abs(x["hidden_prev"]).mean()
+    x = dr.infer_inputs(dr.INFER_CASES["ws300_d64"])
+    assert np.abs(x["Ws_next"]).max() > 100 * np.abs(x["w_ih"]).max()
+
+
+def test_two_term_split_by_hand():
+    """hi + lo of the emulated operand form carries 22 bits: v = 1 + 2^-12 + 2^-21 at scale 2^14 splits into hi = 2^14 (f16 has 11
+    bits), lo = 4 + 2^-7 exactly; 2^-23 more is beyond lo's 11 bits and is rounded away.  Scales: 3 -> 2^13 (row), 2^12 (weights)."""
+    hi, lo = dr._split2(np.array([1 + 2.0 ** -12 + 2.0 ** -21, 1 + 2.0 ** -12 + 2.0 ** -21 + 2.0 ** -25]), 2.0 ** 14)
+    assert hi.tolist() == [2.0 ** 14, 2.0 ** 14] and lo.tolist() == [4 + 2.0 ** -7, 4 + 2.0 ** -7]
+    assert dr._pow2_scale(3.0, 15) == 2.0 ** 13 and dr._pow2_scale(3.0, 14) == 2.0 ** 12 and dr._pow2_scale(0.0, 15) == 1.0
+    assert dr._pow2_scale(2.0 ** 14, 15) == 1.0 and dr._pow2_scale(np.nextafter(2.0 ** 15, 0), 15) == 1.0
+    X, W = np.array([[3.0, 0.5]]), np.array([[0.25, 2.0]])
+    assert dr._prod2(X, 2.0 ** 13, W, 2.0 ** 12)[0, 0] == 1.75      # exactly representable operands: the product is exact
