@@ -432,6 +432,32 @@ size_t rg_paths_scratch_bytes(int64_t n_edges, int32_t k);
 int rg_paths_topk(const int32_t* edges, const float* alpha, const int64_t* offsets, int32_t row_lo, int32_t row_hi, int32_t n_hops,
                   int32_t k, void* scratch, int64_t* path_edge, double* path_prod, int32_t* path_count, void* stream);
 
+/* ---- one message-passing layer over an explicit edge list: rg_layer_fwd's arithmetic on the edges the caller hands over instead of
+ * the ones a frontier and a graph enumerate (explain.RDigraph.rescore: an answer re-scored on its r-digraph with edges masked out).
+ * The hop has n_dst destinations; dst_ptr int32 [n_dst + 1] is a CSR over its n_edges edges (device memory; dst_ptr_host is the same
+ * array in host memory, read before anything is enqueued: it must start at 0, never decrease and end at n_edges).  Per edge src_idx
+ * (its row in hidden [n_src, ld] and a_s [n_src, ap]) and rel (its row in rela [n_rela_rows, ld] and a_r [n_rela_rows, ap]); per
+ * destination row_of_dst (its row in a_q [batch, ap]); w_alpha [attn_dim], b_alpha [1].  Indices outside their table are clamped to
+ * it, never followed.
+ *   alpha_e = sigmoid(w . relu((a_s[s] + a_r[r]) + a_q[b]) + b_alpha)      the forward family's order: on bit-identical inputs the very
+ *                                                                         float rg_layer_fwd multiplies by and rg_explain_emit stores
+ *   agg_out[o] = sum over the edges of o, in list order, of alpha_e * (hidden[s] + rela[r])        [n_dst, ld], every row written whole
+ *   alpha_out [n_edges] = alpha_e, or NULL
+ * Pad columns d .. ld - 1 of agg_out are 0 when those of hidden and rela are.  ld % 4 == 0, d <= ld <= 256; ap one of the padded
+ * attention widths 4, 8, 12, 16, 32.  No float atomics: a destination of more than RG_DIGRAPH_CHUNK edges is cut into chunks of that
+ * many, counted from its own first edge, which separate waves sum into partial rows in scratch; a second launch adds them in chunk
+ * order.  agg_out[o] therefore has the same bits on every run and whatever else the call carries.  scratch: device memory of
+ * rg_digraph_layer_fwd_scratch_bytes(dst_ptr_host, n_dst, ld) bytes, 16-B aligned (0 / NULL when no destination is cut, or the CSR is
+ * malformed).  n_dst == 0 or n_edges == 0 succeeds and launches nothing (agg_out is then left alone).  The call waits for the copy of
+ * the chunk list when a destination is cut; it is not for stream capture. */
+#define RG_DIGRAPH_CHUNK 128
+size_t rg_digraph_layer_fwd_scratch_bytes(const int32_t* dst_ptr_host, int32_t n_dst, int32_t ld);
+int rg_digraph_layer_fwd(int32_t n_dst, int64_t n_edges, const int32_t* dst_ptr, const int32_t* dst_ptr_host, const int32_t* src_idx,
+                         const int32_t* rel, const int32_t* row_of_dst, int32_t n_src, int32_t n_rela_rows, int32_t batch,
+                         const float* hidden, const float* rela, int32_t d, int32_t ld, const float* a_s, const float* a_r,
+                         const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha, int32_t attn_dim, float* agg_out,
+                         float* alpha_out, void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- rule quality: support and confidence of rules (head h, body r_1..r_L) counted on the whole graph; no counterpart in the
  * reference (its *_rule_vis.py scripts only draw).  The graph is used as built, inverse and identity rows included: for a relation id
  * r in 0..n_rela_rows-1, A_r(x, y) holds iff the graph has at least one row (x, r, y) (a repeated fact counts once), and body(x, y)

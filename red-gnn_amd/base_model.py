@@ -222,6 +222,15 @@ class BaseModel(object):
         from .explain import split_rules
         return split_rules(self.model, self.loader, data, k, self.n_tbatch, max_queries)
 
+    def fidelity(self, data="test", k=4, batch=50, max_queries=None):
+        """model.fidelity over the valid or test split: the first (smallest) answer of each of its first ``max_queries`` queries
+        (default: all) is one row, the rows are walked in batches of ``batch``.  Returns dict(n = rows, k, necessity_mean /
+        necessity_median / sufficiency_gap_mean / sufficiency_gap_median: lists over j = 1..k, disconnected: per j the share of rows
+        whose answer was reached and no longer is once the best j paths' facts are deleted).  Static and inductive models;
+        single-process: under a process group every rank computes the whole result."""
+        from .explain import split_fidelity
+        return split_fidelity(self, data, k, batch, max_queries)
+
     def rule_quality(self, table=None, data="test", k=1, max_queries=None):
         """model.rule_quality of a rule table on the graph the valid or test split is scored on (the mode ``rules`` explains in), over
         every entity as a source.  ``table=None``: the table is mined first, ``self.rules(data, k, max_queries)``.  Returns an

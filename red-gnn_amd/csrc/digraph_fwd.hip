@@ -1,0 +1,258 @@
+// One message-passing layer over an explicit, destination-segmented edge list (rg_digraph_layer_fwd): the executor behind
+// explain.RDigraph.rescore, which re-scores an answer on its r-digraph with some edges masked out.  Every other layer kernel
+// enumerates its edges from the graph's CSR and the frontier bitmaps; this one is handed them:
+//
+//   for every destination o (a CSR row dst_ptr[o] .. dst_ptr[o + 1] of the edge list), b = row_of_dst[o]:
+//     for every edge e of the row, in list order, s = src_idx[e], r = rel[e]:
+//       alpha_e = sigmoid(w . relu((a_s[s] + a_r[r]) + a_q[b]) + b_alpha)        attn.h attn_acc_fwd / attn_alpha: the forward's float
+//       acc    += alpha_e * (hidden[s] + rela[r])
+//     agg[o] = acc
+//
+// Mapping (wave64): a destination is owned by a group of G lanes, G * 4 >= ld floats, so a row is one float4 per lane and a wave
+// holds 64 / G destinations.  A round takes G edges of the destination: lane j forms the attention scalar of edge j (and stores it
+// to alpha_out), then the group walks the round's edges in order, each lane gathering its float4 of hidden[s] and rela[r], four
+// gathers in flight.  All lanes of a wave run the same number of rounds (the longest destination's) with their stores predicated, so
+// the lane exchanges never read an inactive lane.
+//
+// Split rule (the scatter / gather rule for skewed segment lengths): a destination of more than DIGRAPH_CHUNK edges is cut into
+// chunks of DIGRAPH_CHUNK edges counted from ITS OWN first edge; every chunk is an item of the same launch that sums into a partial
+// row, and a second launch adds the partial rows in chunk order.  A wave per destination alone would run as long as the hub.
+// No float atomics; the sums of a destination are formed in list order inside a chunk and in chunk order across chunks, so agg[o]
+// has the same bits on every run and does not depend on what else the call carries.
+#include <algorithm>
+#include <vector>
+
+#include "attn.h"
+
+namespace rgdg {
+namespace {
+
+constexpr int DIGRAPH_CHUNK = RG_DIGRAPH_CHUNK;   // edges per chunk of a cut destination (include/redgnn.h)
+constexpr int DG_BLOCK = 256;                     // 4 waves
+
+struct DgArgs {
+  int n_dst, n_items;          // items: [0, n_dst) the destinations themselves, then the chunks of the cut ones
+  int E, n_src, n_rela_rows, B;
+  const int32_t* dst_ptr;
+  const int32_t* src_idx;
+  const int32_t* rel;
+  const int32_t* row_of_dst;
+  const int4* chunks;          // [n_items - n_dst] {destination, first edge, end, slot of the partial row}
+  const float4* hidden;
+  const float4* rela;
+  int ld4;
+  const float4* a_s;
+  const float4* a_r;
+  const float4* a_q;
+  const float* w_alpha;
+  const float* b_alpha;
+  int attn_dim;
+  float4* agg;
+  float4* partial;
+  float* alpha_out;
+};
+
+__device__ __forceinline__ int clampi(int x, int hi) { return min(max(x, 0), hi); }
+
+template <int G, int AP4>
+__global__ __launch_bounds__(DG_BLOCK) void digraph_fwd_kernel(DgArgs A) {
+  constexpr int PER_WAVE = 64 / G;
+  const int lane = threadIdx.x & 63;
+  const int lane_g = lane & (G - 1), gbase = lane & ~(G - 1);
+  const int wave = blockIdx.x * (DG_BLOCK / 64) + (threadIdx.x >> 6);
+  const int item = wave * PER_WAVE + lane / G;
+  const bool row_lane = lane_g < A.ld4;
+  const int lane_c = row_lane ? lane_g : A.ld4 - 1;      // loads never branch: idle lanes re-read the last float4
+
+  // the item's destination, edge range and output row; an item without work keeps beg == end and stores nothing
+  int o = 0, beg = 0, end = 0;
+  float4* out = nullptr;
+  if (item < A.n_dst) {
+    o = item;
+    const int lo = clampi(A.dst_ptr[o], A.E), hi = clampi(A.dst_ptr[o + 1], A.E);
+    if (hi - lo <= DIGRAPH_CHUNK) {                      // (a cut destination is written by the combine pass)
+      beg = lo; end = max(hi, lo);
+      out = A.agg + (int64_t)o * A.ld4;
+    }
+  } else if (item < A.n_items) {
+    const int4 c = A.chunks[item - A.n_dst];
+    o = clampi(c.x, A.n_dst - 1);
+    beg = clampi(c.y, A.E); end = min(max(clampi(c.z, A.E), beg), beg + DIGRAPH_CHUNK);
+    out = A.partial + (int64_t)c.w * A.ld4;
+  }
+  const int b = clampi(A.row_of_dst[o], A.B - 1);
+  const float b_alpha = A.b_alpha[0];
+  const float4* aq_p = A.a_q + (int64_t)b * AP4;
+
+  float4 acc = rg::f4zero();
+  for (int c0 = beg; __any(c0 < end); c0 += G) {
+    // ---- one edge per lane: indices and the attention scalar --------------------------------------------------
+    const int c = c0 + lane_g;
+    const bool valid = c < end;
+    int s = 0, r = 0;
+    float alpha = 0.f;
+    if (valid) {
+      s = clampi(A.src_idx[c], A.n_src - 1);
+      r = clampi(A.rel[c], A.n_rela_rows - 1);
+      float z = b_alpha;
+#pragma clang loop unroll_count(AP4 >= 8 ? 2 : AP4)
+      for (int k = 0; k < AP4; ++k)
+        rg::attn_acc_fwd(z, rg::attn_w4(A.w_alpha, A.attn_dim, k), A.a_s[(int64_t)s * AP4 + k], A.a_r[(int64_t)r * AP4 + k], aq_p[k]);
+      alpha = rg::attn_alpha(z);
+      if (A.alpha_out) A.alpha_out[c] = alpha;
+    }
+    const int cnt = min(max(end - c0, 0), G);
+    // ---- the round's edges in order, every lane its float4 of the row; four gathers in flight ------------------
+    for (int j = 0; __any(j < cnt); j += 4) {
+      int su[4], ru[4];
+      float al[4];
+      float4 hv[4], rv[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {      // (slots past cnt hold s = r = 0: row 0 is read and not used)
+        const int from = gbase + ((j + u) & (G - 1));
+        su[u] = __shfl(s, from, 64);
+        ru[u] = __shfl(r, from, 64);
+        al[u] = __shfl(alpha, from, 64);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) hv[u] = A.hidden[(int64_t)su[u] * A.ld4 + lane_c];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) rv[u] = A.rela[(int64_t)ru[u] * A.ld4 + lane_c];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (j + u < cnt) {
+          acc.x = fmaf(al[u], hv[u].x + rv[u].x, acc.x);
+          acc.y = fmaf(al[u], hv[u].y + rv[u].y, acc.y);
+          acc.z = fmaf(al[u], hv[u].z + rv[u].z, acc.z);
+          acc.w = fmaf(al[u], hv[u].w + rv[u].w, acc.w);
+        }
+      }
+    }
+  }
+  if (out && row_lane) out[lane_g] = acc;
+}
+
+// agg[o] of the cut destinations: their chunks' partial rows added in chunk order, the first one initialising the sum
+__global__ void digraph_combine_kernel(const int4* __restrict__ hubs, int n_hubs, const float4* __restrict__ partial,
+                                       float4* __restrict__ agg, int ld4) {
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t h = tid / ld4;
+  const int c = (int)(tid - h * ld4);
+  if (h >= n_hubs) return;
+  const int4 hub = hubs[h];                              // {destination, first slot, chunks, -}
+  const float4* p = partial + (int64_t)hub.y * ld4 + c;
+  float4 acc = p[0];
+  for (int k = 1; k < hub.z; ++k) {
+    const float4 v = p[(int64_t)k * ld4];
+    acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+  }
+  agg[(int64_t)hub.x * ld4 + c] = acc;
+}
+
+// the cut destinations of a CSR on the host: how many, and how many chunks they make
+void count_cuts(const int32_t* ptr, int32_t n_dst, int64_t* n_hubs, int64_t* n_chunks) {
+  *n_hubs = *n_chunks = 0;
+  for (int32_t o = 0; o < n_dst; ++o) {
+    const int64_t len = (int64_t)ptr[o + 1] - ptr[o];
+    if (len > DIGRAPH_CHUNK) { ++*n_hubs; *n_chunks += rg::ceil_div(len, DIGRAPH_CHUNK); }
+  }
+}
+
+size_t list_bytes(int64_t n_hubs, int64_t n_chunks) { return rg::align_up((size_t)(n_hubs + n_chunks) * sizeof(int4), 256); }
+
+template <int G, int AP4>
+int launch(const DgArgs& A, hipStream_t s) {
+  const int64_t waves = rg::ceil_div(A.n_items, 64 / G);
+  hipLaunchKernelGGL((digraph_fwd_kernel<G, AP4>), dim3((unsigned)rg::ceil_div(waves, DG_BLOCK / 64)), dim3(DG_BLOCK), 0, s, A);
+  RG_LAUNCH_CHECK();
+  return 0;
+}
+
+}  // namespace
+}  // namespace rgdg
+
+extern "C" size_t rg_digraph_layer_fwd_scratch_bytes(const int32_t* dst_ptr_host, int32_t n_dst, int32_t ld) {
+  if (!dst_ptr_host || n_dst <= 0 || ld <= 0) return 0;
+  for (int32_t o = 0; o < n_dst; ++o)
+    if (dst_ptr_host[o + 1] < dst_ptr_host[o]) return 0;
+  int64_t n_hubs, n_chunks;
+  rgdg::count_cuts(dst_ptr_host, n_dst, &n_hubs, &n_chunks);
+  if (n_hubs == 0) return 0;
+  return rgdg::list_bytes(n_hubs, n_chunks) + rg::align_up((size_t)n_chunks * ld * sizeof(float), 256);
+}
+
+extern "C" int rg_digraph_layer_fwd(int32_t n_dst, int64_t n_edges, const int32_t* dst_ptr, const int32_t* dst_ptr_host,
+                                    const int32_t* src_idx, const int32_t* rel, const int32_t* row_of_dst, int32_t n_src,
+                                    int32_t n_rela_rows, int32_t batch, const float* hidden, const float* rela, int32_t d, int32_t ld,
+                                    const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha,
+                                    const float* b_alpha, int32_t attn_dim, float* agg_out, float* alpha_out, void* scratch,
+                                    size_t scratch_bytes, void* stream) {
+  const char* who = "rg_digraph_layer_fwd";
+  RG_CHECK(n_dst >= 0 && n_edges >= 0 && n_edges < ((int64_t)1 << 31), "%s: n_dst=%d n_edges=%lld (need 0 <= n_dst, 0 <= n_edges < 2^31)",
+           who, n_dst, (long long)n_edges);
+  RG_CHECK(n_src >= 0 && n_rela_rows >= 0 && batch >= 0, "%s: n_src=%d n_rela_rows=%d batch=%d (negative size)", who, n_src, n_rela_rows,
+           batch);
+  RG_CHECK(d > 0 && ld >= d && ld % 4 == 0 && ld <= 256, "%s: d=%d ld=%d (need ld%%4==0, d<=ld<=256)", who, d, ld);
+  RG_CHECK(attn_dim > 0 && ap >= attn_dim && ap % 4 == 0, "%s: attn_dim=%d ap=%d", who, attn_dim, ap);
+  if (n_dst == 0) {
+    RG_CHECK(n_edges == 0, "%s: %lld edges without a destination", who, (long long)n_edges);
+    return 0;
+  }
+  RG_CHECK(dst_ptr_host, "%s: NULL argument (dst_ptr_host)", who);
+  RG_CHECK(dst_ptr_host[0] == 0, "%s: dst_ptr starts at %d, not 0", who, dst_ptr_host[0]);
+  for (int32_t o = 0; o < n_dst; ++o)
+    RG_CHECK(dst_ptr_host[o + 1] >= dst_ptr_host[o], "%s: dst_ptr decreases at destination %d", who, o);
+  RG_CHECK(dst_ptr_host[n_dst] == n_edges, "%s: dst_ptr ends at %d, not at the number of edges %lld", who, dst_ptr_host[n_dst],
+           (long long)n_edges);
+  if (n_edges == 0) return 0;                            // nothing to sum and nothing launched: the caller owns agg_out
+  RG_CHECK(dst_ptr && src_idx && rel && row_of_dst && hidden && rela && a_s && a_r && a_q && w_alpha && b_alpha && agg_out,
+           "%s: NULL argument", who);
+  RG_CHECK(n_src > 0 && n_rela_rows > 0 && batch > 0, "%s: edges but n_src=%d n_rela_rows=%d batch=%d", who, n_src, n_rela_rows, batch);
+  RG_CHECK((((uintptr_t)hidden | (uintptr_t)rela | (uintptr_t)a_s | (uintptr_t)a_r | (uintptr_t)a_q | (uintptr_t)agg_out |
+             (uintptr_t)scratch) & 15) == 0, "%s: float buffers must be 16-B aligned", who);
+  int64_t n_hubs, n_chunks;
+  rgdg::count_cuts(dst_ptr_host, n_dst, &n_hubs, &n_chunks);
+  RG_CHECK((int64_t)n_dst + n_chunks < ((int64_t)1 << 31), "%s: %lld items overflow int32", who, (long long)(n_dst + n_chunks));
+  const size_t need = n_hubs ? rgdg::list_bytes(n_hubs, n_chunks) + rg::align_up((size_t)n_chunks * ld * sizeof(float), 256) : 0;
+  RG_CHECK(need == 0 || (scratch && scratch_bytes >= need), "%s: scratch %zu B < required %zu B", who, scratch ? scratch_bytes : (size_t)0,
+           need);
+
+  rgdg::DgArgs A;
+  A.n_dst = n_dst; A.n_items = (int)(n_dst + n_chunks); A.E = (int)n_edges; A.n_src = n_src; A.n_rela_rows = n_rela_rows; A.B = batch;
+  A.dst_ptr = dst_ptr; A.src_idx = src_idx; A.rel = rel; A.row_of_dst = row_of_dst;
+  A.hidden = (const float4*)hidden; A.rela = (const float4*)rela; A.ld4 = ld / 4;
+  A.a_s = (const float4*)a_s; A.a_r = (const float4*)a_r; A.a_q = (const float4*)a_q;
+  A.w_alpha = w_alpha; A.b_alpha = b_alpha; A.attn_dim = attn_dim;
+  A.agg = (float4*)agg_out; A.alpha_out = alpha_out;
+  int4* hubs_dev = (int4*)scratch;
+  A.chunks = hubs_dev + n_hubs;
+  A.partial = n_hubs ? (float4*)((char*)scratch + rgdg::list_bytes(n_hubs, n_chunks)) : nullptr;
+  // every argument error is out before anything is enqueued: the width dispatch is probed first
+  if (rg::with_ap4(ap / 4, who, [](auto) { return 0; })) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  if (n_hubs) {
+    std::vector<int4> list((size_t)(n_hubs + n_chunks));
+    int64_t h = 0, slot = 0;
+    for (int32_t o = 0; o < n_dst; ++o) {
+      const int32_t lo = dst_ptr_host[o], hi = dst_ptr_host[o + 1];
+      if (hi - lo <= rgdg::DIGRAPH_CHUNK) continue;
+      const int n_c = (int)rg::ceil_div(hi - lo, rgdg::DIGRAPH_CHUNK);
+      list[h++] = make_int4(o, (int)slot, n_c, 0);
+      for (int k = 0; k < n_c; ++k, ++slot)
+        list[n_hubs + slot] = make_int4(o, lo + k * rgdg::DIGRAPH_CHUNK, std::min(hi, lo + (k + 1) * rgdg::DIGRAPH_CHUNK), (int)slot);
+    }
+    // (a copy from pageable memory: the runtime is done with the vector when the call returns)
+    RG_HIP(hipMemcpyAsync(hubs_dev, list.data(), list.size() * sizeof(int4), hipMemcpyHostToDevice, s));
+  }
+  const int rc = rg::with_g(A.ld4, [&](auto g) {
+    return rg::with_ap4(ap / 4, who, [&](auto a4) { return rgdg::launch<decltype(g)::value, decltype(a4)::value>(A, s); });
+  });
+  if (rc) return rc;
+  if (n_hubs) {
+    const int64_t threads = n_hubs * A.ld4;
+    hipLaunchKernelGGL(rgdg::digraph_combine_kernel, dim3((unsigned)rg::ceil_div(threads, 256)), dim3(256), 0, s, hubs_dev, (int)n_hubs,
+                       (const float4*)A.partial, A.agg, A.ld4);
+    RG_LAUNCH_CHECK();
+  }
+  return 0;
+}

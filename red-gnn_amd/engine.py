@@ -1106,6 +1106,73 @@ def paths_topk(edges, alpha, offsets, n_hops, k, scratch_bytes=PATHS_SCRATCH_BYT
     return path_edge, path_prod, path_count
 
 
+DIGRAPH_CHUNK = 128                  # include/redgnn.h: RG_DIGRAPH_CHUNK
+
+DIGRAPH_EVENTS = None                # probes: a list that collects (start, end, n_dst, n_edges) of every digraph_layer_fwd
+
+
+def digraph_chunks(dst_ptr_host):
+    """(cut destinations, chunks they make, longest destination) of a hop's CSR (numpy int [n_dst + 1]): a destination of more than
+    DIGRAPH_CHUNK edges is cut into chunks of that many, summed by separate waves."""
+    length = np.diff(np.asarray(dst_ptr_host, np.int64))
+    hub = length > DIGRAPH_CHUNK
+    return int(hub.sum()), int(((length[hub] + DIGRAPH_CHUNK - 1) // DIGRAPH_CHUNK).sum()), int(length.max()) if length.size else 0
+
+
+def digraph_layer_fwd(dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s, a_r, a_q, w_alpha, b_alpha, attn_dim, want_alpha=True,
+                      dst_ptr_host=None):
+    """One message-passing layer over an explicit, destination-segmented edge list (rg_digraph_layer_fwd): (agg fp32 [n_dst, ld], alpha
+    fp32 [E] or None).  ``dst_ptr`` int32 [n_dst + 1] is the CSR of the hop's edges by destination, ``src_idx`` / ``rel`` int32 [E] an
+    edge's row in ``hidden`` / ``a_s`` and in ``rela`` / ``a_r``, ``row_of_dst`` int32 [n_dst] a destination's row in ``a_q``
+    (``dst_ptr_host``: the CSR as a numpy array, if at hand).  Shapes, dtypes and index ranges are checked here (ValueError); the sums
+    are deterministic and a destination's row does not depend on the rest of the call."""
+    who = "digraph_layer_fwd"
+    for name, t in (("dst_ptr", dst_ptr), ("src_idx", src_idx), ("rel", rel), ("row_of_dst", row_of_dst)):
+        if not (torch.is_tensor(t) and t.dtype == torch.int32 and t.dim() == 1):
+            raise ValueError("%s: %s must be an int32 vector" % (who, name))
+    for name, t in (("hidden", hidden), ("rela", rela), ("a_s", a_s), ("a_r", a_r), ("a_q", a_q)):
+        if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.dim() == 2):
+            raise ValueError("%s: %s must be a float32 matrix" % (who, name))
+    n_dst, E = dst_ptr.numel() - 1, src_idx.numel()
+    ld, ap = hidden.shape[1], a_s.shape[1]
+    if n_dst < 0 or rel.numel() != E or row_of_dst.numel() != n_dst:
+        raise ValueError("%s: dst_ptr [%d], src_idx [%d], rel [%d] and row_of_dst [%d] do not fit together"
+                         % (who, dst_ptr.numel(), E, rel.numel(), row_of_dst.numel()))
+    if rela.shape[1] != ld or a_r.shape[1] != ap or a_q.shape[1] != ap or a_s.shape[0] != hidden.shape[0] or a_r.shape[0] != rela.shape[0]:
+        raise ValueError("%s: hidden %s, rela %s, a_s %s, a_r %s and a_q %s do not fit together"
+                         % (who, tuple(hidden.shape), tuple(rela.shape), tuple(a_s.shape), tuple(a_r.shape), tuple(a_q.shape)))
+    _require_gpu(hidden.device)
+    tensors = (dst_ptr, src_idx, rel, row_of_dst, hidden, rela, a_s, a_r, a_q, w_alpha, b_alpha)
+    if not all(t.is_cuda and t.is_contiguous() for t in tensors):
+        raise ValueError("%s: every tensor must be contiguous and on the device" % who)
+    dev = hidden.device
+    agg = torch.zeros((max(n_dst, 0), ld), dtype=torch.float32, device=dev)
+    alpha = torch.zeros(E, dtype=torch.float32, device=dev) if want_alpha else None
+    ptr_h = np.ascontiguousarray(dst_ptr.cpu().numpy() if dst_ptr_host is None else dst_ptr_host, dtype=np.int32)
+    if ptr_h.shape != (n_dst + 1,) or ptr_h[0] != 0 or ptr_h[-1] != E or (np.diff(ptr_h) < 0).any():
+        raise ValueError("%s: dst_ptr must start at 0, never decrease and end at the number of edges (%d)" % (who, E))
+    if E:
+        lo = torch.stack([src_idx.min(), rel.min(), row_of_dst.min()]).tolist()
+        hi = torch.stack([src_idx.max(), rel.max(), row_of_dst.max()]).tolist()
+        for name, a, b, n in zip(("src_idx", "rel", "row_of_dst"), lo, hi, (hidden.shape[0], rela.shape[0], a_q.shape[0])):
+            if a < 0 or b >= n:
+                raise ValueError("%s: %s out of range (%d..%d, %d rows)" % (who, name, a, b, n))
+    L, p = _lib.lib(), _lib.ptr
+    nbytes = int(L.rg_digraph_layer_fwd_scratch_bytes(p(ptr_h), n_dst, ld)) if n_dst > 0 else 0
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    ev = None
+    if DIGRAPH_EVENTS is not None:
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        ev[0].record()
+    _lib.check(L.rg_digraph_layer_fwd(n_dst, E, p(dst_ptr), p(ptr_h), p(src_idx), p(rel), p(row_of_dst), hidden.shape[0], rela.shape[0],
+                                      a_q.shape[0], p(hidden), p(rela), int(d), ld, p(a_s), p(a_r), p(a_q), ap, p(w_alpha), p(b_alpha),
+                                      int(attn_dim), p(agg), p(alpha), p(scratch), nbytes, _lib.stream_ptr()))
+    if ev is not None:
+        ev[1].record()
+        DIGRAPH_EVENTS.append((ev[0], ev[1], n_dst, E))
+    return agg, alpha
+
+
 RULE_MAX_HOPS = 32                   # csrc/rule_bits.h: RULE_MAX_HOPS
 RULE_MAX_RULES = 65535               # ... RULE_MAX_RULES (rules of one call)
 RULE_SCRATCH_BYTES = 1 << 30         # default scratch budget of rule_ground

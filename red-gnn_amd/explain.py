@@ -8,6 +8,8 @@ s -> o through the query's subgraph (identity self-loops count as steps); each e
     rels_, ents, prod = rd.strongest_paths()         # the path of largest alpha product per row
     paths = rd.top_paths(k=4)                        # the k best paths per row (HIP: csrc/paths.hip), an explain.PathSet
     table = model.rules(subs, rels, objs, k=2)       # their relation sequences counted as rules: an explain.RuleTable
+    rs = rd.rescore(model, keep=~paths.fact_mask(1))  # o re-scored with the best path's facts deleted (HIP: csrc/digraph_fwd.hip)
+    fid = model.fidelity(subs, rels, objs, k=4)      # necessity and sufficiency of the best 1..k paths: an explain.Fidelity
 
 The extraction runs in HIP (csrc/explain.hip): a forward keeps all L + 1 frontier levels and each layer's attention projection, then
 one backward marking pass per hop reads only the marked tails' CSR rows.  This module holds the result type and the host drivers.
@@ -30,6 +32,7 @@ from dataclasses import dataclass, fields, replace
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 from . import engine
 from .models import _pad4, pad_attn
@@ -54,6 +57,9 @@ class RDigraph:
     data_row int32 [E]     extrapolation only (None otherwise): the edge's index into the model's data array, -1 for a self-loop;
                            there ``time`` is the day the forward used for the edge (the row's day; a self-loop's: the first day of
                            the row's window) and ``q_time`` the query's day
+    q_sub    int64 [B]     static and inductive models (None otherwise): the subject s of each row
+    q_rel    int64 [B]     ... and its query relation r; ``rescore`` needs both
+    n_rel    int           ... and the KG's relation count (ids >= n_rel are inverses, 2 * n_rel the identity); ``fact_mask`` needs it
     """
     edges: torch.Tensor
     alpha: torch.Tensor
@@ -64,6 +70,26 @@ class RDigraph:
     time: torch.Tensor = None
     q_time: torch.Tensor = None
     data_row: torch.Tensor = None
+    q_sub: torch.Tensor = None
+    q_rel: torch.Tensor = None
+    n_rel: int = None
+
+    def rescore(self, model, keep=None, mode="test"):
+        """The model's score of o on the digraph with only the edges ``keep`` (bool or uint8 [E] over ``edges``; None: all of them):
+        an explain.Rescore.  RED-GNN's score of o depends on the r-digraph's edges alone, so this is the model's score on the knowledge
+        graph with the facts behind the dropped edges deleted - a forward over the compact edge list, one HIP message-passing launch
+        per hop (rg_digraph_layer_fwd; csrc/digraph_fwd.hip) and the dense step of the inference forward, no graph rebuild.  A kept
+        edge whose head is no longer visited one hop down is dead (``live``); a row whose o has no length-L walk left scores exactly 0.
+        ``model``: the RED_GNN_trans / RED_GNN_induc that explained, ``mode`` the one it explained in.  Eval semantics under no_grad.
+        The digraph is checked on the host first (ValueError); temporal digraphs are out of scope (ValueError)."""
+        return rescore(self, model, keep, mode)
+
+    def fact_mask(self, facts, rows=None):
+        """bool [E]: the edges that stand for one of the facts ``facts`` int [F, 3] = (h, r, t), at any hop: an edge is marked if its
+        (head, rel, tail) is a fact or a fact's twin (t, inv(r), h), inv(r) = r + n_rel below n_rel and r - n_rel from there on.  The
+        identity relation 2 * n_rel is never marked: a self-loop is part of the model, not a fact.  ``rows`` int [F]: fact f counts
+        for the edges of row rows[f] only (None: for every row).  Static digraphs that carry ``n_rel``."""
+        return fact_mask(self, facts, rows)
 
     def direction(self):
         """int8 [E]: each edge's direction against its row's query time, the temporal forward's convention (dt = edge time - query
@@ -218,6 +244,17 @@ class PathSet:
         if self.digraph.data_row is None:
             raise ValueError("data_rows: this r-digraph carries no data rows (extrapolation digraphs do)")
         return self._gather(self.digraph.data_row, -1)
+
+    def fact_mask(self, j):
+        """bool [E]: digraph.fact_mask of the facts the best ``j`` paths of each row step over (1 <= j <= k; a row with fewer paths
+        gives all it has), every fact for its own row.  Identity steps are no facts."""
+        k = self.edge.shape[1]
+        _check_count(j, "fact_mask", "j", k)
+        rd = self.digraph
+        at = self.edge[:, :int(j)].reshape(-1)
+        at = at[at >= 0]
+        e = rd.edges[at].long()
+        return rd.fact_mask(e[:, 2:5], rows=e[:, 0])
 
 
 def _check_count(x, who, name, most=None):
@@ -1131,7 +1168,8 @@ def explain(model, subs, rels, objs=None, mode="test", min_alpha=0.0):
         rows = torch.arange(n, device=device)
         score = scores[rows, objs_t].contiguous()
         edges, alpha, offsets, _ = _assemble(hops, n, L, device)
-    return RDigraph(edges=edges, alpha=alpha, offsets=offsets, reached=reached, score=score, n_hops=L)
+    return RDigraph(edges=edges, alpha=alpha, offsets=offsets, reached=reached, score=score, n_hops=L,
+                    q_sub=torch.as_tensor(subs_h, dtype=torch.int64).to(device), q_rel=q_rel.clone(), n_rel=int(model.n_rel))
 
 
 def _assemble(hops, n, L, device):
@@ -1268,3 +1306,262 @@ def _forward_sweep(hops, L, n_ent):
         ok = torch.isin(e[:, 0].long() * n_ent + e[:, 1].long(), reach)
         hops[l] = tuple(x[ok].contiguous() for x in hops[l])          # (edges, alpha[, time]): the lists stay aligned
     return hops
+
+
+# ---- explanation fidelity: answers re-scored on an edited r-digraph ----------------------------------------------------------------
+@dataclass
+class Rescore:
+    """An answer re-scored on its r-digraph with some edges taken away (RDigraph.rescore).  Tensors on the digraph's device.
+
+    score    float32 [B]  the model's score of o on the kept digraph, exactly 0 where o is not reached
+    reached  bool [B]     o still has a length-L walk from s through kept edges
+    live     bool [E]     the edge is kept AND its head is visited at hop - 1 (a forward sweep from s); only live edges carry messages
+    alpha    float32 [E]  the attention recomputed on the edited digraph, 0 for dead edges
+    """
+    score: torch.Tensor
+    reached: torch.Tensor
+    live: torch.Tensor
+    alpha: torch.Tensor
+
+
+@dataclass
+class Fidelity:
+    """How much of an answer's score its best paths carry (model.fidelity).  Tensors on the device.
+
+    score            float32 [B]     the model's score of o (RDigraph.score)
+    without          float32 [B, k]  ... with the facts of the row's best j paths deleted, j = 1..k (both directions, every hop)
+    only             float32 [B, k]  ... with only the facts of the best j paths, and every self-loop, kept
+    reached_without  bool [B, k]     o is still reached after the deletion
+    reached_only     bool [B, k]     o is reached through the kept facts
+    count            int32 [B]       paths found for the row (<= k); for j past it a row repeats its value at j = count
+    paths            PathSet         the paths, with the digraph they index
+    """
+    score: torch.Tensor
+    without: torch.Tensor
+    only: torch.Tensor
+    reached_without: torch.Tensor
+    reached_only: torch.Tensor
+    count: torch.Tensor
+    paths: PathSet
+
+    def necessity(self):
+        """float32 [B, k]: score - without, what the answer loses when the best j paths' facts go (comprehensiveness)."""
+        return self.score[:, None] - self.without
+
+    def sufficiency_gap(self):
+        """float32 [B, k]: score - only, what the best j paths' facts alone fail to reproduce (0: they are sufficient)."""
+        return self.score[:, None] - self.only
+
+    def format(self):
+        """One line per row: the score, then per j the score without and with only the best j paths (``x``: o no longer reached)."""
+        sc, wo, on = self.score.cpu().tolist(), self.without.cpu().tolist(), self.only.cpu().tolist()
+        rw, ro, cnt = self.reached_without.cpu().tolist(), self.reached_only.cpu().tolist(), self.count.cpu().tolist()
+        cell = lambda v, ok: "%.4f" % v if ok else "x"
+        return ["row %d: score %.4f paths %d  without %s  only %s" % (b, sc[b], cnt[b], " ".join(cell(v, ok) for v, ok in zip(wo[b], rw[b])),
+                                                                      " ".join(cell(v, ok) for v, ok in zip(on[b], ro[b])))
+                for b in range(len(sc))]
+
+
+def _check_static_digraph(rd, who):
+    """The host checks of a static r-digraph's tensors (ValueError naming the argument); returns (E, B)."""
+    if rd.time is not None or rd.q_time is not None or rd.data_row is not None:
+        raise ValueError("%s: a temporal r-digraph (time is set) is out of scope; static and inductive models only" % who)
+    if isinstance(rd.n_hops, (bool, np.bool_)) or not isinstance(rd.n_hops, (int, np.integer)) or not 1 <= rd.n_hops <= 32:
+        raise ValueError("%s: n_hops must be an integer in 1..32 (got %r)" % (who, rd.n_hops))
+    e, a, o = rd.edges, rd.alpha, rd.offsets
+    if not all(torch.is_tensor(t) for t in (e, a, o)):
+        raise ValueError("%s: edges, alpha and offsets must be tensors" % who)
+    if e.dtype != torch.int32 or e.dim() != 2 or e.shape[1] != 5:
+        raise ValueError("%s: edges must be int32 [E, 5] (got %s %s)" % (who, e.dtype, tuple(e.shape)))
+    if a.dtype != torch.float32 or a.shape != (e.shape[0],):
+        raise ValueError("%s: alpha must be float32 [%d] (got %s %s)" % (who, e.shape[0], a.dtype, tuple(a.shape)))
+    if o.dtype != torch.int64 or o.dim() != 1 or o.numel() < 1:
+        raise ValueError("%s: offsets must be int64 [B + 1] (got %s %s)" % (who, o.dtype, tuple(o.shape)))
+    off = o.detach().cpu().numpy()
+    if off[0] != 0 or off[-1] != e.shape[0] or (np.diff(off) < 0).any():
+        raise ValueError("%s: offsets must start at 0, never decrease and end at the number of edges (%d)" % (who, e.shape[0]))
+    if isinstance(rd.n_rel, (bool, np.bool_)) or not isinstance(rd.n_rel, (int, np.integer)) or rd.n_rel < 1:
+        raise ValueError("%s: n_rel must be a positive integer (got %r); model.explain sets it" % (who, rd.n_rel))
+    return e.shape[0], o.numel() - 1
+
+
+def fact_mask(rd, facts, rows=None):
+    """RDigraph.fact_mask (see there)."""
+    who = "fact_mask"
+    E, B = _check_static_digraph(rd, who)
+    dev = rd.edges.device
+    f = (facts.detach() if torch.is_tensor(facts) else torch.as_tensor(np.asarray(facts))).to(dev)
+    if f.is_floating_point() or f.dtype == torch.bool or f.dim() != 2 or f.shape[1] != 3:
+        raise ValueError("%s: facts must be integers [F, 3] = (h, r, t) (got %s %s)" % (who, f.dtype, tuple(f.shape)))
+    f = f.long()
+    n_rel = int(rd.n_rel)
+    if f.shape[0] and (int(f.min()) < 0 or int(f[:, 1].max()) > 2 * n_rel):
+        raise ValueError("%s: facts hold a negative id or a relation above 2*n_rel = %d" % (who, 2 * n_rel))
+    r_of = None
+    if rows is not None:
+        r_of = (rows.detach() if torch.is_tensor(rows) else torch.as_tensor(np.asarray(rows))).to(dev)
+        if r_of.is_floating_point() or r_of.dtype == torch.bool or r_of.shape != (f.shape[0],):
+            raise ValueError("%s: rows must be integers [%d], one per fact (got %s %s)" % (who, f.shape[0], r_of.dtype, tuple(r_of.shape)))
+        r_of = r_of.long()
+        if r_of.numel() and (int(r_of.min()) < 0 or int(r_of.max()) >= B):
+            raise ValueError("%s: rows out of range (the digraph has %d rows)" % (who, B))
+    mask = torch.zeros(E, dtype=torch.bool, device=dev)
+    fact = f[:, 1] != 2 * n_rel                           # the identity is no fact
+    f = f[fact]
+    if E == 0 or f.shape[0] == 0:
+        return mask
+    e = rd.edges.long()
+    n_key = int(max(e[:, 2].max(), e[:, 4].max(), f[:, 0].max(), f[:, 2].max())) + 1
+    n_r = 2 * n_rel + 1
+    key = lambda row, h, r, t: ((row * n_key + h) * n_r + r) * n_key + t
+    inv = torch.where(f[:, 1] < n_rel, f[:, 1] + n_rel, f[:, 1] - n_rel)
+    f_row = torch.zeros_like(f[:, 0]) if r_of is None else r_of[fact]
+    e_row = torch.zeros_like(e[:, 0]) if r_of is None else e[:, 0]
+    want = torch.cat([key(f_row, f[:, 0], f[:, 1], f[:, 2]), key(f_row, f[:, 2], inv, f[:, 0])])
+    return torch.isin(key(e_row, e[:, 2], e[:, 3], e[:, 4]), want) & (e[:, 3] != 2 * n_rel)
+
+
+def _sorted_find(keys, want):
+    """(position int64, found bool) of every ``want`` in the sorted, duplicate-free ``keys``."""
+    if keys.numel() == 0:
+        return torch.zeros_like(want), torch.zeros_like(want, dtype=torch.bool)
+    pos = torch.searchsorted(keys, want).clamp_(max=keys.numel() - 1)
+    return pos, keys[pos] == want
+
+
+def rescore(rd, model, keep=None, mode="test"):
+    """RDigraph.rescore (see there)."""
+    who = "rescore"
+    E, B = _check_static_digraph(rd, who)
+    for name in ("q_sub", "q_rel"):
+        t = getattr(rd, name)
+        if not torch.is_tensor(t) or t.dtype != torch.int64 or t.shape != (B,):
+            raise ValueError("%s: %s must be int64 [%d], the rows' queries (model.explain sets it)" % (who, name, B))
+    for name in ("n_layer", "hidden_dim", "attn_dim", "gnn_layers", "W_final", "gate", "loader"):
+        if not hasattr(model, name):
+            raise ValueError("%s: model must be a RED_GNN_trans or RED_GNN_induc (got %s)" % (who, type(model).__name__))
+    L = int(rd.n_hops)
+    if model.n_layer != L or model.n_rel != rd.n_rel:
+        raise ValueError("%s: the digraph has n_hops=%d, n_rel=%d, the model n_layer=%d, n_rel=%d" % (who, L, rd.n_rel, model.n_layer,
+                                                                                                    model.n_rel))
+    if keep is not None:
+        keep = keep if torch.is_tensor(keep) else torch.as_tensor(np.asarray(keep)).to(rd.edges.device)      # (an array goes along)
+        if keep.dtype not in (torch.bool, torch.uint8) or keep.shape != (E,):
+            raise ValueError("%s: keep must be bool or uint8 [%d], one per edge (got %s %s)" % (who, E, keep.dtype, tuple(keep.shape)))
+    dev = rd.edges.device
+    tensors = [rd.edges, rd.alpha, rd.offsets, rd.q_sub, rd.q_rel] + ([keep] if keep is not None else [])
+    if not all(t.is_cuda for t in tensors) or any(t.device != dev for t in tensors):
+        raise ValueError("%s: the layers run in HIP and need the digraph (and keep) on one device (got CPU tensors or mixed devices)" % who)
+    n_ent = model.loader.graph_for(mode).n_ent
+    e = rd.edges.long()
+    row, hop, head, rel, tail = e.unbind(1)
+    if B and (int(rd.q_sub.min()) < 0 or int(rd.q_sub.max()) >= n_ent or int(rd.q_rel.min()) < 0 or int(rd.q_rel.max()) > 2 * rd.n_rel):
+        raise ValueError("%s: q_sub / q_rel out of range (n_ent=%d, 2*n_rel+1=%d)" % (who, n_ent, 2 * rd.n_rel + 1))
+    if E:
+        lo, hi = e.min(0).values.tolist(), e.max(0).values.tolist()
+        if lo[0] < 0 or hi[0] >= B or lo[1] < 1 or hi[1] > L or min(lo[2], lo[4]) < 0 or max(hi[2], hi[4]) >= n_ent or lo[3] < 0 \
+                or hi[3] > 2 * rd.n_rel:
+            raise ValueError("%s: edges hold a row, hop, entity or relation out of range (B=%d, L=%d, n_ent=%d in mode %r, 2*n_rel+1=%d)"
+                             % (who, B, L, n_ent, mode, 2 * rd.n_rel + 1))
+    d, a = model.hidden_dim, model.attn_dim
+    ld, ap = max(16, _pad4(d)), pad_attn(a)
+    fused = model.fused_dense and engine.dense_supported(d, a)
+    i32 = lambda t: t.to(torch.int32).contiguous()
+    live = torch.zeros(E, dtype=torch.bool, device=dev)
+    alpha = torch.zeros(E, dtype=torch.float32, device=dev)
+    score = torch.zeros(B, dtype=torch.float32, device=dev)
+    reached = torch.zeros(B, dtype=torch.bool, device=dev)
+    kept = torch.ones(E, dtype=torch.bool, device=dev) if keep is None else keep.bool()
+    with torch.no_grad():
+        from .models import gru_step, tall_linear
+        tables = model.inference_tables(rd.q_rel.contiguous(), ld, ap)
+        keys_prev = torch.arange(B, device=dev) * n_ent + rd.q_sub            # hop 0: the node (row, s) of every row, sorted
+        hidden = torch.zeros((B, ld), device=dev)
+        a_s = torch.zeros((B, ap), device=dev)                                # hidden == 0 at layer 0
+        for l in range(1, L + 1):
+            layer, last = model.gnn_layers[l - 1], l == L
+            at = torch.nonzero((hop == l) & kept).reshape(-1)
+            src, ok = _sorted_find(keys_prev, row[at] * n_ent + head[at])
+            at, src = at[ok], src[ok]                                         # the forward sweep: the head is visited one hop down
+            if at.numel() == 0:
+                break                                                         # nothing is reached from here on: every score stays 0
+            live[at] = True
+            tk = row[at] * n_ent + tail[at]
+            if bool((tk[1:] < tk[:-1]).any()):
+                raise ValueError("%s: edges must be ordered by (row, hop, tail), as model.explain returns them" % who)
+            keys, counts = torch.unique_consecutive(tk, return_counts=True)   # the hop's node list: sorted unique (row, tail)
+            dst_ptr = torch.zeros(keys.numel() + 1, dtype=torch.int32, device=dev)
+            dst_ptr[1:] = torch.cumsum(counts, 0)
+            row_of = keys // n_ent
+            if last and bool((row_of[1:] == row_of[:-1]).any()):
+                raise ValueError("%s: the hop-%d edges of a row must share their tail, the row's answer" % (who, L))
+            prev_idx, had = _sorted_find(keys_prev, keys)
+            prev_idx = i32(torch.where(had, prev_idx, torch.full_like(prev_idx, -1)))
+            a_r, a_q, rela_p = tables[l - 1]
+            agg, al = engine.digraph_layer_fwd(dst_ptr, i32(src), i32(rel[at]), i32(row_of), hidden, rela_p.contiguous(), d, a_s,
+                                               a_r.contiguous(), a_q.contiguous(), layer.w_alpha.weight.detach().reshape(-1).contiguous(),
+                                               layer.w_alpha.bias.detach().contiguous(), a)
+            alpha[at] = al
+            if fused:                                                         # the dense step of _forward_inference
+                node_rows = torch.stack([row_of, torch.zeros_like(row_of)], 1).to(torch.int32).contiguous()
+                hidden, a_s = engine.dense_fwd(agg, hidden, prev_idx, d, layer.W_h.weight, model.act_name, model.gate,
+                                               Ws_next=None if last else model.gnn_layers[l].Ws_attn.weight, attn_dim=a, ap=ap,
+                                               W_final=model.W_final.weight if last else None, nodes=node_rows, n_ent=1,
+                                               scores_all=score, precision=model.dense_precision, want_hidden=not last)
+            else:                                                             # ... and of _run's ``kept`` branch
+                x = layer.act(tall_linear(agg[:, :d], layer.W_h.weight))
+                h0 = torch.zeros((keys.numel(), d), device=dev)
+                h0[had] = hidden[:, :d][prev_idx[had].long()]
+                hid = gru_step(x, h0, model.gate)
+                if last:
+                    score[row_of] = tall_linear(hid, model.W_final.weight).squeeze(-1)
+                else:
+                    w_s = model.gnn_layers[l].Ws_attn.weight
+                    a_s = tall_linear(hid, F.pad(w_s, (0, 0, 0, ap - a)) if ap != a else w_s).contiguous()
+                    hidden = (F.pad(hid, (0, ld - d)) if ld != d else hid).contiguous()
+            if last:
+                reached[row_of] = True
+            keys_prev = keys
+    return Rescore(score=score, reached=reached, live=live, alpha=alpha)
+
+
+def fidelity(model, subs, rels, objs=None, k=4, mode="test"):
+    """RED_GNN_trans.fidelity (see there)."""
+    _check_count(k, "fidelity", "k", engine.PATHS_MAX_K)
+    rd = model.explain(subs, rels, objs, mode=mode)
+    paths = rd.top_paths(int(k))
+    loops = rd.edges[:, 3] == 2 * model.n_rel
+    cols = {name: [] for name in ("without", "only", "reached_without", "reached_only")}
+    for j in range(1, int(k) + 1):
+        m = paths.fact_mask(j)
+        wo, on = rd.rescore(model, keep=~m, mode=mode), rd.rescore(model, keep=m | loops, mode=mode)
+        for name, v in (("without", wo.score), ("only", on.score), ("reached_without", wo.reached), ("reached_only", on.reached)):
+            cols[name].append(v)
+    return Fidelity(score=rd.score, count=paths.count, paths=paths, **{name: torch.stack(v, 1) for name, v in cols.items()})
+
+
+def split_fidelity(base, data="test", k=4, batch=50, max_queries=None):
+    """BaseModel.fidelity (see there)."""
+    if data not in ("valid", "test"):
+        raise ValueError("fidelity: data must be 'valid' or 'test' (got %r)" % (data,))
+    _check_count(k, "fidelity", "k", engine.PATHS_MAX_K)
+    _check_count(batch, "fidelity", "batch")
+    loader = base.loader
+    query, answer = (loader.valid_q, loader.valid_a) if data == "valid" else (loader.test_q, loader.test_a)
+    n = len(query) if max_queries is None else min(len(query), int(max_queries))
+    rows = [(int(query[i][0]), int(query[i][1]), min(int(x) for x in answer[i])) for i in range(n) if len(answer[i])]
+    if not rows:
+        raise ValueError("fidelity: no queries with an answer in the %s split (n=%d)" % (data, n))
+    rows = np.array(rows, dtype=np.int64)
+    mode = loader.eval_mode(data) if hasattr(loader, "eval_mode") else data
+    nec, gap, cut = [], [], []
+    for lo in range(0, len(rows), int(batch)):
+        part = rows[lo:lo + int(batch)]
+        f = base.model.fidelity(part[:, 0], part[:, 1], part[:, 2], k=int(k), mode=mode)
+        nec.append(f.necessity().double().cpu())
+        gap.append(f.sufficiency_gap().double().cpu())
+        cut.append((f.paths.digraph.reached[:, None] & ~f.reached_without).cpu())
+    nec, gap, cut = torch.cat(nec), torch.cat(gap), torch.cat(cut)
+    return dict(n=int(nec.shape[0]), k=int(k), necessity_mean=nec.mean(0).tolist(), necessity_median=nec.median(0).values.tolist(),
+                sufficiency_gap_mean=gap.mean(0).tolist(), sufficiency_gap_median=gap.median(0).values.tolist(),
+                disconnected=cut.double().mean(0).tolist())

@@ -404,6 +404,16 @@ class RED_GNN_trans(nn.Module):
         from . import explain as _explain
         return _explain.rules(self, subs, rels, objs, k, mode, min_alpha)
 
+    def fidelity(self, subs, rels, objs=None, k=4, mode="test"):
+        """Whether the paths ``explain`` shows carry the answer: per row (s, r, o) the score of o with the facts of its best j paths
+        deleted (necessity, or comprehensiveness) and with only those facts and the self-loops kept (sufficiency), j = 1..k.  One
+        explain, one top_paths(k) and 2k RDigraph.rescore calls: exact forwards over the compact r-digraph with edges masked out
+        (rg_digraph_layer_fwd), no graph rebuild.  A fact is deleted in both directions and at every hop.  Returns an
+        explain.Fidelity (device tensors): ``necessity()`` = score - without, ``sufficiency_gap()`` = score - only, [B, k] each.
+        ``objs=None``: each row's own top answer, as explain.  Eval semantics under no_grad."""
+        from . import explain as _explain
+        return _explain.fidelity(self, subs, rels, objs, k, mode)
+
     def rule_quality(self, table, mode="test", sources=None, scratch_bytes=engine.RULE_SCRATCH_BYTES):
         """How the rules of an explain.RuleTable hold in the graph of ``mode`` (loader.graph_for): per rule the number of entity pairs
         the body connects, how many of them the head connects too (AMIE's support), and standard / PCA confidence and head coverage
@@ -667,6 +677,9 @@ class RED_GNN_induc(RED_GNN_trans):
 
     def rules(self, subs, rels, objs=None, k=1, mode="transductive", min_alpha=0.0):
         return super().rules(subs, rels, objs=objs, k=k, mode=mode, min_alpha=min_alpha)
+
+    def fidelity(self, subs, rels, objs=None, k=4, mode="transductive"):
+        return super().fidelity(subs, rels, objs=objs, k=k, mode=mode)
 
     def rule_quality(self, table, mode="transductive", sources=None, scratch_bytes=engine.RULE_SCRATCH_BYTES):
         return super().rule_quality(table, mode=mode, sources=sources, scratch_bytes=scratch_bytes)
