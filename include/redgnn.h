@@ -458,6 +458,25 @@ int rg_digraph_layer_fwd(int32_t n_dst, int64_t n_edges, const int32_t* dst_ptr,
                          const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha, int32_t attn_dim, float* agg_out,
                          float* alpha_out, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- ... with a time per edge: rg_tlayer_fwd's arithmetic (n_dir = 3, temporal interpolation) or rg_xlayer_fwd's (n_dir = 1, the
+ * extrapolation form) on an explicit edge list (explain.RDigraph.rescore of a temporal r-digraph).  Everything rg_digraph_layer_fwd
+ * states holds - the same kernel with the time path compiled in, the same split rule, scratch size and argument checks - plus:
+ * edge_time int32 [n_edges], q_time int32 [batch], time_tab [n_dir * n_time, ld] (16-B aligned), n_time > 0, n_dir 1 or 3.  hidden
+ * then has n_dir * n_src rows and rela n_dir * n_rela_rows; a_s keeps n_src rows and a_r n_rela_rows: the attention reads the
+ * un-directed s and r, so alpha_e is the float of rg_digraph_layer_fwd (pass b_alpha = 0: the temporal attention has no bias).
+ *   n_dir == 3:  dt = edge_time[e] - q_time[b], dir = 0 (dt < 0) / 1 (dt == 0) / 2 (dt > 0)
+ *                m_e = hidden[3 s + dir] + (rela[dir * n_rela_rows + r] + time_tab[dir * n_time + min(|dt|, n_time - 1)])
+ *   n_dir == 1:  edge_time[e] is the day the caller resolved for the edge (a data row's day; a self-loop's: the first day of the
+ *                query's window), m_e = hidden[s] + (rela[r] + time_tab[clamp(q_time[b] - edge_time[e], 0, n_time - 1)])
+ *   agg_out[o] = sum over the edges of o, in list order, of alpha_e * m_e (fmaf)
+ * The time row is clamped into its table whatever the times hold. */
+int rg_digraph_tlayer_fwd(int32_t n_dst, int64_t n_edges, const int32_t* dst_ptr, const int32_t* dst_ptr_host, const int32_t* src_idx,
+                          const int32_t* rel, const int32_t* edge_time, const int32_t* row_of_dst, const int32_t* q_time, int32_t n_src,
+                          int32_t n_rela_rows, int32_t batch, int32_t n_time, int32_t n_dir, const float* hidden, const float* rela,
+                          const float* time_tab, int32_t d, int32_t ld, const float* a_s, const float* a_r, const float* a_q, int32_t ap,
+                          const float* w_alpha, const float* b_alpha, int32_t attn_dim, float* agg_out, float* alpha_out, void* scratch,
+                          size_t scratch_bytes, void* stream);
+
 /* ---- rule quality: support and confidence of rules (head h, body r_1..r_L) counted on the whole graph; no counterpart in the
  * reference (its *_rule_vis.py scripts only draw).  The graph is used as built, inverse and identity rows included: for a relation id
  * r in 0..n_rela_rows-1, A_r(x, y) holds iff the graph has at least one row (x, r, y) (a repeated fact counts once), and body(x, y)

@@ -26,7 +26,7 @@ SYMBOLS = [
     "rg_xattn_profile", "rg_rows_linear",
     "rg_segment_eval",
     "rg_paths_scratch_bytes", "rg_paths_topk",
-    "rg_digraph_layer_fwd_scratch_bytes", "rg_digraph_layer_fwd",
+    "rg_digraph_layer_fwd_scratch_bytes", "rg_digraph_layer_fwd", "rg_digraph_tlayer_fwd",
     "rg_rule_ground_scratch_bytes", "rg_rule_ground",
     "rg_rule_apply_scratch_bytes", "rg_rule_apply",
     "rg_trule_ground_scratch_bytes", "rg_trule_ground",
@@ -149,6 +149,8 @@ def lib():
     L.rg_digraph_layer_fwd_scratch_bytes.restype = sz
     L.rg_digraph_layer_fwd.argtypes = [i32, i64, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp,
                                        vp, sz, vp]
+    L.rg_digraph_tlayer_fwd.argtypes = [i32, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, i32,
+                                        vp, vp, i32, vp, vp, vp, sz, vp]
     L.rg_rule_ground_scratch_bytes.argtypes = [i32, i32, i32]
     L.rg_rule_ground_scratch_bytes.restype = sz
     L.rg_rule_ground.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp, vp, vp]

@@ -19,7 +19,15 @@
 // row, and a second launch adds the partial rows in chunk order.  A wave per destination alone would run as long as the hub.
 // No float atomics; the sums of a destination are formed in list order inside a chunk and in chunk order across chunks, so agg[o]
 // has the same bits on every run and does not depend on what else the call carries.
+//
+// The timed form (rg_digraph_tlayer_fwd, template parameter TIMED; the static instantiation compiles to what it did without it): an
+// edge also has a time, a query a time, and the message a third table,
+//       n_dir == 3   dt = edge_time[e] - q_time[b], dir = 0 / 1 / 2 for dt < 0 / == 0 / > 0           (rg_tlayer_fwd's rows)
+//                    acc += alpha_e * (hidden[3 s + dir] + (rela[dir * n_rela_rows + r] + time_tab[dir * n_time + min(|dt|, n_time - 1)]))
+//       n_dir == 1   acc += alpha_e * (hidden[s] + (rela[r] + time_tab[clamp(q_time[b] - edge_time[e], 0, n_time - 1)]))   (rg_xlayer_fwd's)
+// alpha_e read from the un-directed s and r as above.  The group then exchanges four values per edge and has twelve gathers in flight.
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "attn.h"
@@ -52,10 +60,18 @@ struct DgArgs {
   float* alpha_out;
 };
 
+// what the timed form (rg_digraph_tlayer_fwd) reads on top: kept apart so that the static kernel's arguments stay what they were
+struct DgTimedArgs : DgArgs {
+  const int32_t* edge_time;    // [E]
+  const int32_t* q_time;       // [B]
+  const float4* time_tab;      // [n_dir * n_time, ld]
+  int n_time, n_dir;           // n_dir 3: interpolation (rows by direction), 1: extrapolation form (one table of lags)
+};
+
 __device__ __forceinline__ int clampi(int x, int hi) { return min(max(x, 0), hi); }
 
-template <int G, int AP4>
-__global__ __launch_bounds__(DG_BLOCK) void digraph_fwd_kernel(DgArgs A) {
+template <int G, int AP4, bool TIMED>
+__global__ __launch_bounds__(DG_BLOCK) void digraph_fwd_kernel(std::conditional_t<TIMED, DgTimedArgs, DgArgs> A) {
   constexpr int PER_WAVE = 64 / G;
   const int lane = threadIdx.x & 63;
   const int lane_g = lane & (G - 1), gbase = lane & ~(G - 1);
@@ -83,13 +99,15 @@ __global__ __launch_bounds__(DG_BLOCK) void digraph_fwd_kernel(DgArgs A) {
   const int b = clampi(A.row_of_dst[o], A.B - 1);
   const float b_alpha = A.b_alpha[0];
   const float4* aq_p = A.a_q + (int64_t)b * AP4;
+  int qt = 0;
+  if constexpr (TIMED) qt = A.q_time[b];
 
   float4 acc = rg::f4zero();
   for (int c0 = beg; __any(c0 < end); c0 += G) {
     // ---- one edge per lane: indices and the attention scalar --------------------------------------------------
     const int c = c0 + lane_g;
     const bool valid = c < end;
-    int s = 0, r = 0;
+    int s = 0, r = 0, trow = 0;
     float alpha = 0.f;
     if (valid) {
       s = clampi(A.src_idx[c], A.n_src - 1);
@@ -100,11 +118,25 @@ __global__ __launch_bounds__(DG_BLOCK) void digraph_fwd_kernel(DgArgs A) {
         rg::attn_acc_fwd(z, rg::attn_w4(A.w_alpha, A.attn_dim, k), A.a_s[(int64_t)s * AP4 + k], A.a_r[(int64_t)r * AP4 + k], aq_p[k]);
       alpha = rg::attn_alpha(z);
       if (A.alpha_out) A.alpha_out[c] = alpha;
+      if constexpr (TIMED) {
+        // the rows of the message, as layer_fwd_kernel.h forms them (the attention above read the un-directed s and r); 64-bit
+        // differences, so that no pair of times overflows, and the time row clamped into its table
+        const int64_t et = A.edge_time[c];
+        if (A.n_dir == 3) {
+          const int64_t dt = et - qt;
+          const int dir = dt > 0 ? 2 : (dt == 0 ? 1 : 0);
+          s = s * 3 + dir;
+          r = dir * A.n_rela_rows + r;
+          trow = dir * A.n_time + (int)min(dt < 0 ? -dt : dt, (int64_t)(A.n_time - 1));
+        } else {
+          trow = (int)min(max((int64_t)qt - et, (int64_t)0), (int64_t)(A.n_time - 1));
+        }
+      }
     }
     const int cnt = min(max(end - c0, 0), G);
-    // ---- the round's edges in order, every lane its float4 of the row; four gathers in flight ------------------
+    // ---- the round's edges in order, every lane its float4 of the row; four edges' gathers in flight -----------
     for (int j = 0; __any(j < cnt); j += 4) {
-      int su[4], ru[4];
+      int su[4], ru[4], tu[4];
       float al[4];
       float4 hv[4], rv[4];
 #pragma unroll
@@ -113,11 +145,19 @@ __global__ __launch_bounds__(DG_BLOCK) void digraph_fwd_kernel(DgArgs A) {
         su[u] = __shfl(s, from, 64);
         ru[u] = __shfl(r, from, 64);
         al[u] = __shfl(alpha, from, 64);
+        if constexpr (TIMED) tu[u] = __shfl(trow, from, 64);
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u) hv[u] = A.hidden[(int64_t)su[u] * A.ld4 + lane_c];
 #pragma unroll
       for (int u = 0; u < 4; ++u) rv[u] = A.rela[(int64_t)ru[u] * A.ld4 + lane_c];
+      if constexpr (TIMED) {             // rela[rrow] + time_tab[trow] first, then hidden: layer_fwd_kernel.h's association
+        float4 tv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) tv[u] = A.time_tab[(int64_t)tu[u] * A.ld4 + lane_c];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { rv[u].x += tv[u].x; rv[u].y += tv[u].y; rv[u].z += tv[u].z; rv[u].w += tv[u].w; }
+      }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         if (j + u < cnt) {
@@ -160,11 +200,107 @@ void count_cuts(const int32_t* ptr, int32_t n_dst, int64_t* n_hubs, int64_t* n_c
 
 size_t list_bytes(int64_t n_hubs, int64_t n_chunks) { return rg::align_up((size_t)(n_hubs + n_chunks) * sizeof(int4), 256); }
 
-template <int G, int AP4>
-int launch(const DgArgs& A, hipStream_t s) {
+template <int G, int AP4, bool TIMED>
+int launch(const std::conditional_t<TIMED, DgTimedArgs, DgArgs>& A, hipStream_t s) {
   const int64_t waves = rg::ceil_div(A.n_items, 64 / G);
-  hipLaunchKernelGGL((digraph_fwd_kernel<G, AP4>), dim3((unsigned)rg::ceil_div(waves, DG_BLOCK / 64)), dim3(DG_BLOCK), 0, s, A);
+  hipLaunchKernelGGL((digraph_fwd_kernel<G, AP4, TIMED>), dim3((unsigned)rg::ceil_div(waves, DG_BLOCK / 64)), dim3(DG_BLOCK), 0, s, A);
   RG_LAUNCH_CHECK();
+  return 0;
+}
+
+// the time arguments of rg_digraph_tlayer_fwd; nullptr: the static entry point
+struct TimeIn {
+  const int32_t* edge_time;
+  const int32_t* q_time;
+  const float* time_tab;
+  int32_t n_time, n_dir;
+};
+
+// both entry points: every check, then the chunk list, the layer launch and the combine launch
+int run(const char* who, const TimeIn* T, int32_t n_dst, int64_t n_edges, const int32_t* dst_ptr, const int32_t* dst_ptr_host,
+        const int32_t* src_idx, const int32_t* rel, const int32_t* row_of_dst, int32_t n_src, int32_t n_rela_rows, int32_t batch,
+        const float* hidden, const float* rela, int32_t d, int32_t ld, const float* a_s, const float* a_r, const float* a_q, int32_t ap,
+        const float* w_alpha, const float* b_alpha, int32_t attn_dim, float* agg_out, float* alpha_out, void* scratch,
+        size_t scratch_bytes, void* stream) {
+  RG_CHECK(n_dst >= 0 && n_edges >= 0 && n_edges < ((int64_t)1 << 31), "%s: n_dst=%d n_edges=%lld (need 0 <= n_dst, 0 <= n_edges < 2^31)",
+           who, n_dst, (long long)n_edges);
+  RG_CHECK(n_src >= 0 && n_rela_rows >= 0 && batch >= 0, "%s: n_src=%d n_rela_rows=%d batch=%d (negative size)", who, n_src, n_rela_rows,
+           batch);
+  RG_CHECK(d > 0 && ld >= d && ld % 4 == 0 && ld <= 256, "%s: d=%d ld=%d (need ld%%4==0, d<=ld<=256)", who, d, ld);
+  RG_CHECK(attn_dim > 0 && ap >= attn_dim && ap % 4 == 0, "%s: attn_dim=%d ap=%d", who, attn_dim, ap);
+  if (T) {
+    RG_CHECK(T->n_dir == 1 || T->n_dir == 3, "%s: n_dir=%d (need 1 or 3)", who, T->n_dir);
+    RG_CHECK(T->n_time > 0 && (int64_t)T->n_dir * T->n_time < ((int64_t)1 << 31), "%s: n_time=%d (need a positive table size)", who,
+             T->n_time);
+    RG_CHECK((int64_t)3 * n_src < ((int64_t)1 << 31) && (int64_t)3 * n_rela_rows < ((int64_t)1 << 31),
+             "%s: n_src=%d n_rela_rows=%d (three rows each overflow int32)", who, n_src, n_rela_rows);
+  }
+  if (n_dst == 0) {
+    RG_CHECK(n_edges == 0, "%s: %lld edges without a destination", who, (long long)n_edges);
+    return 0;
+  }
+  RG_CHECK(dst_ptr_host, "%s: NULL argument (dst_ptr_host)", who);
+  RG_CHECK(dst_ptr_host[0] == 0, "%s: dst_ptr starts at %d, not 0", who, dst_ptr_host[0]);
+  for (int32_t o = 0; o < n_dst; ++o)
+    RG_CHECK(dst_ptr_host[o + 1] >= dst_ptr_host[o], "%s: dst_ptr decreases at destination %d", who, o);
+  RG_CHECK(dst_ptr_host[n_dst] == n_edges, "%s: dst_ptr ends at %d, not at the number of edges %lld", who, dst_ptr_host[n_dst],
+           (long long)n_edges);
+  if (n_edges == 0) return 0;                            // nothing to sum and nothing launched: the caller owns agg_out
+  RG_CHECK(dst_ptr && src_idx && rel && row_of_dst && hidden && rela && a_s && a_r && a_q && w_alpha && b_alpha && agg_out,
+           "%s: NULL argument", who);
+  RG_CHECK(!T || (T->edge_time && T->q_time && T->time_tab), "%s: NULL argument (edge_time, q_time or time_tab)", who);
+  RG_CHECK(n_src > 0 && n_rela_rows > 0 && batch > 0, "%s: edges but n_src=%d n_rela_rows=%d batch=%d", who, n_src, n_rela_rows, batch);
+  RG_CHECK((((uintptr_t)hidden | (uintptr_t)rela | (uintptr_t)a_s | (uintptr_t)a_r | (uintptr_t)a_q | (uintptr_t)agg_out |
+             (uintptr_t)scratch | (uintptr_t)(T ? T->time_tab : nullptr)) & 15) == 0, "%s: float buffers must be 16-B aligned", who);
+  int64_t n_hubs, n_chunks;
+  count_cuts(dst_ptr_host, n_dst, &n_hubs, &n_chunks);
+  RG_CHECK((int64_t)n_dst + n_chunks < ((int64_t)1 << 31), "%s: %lld items overflow int32", who, (long long)(n_dst + n_chunks));
+  const size_t need = n_hubs ? list_bytes(n_hubs, n_chunks) + rg::align_up((size_t)n_chunks * ld * sizeof(float), 256) : 0;
+  RG_CHECK(need == 0 || (scratch && scratch_bytes >= need), "%s: scratch %zu B < required %zu B", who, scratch ? scratch_bytes : (size_t)0,
+           need);
+
+  DgTimedArgs A;
+  A.n_dst = n_dst; A.n_items = (int)(n_dst + n_chunks); A.E = (int)n_edges; A.n_src = n_src; A.n_rela_rows = n_rela_rows; A.B = batch;
+  A.dst_ptr = dst_ptr; A.src_idx = src_idx; A.rel = rel; A.row_of_dst = row_of_dst;
+  A.hidden = (const float4*)hidden; A.rela = (const float4*)rela; A.ld4 = ld / 4;
+  A.a_s = (const float4*)a_s; A.a_r = (const float4*)a_r; A.a_q = (const float4*)a_q;
+  A.w_alpha = w_alpha; A.b_alpha = b_alpha; A.attn_dim = attn_dim;
+  A.agg = (float4*)agg_out; A.alpha_out = alpha_out;
+  A.edge_time = T ? T->edge_time : nullptr; A.q_time = T ? T->q_time : nullptr; A.time_tab = T ? (const float4*)T->time_tab : nullptr;
+  A.n_time = T ? T->n_time : 0; A.n_dir = T ? T->n_dir : 0;
+  int4* hubs_dev = (int4*)scratch;
+  A.chunks = hubs_dev + n_hubs;
+  A.partial = n_hubs ? (float4*)((char*)scratch + list_bytes(n_hubs, n_chunks)) : nullptr;
+  // every argument error is out before anything is enqueued: the width dispatch is probed first
+  if (rg::with_ap4(ap / 4, who, [](auto) { return 0; })) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  if (n_hubs) {
+    std::vector<int4> list((size_t)(n_hubs + n_chunks));
+    int64_t h = 0, slot = 0;
+    for (int32_t o = 0; o < n_dst; ++o) {
+      const int32_t lo = dst_ptr_host[o], hi = dst_ptr_host[o + 1];
+      if (hi - lo <= DIGRAPH_CHUNK) continue;
+      const int n_c = (int)rg::ceil_div(hi - lo, DIGRAPH_CHUNK);
+      list[h++] = make_int4(o, (int)slot, n_c, 0);
+      for (int k = 0; k < n_c; ++k, ++slot)
+        list[n_hubs + slot] = make_int4(o, lo + k * DIGRAPH_CHUNK, std::min(hi, lo + (k + 1) * DIGRAPH_CHUNK), (int)slot);
+    }
+    // (a copy from pageable memory: the runtime is done with the vector when the call returns)
+    RG_HIP(hipMemcpyAsync(hubs_dev, list.data(), list.size() * sizeof(int4), hipMemcpyHostToDevice, s));
+  }
+  const int rc = rg::with_g(A.ld4, [&](auto g) {
+    return rg::with_ap4(ap / 4, who, [&](auto a4) {
+      if (T) return launch<decltype(g)::value, decltype(a4)::value, true>(A, s);
+      return launch<decltype(g)::value, decltype(a4)::value, false>(A, s);
+    });
+  });
+  if (rc) return rc;
+  if (n_hubs) {
+    const int64_t threads = n_hubs * A.ld4;
+    hipLaunchKernelGGL(digraph_combine_kernel, dim3((unsigned)rg::ceil_div(threads, 256)), dim3(256), 0, s, hubs_dev, (int)n_hubs,
+                       (const float4*)A.partial, A.agg, A.ld4);
+    RG_LAUNCH_CHECK();
+  }
   return 0;
 }
 
@@ -187,72 +323,20 @@ extern "C" int rg_digraph_layer_fwd(int32_t n_dst, int64_t n_edges, const int32_
                                     const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha,
                                     const float* b_alpha, int32_t attn_dim, float* agg_out, float* alpha_out, void* scratch,
                                     size_t scratch_bytes, void* stream) {
-  const char* who = "rg_digraph_layer_fwd";
-  RG_CHECK(n_dst >= 0 && n_edges >= 0 && n_edges < ((int64_t)1 << 31), "%s: n_dst=%d n_edges=%lld (need 0 <= n_dst, 0 <= n_edges < 2^31)",
-           who, n_dst, (long long)n_edges);
-  RG_CHECK(n_src >= 0 && n_rela_rows >= 0 && batch >= 0, "%s: n_src=%d n_rela_rows=%d batch=%d (negative size)", who, n_src, n_rela_rows,
-           batch);
-  RG_CHECK(d > 0 && ld >= d && ld % 4 == 0 && ld <= 256, "%s: d=%d ld=%d (need ld%%4==0, d<=ld<=256)", who, d, ld);
-  RG_CHECK(attn_dim > 0 && ap >= attn_dim && ap % 4 == 0, "%s: attn_dim=%d ap=%d", who, attn_dim, ap);
-  if (n_dst == 0) {
-    RG_CHECK(n_edges == 0, "%s: %lld edges without a destination", who, (long long)n_edges);
-    return 0;
-  }
-  RG_CHECK(dst_ptr_host, "%s: NULL argument (dst_ptr_host)", who);
-  RG_CHECK(dst_ptr_host[0] == 0, "%s: dst_ptr starts at %d, not 0", who, dst_ptr_host[0]);
-  for (int32_t o = 0; o < n_dst; ++o)
-    RG_CHECK(dst_ptr_host[o + 1] >= dst_ptr_host[o], "%s: dst_ptr decreases at destination %d", who, o);
-  RG_CHECK(dst_ptr_host[n_dst] == n_edges, "%s: dst_ptr ends at %d, not at the number of edges %lld", who, dst_ptr_host[n_dst],
-           (long long)n_edges);
-  if (n_edges == 0) return 0;                            // nothing to sum and nothing launched: the caller owns agg_out
-  RG_CHECK(dst_ptr && src_idx && rel && row_of_dst && hidden && rela && a_s && a_r && a_q && w_alpha && b_alpha && agg_out,
-           "%s: NULL argument", who);
-  RG_CHECK(n_src > 0 && n_rela_rows > 0 && batch > 0, "%s: edges but n_src=%d n_rela_rows=%d batch=%d", who, n_src, n_rela_rows, batch);
-  RG_CHECK((((uintptr_t)hidden | (uintptr_t)rela | (uintptr_t)a_s | (uintptr_t)a_r | (uintptr_t)a_q | (uintptr_t)agg_out |
-             (uintptr_t)scratch) & 15) == 0, "%s: float buffers must be 16-B aligned", who);
-  int64_t n_hubs, n_chunks;
-  rgdg::count_cuts(dst_ptr_host, n_dst, &n_hubs, &n_chunks);
-  RG_CHECK((int64_t)n_dst + n_chunks < ((int64_t)1 << 31), "%s: %lld items overflow int32", who, (long long)(n_dst + n_chunks));
-  const size_t need = n_hubs ? rgdg::list_bytes(n_hubs, n_chunks) + rg::align_up((size_t)n_chunks * ld * sizeof(float), 256) : 0;
-  RG_CHECK(need == 0 || (scratch && scratch_bytes >= need), "%s: scratch %zu B < required %zu B", who, scratch ? scratch_bytes : (size_t)0,
-           need);
+  return rgdg::run("rg_digraph_layer_fwd", nullptr, n_dst, n_edges, dst_ptr, dst_ptr_host, src_idx, rel, row_of_dst, n_src, n_rela_rows,
+                   batch, hidden, rela, d, ld, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim, agg_out, alpha_out, scratch, scratch_bytes,
+                   stream);
+}
 
-  rgdg::DgArgs A;
-  A.n_dst = n_dst; A.n_items = (int)(n_dst + n_chunks); A.E = (int)n_edges; A.n_src = n_src; A.n_rela_rows = n_rela_rows; A.B = batch;
-  A.dst_ptr = dst_ptr; A.src_idx = src_idx; A.rel = rel; A.row_of_dst = row_of_dst;
-  A.hidden = (const float4*)hidden; A.rela = (const float4*)rela; A.ld4 = ld / 4;
-  A.a_s = (const float4*)a_s; A.a_r = (const float4*)a_r; A.a_q = (const float4*)a_q;
-  A.w_alpha = w_alpha; A.b_alpha = b_alpha; A.attn_dim = attn_dim;
-  A.agg = (float4*)agg_out; A.alpha_out = alpha_out;
-  int4* hubs_dev = (int4*)scratch;
-  A.chunks = hubs_dev + n_hubs;
-  A.partial = n_hubs ? (float4*)((char*)scratch + rgdg::list_bytes(n_hubs, n_chunks)) : nullptr;
-  // every argument error is out before anything is enqueued: the width dispatch is probed first
-  if (rg::with_ap4(ap / 4, who, [](auto) { return 0; })) return 1;
-  hipStream_t s = (hipStream_t)stream;
-  if (n_hubs) {
-    std::vector<int4> list((size_t)(n_hubs + n_chunks));
-    int64_t h = 0, slot = 0;
-    for (int32_t o = 0; o < n_dst; ++o) {
-      const int32_t lo = dst_ptr_host[o], hi = dst_ptr_host[o + 1];
-      if (hi - lo <= rgdg::DIGRAPH_CHUNK) continue;
-      const int n_c = (int)rg::ceil_div(hi - lo, rgdg::DIGRAPH_CHUNK);
-      list[h++] = make_int4(o, (int)slot, n_c, 0);
-      for (int k = 0; k < n_c; ++k, ++slot)
-        list[n_hubs + slot] = make_int4(o, lo + k * rgdg::DIGRAPH_CHUNK, std::min(hi, lo + (k + 1) * rgdg::DIGRAPH_CHUNK), (int)slot);
-    }
-    // (a copy from pageable memory: the runtime is done with the vector when the call returns)
-    RG_HIP(hipMemcpyAsync(hubs_dev, list.data(), list.size() * sizeof(int4), hipMemcpyHostToDevice, s));
-  }
-  const int rc = rg::with_g(A.ld4, [&](auto g) {
-    return rg::with_ap4(ap / 4, who, [&](auto a4) { return rgdg::launch<decltype(g)::value, decltype(a4)::value>(A, s); });
-  });
-  if (rc) return rc;
-  if (n_hubs) {
-    const int64_t threads = n_hubs * A.ld4;
-    hipLaunchKernelGGL(rgdg::digraph_combine_kernel, dim3((unsigned)rg::ceil_div(threads, 256)), dim3(256), 0, s, hubs_dev, (int)n_hubs,
-                       (const float4*)A.partial, A.agg, A.ld4);
-    RG_LAUNCH_CHECK();
-  }
-  return 0;
+extern "C" int rg_digraph_tlayer_fwd(int32_t n_dst, int64_t n_edges, const int32_t* dst_ptr, const int32_t* dst_ptr_host,
+                                     const int32_t* src_idx, const int32_t* rel, const int32_t* edge_time, const int32_t* row_of_dst,
+                                     const int32_t* q_time, int32_t n_src, int32_t n_rela_rows, int32_t batch, int32_t n_time,
+                                     int32_t n_dir, const float* hidden, const float* rela, const float* time_tab, int32_t d, int32_t ld,
+                                     const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha,
+                                     const float* b_alpha, int32_t attn_dim, float* agg_out, float* alpha_out, void* scratch,
+                                     size_t scratch_bytes, void* stream) {
+  const rgdg::TimeIn T{edge_time, q_time, time_tab, n_time, n_dir};
+  return rgdg::run("rg_digraph_tlayer_fwd", &T, n_dst, n_edges, dst_ptr, dst_ptr_host, src_idx, rel, row_of_dst, n_src, n_rela_rows,
+                   batch, hidden, rela, d, ld, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim, agg_out, alpha_out, scratch, scratch_bytes,
+                   stream);
 }

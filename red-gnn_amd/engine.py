@@ -1108,7 +1108,7 @@ def paths_topk(edges, alpha, offsets, n_hops, k, scratch_bytes=PATHS_SCRATCH_BYT
 
 DIGRAPH_CHUNK = 128                  # include/redgnn.h: RG_DIGRAPH_CHUNK
 
-DIGRAPH_EVENTS = None                # probes: a list that collects (start, end, n_dst, n_edges) of every digraph_layer_fwd
+DIGRAPH_EVENTS = None                # probes: a list that collects (start, end, n_dst, n_edges) of every digraph_(t)layer_fwd
 
 
 def digraph_chunks(dst_ptr_host):
@@ -1126,11 +1126,38 @@ def digraph_layer_fwd(dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s, a
     edge's row in ``hidden`` / ``a_s`` and in ``rela`` / ``a_r``, ``row_of_dst`` int32 [n_dst] a destination's row in ``a_q``
     (``dst_ptr_host``: the CSR as a numpy array, if at hand).  Shapes, dtypes and index ranges are checked here (ValueError); the sums
     are deterministic and a destination's row does not depend on the rest of the call."""
-    who = "digraph_layer_fwd"
-    for name, t in (("dst_ptr", dst_ptr), ("src_idx", src_idx), ("rel", rel), ("row_of_dst", row_of_dst)):
+    return _digraph_layer("digraph_layer_fwd", dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s, a_r, a_q, w_alpha, b_alpha,
+                          attn_dim, want_alpha, dst_ptr_host, None)
+
+
+def digraph_tlayer_fwd(dst_ptr, src_idx, rel, row_of_dst, hidden, rela, time_tab, d, a_s, a_r, a_q, w_alpha, b_alpha, attn_dim, edge_time,
+                       q_time, n_dir=3, want_alpha=True, dst_ptr_host=None):
+    """digraph_layer_fwd with a time per edge (rg_digraph_tlayer_fwd): ``edge_time`` int32 [E], ``q_time`` int32 [B] (a row of ``a_q``
+    each) and ``time_tab`` fp32 [n_dir * n_time, ld].  n_dir = 3, the interpolation layer: ``hidden`` [3 n_src, ld] and ``rela``
+    [3 n_rela_rows, ld] hold a row per direction past / now / future of dt = edge time - query time, ``time_tab`` a row per direction
+    and |dt|, and ``edge_time`` lies in 0..n_time-1.  n_dir = 1, the extrapolation form: plain tables, ``time_tab`` is read at
+    clamp(query day - edge day, 0, n_time - 1) and ``edge_time`` >= 0 is the day the caller resolved for the edge.  ``a_s`` [n_src, ap]
+    and ``a_r`` [n_rela_rows, ap] are not directed.  The same checks (ValueError), the same determinism."""
+    return _digraph_layer("digraph_tlayer_fwd", dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s, a_r, a_q, w_alpha, b_alpha,
+                          attn_dim, want_alpha, dst_ptr_host, (edge_time, q_time, time_tab, n_dir))
+
+
+def _digraph_layer(who, dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s, a_r, a_q, w_alpha, b_alpha, attn_dim, want_alpha,
+                   dst_ptr_host, timed):
+    """Both wrappers: the host checks, the scratch, the launch.  ``timed``: None or (edge_time, q_time, time_tab, n_dir)."""
+    ints, floats = [("dst_ptr", dst_ptr), ("src_idx", src_idx), ("rel", rel), ("row_of_dst", row_of_dst)], \
+        [("hidden", hidden), ("rela", rela), ("a_s", a_s), ("a_r", a_r), ("a_q", a_q)]
+    n_dir = 1
+    if timed is not None:
+        edge_time, q_time, time_tab, n_dir = timed
+        if isinstance(n_dir, (bool, np.bool_)) or not isinstance(n_dir, (int, np.integer)) or n_dir not in (1, 3):
+            raise ValueError("%s: n_dir must be 1 or 3 (got %r)" % (who, n_dir))
+        ints += [("edge_time", edge_time), ("q_time", q_time)]
+        floats.append(("time_tab", time_tab))
+    for name, t in ints:
         if not (torch.is_tensor(t) and t.dtype == torch.int32 and t.dim() == 1):
             raise ValueError("%s: %s must be an int32 vector" % (who, name))
-    for name, t in (("hidden", hidden), ("rela", rela), ("a_s", a_s), ("a_r", a_r), ("a_q", a_q)):
+    for name, t in floats:
         if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.dim() == 2):
             raise ValueError("%s: %s must be a float32 matrix" % (who, name))
     n_dst, E = dst_ptr.numel() - 1, src_idx.numel()
@@ -1138,11 +1165,18 @@ def digraph_layer_fwd(dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s, a
     if n_dst < 0 or rel.numel() != E or row_of_dst.numel() != n_dst:
         raise ValueError("%s: dst_ptr [%d], src_idx [%d], rel [%d] and row_of_dst [%d] do not fit together"
                          % (who, dst_ptr.numel(), E, rel.numel(), row_of_dst.numel()))
-    if rela.shape[1] != ld or a_r.shape[1] != ap or a_q.shape[1] != ap or a_s.shape[0] != hidden.shape[0] or a_r.shape[0] != rela.shape[0]:
+    if rela.shape[1] != ld or a_r.shape[1] != ap or a_q.shape[1] != ap or n_dir * a_s.shape[0] != hidden.shape[0] \
+            or n_dir * a_r.shape[0] != rela.shape[0]:
         raise ValueError("%s: hidden %s, rela %s, a_s %s, a_r %s and a_q %s do not fit together"
                          % (who, tuple(hidden.shape), tuple(rela.shape), tuple(a_s.shape), tuple(a_r.shape), tuple(a_q.shape)))
+    n_time = 0
+    if timed is not None:
+        n_time = time_tab.shape[0] // n_dir
+        if edge_time.numel() != E or q_time.numel() != a_q.shape[0] or time_tab.shape[1] != ld or n_time < 1 or n_time * n_dir != time_tab.shape[0]:
+            raise ValueError("%s: edge_time [%d] (%d edges), q_time [%d] (a_q %s) and time_tab %s (n_dir * n_time rows of %d) do not fit together"
+                             % (who, edge_time.numel(), E, q_time.numel(), tuple(a_q.shape), tuple(time_tab.shape), ld))
     _require_gpu(hidden.device)
-    tensors = (dst_ptr, src_idx, rel, row_of_dst, hidden, rela, a_s, a_r, a_q, w_alpha, b_alpha)
+    tensors = tuple(t for _, t in ints + floats) + (w_alpha, b_alpha)
     if not all(t.is_cuda and t.is_contiguous() for t in tensors):
         raise ValueError("%s: every tensor must be contiguous and on the device" % who)
     dev = hidden.device
@@ -1152,9 +1186,12 @@ def digraph_layer_fwd(dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s, a
     if ptr_h.shape != (n_dst + 1,) or ptr_h[0] != 0 or ptr_h[-1] != E or (np.diff(ptr_h) < 0).any():
         raise ValueError("%s: dst_ptr must start at 0, never decrease and end at the number of edges (%d)" % (who, E))
     if E:
-        lo = torch.stack([src_idx.min(), rel.min(), row_of_dst.min()]).tolist()
-        hi = torch.stack([src_idx.max(), rel.max(), row_of_dst.max()]).tolist()
-        for name, a, b, n in zip(("src_idx", "rel", "row_of_dst"), lo, hi, (hidden.shape[0], rela.shape[0], a_q.shape[0])):
+        checked = [("src_idx", src_idx, a_s.shape[0]), ("rel", rel, a_r.shape[0]), ("row_of_dst", row_of_dst, a_q.shape[0])]
+        if timed is not None:                 # n_dir 3: a time id; n_dir 1: a day, any that is not negative
+            checked.append(("edge_time", edge_time, n_time if n_dir == 3 else 1 << 31))
+        lo = torch.stack([t.min() for _, t, _ in checked]).tolist()
+        hi = torch.stack([t.max() for _, t, _ in checked]).tolist()
+        for (name, _, n), a, b in zip(checked, lo, hi):
             if a < 0 or b >= n:
                 raise ValueError("%s: %s out of range (%d..%d, %d rows)" % (who, name, a, b, n))
     L, p = _lib.lib(), _lib.ptr
@@ -1164,9 +1201,15 @@ def digraph_layer_fwd(dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s, a
     if DIGRAPH_EVENTS is not None:
         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         ev[0].record()
-    _lib.check(L.rg_digraph_layer_fwd(n_dst, E, p(dst_ptr), p(ptr_h), p(src_idx), p(rel), p(row_of_dst), hidden.shape[0], rela.shape[0],
-                                      a_q.shape[0], p(hidden), p(rela), int(d), ld, p(a_s), p(a_r), p(a_q), ap, p(w_alpha), p(b_alpha),
-                                      int(attn_dim), p(agg), p(alpha), p(scratch), nbytes, _lib.stream_ptr()))
+    if timed is None:
+        _lib.check(L.rg_digraph_layer_fwd(n_dst, E, p(dst_ptr), p(ptr_h), p(src_idx), p(rel), p(row_of_dst), a_s.shape[0], a_r.shape[0],
+                                          a_q.shape[0], p(hidden), p(rela), int(d), ld, p(a_s), p(a_r), p(a_q), ap, p(w_alpha), p(b_alpha),
+                                          int(attn_dim), p(agg), p(alpha), p(scratch), nbytes, _lib.stream_ptr()))
+    else:
+        _lib.check(L.rg_digraph_tlayer_fwd(n_dst, E, p(dst_ptr), p(ptr_h), p(src_idx), p(rel), p(edge_time), p(row_of_dst), p(q_time),
+                                           a_s.shape[0], a_r.shape[0], a_q.shape[0], n_time, int(n_dir), p(hidden), p(rela), p(time_tab),
+                                           int(d), ld, p(a_s), p(a_r), p(a_q), ap, p(w_alpha), p(b_alpha), int(attn_dim), p(agg), p(alpha),
+                                           p(scratch), nbytes, _lib.stream_ptr()))
     if ev is not None:
         ev[1].record()
         DIGRAPH_EVENTS.append((ev[0], ev[1], n_dst, E))

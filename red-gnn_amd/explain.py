@@ -16,7 +16,8 @@ one backward marking pass per hop reads only the marked tails' CSR rows.  This m
 
 Temporal interpolation (T_RED_GNN.explain, rg_texplain_*): ``rd = model.explain(batch, objs)`` with the batch dict of forward; every
 edge also carries its time id (``rd.time``), ``rd.q_time`` is the rows' query time and ``rd.direction()`` the forward's past / now /
-future of each edge.  ``table = model.rules(batch, objs, k=2)`` counts the best paths as temporal rules, steps (relation, direction)
+future of each edge.  ``rd.rescore(model, keep)`` re-scores the answers on the kept edges (rg_digraph_tlayer_fwd), ``rd.fact_mask``
+takes quadruples (h, r, t, time id) and ``model.fidelity(batch, objs, k, inverse_offset)`` is the static model's fidelity.  ``table = model.rules(batch, objs, k=2)`` counts the best paths as temporal rules, steps (relation, direction)
 with identity steps written as direction 3 = any (TemporalRuleTable), and ``model.rule_quality(table)`` counts how they hold in the
 quadruple graph per anchor (entity, query time id) (TemporalRuleQuality; engine.trule_ground, csrc/trule_ground.hip).
 
@@ -57,9 +58,13 @@ class RDigraph:
     data_row int32 [E]     extrapolation only (None otherwise): the edge's index into the model's data array, -1 for a self-loop;
                            there ``time`` is the day the forward used for the edge (the row's day; a self-loop's: the first day of
                            the row's window) and ``q_time`` the query's day
-    q_sub    int64 [B]     static and inductive models (None otherwise): the subject s of each row
+    q_sub    int64 [B]     static, inductive and temporal interpolation models (None otherwise): the subject s of each row
     q_rel    int64 [B]     ... and its query relation r; ``rescore`` needs both
-    n_rel    int           ... and the KG's relation count (ids >= n_rel are inverses, 2 * n_rel the identity); ``fact_mask`` needs it
+    n_rel    int           ... static and inductive: the KG's relation count (ids >= n_rel are inverses, 2 * n_rel the identity);
+                           temporal interpolation: the model's n_rel, the identity's relation id (the tables have n_rel + 1 rows);
+                           ``fact_mask`` needs it
+    n_time   int           temporal interpolation only (None otherwise): the number of time ids; with it ``rescore`` and ``fact_mask``
+                           take the digraph as a temporal one
     """
     edges: torch.Tensor
     alpha: torch.Tensor
@@ -73,6 +78,7 @@ class RDigraph:
     q_sub: torch.Tensor = None
     q_rel: torch.Tensor = None
     n_rel: int = None
+    n_time: int = None
 
     def rescore(self, model, keep=None, mode="test"):
         """The model's score of o on the digraph with only the edges ``keep`` (bool or uint8 [E] over ``edges``; None: all of them):
@@ -81,15 +87,24 @@ class RDigraph:
         per hop (rg_digraph_layer_fwd; csrc/digraph_fwd.hip) and the dense step of the inference forward, no graph rebuild.  A kept
         edge whose head is no longer visited one hop down is dead (``live``); a row whose o has no length-L walk left scores exactly 0.
         ``model``: the RED_GNN_trans / RED_GNN_induc that explained, ``mode`` the one it explained in.  Eval semantics under no_grad.
-        The digraph is checked on the host first (ValueError); temporal digraphs are out of scope (ValueError)."""
+        A temporal interpolation digraph (temporal.T_RED_GNN.explain: ``time``, ``q_time``, ``q_sub``, ``q_rel``, ``n_rel`` and
+        ``n_time`` set) is re-scored by the temporal.T_RED_GNN that explained it, one rg_digraph_tlayer_fwd launch per hop with the
+        tables T_RED_GNN's forward forms; ``mode`` must be "test" there, the full graph explain walks.  The digraph is checked on the
+        host first (ValueError); extrapolation digraphs, and any other mix of temporal fields and models, are a ValueError."""
         return rescore(self, model, keep, mode)
 
-    def fact_mask(self, facts, rows=None):
+    def fact_mask(self, facts, rows=None, inverse_offset=None):
         """bool [E]: the edges that stand for one of the facts ``facts`` int [F, 3] = (h, r, t), at any hop: an edge is marked if its
         (head, rel, tail) is a fact or a fact's twin (t, inv(r), h), inv(r) = r + n_rel below n_rel and r - n_rel from there on.  The
         identity relation 2 * n_rel is never marked: a self-loop is part of the model, not a fact.  ``rows`` int [F]: fact f counts
-        for the edges of row rows[f] only (None: for every row).  Static digraphs that carry ``n_rel``."""
-        return fact_mask(self, facts, rows)
+        for the edges of row rows[f] only (None: for every row).  Static digraphs that carry ``n_rel``.
+
+        On a temporal interpolation digraph ``facts`` is int [F, 4] = (h, r, t, time id): an edge is marked if its (head, rel, tail,
+        time) is one of them - every copy of a quadruple the graph holds more than once - and never the identity relation ``n_rel``.
+        How a quadruple graph writes inverses belongs to the data, not to the model: with ``inverse_offset`` = m the twin
+        (t, r + m if r < m else r - m, h, time id) is marked too (None: the quadruples as given).  A static digraph takes no
+        ``inverse_offset``."""
+        return fact_mask(self, facts, rows, inverse_offset)
 
     def direction(self):
         """int8 [E]: each edge's direction against its row's query time, the temporal forward's convention (dt = edge time - query
@@ -245,16 +260,20 @@ class PathSet:
             raise ValueError("data_rows: this r-digraph carries no data rows (extrapolation digraphs do)")
         return self._gather(self.digraph.data_row, -1)
 
-    def fact_mask(self, j):
+    def fact_mask(self, j, inverse_offset=None):
         """bool [E]: digraph.fact_mask of the facts the best ``j`` paths of each row step over (1 <= j <= k; a row with fewer paths
-        gives all it has), every fact for its own row.  Identity steps are no facts."""
+        gives all it has), every fact for its own row.  Identity steps are no facts.  On a temporal digraph the facts are the steps'
+        quadruples and ``inverse_offset`` is passed on."""
         k = self.edge.shape[1]
         _check_count(j, "fact_mask", "j", k)
         rd = self.digraph
         at = self.edge[:, :int(j)].reshape(-1)
         at = at[at >= 0]
         e = rd.edges[at].long()
-        return rd.fact_mask(e[:, 2:5], rows=e[:, 0])
+        if _has_times(rd):
+            _check_temporal_fields(rd, "fact_mask")
+            return rd.fact_mask(torch.cat([e[:, 2:5], rd.time[at].long()[:, None]], 1), rows=e[:, 0], inverse_offset=inverse_offset)
+        return rd.fact_mask(e[:, 2:5], rows=e[:, 0], inverse_offset=inverse_offset)
 
 
 def _check_count(x, who, name, most=None):
@@ -1236,7 +1255,8 @@ def explain_temporal(model, batch, objs=None, min_alpha=0.0):
         score = scores[rows, objs_t].contiguous()
         edges, alpha, offsets, time = _assemble(hops, n, L, device)
     return RDigraph(edges=edges, alpha=alpha, offsets=offsets, reached=reached, score=score, n_hops=L, time=time,
-                    q_time=q_time.clone())
+                    q_time=q_time.clone(), q_sub=torch.as_tensor(heads_h, dtype=torch.int64).to(device), q_rel=kept[0]["q_rel"].clone(),
+                    n_rel=int(model.n_rel), n_time=int(model.n_time))
 
 
 def explain_extrapolation(model, X, objs=None, min_alpha=0.0):
@@ -1362,10 +1382,50 @@ class Fidelity:
                 for b in range(len(sc))]
 
 
+def _has_times(rd):
+    """The digraph carries a temporal field: it is not a static one, whatever else it is."""
+    return rd.time is not None or rd.q_time is not None or rd.data_row is not None
+
+
 def _check_static_digraph(rd, who):
     """The host checks of a static r-digraph's tensors (ValueError naming the argument); returns (E, B)."""
-    if rd.time is not None or rd.q_time is not None or rd.data_row is not None:
-        raise ValueError("%s: a temporal r-digraph (time is set) is out of scope; static and inductive models only" % who)
+    if _has_times(rd):
+        raise ValueError("%s: a temporal r-digraph (time is set) is out of scope here; static and inductive models only" % who)
+    return _check_digraph_tensors(rd, who)
+
+
+def _check_temporal_fields(rd, who):
+    """A temporal r-digraph is a temporal interpolation one, as temporal.T_RED_GNN.explain returns it: every field rescore and
+    fact_mask read is set and there are no data rows (ValueError naming what is missing).  No tensor is read."""
+    if rd.data_row is not None:
+        raise ValueError("%s: a temporal r-digraph with data_row set is an extrapolation digraph, which is out of scope; temporal "
+                         "interpolation (temporal.T_RED_GNN.explain) only" % who)
+    missing = [name for name in ("time", "q_time", "q_sub", "q_rel", "n_rel", "n_time") if getattr(rd, name) is None]
+    if missing:
+        raise ValueError("%s: a temporal r-digraph needs time, q_time, q_sub, q_rel, n_rel and n_time, as temporal.T_RED_GNN.explain "
+                         "sets them (missing: %s)" % (who, ", ".join(missing)))
+
+
+def _check_temporal_digraph(rd, who):
+    """The host checks of a temporal interpolation r-digraph: its fields (_check_temporal_fields), then the tensors (ValueError
+    naming the argument); returns (E, B)."""
+    _check_temporal_fields(rd, who)
+    E, B = _check_digraph_tensors(rd, who)
+    if isinstance(rd.n_time, (bool, np.bool_)) or not isinstance(rd.n_time, (int, np.integer)) or rd.n_time < 1:
+        raise ValueError("%s: n_time must be a positive integer (got %r)" % (who, rd.n_time))
+    t, q = rd.time, rd.q_time
+    if not torch.is_tensor(t) or t.dtype != torch.int32 or t.shape != (E,):
+        raise ValueError("%s: time must be int32 [%d], one per edge" % (who, E))
+    if not torch.is_tensor(q) or q.dtype != torch.int32 or q.shape != (B,):
+        raise ValueError("%s: q_time must be int32 [%d], one per row" % (who, B))
+    for name, x in (("time", t), ("q_time", q)):
+        if x.numel() and (int(x.min()) < 0 or int(x.max()) >= rd.n_time):
+            raise ValueError("%s: %s holds a time id outside 0..%d" % (who, name, rd.n_time - 1))
+    return E, B
+
+
+def _check_digraph_tensors(rd, who):
+    """edges, alpha, offsets, n_hops and n_rel of any r-digraph; returns (E, B)."""
     if isinstance(rd.n_hops, (bool, np.bool_)) or not isinstance(rd.n_hops, (int, np.integer)) or not 1 <= rd.n_hops <= 32:
         raise ValueError("%s: n_hops must be an integer in 1..32 (got %r)" % (who, rd.n_hops))
     e, a, o = rd.edges, rd.alpha, rd.offsets
@@ -1385,18 +1445,35 @@ def _check_static_digraph(rd, who):
     return e.shape[0], o.numel() - 1
 
 
-def fact_mask(rd, facts, rows=None):
+def fact_mask(rd, facts, rows=None, inverse_offset=None):
     """RDigraph.fact_mask (see there)."""
     who = "fact_mask"
-    E, B = _check_static_digraph(rd, who)
+    timed = _has_times(rd)
+    E, B = _check_temporal_digraph(rd, who) if timed else _check_static_digraph(rd, who)
     dev = rd.edges.device
     f = (facts.detach() if torch.is_tensor(facts) else torch.as_tensor(np.asarray(facts))).to(dev)
-    if f.is_floating_point() or f.dtype == torch.bool or f.dim() != 2 or f.shape[1] != 3:
-        raise ValueError("%s: facts must be integers [F, 3] = (h, r, t) (got %s %s)" % (who, f.dtype, tuple(f.shape)))
-    f = f.long()
     n_rel = int(rd.n_rel)
-    if f.shape[0] and (int(f.min()) < 0 or int(f[:, 1].max()) > 2 * n_rel):
-        raise ValueError("%s: facts hold a negative id or a relation above 2*n_rel = %d" % (who, 2 * n_rel))
+    if timed:
+        if f.is_floating_point() or f.dtype == torch.bool or f.dim() != 2 or f.shape[1] != 4:
+            raise ValueError("%s: on a temporal r-digraph facts must be integers [F, 4] = (h, r, t, time id) (got %s %s)"
+                             % (who, f.dtype, tuple(f.shape)))
+        f = f.long()
+        if f.shape[0] and (int(f.min()) < 0 or int(f[:, 1].max()) > n_rel):
+            raise ValueError("%s: facts hold a negative id or a relation above n_rel = %d" % (who, n_rel))
+        if f.shape[0] and int(f[:, 3].max()) >= rd.n_time:
+            raise ValueError("%s: facts hold a time id outside 0..%d" % (who, rd.n_time - 1))
+        m = inverse_offset
+        if m is not None and (isinstance(m, (bool, np.bool_)) or not isinstance(m, (int, np.integer)) or m < 1 or 2 * m > n_rel):
+            raise ValueError("%s: inverse_offset must be an integer m with 1 <= m and 2 m <= n_rel = %d, relation r's inverse being r + m "
+                             "below m and r - m from there on (got %r)" % (who, n_rel, m))
+    else:
+        if inverse_offset is not None:
+            raise ValueError("%s: inverse_offset is for temporal r-digraphs; a static one knows its inverses (r + n_rel)" % who)
+        if f.is_floating_point() or f.dtype == torch.bool or f.dim() != 2 or f.shape[1] != 3:
+            raise ValueError("%s: facts must be integers [F, 3] = (h, r, t) (got %s %s)" % (who, f.dtype, tuple(f.shape)))
+        f = f.long()
+        if f.shape[0] and (int(f.min()) < 0 or int(f[:, 1].max()) > 2 * n_rel):
+            raise ValueError("%s: facts hold a negative id or a relation above 2*n_rel = %d" % (who, 2 * n_rel))
     r_of = None
     if rows is not None:
         r_of = (rows.detach() if torch.is_tensor(rows) else torch.as_tensor(np.asarray(rows))).to(dev)
@@ -1406,6 +1483,22 @@ def fact_mask(rd, facts, rows=None):
         if r_of.numel() and (int(r_of.min()) < 0 or int(r_of.max()) >= B):
             raise ValueError("%s: rows out of range (the digraph has %d rows)" % (who, B))
     mask = torch.zeros(E, dtype=torch.bool, device=dev)
+    if timed:
+        fact = f[:, 1] != n_rel                           # the identity is no fact
+        f = f[fact]
+        if E == 0 or f.shape[0] == 0:
+            return mask
+        e = rd.edges.long()
+        n_key = int(max(e[:, 2].max(), e[:, 4].max(), f[:, 0].max(), f[:, 2].max())) + 1
+        n_r, n_t = n_rel + 1, int(rd.n_time)
+        key = lambda row, h, r, t, tm: (((row * n_key + h) * n_r + r) * n_key + t) * n_t + tm
+        f_row = torch.zeros_like(f[:, 0]) if r_of is None else r_of[fact]
+        e_row = torch.zeros_like(e[:, 0]) if r_of is None else e[:, 0]
+        want = key(f_row, f[:, 0], f[:, 1], f[:, 2], f[:, 3])
+        if inverse_offset is not None:
+            m = int(inverse_offset)
+            want = torch.cat([want, key(f_row, f[:, 2], torch.where(f[:, 1] < m, f[:, 1] + m, f[:, 1] - m), f[:, 0], f[:, 3])])
+        return torch.isin(key(e_row, e[:, 2], e[:, 3], e[:, 4], rd.time.long()), want) & (e[:, 3] != n_rel)
     fact = f[:, 1] != 2 * n_rel                           # the identity is no fact
     f = f[fact]
     if E == 0 or f.shape[0] == 0:
@@ -1429,9 +1522,122 @@ def _sorted_find(keys, want):
     return pos, keys[pos] == want
 
 
+def _hop_index(who, l, L, at, row, head, tail, keys_prev, n_ent, live):
+    """The index arrays of hop l of a rescore from its kept edges ``at`` (indices into the digraph's edges, in order): the forward
+    sweep against the previous hop's sorted node keys (``live`` is marked), then the hop's node list - the sorted unique (row, tail) -
+    and its CSR.  Returns None where no edge is live, else (at, src, keys, dst_ptr, row_of, prev_idx, had): the live edges, their
+    head's position in ``keys_prev``, the node keys row * n_ent + tail, the CSR of the edges by node (int32), the nodes' rows, and
+    each node's position in ``keys_prev`` (int32, -1 where ``had`` is False)."""
+    src, ok = _sorted_find(keys_prev, row[at] * n_ent + head[at])
+    at, src = at[ok], src[ok]                                         # the forward sweep: the head is visited one hop down
+    if at.numel() == 0:
+        return None                                                   # nothing is reached from here on: every score stays 0
+    live[at] = True
+    tk = row[at] * n_ent + tail[at]
+    if bool((tk[1:] < tk[:-1]).any()):
+        raise ValueError("%s: edges must be ordered by (row, hop, tail), as model.explain returns them" % who)
+    keys, counts = torch.unique_consecutive(tk, return_counts=True)   # the hop's node list: sorted unique (row, tail)
+    dst_ptr = torch.zeros(keys.numel() + 1, dtype=torch.int32, device=tk.device)
+    dst_ptr[1:] = torch.cumsum(counts, 0)
+    row_of = keys // n_ent
+    if l == L and bool((row_of[1:] == row_of[:-1]).any()):
+        raise ValueError("%s: the hop-%d edges of a row must share their tail, the row's answer" % (who, L))
+    prev_idx, had = _sorted_find(keys_prev, keys)
+    prev_idx = torch.where(had, prev_idx, torch.full_like(prev_idx, -1)).to(torch.int32).contiguous()
+    return at, src, keys, dst_ptr, row_of, prev_idx, had
+
+
+def _check_keep(who, keep, E, device):
+    if keep is not None:
+        keep = keep if torch.is_tensor(keep) else torch.as_tensor(np.asarray(keep)).to(device)      # (an array goes along)
+        if keep.dtype not in (torch.bool, torch.uint8) or keep.shape != (E,):
+            raise ValueError("%s: keep must be bool or uint8 [%d], one per edge (got %s %s)" % (who, E, keep.dtype, tuple(keep.shape)))
+    return keep
+
+
+def rescore_temporal(rd, model, keep=None, mode="test"):
+    """RDigraph.rescore of a temporal interpolation digraph (see there): T_RED_GNN._run's layer over the kept edges, hop by hop."""
+    from .temporal import T_RED_GNN, eval_semantics
+    who = "rescore"
+    if not isinstance(model, T_RED_GNN):
+        raise ValueError("%s: a temporal r-digraph (time, q_time or data_row is set) is re-scored by the temporal.T_RED_GNN that "
+                         "explained it (got %s)" % (who, type(model).__name__))
+    E, B = _check_temporal_digraph(rd, who)
+    if mode != "test":
+        raise ValueError("%s: a temporal r-digraph is explained on the full graph; mode must be 'test' (got %r)" % (who, mode))
+    for name in ("q_sub", "q_rel"):
+        t = getattr(rd, name)
+        if not torch.is_tensor(t) or t.dtype != torch.int64 or t.shape != (B,):
+            raise ValueError("%s: %s must be int64 [%d], the rows' queries (model.explain sets it)" % (who, name, B))
+    L = int(rd.n_hops)
+    if model.n_layer != L or model.n_rel != rd.n_rel or model.n_time != rd.n_time:
+        raise ValueError("%s: the temporal digraph has n_hops=%d, n_rel=%d, n_time=%d, the model n_layer=%d, n_rel=%d, n_time=%d"
+                         % (who, L, rd.n_rel, rd.n_time, model.n_layer, model.n_rel, model.n_time))
+    keep = _check_keep(who, keep, E, rd.edges.device)
+    dev = rd.edges.device
+    tensors = [rd.edges, rd.alpha, rd.offsets, rd.q_sub, rd.q_rel, rd.time, rd.q_time] + ([keep] if keep is not None else [])
+    if not all(t.is_cuda for t in tensors) or any(t.device != dev for t in tensors):
+        raise ValueError("%s: the layers run in HIP and need the digraph (and keep) on one device (got CPU tensors or mixed devices)" % who)
+    n_ent, n_rel = model.n_ent, int(rd.n_rel)
+    e = rd.edges.long()
+    row, hop, head, rel, tail = e.unbind(1)
+    if B and (int(rd.q_sub.min()) < 0 or int(rd.q_sub.max()) >= n_ent or int(rd.q_rel.min()) < 0 or int(rd.q_rel.max()) > n_rel):
+        raise ValueError("%s: q_sub / q_rel out of range (n_ent=%d, n_rel+1=%d)" % (who, n_ent, n_rel + 1))
+    if E:
+        lo, hi = e.min(0).values.tolist(), e.max(0).values.tolist()
+        if lo[0] < 0 or hi[0] >= B or lo[1] < 1 or hi[1] > L or min(lo[2], lo[4]) < 0 or max(hi[2], hi[4]) >= n_ent or lo[3] < 0 \
+                or hi[3] > n_rel:
+            raise ValueError("%s: edges hold a row, hop, entity or relation out of range (B=%d, L=%d, n_ent=%d, n_rel+1=%d)"
+                             % (who, B, L, n_ent, n_rel + 1))
+    d, a = model.hidden_dim, model.attn_dim
+    ld, ap = max(16, _pad4(d)), pad_attn(a)
+    i32 = lambda t: t.to(torch.int32).contiguous()
+    padc = lambda t: F.pad(t, (0, ld - d)) if ld != d else t
+    pad_rows = lambda w: F.pad(w, (0, 0, 0, ap - a)) if ap != a else w
+    live = torch.zeros(E, dtype=torch.bool, device=dev)
+    alpha = torch.zeros(E, dtype=torch.float32, device=dev)
+    score = torch.zeros(B, dtype=torch.float32, device=dev)
+    reached = torch.zeros(B, dtype=torch.bool, device=dev)
+    kept = torch.ones(E, dtype=torch.bool, device=dev) if keep is None else keep.bool()
+    with torch.no_grad(), eval_semantics(model):
+        from .models import tall_linear
+        # the tables of T_RED_GNN._run, formed the same way
+        w_dir = torch.cat([model.past_linear.weight, model.now_linear.weight, model.future_linear.weight], 0)     # [3d, d]
+        time_dir = padc(F.linear(model.time_embed.weight, w_dir).view(model.n_time, 3, d).transpose(0, 1).reshape(3 * model.n_time, d)).contiguous()
+        zero_b = torch.zeros(1, device=dev)                                   # the temporal attention has no bias
+        q_time = rd.q_time.contiguous()
+        keys_prev = torch.arange(B, device=dev) * n_ent + rd.q_sub            # hop 0: the node (row, s) of every row, sorted
+        hidden = torch.zeros((B, d), device=dev)
+        for l in range(1, L + 1):
+            at = torch.nonzero((hop == l) & kept).reshape(-1)
+            index = _hop_index(who, l, L, at, row, head, tail, keys_prev, n_ent, live)
+            if index is None:
+                break
+            at, src, keys, dst_ptr, row_of, _, _ = index
+            rela, w1, w2 = model._tables(l - 1)
+            n_old = hidden.shape[0]
+            a_s = tall_linear(hidden, pad_rows(w1[:, :d])).contiguous()                   # [n_old, ap]
+            a_r = F.linear(rela, pad_rows(w1[:, d:2 * d])).contiguous()                  # [n_rel + 1, ap]
+            a_q = F.linear(rela[rd.q_rel], pad_rows(w1[:, 2 * d:])).contiguous()         # [B, ap]
+            hidden_dir = padc(tall_linear(hidden, w_dir).view(n_old * 3, d)).contiguous()            # row 3 s + dir
+            rela_dir = padc(F.linear(rela, w_dir).view(-1, 3, d).transpose(0, 1).reshape(-1, d)).contiguous()   # row dir * (R + 1) + r
+            agg, al = engine.digraph_tlayer_fwd(dst_ptr, i32(src), i32(rel[at]), i32(row_of), hidden_dir, rela_dir, time_dir, d, a_s, a_r,
+                                                a_q, w2.reshape(-1).contiguous(), zero_b, a, edge_time=rd.time[at].contiguous(),
+                                                q_time=q_time, n_dir=3)
+            alpha[at] = al
+            hidden = model.act(agg[:, :d])                                    # no GRU, and eval semantics: no dropout
+            keys_prev = keys
+            if l == L:
+                score[row_of] = tall_linear(hidden, model.linear_classifier.weight, model.linear_classifier.bias).reshape(-1)
+                reached[row_of] = True
+    return Rescore(score=score, reached=reached, live=live, alpha=alpha)
+
+
 def rescore(rd, model, keep=None, mode="test"):
     """RDigraph.rescore (see there)."""
     who = "rescore"
+    if _has_times(rd):
+        return rescore_temporal(rd, model, keep, mode)
     E, B = _check_static_digraph(rd, who)
     for name in ("q_sub", "q_rel"):
         t = getattr(rd, name)
@@ -1444,10 +1650,7 @@ def rescore(rd, model, keep=None, mode="test"):
     if model.n_layer != L or model.n_rel != rd.n_rel:
         raise ValueError("%s: the digraph has n_hops=%d, n_rel=%d, the model n_layer=%d, n_rel=%d" % (who, L, rd.n_rel, model.n_layer,
                                                                                                     model.n_rel))
-    if keep is not None:
-        keep = keep if torch.is_tensor(keep) else torch.as_tensor(np.asarray(keep)).to(rd.edges.device)      # (an array goes along)
-        if keep.dtype not in (torch.bool, torch.uint8) or keep.shape != (E,):
-            raise ValueError("%s: keep must be bool or uint8 [%d], one per edge (got %s %s)" % (who, E, keep.dtype, tuple(keep.shape)))
+    keep = _check_keep(who, keep, E, rd.edges.device)
     dev = rd.edges.device
     tensors = [rd.edges, rd.alpha, rd.offsets, rd.q_sub, rd.q_rel] + ([keep] if keep is not None else [])
     if not all(t.is_cuda for t in tensors) or any(t.device != dev for t in tensors):
@@ -1481,22 +1684,10 @@ def rescore(rd, model, keep=None, mode="test"):
         for l in range(1, L + 1):
             layer, last = model.gnn_layers[l - 1], l == L
             at = torch.nonzero((hop == l) & kept).reshape(-1)
-            src, ok = _sorted_find(keys_prev, row[at] * n_ent + head[at])
-            at, src = at[ok], src[ok]                                         # the forward sweep: the head is visited one hop down
-            if at.numel() == 0:
+            index = _hop_index(who, l, L, at, row, head, tail, keys_prev, n_ent, live)
+            if index is None:
                 break                                                         # nothing is reached from here on: every score stays 0
-            live[at] = True
-            tk = row[at] * n_ent + tail[at]
-            if bool((tk[1:] < tk[:-1]).any()):
-                raise ValueError("%s: edges must be ordered by (row, hop, tail), as model.explain returns them" % who)
-            keys, counts = torch.unique_consecutive(tk, return_counts=True)   # the hop's node list: sorted unique (row, tail)
-            dst_ptr = torch.zeros(keys.numel() + 1, dtype=torch.int32, device=dev)
-            dst_ptr[1:] = torch.cumsum(counts, 0)
-            row_of = keys // n_ent
-            if last and bool((row_of[1:] == row_of[:-1]).any()):
-                raise ValueError("%s: the hop-%d edges of a row must share their tail, the row's answer" % (who, L))
-            prev_idx, had = _sorted_find(keys_prev, keys)
-            prev_idx = i32(torch.where(had, prev_idx, torch.full_like(prev_idx, -1)))
+            at, src, keys, dst_ptr, row_of, prev_idx, had = index
             a_r, a_q, rela_p = tables[l - 1]
             agg, al = engine.digraph_layer_fwd(dst_ptr, i32(src), i32(rel[at]), i32(row_of), hidden, rela_p.contiguous(), d, a_s,
                                                a_r.contiguous(), a_q.contiguous(), layer.w_alpha.weight.detach().reshape(-1).contiguous(),
@@ -1525,19 +1716,59 @@ def rescore(rd, model, keep=None, mode="test"):
     return Rescore(score=score, reached=reached, live=live, alpha=alpha)
 
 
-def fidelity(model, subs, rels, objs=None, k=4, mode="test"):
-    """RED_GNN_trans.fidelity (see there)."""
-    _check_count(k, "fidelity", "k", engine.PATHS_MAX_K)
-    rd = model.explain(subs, rels, objs, mode=mode)
+def _fidelity_of(rd, model, k, loops, mode, inverse_offset=None):
+    """The Fidelity of a digraph: top_paths(k), then per j the two rescores - without the best j paths' facts, and with them and the
+    self-loops ``loops`` (bool [E]) alone."""
     paths = rd.top_paths(int(k))
-    loops = rd.edges[:, 3] == 2 * model.n_rel
     cols = {name: [] for name in ("without", "only", "reached_without", "reached_only")}
     for j in range(1, int(k) + 1):
-        m = paths.fact_mask(j)
+        m = paths.fact_mask(j, inverse_offset=inverse_offset)
         wo, on = rd.rescore(model, keep=~m, mode=mode), rd.rescore(model, keep=m | loops, mode=mode)
         for name, v in (("without", wo.score), ("only", on.score), ("reached_without", wo.reached), ("reached_only", on.reached)):
             cols[name].append(v)
     return Fidelity(score=rd.score, count=paths.count, paths=paths, **{name: torch.stack(v, 1) for name, v in cols.items()})
+
+
+def fidelity(model, subs, rels, objs=None, k=4, mode="test"):
+    """RED_GNN_trans.fidelity (see there)."""
+    _check_count(k, "fidelity", "k", engine.PATHS_MAX_K)
+    rd = model.explain(subs, rels, objs, mode=mode)
+    return _fidelity_of(rd, model, k, rd.edges[:, 3] == 2 * model.n_rel, mode)
+
+
+def temporal_fidelity(model, batch, objs=None, k=4, inverse_offset=None):
+    """temporal.T_RED_GNN.fidelity (see there)."""
+    _check_count(k, "fidelity", "k", engine.PATHS_MAX_K)
+    if objs is None and "tail" in batch:
+        objs = batch["tail"]
+    rd = model.explain(batch, objs)
+    return _fidelity_of(rd, model, k, rd.edges[:, 3] == model.n_rel, "test", inverse_offset)
+
+
+def temporal_fidelity_all(model, quads, k=4, batch_size=64, inverse_offset=None):
+    """temporal.T_RED_GNN.fidelity_all (see there)."""
+    q = np.asarray(quads.detach().cpu().numpy() if torch.is_tensor(quads) else quads)
+    if q.ndim != 2 or q.shape[1] != 4 or len(q) == 0 or q.dtype == np.bool_ or not np.issubdtype(q.dtype, np.integer):
+        raise ValueError("fidelity_all: quads must be a non-empty integer array [n, 4] = (head, rel, tail, time id) (got %s %s)"
+                         % (q.dtype, q.shape))
+    _check_count(k, "fidelity_all", "k", engine.PATHS_MAX_K)
+    _check_count(batch_size, "fidelity_all", "batch_size")
+    parts = []
+    for lo in range(0, len(q), int(batch_size)):
+        part = q[lo:lo + int(batch_size)]
+        parts.append(model.fidelity({"head": part[:, 0], "relation": part[:, 1], "time": part[:, 3]}, part[:, 2], k=int(k),
+                                    inverse_offset=inverse_offset))
+    return _fidelity_summary(parts, k)
+
+
+def _fidelity_summary(parts, k):
+    """The dict BaseModel.fidelity returns, from the Fidelity of every batch."""
+    nec = torch.cat([f.necessity().double().cpu() for f in parts])
+    gap = torch.cat([f.sufficiency_gap().double().cpu() for f in parts])
+    cut = torch.cat([(f.paths.digraph.reached[:, None] & ~f.reached_without).cpu() for f in parts])
+    return dict(n=int(nec.shape[0]), k=int(k), necessity_mean=nec.mean(0).tolist(), necessity_median=nec.median(0).values.tolist(),
+                sufficiency_gap_mean=gap.mean(0).tolist(), sufficiency_gap_median=gap.median(0).values.tolist(),
+                disconnected=cut.double().mean(0).tolist())
 
 
 def split_fidelity(base, data="test", k=4, batch=50, max_queries=None):
@@ -1554,14 +1785,8 @@ def split_fidelity(base, data="test", k=4, batch=50, max_queries=None):
         raise ValueError("fidelity: no queries with an answer in the %s split (n=%d)" % (data, n))
     rows = np.array(rows, dtype=np.int64)
     mode = loader.eval_mode(data) if hasattr(loader, "eval_mode") else data
-    nec, gap, cut = [], [], []
+    parts = []
     for lo in range(0, len(rows), int(batch)):
         part = rows[lo:lo + int(batch)]
-        f = base.model.fidelity(part[:, 0], part[:, 1], part[:, 2], k=int(k), mode=mode)
-        nec.append(f.necessity().double().cpu())
-        gap.append(f.sufficiency_gap().double().cpu())
-        cut.append((f.paths.digraph.reached[:, None] & ~f.reached_without).cpu())
-    nec, gap, cut = torch.cat(nec), torch.cat(gap), torch.cat(cut)
-    return dict(n=int(nec.shape[0]), k=int(k), necessity_mean=nec.mean(0).tolist(), necessity_median=nec.median(0).values.tolist(),
-                sufficiency_gap_mean=gap.mean(0).tolist(), sufficiency_gap_median=gap.median(0).values.tolist(),
-                disconnected=cut.double().mean(0).tolist())
+        parts.append(base.model.fidelity(part[:, 0], part[:, 1], part[:, 2], k=int(k), mode=mode))
+    return _fidelity_summary(parts, k)

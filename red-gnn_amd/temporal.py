@@ -14,7 +14,8 @@ hoisted per node / relation / |dt| (W(h + r + tau) = Wh + Wr + Wtau).  The atten
 relation - is ``attention_profile`` (rg_tattn_profile; with the edge direction past / now / future as one more axis), the r-digraph the
 reference draws in model_cuda_rule_vis.py is ``explain`` (rg_texplain_*; every edge with its time id), ``rules`` / ``rules_all`` count
 its best paths as temporal rules, ``rule_quality`` counts how those hold in the quadruple graph (rg_trule_ground), ``rule_scores`` /
-``rule_predict`` / ``rule_evaluate`` apply them to queries (rg_trule_apply: what the rules alone predict, and how well), and ``predict`` gives the
+``rule_predict`` / ``rule_evaluate`` apply them to queries (rg_trule_apply: what the rules alone predict, and how well), ``fidelity`` /
+``fidelity_all`` re-score an answer on its r-digraph without, and with only, its best paths' quadruples (rg_digraph_tlayer_fwd), and ``predict`` gives the
 filtered top-k answers of (head, relation, time) queries (rg_topk).  The validation loop of main.py:125-183 is ``evaluate`` /
 ``rank_batch`` (evaluation.py, rg_segment_eval): loss, raw and filtered ranks from the visited pairs, without the [B, n_ent] matrix.
 Training: ``mode='train'`` drops the batch's own quadruples (``batch['example_idx']`` rows of ``params.graph``,
@@ -138,6 +139,24 @@ class T_RED_GNN(nn.Module):
             t = self.rules({"head": part[:, 0], "relation": part[:, 1], "time": part[:, 3]}, part[:, 2], k=k)
             table = t if table is None else table + t
         return table
+
+    def fidelity(self, batch, objs=None, k=4, inverse_offset=None):
+        """How much of each answer's score its best paths carry, as RED_GNN_trans.fidelity: one explain, one top_paths(k) and 2k
+        RDigraph.rescore calls (rg_digraph_tlayer_fwd per hop, no graph rebuild) - the answers re-scored without the quadruples of the
+        row's best j paths (``without``) and with those quadruples and the identity edges alone (``only``), j = 1..k: an
+        explain.Fidelity.  objs=None: batch["tail"] where the batch has it, else the model's own top answer per row, as rules.
+        ``inverse_offset`` = m: a quadruple is deleted together with its inverse twin (t, r + m if r < m else r - m, h, time id), the
+        way the data wrote its inverses (m = the number of base relations for the reference's loaders); None: only the quadruples
+        the paths step over."""
+        from . import explain as _explain
+        return _explain.temporal_fidelity(self, batch, objs, k, inverse_offset)
+
+    def fidelity_all(self, quads, k=4, batch_size=64, inverse_offset=None):
+        """fidelity over ``quads`` int [n, 4] = (head, rel, tail, time id), each row a query with its tail as the answer, walked in
+        batches of ``batch_size`` rows: the dict BaseModel.fidelity returns (n, k, necessity_mean / _median, sufficiency_gap_mean /
+        _median, disconnected, each a list over j = 1..k)."""
+        from . import explain as _explain
+        return _explain.temporal_fidelity_all(self, quads, k, batch_size, inverse_offset)
 
     def rule_quality(self, table, anchors=None, scratch_bytes=engine.RULE_SCRATCH_BYTES):
         """How the rules of ``table`` (an explain.TemporalRuleTable) hold in the full quadruple graph, the one explain walks:
