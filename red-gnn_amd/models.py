@@ -142,8 +142,8 @@ class _DenseStep(torch.autograd.Function):
     def forward(ctx, agg, hidden_prev, W_h, w_ih, w_hh, b_ih, b_hh, Ws_next, prev_idx, old_new, mask, act, gate, keep):
         """Ws_next: the NEXT layer's Ws_attn.weight [attn, d] or None.  With it the kernel also emits a_s = hidden_new Ws_next^T
         (the hoisted attention projection, as the inference kernel does) and the step returns (hidden_new, a_s [n, ap])."""
-        agg, hidden_prev = agg.contiguous(), hidden_prev.contiguous()
-        hidden, x, ws, a_s = engine.dense_train_fwd(agg, hidden_prev, prev_idx, W_h, act, gate, mask, Ws_next)
+        agg, hidden_prev = agg.contiguous(), hidden_prev.contiguous()      # (no old row: nothing to gather, the kernel gets prev_idx = NULL)
+        hidden, x, ws, a_s = engine.dense_train_fwd(agg, hidden_prev, prev_idx if hidden_prev.shape[0] else None, W_h, act, gate, mask, Ws_next)
         none = agg.new_zeros(0)
         ctx.save_for_backward(agg, x, ws, W_h, w_ih, w_hh, old_new, mask if mask is not None else none,
                               Ws_next if Ws_next is not None else none, hidden if Ws_next is not None else none)

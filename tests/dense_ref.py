@@ -14,6 +14,9 @@ rg_dense_train_bwd / _bwd2, rg_rows_addmm and rg_attn_tables), plus the case tab
                dx = dgi W_ih;  dh0 = g z + dgh W_hh;  dpre = dx * mask * act'(.);  dagg = dpre W_h
                    act' : 1 | 1[x > 0] | 1 - y^2 with y = x * keep under a mask (x = tanh(pre) / keep where kept), y = x without
                grad_prev[prev_idx[m]] = dh0[m] for prev_idx[m] >= 0  (prev_idx NULL: grad_prev = dh0)
+               weight gradients (``backward`` given agg; what models._DenseStep.backward returns besides dagg and grad_prev):
+               grad_W_h = dpre^T agg;  grad_w_ih = dgi^T x;  grad_w_hh = dgh^T h0;  grad_b_ih = dgi.sum(0);  grad_b_hh = dgh.sum(0)
+               with Ws_next: grad_Ws = g_as[:, :a]^T hidden, and g above = grad_hidden + g_as[:, :a] Ws_next (returned as grad_hidden)
     rows_addmm out = base + g[:, :k] W          attn_tables a_r = rela Wr^T, a_q = rela[q_rel] Wqr^T + bqr, rela padded to ld columns
 
 Every function takes ``dtype``: np.float64 is the reference; np.float32 (the same code, the same order) is the yardstick of what a
@@ -37,6 +40,13 @@ n0 (``N0_STEP`` = 12) is the elementwise work between the sums of the step that 
 12.  The two row-wise products have n0 = 1 (the final add).  ``C_BOUND`` / ``C_BOUND_ROWS`` below are 4 x the worst ratio
 |ref32 - ref64| / ((n + n0) u S) measured over every element of every output of every case of the table (test_dense_ref.py keeps
 that measurement honest: it fails if a case exceeds REF32_WORST_RATIO / REF32_WORST_RATIO_ROWS).
+
+The weight gradients are sums over the node rows.  Their fp32 evaluation sums in the shape of rg_gram_tn (tests/gram_ref.py: waves of
+rows_per_wave rows, four chains of 256 partials), their n is the n of the summed quantity (3 d for dpre, 0 for dgi / dgh; a + 1 more
+throughout when g itself is the sum grad_hidden + g_as Ws_next) plus the longest chain of that shape (gram_ref.n_terms: rows_per_wave
++ 256 + 3 for a product, 4 more for a column sum), and their S is the same product over the S of the summed quantity.  The same n
+serves the routes that form these sums with a library GEMM (fewer than 32768 rows, d = 128).  ``REF32_WORST_RATIO_WGRAD`` /
+``C_BOUND_WGRAD`` are their own constants, measured over ROUTE_CASES.
 """
 import types
 
@@ -56,10 +66,17 @@ C_BOUND = 4.0 * REF32_WORST_RATIO
 C_BOUND_ROWS = 4.0 * REF32_WORST_RATIO_ROWS
 N0_STEP = 12
 N0_ROWS = 1
+# measured: max over ROUTE_CASES, the WGRAD_OUTPUTS and their elements of |ref32 - ref64| / ((n + n0) u S), rounded up
+# (test_dense_ref.py::test_fp32_weight_gradients_within_their_bound prints the per-case figures; the worst: bwd2_d64_as16's grad_Ws
+# 0.00047, aten_d128's grad_w_ih 0.00040).  Three orders below REF32_WORST_RATIO: over a chain of ~355 additions the roundings mostly
+# cancel, where a dgi entry is five products in a row against n = 0
+REF32_WORST_RATIO_WGRAD = 0.0005
+C_BOUND_WGRAD = 4.0 * REF32_WORST_RATIO_WGRAD
 
 ACT = {"idd": 0, "relu": 1, "tanh": 2}
 FWD_OUTPUTS = ("hidden", "x", "ws", "a_s")
 BWD_OUTPUTS = ("dgi", "dgh", "dgh_n", "dpre", "dagg", "dh0", "grad_prev")
+WGRAD_OUTPUTS = ("grad_W_h", "grad_w_ih", "grad_w_hh", "grad_b_ih", "grad_b_hh", "grad_Ws")
 
 
 def bound(S, n, n0, c):
@@ -231,17 +248,52 @@ def _scatter_prev(dh0, prev_idx, n_old):
     return out
 
 
-def backward(grad_hidden, ws, x, mask, keep, act, W_h, w_ih, w_hh, prev_idx=None, n_old=0, dtype=np.float64, fault=None):
+def _cat_order(t, d):
+    """fault: the hidden-side blocks assembled as (n, r, z) instead of (r, z, n) (negative tests only)."""
+    return np.concatenate([t[2 * d:], t[:2 * d]], 0)
+
+
+def backward(grad_hidden, ws, x, mask, keep, act, W_h, w_ih, w_hh, prev_idx=None, n_old=0, dtype=np.float64, fault=None, agg=None,
+             g_as=None, Ws_next=None, hidden=None):
     """dgi, dgh [n, 3d], dgh_n, dpre, dagg, dh0 [n, d], grad_prev [n_old, d] (prev_idx NULL: = dh0) in ``dtype``; .S / .n per output name
-    (include/redgnn.h, rg_dense_train_bwd / rg_dense_train_bwd2).  ws / x are the SAVED forward outputs, taken as given."""
+    (include/redgnn.h, rg_dense_train_bwd / rg_dense_train_bwd2).  ws / x are the SAVED forward outputs, taken as given.
+    With ``agg`` also the weight gradients grad_W_h [d, d], grad_w_ih, grad_w_hh [3d, d], grad_b_ih, grad_b_hh [3d]; with ``Ws_next``
+    [a, d], ``g_as`` [n, >= a] and the saved ``hidden`` also grad_Ws [a, d], and everything else from the effective
+    grad_hidden = grad_hidden + g_as[:, :a] Ws_next (models._DenseStep.backward)."""
+    from tests import gram_ref      # imports this module: not at the top
     act = ACT.get(act, act)
     keep = float(np.float32(keep))      # the kernels take keep as a C float
-    args = (grad_hidden, ws, x, mask, keep, act, W_h, w_ih, w_hh)
-    v = _bwd_values(np.dtype(dtype), *args, absolute=False, fault=fault)
-    S = _bwd_values(np.dtype(np.float64), *args, absolute=True)
+    dt = np.dtype(dtype)
+    g, S_g, extra = _c(dt, grad_hidden), np.abs(np.asarray(grad_hidden, np.float64)), 0
+    if Ws_next is not None:
+        a = np.shape(Ws_next)[0]
+        g = g + _c(dt, g_as)[:, :a] @ _c(dt, Ws_next)
+        S_g = S_g + np.abs(np.asarray(g_as, np.float64)[:, :a]) @ np.abs(np.asarray(Ws_next, np.float64))
+        extra = a + 1
+    args = (ws, x, mask, keep, act, W_h, w_ih, w_hh)
+    v = _bwd_values(dt, g, *args, absolute=False, fault=fault)
+    S = _bwd_values(np.dtype(np.float64), S_g, *args, absolute=True)
     d = np.shape(x)[1]
     n = dict(dgi=0, dgh=0, dgh_n=0, dpre=3 * d, dagg=4 * d, dh0=3 * d + 1, grad_prev=3 * d + 1)
+    n = {k: t + extra for k, t in n.items()}
     v["grad_prev"], S["grad_prev"] = _scatter_prev(v["dh0"], prev_idx, n_old), _scatter_prev(S["dh0"], prev_idx, n_old)
+    v["grad_hidden"], S["grad_hidden"], n["grad_hidden"] = g, S_g, extra
+    if agg is not None:
+        rows = np.shape(x)[0]
+        h0 = np.asarray(ws).reshape(rows, 5, d)[:, 3]
+        n_out, n_cs = gram_ref.n_terms(rows)
+        absolute = lambda t: np.abs(np.asarray(t, np.float64))
+        prods = [("grad_W_h", "dpre", agg, None), ("grad_w_ih", "dgi", x, "grad_b_ih"), ("grad_w_hh", "dgh", h0, "grad_b_hh")]
+        for name, left, right, bias in prods:
+            r = gram_ref.gram(v[left], _c(dt, right), dt)
+            v[name], S[name], n[name] = r.out, S[left].T @ absolute(right), n[left] + n_out
+            if bias:
+                v[bias], S[bias], n[bias] = r.colsum, S[left].sum(0), n[left] + n_cs
+        if Ws_next is not None:
+            v["grad_Ws"] = gram_ref.gram(_c(dt, g_as)[:, :a], _c(dt, hidden), dt).out
+            S["grad_Ws"], n["grad_Ws"] = absolute(g_as)[:, :a].T @ absolute(hidden), n_out
+        if fault == "cat_order":
+            v["grad_w_hh"], v["grad_b_hh"] = _cat_order(v["grad_w_hh"], d), _cat_order(v["grad_b_hh"], d)
     return types.SimpleNamespace(S=S, n=n, **v)
 
 
@@ -363,7 +415,7 @@ def inputs(case):
     """Seeded random inputs of a case: dict of float32 arrays (prev_idx int32, q_rel int64) in the kernels' layouts."""
     rng = np.random.default_rng(500 + case.seed)
     f = lambda *shape, scale=1.0: (rng.standard_normal(shape) * scale).astype(np.float32)
-    if case.kind == "step":
+    if case.kind in ("step", "route"):
         d, n = case.d, case.n
         prev_idx, n_old = _prev(rng, case.prev, n)
         x = dict(agg=f(n, d), prev_idx=prev_idx, n_old=n_old,
@@ -372,6 +424,8 @@ def inputs(case):
                  b_ih=f(3 * d, scale=0.3), b_hh=f(3 * d, scale=0.3),
                  mask=((rng.random((n, d)) < case.keep) / np.float32(case.keep)).astype(np.float32) if case.masked else None,
                  Ws_next=f(case.attn_dim, d, scale=d ** -0.5) if case.attn_dim else None, grad_hidden=f(n, d))
+        if case.kind == "route" and case.attn_dim:
+            x["g_as"] = f(n, case.ap)      # the pad columns attn_dim .. ap - 1 carry values too: nothing may read them
         return x
     if case.kind == "addmm":
         return dict(base=f(case.n_rows, case.base_width), g=f(case.n_rows, case.g_width), W=f(case.k, case.cols, scale=case.k ** -0.5))
@@ -398,6 +452,48 @@ def saved(case, x):
 def step_backward(case, x, x_saved, ws_saved, dtype=np.float64, fault=None):
     return backward(x["grad_hidden"], ws_saved, x_saved, x["mask"], case.keep, case.act, x["W_h"], x["w_ih"], x["w_hh"], x["prev_idx"],
                     x["n_old"], dtype=dtype, fault=fault)
+
+
+# ---- the routes of models._DenseStep.backward -------------------------------------------------------------------------------------------
+# One entry per route and width; ``why`` cites the line of red-gnn_amd/models.py the case selects.  A route case runs
+# models._DenseStep.apply forward and backward and checks every gradient it returns against ``backward`` (with agg) on the x / ws the
+# step saved.  Rows: no more than the routing thresholds need (_FUSED_BWD_ROWS = 8192, _TALL_ROWS = 32768).
+def _route(name, d, n, act="relu", masked=False, prev="third", attn_dim=0, seed=0, why=""):
+    c = _step(name, d, n, act, masked, prev, attn_dim, seed, why)
+    c.kind = "route"
+    return c
+
+
+_ROT = [("relu", True), ("tanh", False), ("idd", True), ("relu", False), ("tanh", True), ("idd", False)]      # act, mask over the widths
+_BWD2 = "models.py:166 n >= _TALL_ROWS with old rows -> rg_dense_train_bwd2; models.py:172-174 engine.gram_tn: "
+_ROUTE_LIST = (
+    [_route("bwd2_d%d" % d, d, 32768, *_ROT[i % 6], prev="third", seed=60 + i,
+            why=_BWD2 + "dgi^T x (m = %d), dgi[:, :2d]^T h0 (m = %d, h0 the ws.view(n, 5, d)[:, 3] view), dgh_n^T h0, dpre^T agg (m = n = %d); "
+            "models.py:175 torch.cat([g_rz, g_n]) / ([db_rz, db_n])" % (3 * d, 2 * d, d)) for i, d in enumerate(range(16, 65, 4))]
+    + [_route("bwd2_d%d_as%d" % (d, a), d, 32768, *_ROT[(i + a) % 6], prev="third", attn_dim=a, seed=80 + 2 * i + (a == 16),
+              why=_BWD2 + "with Ws_next: models.py:164 _gram_tn(g_as[:, :a], hidden) -> models.py:68 engine.gram_tn (m = %d, ldg = %d) and "
+              "models.py:165 engine.rows_addmm" % (a, (a + 3) // 4 * 4)) for i, d in enumerate((20, 48, 64)) for a in (5, 16)]
+    + [_route("bwd_d%d" % d, d, 32768, *_ROT[(i + 2) % 6], prev="none", seed=90 + i,
+              why="models.py:166 n_old = 0 -> not bwd2; models.py:176 rg_dense_train_bwd; models.py:180-182 n >= _TALL_ROWS: engine.gram_tn(dgi, x), "
+              "(dgh, h0) with colsum, (dpre, agg)") for i, d in enumerate((16, 36, 64))]
+    + [_route("sums_n8192", 32, 8192, "tanh", True, "third", seed=95,
+              why="models.py:176 n >= _FUSED_BWD_ROWS -> rg_dense_train_bwd; models.py:185 dgi.sum(0) / dgh.sum(0); models.py:201-202 _gram_tn -> "
+              "models.py:66 g.t() @ x below _TALL_ROWS"),
+       _route("sums_n32767", 32, 32767, "relu", True, "third", seed=96, why="the same one row below models.py:180 _TALL_ROWS"),
+       _route("aten_n8191", 32, 8191, "tanh", True, "third", seed=97,
+              why="models.py:176 one row below _FUSED_BWD_ROWS -> models.py:187 aten's GRU-cell backward, three GEMMs; models.py:201-202"),
+       _route("aten_d128", 128, 32768, "relu", True, "third", seed=98,
+              why="models.py:176 dense_train_bwd_supported(128) false -> models.py:187 aten; models.py:201-202 _gram_tn -> models.py:68 engine.gram_tn "
+              "tiled 384 x 128 (engine.py:743)")]
+)
+ROUTE_CASES = {c.name: c for c in _ROUTE_LIST}
+
+
+def route_backward(case, x, x_saved, ws_saved, hidden_saved=None, dtype=np.float64, fault=None):
+    """``backward`` with the weight gradients on what a route case's step saved."""
+    extra = dict(g_as=x["g_as"], Ws_next=x["Ws_next"], hidden=hidden_saved) if case.attn_dim else {}
+    return backward(x["grad_hidden"], ws_saved, x_saved, x["mask"], case.keep, case.act, x["W_h"], x["w_ih"], x["w_hh"], x["prev_idx"],
+                    x["n_old"], dtype=dtype, fault=fault, agg=x["agg"], **extra)
 
 
 # ---- the inference contract (rg_dense_fwd / rg_dense_fwd_dev, precisions 0, 1, 2) ------------------------------------------------------

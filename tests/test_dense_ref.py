@@ -73,7 +73,8 @@ def _torch_step(case, x, mask64):
     ng = torch.tanh(gi[:, 2 * d:] + r * gh[:, 2 * d:])
     hidden = (1 - z) * ng + z * h0
     cell = torch.gru_cell(xx, h0, w_ih, w_hh, b_ih, b_hh)
-    return dict(agg=agg, hp=hp, h0=h0, pre=pre, x=xx, gi=gi, gh=gh, r=r, z=z, ng=ng, hidden=hidden, cell=cell)
+    return dict(agg=agg, hp=hp, h0=h0, pre=pre, x=xx, gi=gi, gh=gh, r=r, z=z, ng=ng, hidden=hidden, cell=cell, W_h=W_h, w_ih=w_ih, w_hh=w_hh,
+                b_ih=b_ih, b_hh=b_hh)
 
 
 @pytest.mark.parametrize("name", ["d20_tanh_mask", "d36_relu_mask", "d32_idd", "d48_tanh", "n17", "as5", "n1"])
@@ -120,6 +121,116 @@ def test_reference_equals_torch(name):
         assert np.array_equal(b.grad_prev[p[p >= 0]], b.dh0[p >= 0]) and b.grad_prev.shape == (x["n_old"], d)
     else:
         assert b.grad_prev.shape == (0, d)
+
+
+@pytest.mark.parametrize("name", ["d20_tanh_mask", "d36_relu_mask", "d32_idd", "n17", "as5", "as16"])
+def test_weight_gradients_equal_torch(name):
+    """backward given agg (and Ws_next) == autograd of the same step in fp64 for every weight and bias gradient models._DenseStep returns,
+    the projection's included: loss = <hidden, g> + <hidden Ws_next^T, g_as[:, :a]>; the pad columns of g_as carry values and change
+    nothing."""
+    case = dr.CASES[name]
+    x = dr.inputs(case)
+    d, a = case.d, case.attn_dim
+    mask64 = None if x["mask"] is None else (x["mask"] > 0) / 0.75
+    case = types.SimpleNamespace(**dict(vars(case), keep=0.75))
+    x = dict(x, mask=mask64)
+    T = _torch_step(case, x, mask64)
+    loss = (T["hidden"] * torch.as_tensor(np.asarray(x["grad_hidden"], np.float64))).sum()
+    extra = {}
+    if a:
+        g_as = np.random.default_rng(3).standard_normal((case.n, case.ap))
+        Ws = torch.tensor(np.asarray(x["Ws_next"], np.float64), requires_grad=True)
+        loss = loss + ((T["hidden"] @ Ws.T) * torch.as_tensor(g_as[:, :a])).sum()
+        extra = dict(g_as=g_as, Ws_next=x["Ws_next"], hidden=T["hidden"].detach().numpy())
+    loss.backward()
+    f = dr.step_forward(case, x)
+    b = dr.backward(x["grad_hidden"], f.ws.reshape(case.n, 5 * d), f.x, mask64, case.keep, case.act, x["W_h"], x["w_ih"], x["w_hh"], x["prev_idx"],
+                    x["n_old"], agg=x["agg"], **extra)
+    tol = dict(rtol=1e-10, atol=1e-11)
+    for k in ("W_h", "w_ih", "w_hh", "b_ih", "b_hh"):
+        np.testing.assert_allclose(getattr(b, "grad_" + k), T[k].grad.numpy(), err_msg=k, **tol)
+        assert (b.S["grad_" + k] >= np.abs(getattr(b, "grad_" + k)) * (1 - 1e-12)).all()
+    np.testing.assert_allclose(b.dagg, T["agg"].grad.numpy(), **tol)
+    n_out, n_cs = 96 + 256 + 3, 96 + 256 + 3 + 4
+    if a:
+        np.testing.assert_allclose(b.grad_Ws, Ws.grad.numpy(), **tol)
+        np.testing.assert_allclose(b.grad_hidden, np.asarray(x["grad_hidden"], np.float64) + g_as[:, :a] @ np.asarray(x["Ws_next"], np.float64), **tol)
+        assert b.n["grad_Ws"] == n_out and b.n["dgi"] == a + 1 and b.n["dagg"] == 4 * d + a + 1 and b.n["grad_w_ih"] == a + 1 + n_out
+    else:
+        assert not hasattr(b, "grad_Ws") and b.n["grad_w_ih"] == b.n["grad_w_hh"] == n_out and b.n["grad_b_ih"] == b.n["grad_b_hh"] == n_cs
+        assert b.n["grad_W_h"] == 3 * d + n_out and b.n["dgi"] == 0
+    # without agg the function is what it was
+    plain = dr.step_backward(case, x, f.x, f.ws.reshape(case.n, 5 * d))
+    assert not hasattr(plain, "grad_W_h") and (a or np.array_equal(plain.dagg, b.dagg))
+
+
+@functools.lru_cache(maxsize=None)
+def _route_ratios(name, fault=None):
+    """Per output: (worst ratio of the fp32 evaluation, share of its elements beyond the GPU's bound) on a route case, fed the fp64
+    forward's x / ws / hidden rounded once."""
+    case = dr.ROUTE_CASES[name]
+    x = dr.inputs(case)
+    f = dr.step_forward(case, x)
+    xs, ws, hs = f.x.astype(np.float32), f.ws.astype(np.float32).reshape(case.n, 5 * case.d), f.hidden.astype(np.float32)
+    b64, b32 = dr.route_backward(case, x, xs, ws, hs), dr.route_backward(case, x, xs, ws, hs, dtype=np.float32, fault=fault)
+    r = {}
+    for o in dr.WGRAD_OUTPUTS + ("dagg", "grad_prev", "grad_hidden"):
+        if hasattr(b64, o):
+            assert getattr(b32, o).dtype == np.float32 and getattr(b32, o).shape == getattr(b64, o).shape
+            c = dr.C_BOUND_WGRAD if o in dr.WGRAD_OUTPUTS else dr.C_BOUND
+            beyond = np.abs(getattr(b32, o).astype(np.float64) - getattr(b64, o)) > dr.bound(b64.S[o], b64.n[o], dr.N0_STEP, c)
+            r[o] = (dr.worst_ratio(getattr(b32, o), getattr(b64, o), b64.S[o], b64.n[o], dr.N0_STEP), float(beyond.mean()) if beyond.size else 0.0)
+    return r
+
+
+@pytest.mark.parametrize("name", list(dr.ROUTE_CASES))
+def test_fp32_weight_gradients_within_their_bound(name):
+    """The weight and bias gradients evaluated in np.float32 - dgi / dgh / dpre in fp32, summed over the rows in rg_gram_tn's shape -
+    against fp64 on every route case: the ratio stays below REF32_WORST_RATIO_WGRAD for every element (the GPU is allowed 4 x that);
+    the row gradients of the same evaluation stay below REF32_WORST_RATIO, also where g itself is a sum (Ws_next).  Prints the ratios."""
+    r = _route_ratios(name)
+    print("%s: %s" % (name, " ".join("%s=%.3g" % (o, v[0]) for o, v in r.items())))
+    assert ("grad_Ws" in r) == bool(dr.ROUTE_CASES[name].attn_dim) and set(dr.WGRAD_OUTPUTS[:5]) <= set(r)
+    for o, (v, _) in r.items():
+        assert v <= (dr.REF32_WORST_RATIO_WGRAD if o in dr.WGRAD_OUTPUTS else dr.REF32_WORST_RATIO), (name, o, v)
+
+
+def test_recorded_weight_gradient_ratio_is_the_measured_one():
+    """REF32_WORST_RATIO_WGRAD is the worst figure of the route table rounded up (bwd2_d64_as16's grad_Ws), within 1.25 x."""
+    worst = max(v[0] for o, v in _route_ratios("bwd2_d64_as16").items() if o in dr.WGRAD_OUTPUTS)
+    assert worst <= dr.REF32_WORST_RATIO_WGRAD <= 1.25 * worst and dr.C_BOUND_WGRAD == 4.0 * dr.REF32_WORST_RATIO_WGRAD, worst
+
+
+@pytest.mark.parametrize("name", ["bwd2_d16", "bwd2_d20_as5", "bwd_d36"])
+def test_bound_rejects_a_wrong_block_order(name):
+    """grad_w_hh and grad_b_hh assembled as (n, r, z) blocks instead of (r, z, n) - torch.cat([g_n, g_rz]) in models.py:175 - fail the
+    GPU's bound on most of their elements; every other gradient still passes."""
+    r = _route_ratios(name, fault="cat_order")
+    for o, (_, beyond) in r.items():
+        if o in ("grad_w_hh", "grad_b_hh"):
+            assert beyond > (0.5 if o == "grad_b_hh" or dr.ROUTE_CASES[name].prev != "none" else -1), (o, beyond)
+        else:
+            assert beyond == 0.0, (o, beyond)
+
+
+def test_route_table_covers_what_it_names():
+    C = list(dr.ROUTE_CASES.values())
+    assert all(c.kind == "route" and c.why and "models.py:" in c.why for c in C) and not set(dr.ROUTE_CASES) & set(dr.CASES)
+    bwd2 = [c for c in C if c.name.startswith("bwd2_")]
+    assert {c.d for c in bwd2 if not c.attn_dim} == set(range(16, 65, 4)) and all(c.n == 32768 and c.prev == "third" for c in bwd2)
+    assert {(c.d, c.attn_dim) for c in bwd2 if c.attn_dim} == {(d, a) for d in (20, 48, 64) for a in (5, 16)}
+    assert {c.act for c in bwd2} == {0, 1, 2} and {c.masked for c in bwd2} == {True, False}
+    assert {(c.d, c.n, c.prev) for c in C if c.name.startswith("bwd_")} == {(d, 32768, "none") for d in (16, 36, 64)}
+    assert {(c.name, c.d, c.n) for c in C if not c.name.startswith("bwd")} == {("sums_n8192", 32, 8192), ("sums_n32767", 32, 32767),
+                                                                               ("aten_n8191", 32, 8191), ("aten_d128", 128, 32768)}
+    why = " ".join(c.why for c in C)      # the four places of _DenseStep.backward that reach engine.gram_tn
+    for line in ("models.py:164", "models.py:172-174", "models.py:180-182", "models.py:201-202", "models.py:68", "models.py:175", "models.py:185",
+                 "models.py:187"):
+        assert line in why, line
+    x = dr.inputs(dr.ROUTE_CASES["bwd2_d20_as5"])
+    assert x["g_as"].shape == (32768, 8) and np.abs(x["g_as"][:, 5:]).min() > 0 and x["n_old"] == (32768 + 2) // 3
+    x = dr.inputs(dr.ROUTE_CASES["bwd_d16"])
+    assert x["n_old"] == 0 and (x["prev_idx"] == -1).all()
 
 
 def test_rows_products_against_numpy():
