@@ -477,6 +477,59 @@ int rg_digraph_tlayer_fwd(int32_t n_dst, int64_t n_edges, const int32_t* dst_ptr
                           const float* w_alpha, const float* b_alpha, int32_t attn_dim, float* agg_out, float* alpha_out, void* scratch,
                           size_t scratch_bytes, void* stream);
 
+/* ---- the per-hop index of an edited r-digraph: the arrays rg_digraph_(t)layer_fwd takes, built from the digraph's own edge list
+ * under a keep mask (csrc/digraph_index.hip; explain.RDigraph.rescore of an extrapolation digraph).  edges int32 [n_edges, 5] =
+ * (row, hop, head, rel, tail) ordered by (row, hop, tail) and offsets int64 [batch + 1] (start at 0, never decrease, end at n_edges:
+ * the caller checks that) are DEVICE arrays, as explain returns them; n_edges < 2^31, n_hops in 1..32.
+ *
+ * rg_digraph_hop_ranges, once per digraph: hop_ptr_out int64 [batch, n_hops + 1] (device), entry (b, l - 1) the first edge of row b
+ * with hop >= l and entry (b, n_hops) offsets[b + 1]: one thread per (row, hop), a binary search inside the row's range.  The call
+ * waits for the array, copies it to hop_ptr_host (host, same shape) and forms per hop the exclusive scan over the rows of the
+ * segment lengths: hop_first_out int32 [n_hops, batch + 1] (device) and hop_edges_host int64 [n_hops] = E_l, the edges of every
+ * hop.  Item i of hop l is then edge hop_ptr[b][l - 1] + i - hop_first[l - 1][b] of the row b with hop_first[l - 1][b] <= i <
+ * hop_first[l - 1][b + 1].  *status_host: RG_DIGRAPH_INDEX_ROW_HOP when a row's first edge has a hop below 1.  batch == 0 launches
+ * nothing.
+ *
+ * rg_digraph_hop_index, per hop l = `hop`: hop_ptr the array above, hop_first the hop's row of hop_first_out, n_hop_edges = E_l;
+ * keep uint8 [n_edges] or NULL (every edge kept); keys_prev int64 [n_prev], sorted and unique, row * n_ent + entity: the nodes one
+ * hop down (hop 0: (b, q_sub[b])).  An edge is live iff it is kept, has hop l and its (row, head) is in keys_prev.  Outputs, device
+ * arrays the caller owns, sized for E_l (dst_ptr_out for E_l + 1), of which the first n_live / n_dst (+ 1) entries are written:
+ *   at_out int32 [n_live]    the live edges' indices, ascending
+ *   src_out int32 [n_live]   the position of (row, head) in keys_prev
+ *   rel_out int32 [n_live], time_out int32 [n_live] = edge_time[at] (edge_time int32 [n_edges]; both NULL: no times)
+ *   keys_out int64 [n_dst]   the hop's nodes, the distinct row * n_ent + tail of the live edges, ascending
+ *   dst_ptr_out int32 [n_dst + 1]  the CSR of the live edges by node;  row_of_out int32 [n_dst];  prev_idx_out int32 [n_dst] the
+ *                            node's position in keys_prev, -1 where it is new
+ *   live uint8 [n_edges]     live[at] = 1, every other byte left as it was
+ * exactly what explain._hop_index forms in torch for the same inputs.  One thread per edge of the hop flags and searches,
+ * rg::scan_exclusive compacts, the node starts are the places where the compacted list's key changes, a second scan numbers them.
+ * *n_live_host, *n_dst_host and *status_host come back in one copy (the call waits for it); status is an OR of
+ *   RG_DIGRAPH_INDEX_ORDER      a row's hop-l tails decrease
+ *   RG_DIGRAPH_INDEX_TWO_TAILS  hop == n_hops and a row has two nodes
+ *   RG_DIGRAPH_INDEX_ROW_HOP    an edge's row is not the row of its range, or its hop is not l
+ *   RG_DIGRAPH_INDEX_ENTITY     a head or tail outside 0..n_ent-1
+ *   RG_DIGRAPH_INDEX_RELATION   a relation outside 0..n_rela_rows-1
+ * over EVERY edge of the hop, kept or not; with a non-zero status the outputs are unspecified (but inside their arrays).  Every index
+ * is clamped before it is used as an address: malformed arrays give a status, never a fault.  Integers only; no bit depends on the
+ * launch geometry.  scratch: rg_digraph_hop_index_scratch_bytes(n_hop_edges) bytes, 256-B aligned (0: nothing to do, or E_l >= 2^31).
+ * n_hop_edges == 0 or n_prev == 0 succeeds with n_live = n_dst = 0 and launches nothing.  Every argument error is reported before
+ * anything is enqueued.  Neither call is for stream capture. */
+#define RG_DIGRAPH_INDEX_ORDER 1
+#define RG_DIGRAPH_INDEX_TWO_TAILS 2
+#define RG_DIGRAPH_INDEX_ROW_HOP 4
+#define RG_DIGRAPH_INDEX_ENTITY 8
+#define RG_DIGRAPH_INDEX_RELATION 16
+int rg_digraph_hop_ranges(const int32_t* edges, const int64_t* offsets, int64_t n_edges, int32_t batch, int32_t n_hops,
+                          int64_t* hop_ptr_out, int32_t* hop_first_out, int64_t* hop_ptr_host, int64_t* hop_edges_host,
+                          int32_t* status_host, void* stream);
+size_t rg_digraph_hop_index_scratch_bytes(int64_t n_hop_edges);
+int rg_digraph_hop_index(const int32_t* edges, const uint8_t* keep, const int32_t* edge_time, int64_t n_edges, int32_t batch,
+                         int32_t n_hops, int32_t hop, const int64_t* hop_ptr, const int32_t* hop_first, int64_t n_hop_edges,
+                         const int64_t* keys_prev, int64_t n_prev, int32_t n_ent, int32_t n_rela_rows, int32_t* at_out,
+                         int32_t* src_out, int32_t* rel_out, int32_t* time_out, int64_t* keys_out, int32_t* dst_ptr_out,
+                         int32_t* row_of_out, int32_t* prev_idx_out, uint8_t* live, void* scratch, size_t scratch_bytes,
+                         int64_t* n_live_host, int64_t* n_dst_host, int32_t* status_host, void* stream);
+
 /* ---- rule quality: support and confidence of rules (head h, body r_1..r_L) counted on the whole graph; no counterpart in the
  * reference (its *_rule_vis.py scripts only draw).  The graph is used as built, inverse and identity rows included: for a relation id
  * r in 0..n_rela_rows-1, A_r(x, y) holds iff the graph has at least one row (x, r, y) (a repeated fact counts once), and body(x, y)

@@ -27,6 +27,7 @@ SYMBOLS = [
     "rg_segment_eval",
     "rg_paths_scratch_bytes", "rg_paths_topk",
     "rg_digraph_layer_fwd_scratch_bytes", "rg_digraph_layer_fwd", "rg_digraph_tlayer_fwd",
+    "rg_digraph_hop_ranges", "rg_digraph_hop_index_scratch_bytes", "rg_digraph_hop_index",
     "rg_rule_ground_scratch_bytes", "rg_rule_ground",
     "rg_rule_apply_scratch_bytes", "rg_rule_apply",
     "rg_trule_ground_scratch_bytes", "rg_trule_ground",
@@ -151,6 +152,11 @@ def lib():
                                        vp, sz, vp]
     L.rg_digraph_tlayer_fwd.argtypes = [i32, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, i32,
                                         vp, vp, i32, vp, vp, vp, sz, vp]
+    L.rg_digraph_hop_ranges.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp, vp, C.POINTER(i32), vp]
+    L.rg_digraph_hop_index_scratch_bytes.argtypes = [i64]
+    L.rg_digraph_hop_index_scratch_bytes.restype = sz
+    L.rg_digraph_hop_index.argtypes = [vp, vp, vp, i64, i32, i32, i32, vp, vp, i64, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                       vp, sz, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32), vp]
     L.rg_rule_ground_scratch_bytes.argtypes = [i32, i32, i32]
     L.rg_rule_ground_scratch_bytes.restype = sz
     L.rg_rule_ground.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp, vp, vp]

@@ -1216,7 +1216,123 @@ def _digraph_layer(who, dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s,
     return agg, alpha
 
 
-RULE_MAX_HOPS = 32                   # csrc/rule_bits.h: RULE_MAX_HOPS
+# include/redgnn.h: RG_DIGRAPH_INDEX_*, with the ValueError each status bit becomes ({who}, {L} filled in by digraph_index_error)
+DIGRAPH_INDEX_STATUS = (
+    (4, "{who}: edges hold a row that is not the row of its range in offsets, or hops that are not 1..{L} in order inside a row"),
+    (8, "{who}: edges hold a head or tail out of range (n_ent={n_ent})"),
+    (16, "{who}: edges hold a relation out of range ({n_rela_rows} relation rows)"),
+    (1, "{who}: edges must be ordered by (row, hop, tail), as model.explain returns them"),
+    (2, "{who}: the hop-{L} edges of a row must share their tail, the row's answer"),
+)
+
+DIGRAPH_INDEX_EVENTS = None          # probes: a list that collects (start, end, hop, n_hop_edges) of every digraph_hop_index
+
+
+def digraph_index_error(status, who, L, n_ent, n_rela_rows):
+    """The ValueError of a non-zero status word of digraph_hop_ranges / digraph_hop_index (the first of DIGRAPH_INDEX_STATUS that is set: an edge in the wrong place
+    or out of range comes before what follows from it), or None."""
+    for bit, text in DIGRAPH_INDEX_STATUS:
+        if status & bit:
+            return ValueError(text.format(who=who, L=L, n_ent=n_ent, n_rela_rows=n_rela_rows))
+    return None
+
+
+def _check_digraph_edges(who, edges):
+    if not (torch.is_tensor(edges) and edges.dtype == torch.int32 and edges.dim() == 2 and edges.shape[1] == 5):
+        raise ValueError("%s: edges must be int32 [E, 5]" % who)
+    if edges.shape[0] >= 1 << 31:
+        raise ValueError("%s: %d edges are beyond the kernels' 2^31 edge indices" % (who, edges.shape[0]))
+
+
+class DigraphHopRanges:
+    """digraph_hop_ranges: hop_ptr int64 [B, L + 1] and hop_first int32 [L, B + 1] on the device, hop_ptr_host (numpy, the former's
+    copy), hop_edges (list of L ints: the edges of every hop) and the status word (0: in order)."""
+
+    def __init__(self, hop_ptr, hop_first, hop_ptr_host, hop_edges, status):
+        self.hop_ptr, self.hop_first, self.hop_ptr_host, self.hop_edges, self.status = hop_ptr, hop_first, hop_ptr_host, hop_edges, status
+
+
+def digraph_hop_ranges(edges, offsets, n_hops):
+    """Where every hop of every row of a compact r-digraph lies (rg_digraph_hop_ranges): a DigraphHopRanges.  ``edges`` int32 [E, 5]
+    ordered by (row, hop, tail) and ``offsets`` int64 [B + 1], device tensors (offsets validated by the caller: starting at 0, never
+    decreasing, ending at E).  Once per digraph; every digraph_hop_index call then touches only its hop's edges."""
+    who = "digraph_hop_ranges"
+    _check_digraph_edges(who, edges)
+    if not (torch.is_tensor(offsets) and offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.numel() >= 1):
+        raise ValueError("%s: offsets must be int64 [B + 1]" % who)
+    if isinstance(n_hops, (bool, np.bool_)) or not isinstance(n_hops, (int, np.integer)) or not 1 <= n_hops <= 32:
+        raise ValueError("%s: n_hops must be an integer in 1..32 (got %r)" % (who, n_hops))
+    _require_gpu(edges.device)
+    if not (edges.is_cuda and offsets.is_cuda and edges.is_contiguous() and offsets.is_contiguous() and offsets.device == edges.device):
+        raise ValueError("%s: edges and offsets must be contiguous and on one device" % who)
+    E, B, L, dev = edges.shape[0], offsets.numel() - 1, int(n_hops), edges.device
+    hop_ptr = torch.zeros((B, L + 1), dtype=torch.int64, device=dev)
+    hop_first = torch.zeros((L, B + 1), dtype=torch.int32, device=dev)
+    ptr_h, n_h, status = np.zeros((B, L + 1), np.int64), np.zeros(L, np.int64), C.c_int32(0)
+    p = _lib.ptr
+    _lib.check(_lib.lib().rg_digraph_hop_ranges(p(edges), p(offsets), E, B, L, p(hop_ptr), p(hop_first), p(ptr_h), p(n_h),
+                                                C.byref(status), _lib.stream_ptr()))
+    return DigraphHopRanges(hop_ptr, hop_first, ptr_h, [int(x) for x in n_h], int(status.value))
+
+
+def digraph_hop_index(edges, ranges, hop, keys_prev, n_ent, n_rela_rows, live, keep=None, edge_time=None):
+    """The index of hop ``hop`` of a rescore (rg_digraph_hop_index): (at int32 [n_live], src int32 [n_live], rel int32 [n_live], time
+    int32 [n_live] or None, keys int64 [n_dst], dst_ptr int32 [n_dst + 1], row_of int32 [n_dst], prev_idx int32 [n_dst], status int) -
+    explain._hop_index's arrays for the same inputs, with the relation and the time of every live edge gathered along.  ``ranges``:
+    digraph_hop_ranges of the same edges; ``keys_prev`` int64, sorted and unique, row * n_ent + entity; ``keep`` uint8 [E] or None;
+    ``edge_time`` int32 [E] or None; ``live`` uint8 [E] receives live[at] = 1.  status != 0 (digraph_index_error): the edges of the hop
+    are malformed and the arrays mean nothing.  No live edge: empty arrays, and nothing else of the hop is read back."""
+    who = "digraph_hop_index"
+    if not isinstance(ranges, DigraphHopRanges):
+        raise ValueError("%s: ranges must be digraph_hop_ranges' result" % who)
+    B, L = ranges.hop_ptr.shape[0], ranges.hop_ptr.shape[1] - 1
+    _check_digraph_edges(who, edges)
+    if isinstance(hop, (bool, np.bool_)) or not isinstance(hop, (int, np.integer)) or not 1 <= hop <= L:
+        raise ValueError("%s: hop must be an integer in 1..%d (got %r)" % (who, L, hop))
+    for name, x in (("n_ent", n_ent), ("n_rela_rows", n_rela_rows)):
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)) or not 1 <= x < 1 << 31:
+            raise ValueError("%s: %s must be a positive integer (got %r)" % (who, name, x))
+    E, dev = edges.shape[0], edges.device
+    if not (torch.is_tensor(keys_prev) and keys_prev.dtype == torch.int64 and keys_prev.dim() == 1):
+        raise ValueError("%s: keys_prev must be an int64 vector" % who)
+    if not (torch.is_tensor(live) and live.dtype == torch.uint8 and live.shape == (E,)):
+        raise ValueError("%s: live must be uint8 [%d], one per edge" % (who, E))
+    if keep is not None and not (torch.is_tensor(keep) and keep.dtype == torch.uint8 and keep.shape == (E,)):
+        raise ValueError("%s: keep must be uint8 [%d], one per edge, or None" % (who, E))
+    if edge_time is not None and not (torch.is_tensor(edge_time) and edge_time.dtype == torch.int32 and edge_time.shape == (E,)):
+        raise ValueError("%s: edge_time must be int32 [%d], one per edge, or None" % (who, E))
+    _require_gpu(dev)
+    tensors = [edges, keys_prev, live, ranges.hop_ptr, ranges.hop_first] + [t for t in (keep, edge_time) if t is not None]
+    if not all(t.is_cuda and t.is_contiguous() and t.device == dev for t in tensors):
+        raise ValueError("%s: every tensor must be contiguous and on one device" % who)
+    n_hop = ranges.hop_edges[hop - 1]
+    if n_hop > E:
+        raise ValueError("%s: the ranges are another digraph's (%d edges in hop %d, %d in all)" % (who, n_hop, hop, E))
+    i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
+    at, src, rel, tm = i32(n_hop), i32(n_hop), i32(n_hop), (i32(n_hop) if edge_time is not None else None)
+    keys, dst_ptr, row_of, prev_idx = torch.empty(n_hop, dtype=torch.int64, device=dev), i32(n_hop + 1), i32(n_hop), i32(n_hop)
+    L_, p = _lib.lib(), _lib.ptr
+    nbytes = int(L_.rg_digraph_hop_index_scratch_bytes(n_hop))
+    scratch = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev) if nbytes else None
+    scr_p = None if scratch is None else C.c_void_p((scratch.data_ptr() + 255) // 256 * 256)
+    n_live, n_dst, status = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+    ev = None
+    if DIGRAPH_INDEX_EVENTS is not None:
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        ev[0].record()
+    _lib.check(L_.rg_digraph_hop_index(p(edges), p(keep), p(edge_time), E, B, L, int(hop), p(ranges.hop_ptr), p(ranges.hop_first[hop - 1]),
+                                       n_hop, p(keys_prev), keys_prev.numel(), int(n_ent), int(n_rela_rows), p(at), p(src), p(rel), p(tm),
+                                       p(keys), p(dst_ptr), p(row_of), p(prev_idx), p(live), scr_p, nbytes, C.byref(n_live),
+                                       C.byref(n_dst), C.byref(status), _lib.stream_ptr()))
+    if ev is not None:
+        ev[1].record()
+        DIGRAPH_INDEX_EVENTS.append((ev[0], ev[1], int(hop), n_hop))
+    nl, nd = int(n_live.value), int(n_dst.value)
+    return (at[:nl], src[:nl], rel[:nl], None if tm is None else tm[:nl], keys[:nd], dst_ptr[:nd + 1] if nl else dst_ptr[:0], row_of[:nd],
+            prev_idx[:nd], int(status.value))
+
+
+RULE_MAX_HOPS = 32                  # csrc/rule_bits.h: RULE_MAX_HOPS
 RULE_MAX_RULES = 65535               # ... RULE_MAX_RULES (rules of one call)
 RULE_SCRATCH_BYTES = 1 << 30         # default scratch budget of rule_ground
 # tools/probe_rule_quality.py sets this to a list to collect (start_event, end_event, n_rules, n_sources) per chunk of rule_ground

@@ -27,7 +27,11 @@ forward; ``rd.data_row`` names the past fact behind every edge (-1: a self-loop,
 steps (relation, lag bin) under the ``lag_edges`` of attention_profile with identity steps written as ANY (LagRuleTable), and
 ``model.rule_quality(table)`` counts how they hold in the model's own data per anchor (entity, query day) under the forward's row
 windows (LagRuleQuality; engine.xrule_ground, csrc/xrule_ground.hip); ``model.rule_scores(quality, X)`` / ``rule_predict`` /
-``rule_evaluate`` apply the weighted rules to queries (engine.xrule_apply, csrc/xrule_apply.hip).
+``rule_evaluate`` apply the weighted rules to queries (engine.xrule_apply, csrc/xrule_apply.hip).  ``rd.rescore(model, keep)`` re-scores
+the forecasts on the kept edges with the windows as they were - per hop the index of the live edges built in HIP from the hop's own
+edges (engine.digraph_hop_index, csrc/digraph_index.hip) and one rg_digraph_tlayer_fwd launch in its n_dir = 1 form -, ``rd.fact_mask``
+takes (s, p, o, day), ``rd.data_row_mask`` data rows, and ``model.fidelity(X, objs, k, inverse_offset)`` / ``fidelity_all`` are the static
+model's fidelity.
 """
 from dataclasses import dataclass, fields, replace
 
@@ -58,13 +62,13 @@ class RDigraph:
     data_row int32 [E]     extrapolation only (None otherwise): the edge's index into the model's data array, -1 for a self-loop;
                            there ``time`` is the day the forward used for the edge (the row's day; a self-loop's: the first day of
                            the row's window) and ``q_time`` the query's day
-    q_sub    int64 [B]     static, inductive and temporal interpolation models (None otherwise): the subject s of each row
+    q_sub    int64 [B]     the subject s of each row
     q_rel    int64 [B]     ... and its query relation r; ``rescore`` needs both
-    n_rel    int           ... static and inductive: the KG's relation count (ids >= n_rel are inverses, 2 * n_rel the identity);
+    n_rel    int           static and inductive: the KG's relation count (ids >= n_rel are inverses, 2 * n_rel the identity);
                            temporal interpolation: the model's n_rel, the identity's relation id (the tables have n_rel + 1 rows);
-                           ``fact_mask`` needs it
+                           extrapolation: the model's n_rel_true, the identity's relation id; ``fact_mask`` needs it
     n_time   int           temporal interpolation only (None otherwise): the number of time ids; with it ``rescore`` and ``fact_mask``
-                           take the digraph as a temporal one
+                           take the digraph as a temporal interpolation one, with ``data_row`` and without it as an extrapolation one
     """
     edges: torch.Tensor
     alpha: torch.Tensor
@@ -90,7 +94,18 @@ class RDigraph:
         A temporal interpolation digraph (temporal.T_RED_GNN.explain: ``time``, ``q_time``, ``q_sub``, ``q_rel``, ``n_rel`` and
         ``n_time`` set) is re-scored by the temporal.T_RED_GNN that explained it, one rg_digraph_tlayer_fwd launch per hop with the
         tables T_RED_GNN's forward forms; ``mode`` must be "test" there, the full graph explain walks.  The digraph is checked on the
-        host first (ValueError); extrapolation digraphs, and any other mix of temporal fields and models, are a ValueError."""
+        host first (ValueError); any mix of temporal fields and models is a ValueError.
+
+        An extrapolation digraph (extrapolation.T_RED_GNN.explain: ``data_row``, ``time``, ``q_time``, ``q_sub``, ``q_rel`` and
+        ``n_rel`` set, ``n_time`` None) is re-scored by the extrapolation.T_RED_GNN that explained it, ``mode`` "test": the inference
+        branch of its forward over the kept edges, per hop the index built in HIP from the hop's own edges (rg_digraph_hop_index,
+        csrc/digraph_index.hip; the digraph is validated there, on the device) and one rg_digraph_tlayer_fwd launch in its n_dir = 1
+        form.  No frontier, no window and no [B, n_ent] array: ``time`` already holds the day the forward used for every edge, a
+        self-loop's first window day included.  What it answers is "the forward with these edges absent AND THE WINDOWS AS THEY
+        WERE".  The reference's time_offset_list makes a window start at the last row of day begin - 1 and end before the last row
+        of day cur_t - 1, with offset 0 for days without rows, so deleting rows from the data itself moves window boundaries when a
+        deleted row is the last of its day or a day loses all its rows; the rescore equals the forward of a model rebuilt from the
+        reduced data only for deletions that do neither."""
         return rescore(self, model, keep, mode)
 
     def fact_mask(self, facts, rows=None, inverse_offset=None):
@@ -103,8 +118,19 @@ class RDigraph:
         time) is one of them - every copy of a quadruple the graph holds more than once - and never the identity relation ``n_rel``.
         How a quadruple graph writes inverses belongs to the data, not to the model: with ``inverse_offset`` = m the twin
         (t, r + m if r < m else r - m, h, time id) is marked too (None: the quadruples as given).  A static digraph takes no
-        ``inverse_offset``."""
+        ``inverse_offset``.
+
+        On an extrapolation digraph ``facts`` is int [F, 4] = (s, p, o, day), days not negative: every data-row edge whose (head,
+        rel, tail, ``time``) is one of them is marked - every copy of a row the data hold more than once - and with
+        ``inverse_offset`` = m (2 m <= n_rel) the twin (o, p + m or p - m, s, day) too; a self-loop is never marked.
+        ``data_row_mask`` names a fact by its exact identity, the data row."""
         return fact_mask(self, facts, rows, inverse_offset)
+
+    def data_row_mask(self, data_rows, rows=None):
+        """bool [E]: the edges whose ``data_row`` is one of ``data_rows`` int [F] (not negative; a self-loop has none).  ``rows`` int
+        [F]: entry f counts for the edges of row rows[f] only.  Extrapolation digraphs only: there the data row is the exact
+        identity of a fact."""
+        return data_row_mask(self, data_rows, rows)
 
     def direction(self):
         """int8 [E]: each edge's direction against its row's query time, the temporal forward's convention (dt = edge time - query
@@ -1313,7 +1339,8 @@ def explain_extrapolation(model, X, objs=None, min_alpha=0.0):
         if kept:                                             # an exception must not leave a windowed frontier in the pool
             kept[0]["frontier"].set_window(None, None, 0)
     return RDigraph(edges=edges, alpha=alpha, offsets=offsets, reached=reached, score=score, n_hops=L, time=time.to(torch.int32),
-                    q_time=q_time.clone(), data_row=data_row)
+                    q_time=q_time.clone(), data_row=data_row, q_sub=torch.as_tensor(src, dtype=torch.int64).to(device),
+                    q_rel=kept[0]["q_rel"].clone(), n_rel=int(model.n_rel_true))
 
 
 def _forward_sweep(hops, L, n_ent):
@@ -1394,13 +1421,29 @@ def _check_static_digraph(rd, who):
     return _check_digraph_tensors(rd, who)
 
 
+_X_FIELDS = ("data_row", "time", "q_time", "q_sub", "q_rel", "n_rel")
+
+
+def _is_extrapolation(rd):
+    """The digraph has data rows and no time ids: the extrapolation form (extrapolation.T_RED_GNN.explain)."""
+    return rd.data_row is not None and rd.n_time is None
+
+
 def _check_temporal_fields(rd, who):
-    """A temporal r-digraph is a temporal interpolation one, as temporal.T_RED_GNN.explain returns it: every field rescore and
-    fact_mask read is set and there are no data rows (ValueError naming what is missing).  No tensor is read."""
-    if rd.data_row is not None:
+    """A temporal r-digraph is a temporal interpolation one, as temporal.T_RED_GNN.explain returns it - every field rescore and
+    fact_mask read is set and there are no data rows - or an extrapolation one, as extrapolation.T_RED_GNN.explain returns it: data
+    rows, the fields of _X_FIELDS and no n_time (ValueError naming what is missing); both data_row and n_time is a mix of the two.
+    No tensor is read."""
+    if rd.data_row is not None and rd.n_time is not None:
         raise ValueError("%s: a temporal r-digraph with data_row set is an extrapolation digraph, which is out of scope; temporal "
                          "interpolation (temporal.T_RED_GNN.explain) only" % who)
-    missing = [name for name in ("time", "q_time", "q_sub", "q_rel", "n_rel", "n_time") if getattr(rd, name) is None]
+    if rd.data_row is not None:
+        missing = [name for name in _X_FIELDS if getattr(rd, name) is None]
+        if missing:
+            raise ValueError("%s: an extrapolation r-digraph needs data_row, time, q_time, q_sub, q_rel and n_rel, as "
+                             "extrapolation.T_RED_GNN.explain sets them (missing: %s)" % (who, ", ".join(missing)))
+        return
+    missing =[name for name in ("time", "q_time", "q_sub", "q_rel", "n_rel", "n_time") if getattr(rd, name) is None]
     if missing:
         raise ValueError("%s: a temporal r-digraph needs time, q_time, q_sub, q_rel, n_rel and n_time, as temporal.T_RED_GNN.explain "
                          "sets them (missing: %s)" % (who, ", ".join(missing)))
@@ -1421,6 +1464,23 @@ def _check_temporal_digraph(rd, who):
     for name, x in (("time", t), ("q_time", q)):
         if x.numel() and (int(x.min()) < 0 or int(x.max()) >= rd.n_time):
             raise ValueError("%s: %s holds a time id outside 0..%d" % (who, name, rd.n_time - 1))
+    return E, B
+
+
+def _check_extrapolation_digraph(rd, who):
+    """The host checks of an extrapolation r-digraph: its fields (ValueError naming extrapolation.T_RED_GNN.explain where it is not
+    one), then the tensors' types and shapes; returns (E, B).  Only q_time, one entry per row, is read."""
+    if not _is_extrapolation(rd):
+        raise ValueError("%s: not an extrapolation r-digraph (data_row set and n_time None, as extrapolation.T_RED_GNN.explain returns it)"
+                         % who)
+    _check_temporal_fields(rd, who)
+    E, B = _check_digraph_tensors(rd, who)
+    for name, n, what in (("time", E, "edge"), ("data_row", E, "edge"), ("q_time", B, "row")):
+        t = getattr(rd, name)
+        if not torch.is_tensor(t) or t.dtype != torch.int32 or t.shape != (n,):
+            raise ValueError("%s: %s must be int32 [%d], one per %s" % (who, name, n, what))
+    if B and int(rd.q_time.min()) < 0:
+        raise ValueError("%s: q_time holds a negative day" % who)
     return E, B
 
 
@@ -1448,19 +1508,19 @@ def _check_digraph_tensors(rd, who):
 def fact_mask(rd, facts, rows=None, inverse_offset=None):
     """RDigraph.fact_mask (see there)."""
     who = "fact_mask"
-    timed = _has_times(rd)
-    E, B = _check_temporal_digraph(rd, who) if timed else _check_static_digraph(rd, who)
+    timed, xtr = _has_times(rd), _is_extrapolation(rd)
+    E, B = (_check_extrapolation_digraph if xtr else _check_temporal_digraph)(rd, who) if timed else _check_static_digraph(rd, who)
     dev = rd.edges.device
     f = (facts.detach() if torch.is_tensor(facts) else torch.as_tensor(np.asarray(facts))).to(dev)
     n_rel = int(rd.n_rel)
     if timed:
         if f.is_floating_point() or f.dtype == torch.bool or f.dim() != 2 or f.shape[1] != 4:
-            raise ValueError("%s: on a temporal r-digraph facts must be integers [F, 4] = (h, r, t, time id) (got %s %s)"
-                             % (who, f.dtype, tuple(f.shape)))
+            raise ValueError("%s: on a temporal r-digraph facts must be integers [F, 4] = (h, r, t, %s) (got %s %s)"
+                             % (who, "day" if xtr else "time id", f.dtype, tuple(f.shape)))
         f = f.long()
         if f.shape[0] and (int(f.min()) < 0 or int(f[:, 1].max()) > n_rel):
-            raise ValueError("%s: facts hold a negative id or a relation above n_rel = %d" % (who, n_rel))
-        if f.shape[0] and int(f[:, 3].max()) >= rd.n_time:
+            raise ValueError("%s: facts hold a negative id%s or a relation above n_rel = %d" % (who, " or day" if xtr else "", n_rel))
+        if not xtr and f.shape[0] and int(f[:, 3].max()) >= rd.n_time:
             raise ValueError("%s: facts hold a time id outside 0..%d" % (who, rd.n_time - 1))
         m = inverse_offset
         if m is not None and (isinstance(m, (bool, np.bool_)) or not isinstance(m, (int, np.integer)) or m < 1 or 2 * m > n_rel):
@@ -1490,7 +1550,8 @@ def fact_mask(rd, facts, rows=None, inverse_offset=None):
             return mask
         e = rd.edges.long()
         n_key = int(max(e[:, 2].max(), e[:, 4].max(), f[:, 0].max(), f[:, 2].max())) + 1
-        n_r, n_t = n_rel + 1, int(rd.n_time)
+        # (an extrapolation digraph has days, not time ids: the key takes the largest one at hand)
+        n_r, n_t = n_rel + 1, int(max(rd.time.max(), f[:, 3].max())) + 1 if xtr else int(rd.n_time)
         key = lambda row, h, r, t, tm: (((row * n_key + h) * n_r + r) * n_key + t) * n_t + tm
         f_row = torch.zeros_like(f[:, 0]) if r_of is None else r_of[fact]
         e_row = torch.zeros_like(e[:, 0]) if r_of is None else e[:, 0]
@@ -1498,7 +1559,8 @@ def fact_mask(rd, facts, rows=None, inverse_offset=None):
         if inverse_offset is not None:
             m = int(inverse_offset)
             want = torch.cat([want, key(f_row, f[:, 2], torch.where(f[:, 1] < m, f[:, 1] + m, f[:, 1] - m), f[:, 0], f[:, 3])])
-        return torch.isin(key(e_row, e[:, 2], e[:, 3], e[:, 4], rd.time.long()), want) & (e[:, 3] != n_rel)
+        hit = torch.isin(key(e_row, e[:, 2], e[:, 3], e[:, 4], rd.time.long()), want) & (e[:, 3] != n_rel)
+        return hit & (rd.data_row.to(dev) >= 0) if xtr else hit       # a self-loop has no data row and is never a fact
     fact = f[:, 1] != 2 * n_rel                           # the identity is no fact
     f = f[fact]
     if E == 0 or f.shape[0] == 0:
@@ -1512,6 +1574,30 @@ def fact_mask(rd, facts, rows=None, inverse_offset=None):
     e_row = torch.zeros_like(e[:, 0]) if r_of is None else e[:, 0]
     want = torch.cat([key(f_row, f[:, 0], f[:, 1], f[:, 2]), key(f_row, f[:, 2], inv, f[:, 0])])
     return torch.isin(key(e_row, e[:, 2], e[:, 3], e[:, 4]), want) & (e[:, 3] != 2 * n_rel)
+
+
+def data_row_mask(rd, data_rows, rows=None):
+    """RDigraph.data_row_mask (see there)."""
+    who = "data_row_mask"
+    E, B = _check_extrapolation_digraph(rd, who)
+    dev = rd.edges.device
+    f = (data_rows.detach() if torch.is_tensor(data_rows) else torch.as_tensor(np.asarray(data_rows))).to(dev)
+    if f.is_floating_point() or f.dtype == torch.bool or f.dim() != 1:
+        raise ValueError("%s: data_rows must be integers [F] (got %s %s)" % (who, f.dtype, tuple(f.shape)))
+    f = f.long()
+    if f.numel() and int(f.min()) < 0:
+        raise ValueError("%s: data_rows hold a negative row (a self-loop has no data row)" % who)
+    row_of = rd.data_row.to(dev).long()
+    if rows is None:
+        return torch.isin(row_of, f) & (row_of >= 0)
+    r_of = (rows.detach() if torch.is_tensor(rows) else torch.as_tensor(np.asarray(rows))).to(dev)
+    if r_of.is_floating_point() or r_of.dtype == torch.bool or r_of.shape != (f.shape[0],):
+        raise ValueError("%s: rows must be integers [%d], one per data row (got %s %s)" % (who, f.shape[0], r_of.dtype, tuple(r_of.shape)))
+    r_of = r_of.long()
+    if r_of.numel() and (int(r_of.min()) < 0 or int(r_of.max()) >= B):
+        raise ValueError("%s: rows out of range (the digraph has %d rows)" % (who, B))
+    n_key = int(max(row_of.max() if E else 0, f.max() if f.numel() else 0)) + 1
+    return torch.isin(rd.edges[:, 0].long() * n_key + row_of, r_of * n_key + f) & (row_of >= 0)
 
 
 def _sorted_find(keys, want):
@@ -1633,9 +1719,115 @@ def rescore_temporal(rd, model, keep=None, mode="test"):
     return Rescore(score=score, reached=reached, live=live, alpha=alpha)
 
 
+def rescore_extrapolation(rd, model, keep=None, mode="test"):
+    """RDigraph.rescore of an extrapolation digraph (see there): the inference branch of extrapolation.T_RED_GNN._run over the kept
+    edges, hop by hop, the per-hop index built in HIP (engine.digraph_hop_index)."""
+    import math
+    from .extrapolation import T_RED_GNN as XModel
+    from .temporal import eval_semantics
+    who = "rescore"
+    _check_temporal_fields(rd, who)
+    if not isinstance(model, XModel):
+        raise ValueError("%s: an extrapolation r-digraph (data_row is set, n_time is not) is re-scored by the extrapolation.T_RED_GNN "
+                         "that explained it (got %s)" % (who, type(model).__name__))
+    if mode != "test":
+        raise ValueError("%s: an extrapolation r-digraph is explained by extrapolation.T_RED_GNN on its own data; mode must be 'test' "
+                         "(got %r)" % (who, mode))
+    E, B = _check_extrapolation_digraph(rd, who)
+    for name in ("q_sub", "q_rel"):
+        t = getattr(rd, name)
+        if not torch.is_tensor(t) or t.dtype != torch.int64 or t.shape != (B,):
+            raise ValueError("%s: %s must be int64 [%d], the rows' queries (model.explain sets it)" % (who, name, B))
+    L = int(rd.n_hops)
+    if model.n_layer != L or model.n_rel_true != rd.n_rel:
+        raise ValueError("%s: the extrapolation digraph has n_hops=%d, n_rel=%d, the model n_layer=%d, n_rel=%d"
+                         % (who, L, rd.n_rel, model.n_layer, model.n_rel_true))
+    keep = _check_keep(who, keep, E, rd.edges.device)
+    dev = rd.edges.device
+    tensors = [rd.edges, rd.alpha, rd.offsets, rd.q_sub, rd.q_rel, rd.time, rd.q_time, rd.data_row] + ([keep] if keep is not None else [])
+    if not all(t.is_cuda for t in tensors) or any(t.device != dev for t in tensors):
+        raise ValueError("%s: the layers run in HIP and need the digraph (and keep) on one device (got CPU tensors or mixed devices)" % who)
+    n_ent, n_rows = model.n_ent, model.n_rel + 1                             # rows of the relation tables: n_rel_true + 2
+    if B and (int(rd.q_sub.min()) < 0 or int(rd.q_sub.max()) >= n_ent or int(rd.q_rel.min()) < 0 or int(rd.q_rel.max()) >= rd.n_rel):
+        raise ValueError("%s: q_sub / q_rel out of range (n_ent=%d, n_rel=%d)" % (who, n_ent, rd.n_rel))
+    d, a = model.hidden_dim, model.attn_dim
+    ld, ap = max(16, _pad4(d)), pad_attn(a)
+    padc = lambda t: F.pad(t, (0, ld - d)) if ld != d else t
+    pad_rows = lambda w: F.pad(w, (0, 0, 0, ap - a)) if ap != a else w
+    live = torch.zeros(E, dtype=torch.uint8, device=dev)
+    alpha = torch.zeros(E, dtype=torch.float32, device=dev)
+    score = torch.zeros(B, dtype=torch.float32, device=dev)
+    reached = torch.zeros(B, dtype=torch.bool, device=dev)
+    keep8 = None if keep is None else keep.to(torch.uint8).contiguous()
+    edges, edge_time, q_time = rd.edges.contiguous(), rd.time.contiguous(), rd.q_time.contiguous()
+    bad = lambda status: engine.digraph_index_error(status, who, L, n_ent, n_rows)
+    with torch.no_grad(), eval_semantics(model):
+        lin = engine.rows_linear                                              # the tables of T_RED_GNN._run without gradients
+        w_past = model.past_linear.weight
+        # a lag is at most the query's day (days are not negative), and rows_linear's rows do not depend on the row count: a table
+        # over 0 .. the largest query day holds the forward's rows for every lag of the digraph, without a pass over the edges
+        n_tab = int(q_time.max()) + 1 if B else 1
+        deltas = torch.arange(n_tab, dtype=torch.float32, device=dev)
+        z = 2 * math.pi * model.time_embed.periodic.weight * deltas.view(-1, 1)
+        pos = model.time_embed.linear_pos
+        t_emb = torch.relu(lin(torch.cat([torch.cos(z), torch.sin(z)], -1), pos.weight[0].t(), pos.bias[0]))
+        time_p = padc(lin(t_emb, w_past)).contiguous()
+        zero_b = torch.zeros(1, device=dev)                                   # the attention has no bias
+        ranges = engine.digraph_hop_ranges(edges, rd.offsets.contiguous(), L)
+        if ranges.status:
+            raise bad(ranges.status)
+        keys_prev = torch.arange(B, device=dev) * n_ent + rd.q_sub            # hop 0: the node (row, s) of every row, sorted
+        hidden = torch.zeros((B, d), device=dev)
+        for l in range(1, L + 1):
+            at, src, rel, tm, keys, dst_ptr, row_of, _, status = engine.digraph_hop_index(edges, ranges, l, keys_prev, n_ent, n_rows, live,
+                                                                                         keep8, edge_time)
+            if status:
+                raise bad(status)
+            if at.numel() == 0:
+                break                                                         # nothing is reached from here on: every score stays 0
+            rela, w1, w2 = model.rela_embed_layer[l - 1].weight, model.attention_1_layer[l - 1].weight, model.attention_2_layer[l - 1].weight
+            a_s = lin(hidden, pad_rows(w1[:, :d])).contiguous()
+            a_r = F.linear(rela, pad_rows(w1[:, d:2 * d])).contiguous()
+            a_q = lin(rela[rd.q_rel], pad_rows(w1[:, 2 * d:])).contiguous()
+            hidden_p = padc(lin(hidden, w_past)).contiguous()
+            rela_p = padc(F.linear(rela, w_past)).contiguous()
+            agg, al = engine.digraph_tlayer_fwd(dst_ptr, src, rel, row_of, hidden_p, rela_p, time_p, d, a_s, a_r, a_q,
+                                                w2.reshape(-1).contiguous(), zero_b, a, edge_time=tm, q_time=q_time, n_dir=1,
+                                                dst_ptr_host=dst_ptr.cpu().numpy())      # the hop's one copy: the kernel cuts hubs there
+            alpha[at.long()] = al
+            hidden = model.act(agg[:, :d])
+            keys_prev = keys
+            if l == L:
+                cls = model.linear_classifier
+                score[row_of.long()] = lin(hidden, cls.weight, cls.bias).reshape(-1)
+                reached[row_of.long()] = True
+    return Rescore(score=score, reached=reached, live=live.bool(), alpha=alpha)
+
+
+def extrapolation_fidelity(model, X, objs=None, k=4, inverse_offset=None):
+    """extrapolation.T_RED_GNN.fidelity (see there)."""
+    _check_count(k, "fidelity", "k", engine.PATHS_MAX_K)
+    rd = model.explain(X, objs)
+    return _fidelity_of(rd, model, k, rd.edges[:, 3] == model.n_rel_true, "test", inverse_offset)
+
+
+def extrapolation_fidelity_all(model, queries, k=4, batch_size=64, inverse_offset=None):
+    """extrapolation.T_RED_GNN.fidelity_all (see there)."""
+    from .extrapolation import _Batch, check_queries
+    _check_count(k, "fidelity_all", "k", engine.PATHS_MAX_K)
+    q = check_queries(model, queries, batch_size, "fidelity_all")
+    parts = []
+    for lo in range(0, len(q), int(batch_size)):
+        b = q[lo:lo + int(batch_size)]
+        parts.append(model.fidelity(_Batch(b[:, 0], b[:, 1], b[:, 3]), b[:, 2], k=int(k), inverse_offset=inverse_offset))
+    return _fidelity_summary(parts, k)
+
+
 def rescore(rd, model, keep=None, mode="test"):
     """RDigraph.rescore (see there)."""
     who = "rescore"
+    if _is_extrapolation(rd):
+        return rescore_extrapolation(rd, model, keep, mode)
     if _has_times(rd):
         return rescore_temporal(rd, model, keep, mode)
     E, B = _check_static_digraph(rd, who)

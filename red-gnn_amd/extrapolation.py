@@ -27,6 +27,11 @@ best paths behind forecasts as lag-binned rules (explain.LagRuleTable) and ``rul
 data, per (entity, query day) anchor under the forward's row windows (csrc/xrule_ground.hip, rg_xrule_ground);
 ``rule_scores`` / ``rule_predict`` / ``rule_evaluate`` apply the weighted rules to queries (s, p, ?, t) under the same windows
 (csrc/xrule_apply.hip, rg_xrule_apply; the drivers are explain.lag_rule_scores / lag_rule_predict / lag_rule_evaluate).
+Explanation fidelity: ``rd.rescore(model, keep)`` re-scores a forecast on the kept edges of its r-digraph with the windows as they
+were - per hop the index of the live edges built in HIP from the hop's own edges (csrc/digraph_index.hip, rg_digraph_hop_ranges /
+rg_digraph_hop_index) and one rg_digraph_tlayer_fwd launch in its n_dir = 1 form; the driver is explain.rescore_extrapolation -,
+``rd.fact_mask`` takes (s, p, o, day), ``rd.data_row_mask`` data rows, and ``T_RED_GNN.fidelity`` / ``fidelity_all`` measure what the
+best k paths carry (explain.Fidelity).
 Without gradients the per-row products of the forward (attention inputs, W_past products, time table, classifier) run through
 rg_rows_linear (csrc/rows_linear.hip), whose rows do not depend on the row count: a query computes the same bits in every batch.
 
@@ -373,6 +378,24 @@ class T_RED_GNN(nn.Module):
             t = self.rules(_Batch(b[:, 0], b[:, 1], b[:, 3]), b[:, 2], k=k, lag_edges=lag_edges)
             table = t if table is None else table + t
         return table
+
+    def fidelity(self, X, objs=None, k=4, inverse_offset=None):
+        """How much of a forecast its best paths carry: for every row of X (as forward's) and the answer objs[b] (None: the row's own
+        top forecast, as rules) an explain.Fidelity - explain -> top_paths(k), then for j = 1..k the answer re-scored without the
+        past facts of the best j paths (``without``) and with only them and the self-loops (``only``), by RDigraph.rescore on the
+        digraph's own edge list (rg_digraph_hop_index, rg_digraph_tlayer_fwd).  A fact is (s, p, o, day) and is deleted for its own
+        row at every hop, every copy of it; with ``inverse_offset`` = m its twin (o, p + m or p - m, s, day) goes too - how a
+        dataset writes reversed relations belongs to the data.  The windows stay as they were (RDigraph.rescore).  No gradients,
+        eval mode (the training flags come back)."""
+        from .explain import extrapolation_fidelity
+        return extrapolation_fidelity(self, X, objs, k, inverse_offset)
+
+    def fidelity_all(self, queries, k=4, batch_size=64, inverse_offset=None):
+        """fidelity over ``queries`` int [n, 4] = (s, p, o, ts) (checked as evaluate's), each row a query with its object as the
+        answer, in batches of ``batch_size``: the dict of BaseModel.fidelity - n, k, necessity_mean / _median, sufficiency_gap_mean /
+        _median and disconnected (the share of reached answers the deletion cuts off), a list over j = 1..k each."""
+        from .explain import extrapolation_fidelity_all
+        return extrapolation_fidelity_all(self, queries, k, batch_size, inverse_offset)
 
     def windows(self):
         """(win_lo, win_hi) int64 [n_day]: the forward's row window [off[max(t - 120, 0)], off[t]) of every query day t, off being
