@@ -477,6 +477,37 @@ int rg_digraph_tlayer_fwd(int32_t n_dst, int64_t n_edges, const int32_t* dst_ptr
                           const float* w_alpha, const float* b_alpha, int32_t attn_dim, float* agg_out, float* alpha_out, void* scratch,
                           size_t scratch_bytes, void* stream);
 
+/* ---- the adjoint of one rg_digraph_layer_fwd hop (static form only) with respect to a gate on every edge, the source states and
+ * their attention projection (csrc/digraph_bwd.hip; explain.RDigraph.saliency).  With a gate g_e on the message of edge e,
+ * agg[o] = sum_e g_e alpha_e (hidden[s] + rela[r]), the call returns the gradients at g == 1 of a scalar whose gradient with respect
+ * to agg is grad_agg [n_dst, ld].  rela, a_r, a_q, w_alpha and b_alpha are CONSTANTS here: there are no parameter gradients, and the
+ * gate does not enter alpha_e.  Per edge e = (s, r, o), b = row_of_dst[o], G = grad_agg:
+ *   alpha_e = sigmoid(w . relu((a_s[s] + a_r[r]) + a_q[b]) + b_alpha)      attn_acc_fwd / attn_alpha: the float the forward multiplied by
+ *   g_alpha = <G[o], hidden[s] + rela[r]>
+ *   grad_gate[e]    = alpha_e * g_alpha                                    [n_edges], by position in the destination-ordered list
+ *   grad_hidden[s] += alpha_e * G[o]                                       [n_src, ld], every row written whole (no edges: zeros)
+ *   grad_a_s[s]    += g_alpha * alpha_e * (1 - alpha_e) * w * 1[pre > 0]   [n_src, ap], every row written whole
+ * grad_hidden and grad_a_s may both be NULL (hop 1 of an r-digraph: its state is the constant 0); grad_gate then has the bits it has
+ * with them.  Pad columns of the outputs are 0 when those of the inputs are.
+ * The edges are the forward's destination-ordered list (rel [n_edges], row_of_dst [n_dst]) seen by source: src_ptr int32 [n_src + 1]
+ * is a CSR over positions k (device; src_ptr_host the same array in host memory, read before anything is enqueued: it must start at
+ * 0, never decrease and end at n_edges), edge_of [n_edges] the position in the destination-ordered list of the edge at k - a stable
+ * permutation, so a source's edges keep their list order - and dst_of_edge [n_edges] the destination of the edge at list position e.
+ * Indices outside their table are clamped to it, never followed.  ld % 4 == 0, d <= ld <= 256; ap one of 4, 8, 12, 16, 32.
+ * No float atomics: a source of more than RG_DIGRAPH_CHUNK out-edges is cut into chunks of that many, counted from its own first
+ * edge, which separate waves sum into partial rows in scratch; a second launch adds them in chunk order.  Every output therefore has
+ * the same bits on every run and whatever else the call carries.  scratch: device memory of
+ * rg_digraph_layer_bwd_scratch_bytes(src_ptr_host, n_src, ld, ap) bytes, 16-B aligned (0 / NULL when no source is cut, or the CSR is
+ * malformed).  n_src == 0 or n_edges == 0 succeeds and launches nothing (the outputs are then left alone).  The call waits for the
+ * copy of the chunk list when a source is cut; it is not for stream capture. */
+size_t rg_digraph_layer_bwd_scratch_bytes(const int32_t* src_ptr_host, int32_t n_src, int32_t ld, int32_t ap);
+int rg_digraph_layer_bwd(int32_t n_src, int32_t n_dst, int64_t n_edges, const int32_t* src_ptr, const int32_t* src_ptr_host,
+                         const int32_t* edge_of, const int32_t* dst_of_edge, const int32_t* rel, const int32_t* row_of_dst,
+                         int32_t n_rela_rows, int32_t batch, const float* hidden, const float* rela, int32_t d, int32_t ld,
+                         const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha,
+                         int32_t attn_dim, const float* grad_agg, float* grad_gate, float* grad_hidden, float* grad_a_s, void* scratch,
+                         size_t scratch_bytes, void* stream);
+
 /* ---- the per-hop index of an edited r-digraph: the arrays rg_digraph_(t)layer_fwd takes, built from the digraph's own edge list
  * under a keep mask (csrc/digraph_index.hip; explain.RDigraph.rescore of an extrapolation digraph).  edges int32 [n_edges, 5] =
  * (row, hop, head, rel, tail) ordered by (row, hop, tail) and offsets int64 [batch + 1] (start at 0, never decrease, end at n_edges:

@@ -1,0 +1,321 @@
+// The adjoint of one rg_digraph_layer_fwd hop (static form) with respect to a gate on every edge, the source states and their
+// attention projection (rg_digraph_layer_bwd): the executor behind explain.RDigraph.saliency.  With a gate g_e multiplying the
+// message of edge e, agg[o] = sum_e g_e alpha_e (hidden[s] + rela[r]), and G = grad_agg, per edge e = (s, r, o), b = row_of_dst[o]:
+//
+//   alpha_e = sigmoid(w . relu((a_s[s] + a_r[r]) + a_q[b]) + b_alpha)        attn.h attn_acc_fwd / attn_alpha: the forward's float
+//   g_alpha = <G[o], hidden[s] + rela[r]>
+//   grad_gate[e]     = alpha_e * g_alpha                                      (at g == 1)
+//   grad_hidden[s]  += alpha_e * G[o]
+//   g_p              = g_alpha * alpha_e * (1 - alpha_e)
+//   grad_a_s[s]     += g_p * w * 1[(a_s[s] + a_r[r]) + a_q[b] > 0]
+//
+// rela, a_r, a_q, w_alpha and b_alpha are constants here: there are no parameter gradients.
+//
+// The sums run over a SOURCE's out-edges, so the hop comes with a source-segmented view next to the destination-ordered lists the
+// forward takes: src_ptr [n_src + 1] over the positions k of edge_of [E], edge_of[k] = e the edge's position in the destination-ordered
+// list (a stable permutation: a source's edges in list order), dst_of_edge[e] = o.
+//
+// Mapping (wave64), the forward's with source and destination exchanged: a source is owned by a group of G lanes, G * 4 >= ld floats,
+// one float4 of its row per lane, 64 / G sources per wave.  A round takes G of the source's edges: lane j forms the attention scalar of
+// edge j and the sign bits of its pre-activation, then the group walks the round's edges in order, each lane gathering its float4 of
+// G[o] and rela[r], four edges' gathers in flight; the row dot product is reduced inside the group and lane j keeps edge j's.  Lane j
+// then stores grad_gate of its edge and adds its edge's g_p * 1[pre > 0] to its own attention accumulator; the lanes' accumulators
+// are added across the group once, when the item ends, and the total is multiplied by w there (w is constant over the sum).  All
+// lanes of a wave run the same number of rounds (the longest source's) with their stores predicated, so the lane exchanges never
+// read an inactive lane.
+//
+// Split rule, the forward's: a source of more than DIGRAPH_CHUNK out-edges is cut into chunks counted from ITS OWN first edge; every
+// chunk is an item of the same launch that sums into partial rows, and a second launch adds the partial rows in chunk order.  Hop 1 of
+// an r-digraph is the case: a row's only source is its subject, with every hop-1 edge.  No float atomics: the sums of a source are
+// formed in list order inside a chunk and in chunk order across chunks, so every output has the same bits on every run and does not
+// depend on what else the call carries.
+#include <algorithm>
+#include <vector>
+
+#include "attn.h"
+
+namespace rgdb {
+namespace {
+
+constexpr int DIGRAPH_CHUNK = RG_DIGRAPH_CHUNK;   // edges per chunk of a cut source (include/redgnn.h)
+constexpr int DB_BLOCK = 256;                     // 4 waves
+
+struct DbArgs {
+  int n_src, n_items;          // items: [0, n_src) the sources themselves, then the chunks of the cut ones
+  int E, n_dst, n_rela_rows, B;
+  const int32_t* src_ptr;
+  const int32_t* edge_of;
+  const int32_t* dst_of_edge;
+  const int32_t* rel;
+  const int32_t* row_of_dst;
+  const int4* chunks;          // [n_items - n_src] {source, first position, end, slot of the partial rows}
+  const float4* hidden;
+  const float4* rela;
+  const float4* grad_agg;
+  int ld4;
+  const float4* a_s;
+  const float4* a_r;
+  const float4* a_q;
+  const float* w_alpha;
+  const float* b_alpha;
+  int attn_dim;
+  float* grad_gate;
+  float4* grad_hidden;         // nullptr: not wanted (then neither is grad_a_s)
+  float4* grad_a_s;
+  float4* partial_h;           // [n_chunks, ld4]
+  float4* partial_as;          // [n_chunks, AP4]
+};
+
+__device__ __forceinline__ int clampi(int x, int hi) { return min(max(x, 0), hi); }
+
+template <int G, int AP4>
+__global__ __launch_bounds__(DB_BLOCK) void digraph_bwd_kernel(DbArgs A) {
+  constexpr int PER_WAVE = 64 / G;
+  const int lane = threadIdx.x & 63;
+  const int lane_g = lane & (G - 1), gbase = lane & ~(G - 1);
+  const int wave = blockIdx.x * (DB_BLOCK / 64) + (threadIdx.x >> 6);
+  const int item = wave * PER_WAVE + lane / G;
+  const bool row_lane = lane_g < A.ld4;
+  const int lane_c = row_lane ? lane_g : A.ld4 - 1;      // loads never branch: idle lanes re-read the last float4
+
+  // the item's source, range of positions and output rows; an item without work keeps beg == end and stores nothing
+  int s = 0, beg = 0, end = 0;
+  float4* out_h = nullptr;
+  float4* out_as = nullptr;
+  if (item < A.n_src) {
+    s = item;
+    const int lo = clampi(A.src_ptr[s], A.E), hi = clampi(A.src_ptr[s + 1], A.E);
+    if (hi - lo <= DIGRAPH_CHUNK) {                      // (a cut source is written by the combine pass)
+      beg = lo; end = max(hi, lo);
+      if (A.grad_hidden) { out_h = A.grad_hidden + (int64_t)s * A.ld4; out_as = A.grad_a_s + (int64_t)s * AP4; }
+    }
+  } else if (item < A.n_items) {
+    const int4 c = A.chunks[item - A.n_src];
+    s = clampi(c.x, A.n_src - 1);
+    beg = clampi(c.y, A.E); end = min(max(clampi(c.z, A.E), beg), beg + DIGRAPH_CHUNK);
+    if (A.grad_hidden) { out_h = A.partial_h + (int64_t)c.w * A.ld4; out_as = A.partial_as + (int64_t)c.w * AP4; }
+  }
+  const float b_alpha = A.b_alpha[0];
+  const float4 hv = A.hidden[(int64_t)s * A.ld4 + lane_c];
+  const float4* as_p = A.a_s + (int64_t)s * AP4;
+
+  float4 acc_h = rg::f4zero();
+  float4 acc_as[AP4];
+#pragma unroll
+  for (int k = 0; k < AP4; ++k) acc_as[k] = rg::f4zero();
+  for (int c0 = beg; __any(c0 < end); c0 += G) {
+    // ---- one edge per lane: indices, the attention scalar and the sign bits of its pre-activation ---------------
+    const int c = c0 + lane_g;
+    const bool valid = c < end;
+    int e = 0, o = 0, r = 0;
+    unsigned pos = 0;                                    // bit 4k + u: component 4k + u of (a_s + a_r) + a_q is > 0
+    float alpha = 0.f;
+    if (valid) {
+      e = clampi(A.edge_of[c], A.E - 1);
+      o = clampi(A.dst_of_edge[e], A.n_dst - 1);
+      r = clampi(A.rel[e], A.n_rela_rows - 1);
+      const float4* aq_p = A.a_q + (int64_t)clampi(A.row_of_dst[o], A.B - 1) * AP4;
+      float z = b_alpha;
+#pragma clang loop unroll_count(AP4 >= 8 ? 2 : AP4)
+      for (int k = 0; k < AP4; ++k) {
+        const float4 as = as_p[k], ar = A.a_r[(int64_t)r * AP4 + k], aq = aq_p[k];
+        rg::attn_acc_fwd(z, rg::attn_w4(A.w_alpha, A.attn_dim, k), as, ar, aq);
+        pos |= (unsigned)(as.x + ar.x + aq.x > 0.f) << (4 * k) | (unsigned)(as.y + ar.y + aq.y > 0.f) << (4 * k + 1) |
+               (unsigned)(as.z + ar.z + aq.z > 0.f) << (4 * k + 2) | (unsigned)(as.w + ar.w + aq.w > 0.f) << (4 * k + 3);
+      }
+      alpha = rg::attn_alpha(z);
+    }
+    const int cnt = min(max(end - c0, 0), G);
+    // ---- the round's edges in order, every lane its float4 of the rows; four edges' gathers in flight -----------
+    float g_alpha = 0.f;
+    for (int j = 0; __any(j < cnt); j += 4) {
+      int ou[4], ru[4];
+      float al[4];
+      float4 gv[4], rv[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {      // (slots past cnt hold o = r = 0: row 0 is read and not used)
+        const int from = gbase + ((j + u) & (G - 1));
+        ou[u] = __shfl(o, from, 64);
+        ru[u] = __shfl(r, from, 64);
+        al[u] = __shfl(alpha, from, 64);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) gv[u] = A.grad_agg[(int64_t)ou[u] * A.ld4 + lane_c];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) rv[u] = A.rela[(int64_t)ru[u] * A.ld4 + lane_c];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        float p = gv[u].x * (hv.x + rv[u].x);
+        p = fmaf(gv[u].y, hv.y + rv[u].y, p);
+        p = fmaf(gv[u].z, hv.z + rv[u].z, p);
+        p = fmaf(gv[u].w, hv.w + rv[u].w, p);
+        const float dot = rg::group_sum<G>(row_lane ? p : 0.f);
+        if (j + u < cnt) {
+          acc_h.x = fmaf(al[u], gv[u].x, acc_h.x);
+          acc_h.y = fmaf(al[u], gv[u].y, acc_h.y);
+          acc_h.z = fmaf(al[u], gv[u].z, acc_h.z);
+          acc_h.w = fmaf(al[u], gv[u].w, acc_h.w);
+        }
+        if (lane_g == j + u) g_alpha = dot;
+      }
+    }
+    // ---- back on the edge's own lane: its gate gradient, and its share of the source's attention gradient ---------
+    if (valid) {
+      A.grad_gate[e] = alpha * g_alpha;
+      const float g_p = g_alpha * alpha * (1.f - alpha);
+#pragma unroll
+      for (int k = 0; k < AP4; ++k) {      // (w is constant over the sum: it multiplies the total, below)
+        acc_as[k].x += (pos >> (4 * k) & 1u) ? g_p : 0.f;
+        acc_as[k].y += (pos >> (4 * k + 1) & 1u) ? g_p : 0.f;
+        acc_as[k].z += (pos >> (4 * k + 2) & 1u) ? g_p : 0.f;
+        acc_as[k].w += (pos >> (4 * k + 3) & 1u) ? g_p : 0.f;
+      }
+    }
+  }
+  if (out_h && row_lane) out_h[lane_g] = acc_h;
+  // the lanes' attention accumulators added across the group (every lane of the wave takes part); float4 k stored by lane k mod G
+#pragma unroll
+  for (int k = 0; k < AP4; ++k) {
+    const float4 w = rg::attn_w4(A.w_alpha, A.attn_dim, k);
+    float4 t;
+    t.x = w.x * rg::group_sum<G>(acc_as[k].x);
+    t.y = w.y * rg::group_sum<G>(acc_as[k].y);
+    t.z = w.z * rg::group_sum<G>(acc_as[k].z);
+    t.w = w.w * rg::group_sum<G>(acc_as[k].w);
+    if (out_as && lane_g == (k & (G - 1))) out_as[k] = t;
+  }
+}
+
+// grad_hidden[s] and grad_a_s[s] of the cut sources: their chunks' partial rows added in chunk order, the first one initialising the
+// sum.  A thread per float4: the ld4 of the state row, then the ap4 of the attention row.
+__global__ void digraph_bwd_combine_kernel(const int4* __restrict__ hubs, int n_hubs, const float4* __restrict__ partial_h,
+                                           const float4* __restrict__ partial_as, float4* __restrict__ grad_hidden,
+                                           float4* __restrict__ grad_a_s, int ld4, int ap4) {
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int w = ld4 + ap4;
+  const int64_t h = tid / w;
+  int c = (int)(tid - h * w);
+  if (h >= n_hubs) return;
+  const int4 hub = hubs[h];                              // {source, first slot, chunks, -}
+  const bool state = c < ld4;
+  const int stride = state ? ld4 : ap4;
+  if (!state) c -= ld4;
+  const float4* p = (state ? partial_h : partial_as) + (int64_t)hub.y * stride + c;
+  float4 acc = p[0];
+  for (int k = 1; k < hub.z; ++k) {
+    const float4 v = p[(int64_t)k * stride];
+    acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+  }
+  (state ? grad_hidden : grad_a_s)[(int64_t)hub.x * stride + c] = acc;
+}
+
+// the cut sources of a CSR on the host: how many, and how many chunks they make
+void count_cuts(const int32_t* ptr, int32_t n_src, int64_t* n_hubs, int64_t* n_chunks) {
+  *n_hubs = *n_chunks = 0;
+  for (int32_t s = 0; s < n_src; ++s) {
+    const int64_t len = (int64_t)ptr[s + 1] - ptr[s];
+    if (len > DIGRAPH_CHUNK) { ++*n_hubs; *n_chunks += rg::ceil_div(len, DIGRAPH_CHUNK); }
+  }
+}
+
+size_t list_bytes(int64_t n_hubs, int64_t n_chunks) { return rg::align_up((size_t)(n_hubs + n_chunks) * sizeof(int4), 256); }
+size_t rows_bytes(int64_t n_chunks, int32_t width) { return rg::align_up((size_t)n_chunks * width * sizeof(float), 256); }
+
+template <int G, int AP4>
+int launch(const DbArgs& A, hipStream_t s) {
+  const int64_t waves = rg::ceil_div(A.n_items, 64 / G);
+  hipLaunchKernelGGL((digraph_bwd_kernel<G, AP4>), dim3((unsigned)rg::ceil_div(waves, DB_BLOCK / 64)), dim3(DB_BLOCK), 0, s, A);
+  RG_LAUNCH_CHECK();
+  return 0;
+}
+
+}  // namespace
+}  // namespace rgdb
+
+extern "C" size_t rg_digraph_layer_bwd_scratch_bytes(const int32_t* src_ptr_host, int32_t n_src, int32_t ld, int32_t ap) {
+  if (!src_ptr_host || n_src <= 0 || ld <= 0 || ap <= 0) return 0;
+  for (int32_t s = 0; s < n_src; ++s)
+    if (src_ptr_host[s + 1] < src_ptr_host[s]) return 0;
+  int64_t n_hubs, n_chunks;
+  rgdb::count_cuts(src_ptr_host, n_src, &n_hubs, &n_chunks);
+  if (n_hubs == 0) return 0;
+  return rgdb::list_bytes(n_hubs, n_chunks) + rgdb::rows_bytes(n_chunks, ld) + rgdb::rows_bytes(n_chunks, ap);
+}
+
+extern "C" int rg_digraph_layer_bwd(int32_t n_src, int32_t n_dst, int64_t n_edges, const int32_t* src_ptr, const int32_t* src_ptr_host,
+                                    const int32_t* edge_of, const int32_t* dst_of_edge, const int32_t* rel, const int32_t* row_of_dst,
+                                    int32_t n_rela_rows, int32_t batch, const float* hidden, const float* rela, int32_t d, int32_t ld,
+                                    const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha,
+                                    const float* b_alpha, int32_t attn_dim, const float* grad_agg, float* grad_gate,
+                                    float* grad_hidden, float* grad_a_s, void* scratch, size_t scratch_bytes, void* stream) {
+  using namespace rgdb;
+  const char* who = "rg_digraph_layer_bwd";
+  RG_CHECK(n_src >= 0 && n_dst >= 0 && n_edges >= 0 && n_edges < ((int64_t)1 << 31),
+           "%s: n_src=%d n_dst=%d n_edges=%lld (need 0 <= n_src, 0 <= n_dst, 0 <= n_edges < 2^31)", who, n_src, n_dst, (long long)n_edges);
+  RG_CHECK(n_rela_rows >= 0 && batch >= 0, "%s: n_rela_rows=%d batch=%d (negative size)", who, n_rela_rows, batch);
+  RG_CHECK(d > 0 && ld >= d && ld % 4 == 0 && ld <= 256, "%s: d=%d ld=%d (need ld%%4==0, d<=ld<=256)", who, d, ld);
+  RG_CHECK(attn_dim > 0 && ap >= attn_dim && ap % 4 == 0, "%s: attn_dim=%d ap=%d", who, attn_dim, ap);
+  RG_CHECK((grad_hidden == nullptr) == (grad_a_s == nullptr), "%s: grad_hidden and grad_a_s come together or not at all", who);
+  if (n_src == 0) {
+    RG_CHECK(n_edges == 0, "%s: %lld edges without a source", who, (long long)n_edges);
+    return 0;
+  }
+  RG_CHECK(src_ptr_host, "%s: NULL argument (src_ptr_host)", who);
+  RG_CHECK(src_ptr_host[0] == 0, "%s: src_ptr starts at %d, not 0", who, src_ptr_host[0]);
+  for (int32_t s = 0; s < n_src; ++s)
+    RG_CHECK(src_ptr_host[s + 1] >= src_ptr_host[s], "%s: src_ptr decreases at source %d", who, s);
+  RG_CHECK(src_ptr_host[n_src] == n_edges, "%s: src_ptr ends at %d, not at the number of edges %lld", who, src_ptr_host[n_src],
+           (long long)n_edges);
+  if (n_edges == 0) return 0;                            // nothing to sum and nothing launched: the caller owns the outputs
+  RG_CHECK(src_ptr && edge_of && dst_of_edge && rel && row_of_dst && hidden && rela && a_s && a_r && a_q && w_alpha && b_alpha &&
+           grad_agg && grad_gate, "%s: NULL argument", who);
+  RG_CHECK(n_dst > 0 && n_rela_rows > 0 && batch > 0, "%s: edges but n_dst=%d n_rela_rows=%d batch=%d", who, n_dst, n_rela_rows, batch);
+  RG_CHECK((((uintptr_t)hidden | (uintptr_t)rela | (uintptr_t)a_s | (uintptr_t)a_r | (uintptr_t)a_q | (uintptr_t)grad_agg |
+             (uintptr_t)grad_hidden | (uintptr_t)grad_a_s | (uintptr_t)scratch) & 15) == 0, "%s: float buffers must be 16-B aligned", who);
+  int64_t n_hubs, n_chunks;
+  count_cuts(src_ptr_host, n_src, &n_hubs, &n_chunks);
+  RG_CHECK((int64_t)n_src + n_chunks < ((int64_t)1 << 31), "%s: %lld items overflow int32", who, (long long)(n_src + n_chunks));
+  const size_t need = n_hubs ? list_bytes(n_hubs, n_chunks) + rows_bytes(n_chunks, ld) + rows_bytes(n_chunks, ap) : 0;
+  RG_CHECK(need == 0 || (scratch && scratch_bytes >= need), "%s: scratch %zu B < required %zu B", who, scratch ? scratch_bytes : (size_t)0,
+           need);
+
+  DbArgs A;
+  A.n_src = n_src; A.n_items = (int)(n_src + n_chunks); A.E = (int)n_edges; A.n_dst = n_dst; A.n_rela_rows = n_rela_rows; A.B = batch;
+  A.src_ptr = src_ptr; A.edge_of = edge_of; A.dst_of_edge = dst_of_edge; A.rel = rel; A.row_of_dst = row_of_dst;
+  A.hidden = (const float4*)hidden; A.rela = (const float4*)rela; A.grad_agg = (const float4*)grad_agg; A.ld4 = ld / 4;
+  A.a_s = (const float4*)a_s; A.a_r = (const float4*)a_r; A.a_q = (const float4*)a_q;
+  A.w_alpha = w_alpha; A.b_alpha = b_alpha; A.attn_dim = attn_dim;
+  A.grad_gate = grad_gate; A.grad_hidden = (float4*)grad_hidden; A.grad_a_s = (float4*)grad_a_s;
+  int4* hubs_dev = (int4*)scratch;
+  A.chunks = hubs_dev + n_hubs;
+  A.partial_h = n_hubs ? (float4*)((char*)scratch + list_bytes(n_hubs, n_chunks)) : nullptr;
+  A.partial_as = n_hubs ? (float4*)((char*)A.partial_h + rows_bytes(n_chunks, ld)) : nullptr;
+  // every argument error is out before anything is enqueued: the width dispatch is probed first
+  if (rg::with_ap4(ap / 4, who, [](auto) { return 0; })) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  if (n_hubs) {
+    std::vector<int4> list((size_t)(n_hubs + n_chunks));
+    int64_t h = 0, slot = 0;
+    for (int32_t v = 0; v < n_src; ++v) {
+      const int32_t lo = src_ptr_host[v], hi = src_ptr_host[v + 1];
+      if (hi - lo <= DIGRAPH_CHUNK) continue;
+      const int n_c = (int)rg::ceil_div(hi - lo, DIGRAPH_CHUNK);
+      list[h++] = make_int4(v, (int)slot, n_c, 0);
+      for (int k = 0; k < n_c; ++k, ++slot)
+        list[n_hubs + slot] = make_int4(v, lo + k * DIGRAPH_CHUNK, std::min(hi, lo + (k + 1) * DIGRAPH_CHUNK), (int)slot);
+    }
+    // (a copy from pageable memory: the runtime is done with the vector when the call returns)
+    RG_HIP(hipMemcpyAsync(hubs_dev, list.data(), list.size() * sizeof(int4), hipMemcpyHostToDevice, s));
+  }
+  const int rc = rg::with_g(A.ld4, [&](auto g) {
+    return rg::with_ap4(ap / 4, who, [&](auto a4) { return launch<decltype(g)::value, decltype(a4)::value>(A, s); });
+  });
+  if (rc) return rc;
+  if (n_hubs && grad_hidden) {
+    const int64_t threads = n_hubs * (A.ld4 + ap / 4);
+    hipLaunchKernelGGL(digraph_bwd_combine_kernel, dim3((unsigned)rg::ceil_div(threads, 256)), dim3(256), 0, s, hubs_dev, (int)n_hubs,
+                       (const float4*)A.partial_h, (const float4*)A.partial_as, A.grad_hidden, A.grad_a_s, A.ld4, ap / 4);
+    RG_LAUNCH_CHECK();
+  }
+  return 0;
+}

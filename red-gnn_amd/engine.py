@@ -1216,6 +1216,87 @@ def _digraph_layer(who, dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s,
     return agg, alpha
 
 
+DIGRAPH_BWD_EVENTS = None            # probes: a list that collects (start, end, n_src, n_edges) of every digraph_layer_bwd
+
+
+def digraph_source_view(dst_ptr, src_idx, n_src):
+    """The source-segmented view of a hop rg_digraph_layer_bwd sums over, from the destination-ordered lists digraph_layer_fwd takes:
+    (src_ptr int32 [n_src + 1], src_ptr_host numpy, edge_of int32 [E], dst_of_edge int32 [E]).  ``edge_of`` is the stable sort of the
+    edges by source, so a source's edges keep their list order; ``dst_of_edge[e]`` is the destination whose CSR row holds e."""
+    E, dev = src_idx.numel(), src_idx.device
+    edge_of = torch.sort(src_idx, stable=True).indices.to(torch.int32)
+    src_ptr = torch.zeros(n_src + 1, dtype=torch.int64, device=dev)
+    if E:
+        src_ptr[1:] = torch.cumsum(torch.bincount(src_idx, minlength=n_src)[:n_src], 0)
+    src_ptr = src_ptr.to(torch.int32)
+    n_dst = dst_ptr.numel() - 1
+    dst_of_edge = torch.repeat_interleave(torch.arange(n_dst, dtype=torch.int32, device=dev), (dst_ptr[1:] - dst_ptr[:-1]).long(),
+                                          output_size=E)
+    return src_ptr, src_ptr.cpu().numpy(), edge_of.contiguous(), dst_of_edge.contiguous()
+
+
+def digraph_layer_bwd(dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s, a_r, a_q, w_alpha, b_alpha, attn_dim, grad_agg,
+                      want_state=True):
+    """The adjoint of digraph_layer_fwd on the same arguments with respect to a gate on every edge's message, ``hidden`` and ``a_s``
+    (rg_digraph_layer_bwd; ``rela``, ``a_r``, ``a_q``, ``w_alpha`` and ``b_alpha`` are constants): (grad_gate fp32 [E] in the order of
+    the edge list, grad_hidden fp32 [n_src, ld], grad_a_s fp32 [n_src, ap]) for ``grad_agg`` fp32 [n_dst, ld]; the last two are None
+    with ``want_state`` False (hop 1: the state is the constant 0), grad_gate's bits unchanged.  The source-segmented view of the hop
+    is built here (digraph_source_view).  The same checks as digraph_layer_fwd (ValueError); no float atomics, the same bits on every
+    run, and a source's rows and its edges' gate gradients do not depend on the rest of the call."""
+    who = "digraph_layer_bwd"
+    for name, t in (("dst_ptr", dst_ptr), ("src_idx", src_idx), ("rel", rel), ("row_of_dst", row_of_dst)):
+        if not (torch.is_tensor(t) and t.dtype == torch.int32 and t.dim() == 1):
+            raise ValueError("%s: %s must be an int32 vector" % (who, name))
+    floats = [("hidden", hidden), ("rela", rela), ("a_s", a_s), ("a_r", a_r), ("a_q", a_q), ("grad_agg", grad_agg)]
+    for name, t in floats:
+        if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.dim() == 2):
+            raise ValueError("%s: %s must be a float32 matrix" % (who, name))
+    n_dst, E = dst_ptr.numel() - 1, src_idx.numel()
+    n_src, ld, ap = hidden.shape[0], hidden.shape[1], a_s.shape[1]
+    if n_dst < 0 or rel.numel() != E or row_of_dst.numel() != n_dst:
+        raise ValueError("%s: dst_ptr [%d], src_idx [%d], rel [%d] and row_of_dst [%d] do not fit together"
+                         % (who, dst_ptr.numel(), E, rel.numel(), row_of_dst.numel()))
+    if rela.shape[1] != ld or a_r.shape[1] != ap or a_q.shape[1] != ap or a_s.shape[0] != n_src or a_r.shape[0] != rela.shape[0] \
+            or tuple(grad_agg.shape) != (n_dst, ld):
+        raise ValueError("%s: hidden %s, rela %s, a_s %s, a_r %s, a_q %s and grad_agg %s (%d destinations) do not fit together"
+                         % (who, tuple(hidden.shape), tuple(rela.shape), tuple(a_s.shape), tuple(a_r.shape), tuple(a_q.shape),
+                            tuple(grad_agg.shape), n_dst))
+    _require_gpu(hidden.device)
+    tensors = (dst_ptr, src_idx, rel, row_of_dst, w_alpha, b_alpha) + tuple(t for _, t in floats)
+    if not all(t.is_cuda and t.is_contiguous() for t in tensors):
+        raise ValueError("%s: every tensor must be contiguous and on the device" % who)
+    dev = hidden.device
+    grad_gate = torch.zeros(E, dtype=torch.float32, device=dev)
+    grad_hidden = torch.zeros((n_src, ld), dtype=torch.float32, device=dev) if want_state else None
+    grad_a_s = torch.zeros((n_src, ap), dtype=torch.float32, device=dev) if want_state else None
+    ptr_h = dst_ptr.cpu().numpy()
+    if ptr_h[0] != 0 or ptr_h[-1] != E or (np.diff(ptr_h) < 0).any():
+        raise ValueError("%s: dst_ptr must start at 0, never decrease and end at the number of edges (%d)" % (who, E))
+    if E:
+        checked = [("src_idx", src_idx, n_src), ("rel", rel, a_r.shape[0]), ("row_of_dst", row_of_dst, a_q.shape[0])]
+        lo = torch.stack([t.min() for _, t, _ in checked]).tolist()
+        hi = torch.stack([t.max() for _, t, _ in checked]).tolist()
+        for (name, _, n), a, b in zip(checked, lo, hi):
+            if a < 0 or b >= n:
+                raise ValueError("%s: %s out of range (%d..%d, %d rows)" % (who, name, a, b, n))
+    src_ptr, src_ptr_h, edge_of, dst_of_edge = digraph_source_view(dst_ptr, src_idx, n_src)
+    L, p = _lib.lib(), _lib.ptr
+    nbytes = int(L.rg_digraph_layer_bwd_scratch_bytes(p(src_ptr_h), n_src, ld, ap)) if n_src > 0 else 0
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    ev = None
+    if DIGRAPH_BWD_EVENTS is not None:
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        ev[0].record()
+    _lib.check(L.rg_digraph_layer_bwd(n_src, n_dst, E, p(src_ptr), p(src_ptr_h), p(edge_of), p(dst_of_edge), p(rel), p(row_of_dst),
+                                      a_r.shape[0], a_q.shape[0], p(hidden), p(rela), int(d), ld, p(a_s), p(a_r), p(a_q), ap, p(w_alpha),
+                                      p(b_alpha), int(attn_dim), p(grad_agg), p(grad_gate), p(grad_hidden), p(grad_a_s), p(scratch), nbytes,
+                                      _lib.stream_ptr()))
+    if ev is not None:
+        ev[1].record()
+        DIGRAPH_BWD_EVENTS.append((ev[0], ev[1], n_src, E))
+    return grad_gate, grad_hidden, grad_a_s
+
+
 # include/redgnn.h: RG_DIGRAPH_INDEX_*, with the ValueError each status bit becomes ({who}, {L} filled in by digraph_index_error)
 DIGRAPH_INDEX_STATUS = (
     (4, "{who}: edges hold a row that is not the row of its range in offsets, or hops that are not 1..{L} in order inside a row"),

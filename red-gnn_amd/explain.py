@@ -10,6 +10,7 @@ s -> o through the query's subgraph (identity self-loops count as steps); each e
     table = model.rules(subs, rels, objs, k=2)       # their relation sequences counted as rules: an explain.RuleTable
     rs = rd.rescore(model, keep=~paths.fact_mask(1))  # o re-scored with the best path's facts deleted (HIP: csrc/digraph_fwd.hip)
     fid = model.fidelity(subs, rels, objs, k=4)      # necessity and sufficiency of the best 1..k paths: an explain.Fidelity
+    sal = rd.saliency(model)                         # d score / d (a gate on every edge), one pass (HIP: csrc/digraph_bwd.hip): an explain.Saliency
 
 The extraction runs in HIP (csrc/explain.hip): a forward keeps all L + 1 frontier levels and each layer's attention projection, then
 one backward marking pass per hop reads only the marked tails' CSR rows.  This module holds the result type and the host drivers.
@@ -33,6 +34,7 @@ edges (engine.digraph_hop_index, csrc/digraph_index.hip) and one rg_digraph_tlay
 takes (s, p, o, day), ``rd.data_row_mask`` data rows, and ``model.fidelity(X, objs, k, inverse_offset)`` / ``fidelity_all`` are the static
 model's fidelity.
 """
+import types
 from dataclasses import dataclass, fields, replace
 
 import numpy as np
@@ -107,6 +109,17 @@ class RDigraph:
         deleted row is the last of its day or a day loses all its rows; the rescore equals the forward of a model rebuilt from the
         reduced data only for deletions that do neither."""
         return rescore(self, model, keep, mode)
+
+    def saliency(self, model, keep=None, mode="test"):
+        """How much the score of o depends on every edge: an explain.Saliency.  Give every edge e a gate g_e that multiplies its
+        message, agg[o] = sum_e g_e alpha_e (hidden[s] + rela[r]) in the forward ``rescore`` states; ``edge_grad[e]`` is d score / d g_e
+        at g == 1 with the parameters fixed.  The gate does not enter alpha_e directly; it does enter the attention of later hops
+        through the states.  One pass instead of one ``rescore`` per fact: the hop loop of ``rescore`` (same checks, same ``keep``,
+        the same ``score``, ``reached``, ``live`` and ``alpha`` bit for bit), then the hops backwards - the dense step's adjoint
+        through tall_linear / gru_step with the parameters detached, the edge-list layer's in HIP (rg_digraph_layer_bwd,
+        csrc/digraph_bwd.hip: no float atomics, the same bits on every run).  Dead edges and rows whose answer is not reached get
+        exactly 0.  Static and inductive models only: a temporal or extrapolation digraph is a ValueError."""
+        return saliency(self, model, keep, mode)
 
     def fact_mask(self, facts, rows=None, inverse_offset=None):
         """bool [E]: the edges that stand for one of the facts ``facts`` int [F, 3] = (h, r, t), at any hop: an edge is marked if its
@@ -1830,6 +1843,12 @@ def rescore(rd, model, keep=None, mode="test"):
         return rescore_extrapolation(rd, model, keep, mode)
     if _has_times(rd):
         return rescore_temporal(rd, model, keep, mode)
+    return _rescore_static(rd, model, keep, mode, who)
+
+
+def _rescore_static(rd, model, keep, mode, who, tape=None):
+    """RDigraph.rescore of a static r-digraph for ``who`` (rescore, saliency).  ``tape``: a list that receives, per hop walked, what the
+    hop's adjoint needs (RDigraph.saliency): the hop, its index arrays, the state and projection it read and the sums it formed."""
     E, B = _check_static_digraph(rd, who)
     for name in ("q_sub", "q_rel"):
         t = getattr(rd, name)
@@ -1885,6 +1904,10 @@ def rescore(rd, model, keep=None, mode="test"):
                                                a_r.contiguous(), a_q.contiguous(), layer.w_alpha.weight.detach().reshape(-1).contiguous(),
                                                layer.w_alpha.bias.detach().contiguous(), a)
             alpha[at] = al
+            if tape is not None:
+                tape.append(dict(l=l, at=at, dst_ptr=dst_ptr, src=i32(src), rel=i32(rel[at]), row_of=i32(row_of), hidden=hidden, a_s=a_s,
+                                 agg=agg, prev_idx=prev_idx, had=had, a_r=a_r.contiguous(), a_q=a_q.contiguous(),
+                                 rela=rela_p.contiguous()))
             if fused:                                                         # the dense step of _forward_inference
                 node_rows = torch.stack([row_of, torch.zeros_like(row_of)], 1).to(torch.int32).contiguous()
                 hidden, a_s = engine.dense_fwd(agg, hidden, prev_idx, d, layer.W_h.weight, model.act_name, model.gate,
@@ -1906,6 +1929,150 @@ def rescore(rd, model, keep=None, mode="test"):
                 reached[row_of] = True
             keys_prev = keys
     return Rescore(score=score, reached=reached, live=live, alpha=alpha)
+
+
+def _segment_sums(values, group, n_groups):
+    """float32 [n_groups]: the sum of ``values`` per ``group`` (int64, never decreasing), each group's values added in a fixed order -
+    laid out as one matrix row per group and summed along it, no atomics: the same bits on every run."""
+    out = torch.zeros(n_groups, dtype=torch.float32, device=values.device)
+    if values.numel() == 0:
+        return out
+    counts = torch.bincount(group, minlength=n_groups)
+    first = torch.cumsum(counts, 0) - counts
+    m = torch.zeros((n_groups, int(counts.max())), dtype=torch.float32, device=values.device)
+    m[group, torch.arange(group.numel(), device=group.device) - first[group]] = values
+    return m.sum(1)
+
+
+@dataclass
+class Saliency:
+    """The gradient of an answer's score with respect to a gate on every edge of its r-digraph (RDigraph.saliency).  Tensors on the
+    digraph's device.
+
+    score      float32 [B]  the model's score of o on the kept digraph, exactly 0 where o is not reached     (as Rescore's)
+    reached    bool [B]     o has a length-L walk from s through kept edges
+    live       bool [E]     the edge is kept and its head is visited at hop - 1; only live edges carry messages
+    alpha      float32 [E]  the attention on the kept digraph, 0 for dead edges
+    edge_grad  float32 [E]  d score(o of the edge's row) / d g_e at g == 1, g_e multiplying the edge's message; exactly 0 for dead
+                            edges and for the rows that are not reached
+    digraph    RDigraph     the digraph the edges are those of
+    """
+    score: torch.Tensor
+    reached: torch.Tensor
+    live: torch.Tensor
+    alpha: torch.Tensor
+    edge_grad: torch.Tensor
+    digraph: RDigraph
+
+    def fact_grad(self, inverse_offset=None):
+        """(row int64 [F], fact int64 [F, 3] = (h, r, t) with r < n_rel, grad float32 [F]) ordered by (row, h, r, t): ``edge_grad``
+        summed over all copies of a base fact in its row - the edge (h, r, t) and its twin (t, r + n_rel, h), at every hop; the
+        identity relation 2 * n_rel is no fact.  RDigraph.fact_mask's grouping rule: to first order the score of the row changes by
+        -grad when the fact is deleted.  ``inverse_offset`` is fact_mask's: a static digraph knows its inverses and takes None."""
+        rd = self.digraph
+        E, _ = _check_static_digraph(rd, "fact_grad")
+        if inverse_offset is not None:
+            raise ValueError("fact_grad: inverse_offset is for temporal r-digraphs; a static one knows its inverses (r + n_rel)")
+        n_rel, dev = int(rd.n_rel), rd.edges.device
+        e = rd.edges.long()
+        e = e[e[:, 3] != 2 * n_rel]
+        if e.shape[0] == 0:
+            return (torch.zeros(0, dtype=torch.int64, device=dev), torch.zeros((0, 3), dtype=torch.int64, device=dev),
+                    torch.zeros(0, dtype=torch.float32, device=dev))
+        inv = e[:, 3] >= n_rel
+        h, r, t = torch.where(inv, e[:, 4], e[:, 2]), torch.where(inv, e[:, 3] - n_rel, e[:, 3]), torch.where(inv, e[:, 2], e[:, 4])
+        n_key = int(max(h.max(), t.max())) + 1
+        key = ((e[:, 0] * n_key + h) * n_rel + r) * n_key + t
+        key, order = torch.sort(key, stable=True)                         # copies of a fact in edge order: a fixed order of the sum
+        keys, group = torch.unique_consecutive(key, return_inverse=True)
+        grad = _segment_sums(self.edge_grad[rd.edges[:, 3].long() != 2 * n_rel][order], group, keys.numel())
+        t_, rest = keys % n_key, keys // n_key
+        r_, rest = rest % n_rel, rest // n_rel
+        return rest // n_key, torch.stack([rest % n_key, r_, t_], 1), grad
+
+    def top(self, k):
+        """The k facts of every row with the largest |grad| (fact_grad), largest first, ties in (h, r, t) order: (fact int64 [B, k, 3],
+        grad float32 [B, k], count int64 [B]); -1 and 0 where the row has fewer than k facts."""
+        _check_count(k, "top", "k")
+        k, B, dev = int(k), self.score.numel(), self.edge_grad.device
+        row, fact, grad = self.fact_grad()
+        order = torch.sort(-grad.abs(), stable=True).indices
+        order = order[torch.sort(row[order], stable=True).indices]        # by row, inside a row by |grad| descending
+        row, fact, grad = row[order], fact[order], grad[order]
+        total = torch.bincount(row, minlength=B)
+        rank = torch.arange(row.numel(), device=dev) - (torch.cumsum(total, 0) - total)[row]
+        sel = rank < k
+        out_f = torch.full((B, k, 3), -1, dtype=torch.int64, device=dev)
+        out_g = torch.zeros((B, k), dtype=torch.float32, device=dev)
+        out_f[row[sel], rank[sel]] = fact[sel]
+        out_g[row[sel], rank[sel]] = grad[sel]
+        return out_f, out_g, total.clamp(max=k)
+
+    def deletion_estimate(self, mask):
+        """float32 [B]: score - the sum of ``edge_grad`` over the live edges of ``mask`` (bool or uint8 [E]) per row, the first-order
+        estimate of ``rescore(keep=~mask).score``: every gate of the mask taken from 1 to 0 along the tangent."""
+        rd = self.digraph
+        E = self.edge_grad.numel()
+        mask = _check_keep("deletion_estimate", mask, E, self.edge_grad.device)
+        if mask is None:
+            raise ValueError("deletion_estimate: mask must be bool or uint8 [%d], one per edge (got None)" % E)
+        gone = mask.bool() & self.live
+        return self.score - _segment_sums(torch.where(gone, self.edge_grad, torch.zeros_like(self.edge_grad)), rd.edges[:, 0].long(),
+                                          self.score.numel())
+
+    def format(self, id2rel=None, k=3):
+        """One line per row: the score (``x``: o is not reached), then the row's ``k`` facts of largest |grad| as (h, relation, t)
+        with their gradient; ``id2rel`` names the relations."""
+        fact, grad, count = (t.cpu().tolist() for t in self.top(k))
+        sc, ok = self.score.cpu().tolist(), self.reached.cpu().tolist()
+        name = lambda r: str(id2rel[r]) if id2rel is not None else "r%d" % r
+        return ["row %d: score %s  %s" % (b, "%.4f" % sc[b] if ok[b] else "x",
+                                         "  ".join("(%d, %s, %d) %+.4f" % (f[0], name(f[1]), f[2], g)
+                                                   for f, g in zip(fact[b][:count[b]], grad[b])))
+                for b in range(len(sc))]
+
+
+def saliency(rd, model, keep=None, mode="test"):
+    """RDigraph.saliency (see there): _rescore_static with a tape, then the hops backwards."""
+    from .models import gru_step, tall_linear
+    tape = []
+    rs = _rescore_static(rd, model, keep, mode, "saliency", tape)
+    dev, L = rd.edges.device, int(rd.n_hops)
+    d, a = model.hidden_dim, model.attn_dim
+    ld, ap = max(16, _pad4(d)), pad_attn(a)
+    edge_grad = torch.zeros(rd.edges.shape[0], dtype=torch.float32, device=dev)
+    if len(tape) < L:                                                     # no row reaches its answer: nothing depends on any edge
+        return Saliency(score=rs.score, reached=rs.reached, live=rs.live, alpha=rs.alpha, edge_grad=edge_grad, digraph=rd)
+    gate = types.SimpleNamespace(**{name: getattr(model.gate, name).detach()
+                                    for name in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")})
+    g_hidden = g_a_s = None                                               # d (sum of the scores) / d (the hop's new state, its projection)
+    for t in reversed(tape):
+        l = t["l"]
+        layer, last, first = model.gnn_layers[l - 1], t["l"] == L, t["l"] == 1
+        # ---- the dense step's adjoint: _rescore_static's tall_linear / gru_step branch re-run on the hop's sums, parameters detached
+        with torch.enable_grad():
+            agg = t["agg"].detach().requires_grad_(True)
+            prev = t["hidden"].detach().requires_grad_(not first)        # hop 1 reads the constant 0
+            x = layer.act(tall_linear(agg[:, :d], layer.W_h.weight.detach()))
+            h0 = torch.zeros((agg.shape[0], d), device=dev)
+            h0[t["had"]] = prev[:, :d][t["prev_idx"][t["had"]].long()]
+            hid = gru_step(x, h0, gate)
+            if last:
+                outs, seeds = [tall_linear(hid, model.W_final.weight.detach()).squeeze(-1)], [torch.ones(agg.shape[0], device=dev)]
+            else:
+                w_s = model.gnn_layers[l].Ws_attn.weight.detach()
+                outs = [F.pad(hid, (0, ld - d)) if ld != d else hid, tall_linear(hid, F.pad(w_s, (0, 0, 0, ap - a)) if ap != a else w_s)]
+                seeds = [g_hidden, g_a_s]
+            grads = torch.autograd.grad(outs, [agg] if first else [agg, prev], seeds)
+        # ---- the edge-list layer's, in HIP
+        gate_grad, g_hidden, g_a_s = engine.digraph_layer_bwd(
+            t["dst_ptr"], t["src"], t["rel"], t["row_of"], t["hidden"], t["rela"], d, t["a_s"], t["a_r"], t["a_q"],
+            layer.w_alpha.weight.detach().reshape(-1).contiguous(), layer.w_alpha.bias.detach().contiguous(), a, grads[0].contiguous(),
+            want_state=not first)
+        edge_grad[t["at"]] = gate_grad
+        if not first:
+            g_hidden = g_hidden + grads[1]                                # the carry: the state also enters the next GRU step as h0
+    return Saliency(score=rs.score, reached=rs.reached, live=rs.live, alpha=rs.alpha, edge_grad=edge_grad, digraph=rd)
 
 
 def _fidelity_of(rd, model, k, loops, mode, inverse_offset=None):

@@ -573,6 +573,14 @@ class RED_GNN_trans(nn.Module):
         [B, ap] (models.py:33,36, the three attention Linear layers hoisted), rela_i padded to ld columns."""
         return engine.attn_tables(list(self.gnn_layers), q_rel.contiguous(), self.hidden_dim, ld, self.attn_dim, ap)
 
+    def saliency(self, subs, rels, objs=None, mode="test"):
+        """How much the score of o depends on every fact of its r-digraph, in one pass: ``explain`` followed by RDigraph.saliency -
+        the gradient of the score with respect to a gate on every edge's message (the edge-list layer's adjoint in HIP,
+        rg_digraph_layer_bwd).  Returns an explain.Saliency (device tensors): ``edge_grad`` per edge of ``.digraph``, ``fact_grad()`` /
+        ``top(k)`` per fact, ``deletion_estimate(mask)`` the first-order estimate of a rescore.  ``objs=None``: each row's own top
+        answer, as explain.  Eval semantics; the parameters get no gradient.  (Kept below _run: tests cite that function's lines.)"""
+        return self.explain(subs, rels, objs, mode=mode).saliency(self, mode=mode)
+
     def _forward_graphed(self, graph, q_sub, q_rel, n, device):
         """Replay (or, on the third call with the same graph and batch size, capture) the forward as a HIP graph.
         Returns None when this call should run eagerly: the first two calls of a shape (the eager run also provides the
@@ -680,6 +688,9 @@ class RED_GNN_induc(RED_GNN_trans):
 
     def fidelity(self, subs, rels, objs=None, k=4, mode="transductive"):
         return super().fidelity(subs, rels, objs=objs, k=k, mode=mode)
+
+    def saliency(self, subs, rels, objs=None, mode="transductive"):
+        return super().saliency(subs, rels, objs=objs, mode=mode)
 
     def rule_quality(self, table, mode="transductive", sources=None, scratch_bytes=engine.RULE_SCRATCH_BYTES):
         return super().rule_quality(table, mode=mode, sources=sources, scratch_bytes=scratch_bytes)
