@@ -170,10 +170,16 @@ int rg_frontier_edges(const rg_frontier* f, const rg_graph* g, int32_t level,
  *      and a_s are read at row b of query b.  Any other level or frontier: an error.  What walk 0 runs whenever it applies.
  * rg_layer_fwd_plan returns what walk 0 would pick among the general walks 1 .. 7 for given sizes (n_old, n_new nodes, n_edges of the
  * hop), and rg_layer_fwd_single_source whether walk 8 applies to `level` (1 or 0), which walk 0 then takes ahead of that plan: callers
- * that enqueue without read-backs (rg_frontier_expand_async) record the code from an eager run and pass it explicitly. */
+ * that enqueue without read-backs (rg_frontier_expand_async) record the code from an eager run and pass it explicitly.
+ * rg_layer_fwd_wp_tickets returns the work items a wave takes per queue ticket (1 .. 32) that rg_layer_fwd would give the word-parallel
+ * walk `walk` (2 .. 7) on `level` if called now - sized from the hop's edge count as the frontier holds it (known after
+ * rg_frontier_expand, else the value of rg_frontier_set_edge_hint, else unknown) - and the walk's number of work items in *n_items_out
+ * (may be NULL); 0 (and 0 items) for a walk that takes no such tickets (0, 1, 8) or a graph without packed entries.  It steers
+ * speed only; tests read it to know which ticket sizes they ran. */
 size_t rg_layer_fwd_scratch_bytes(const rg_frontier* f, const rg_graph* g, int32_t ld);
 int rg_layer_fwd_plan(const rg_frontier* f, const rg_graph* g, int32_t level, int64_t n_old, int64_t n_new,
                       int64_t n_edges, int32_t ld);
+int rg_layer_fwd_wp_tickets(const rg_frontier* f, const rg_graph* g, int32_t level, int32_t walk, int64_t* n_items_out);
 int rg_layer_fwd_single_source(const rg_frontier* f, const rg_graph* g, int32_t level);
 int rg_layer_fwd(const rg_frontier* f, const rg_graph* g, int32_t level, int64_t n_new,
                  const float* hidden, const float* rela, int32_t d, int32_t ld,

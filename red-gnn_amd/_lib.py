@@ -15,7 +15,7 @@ SYMBOLS = [
     "rg_graph_create", "rg_graph_create_device", "rg_graph_export_packs", "rg_tgraph_create", "rg_tgraph_create_excluding", "rg_graph_destroy", "rg_graph_n_fact", "rg_graph_export", "rg_graph_export_out_by_tail",
     "rg_frontier_workspace_bytes", "rg_frontier_create", "rg_frontier_destroy", "rg_frontier_reset",
     "rg_frontier_reset_nodes", "rg_frontier_expand", "rg_frontier_nodes", "rg_frontier_edges_scratch_bytes", "rg_frontier_edges",
-    "rg_layer_fwd_scratch_bytes", "rg_layer_fwd", "rg_layer_fwd_plan", "rg_layer_fwd_single_source", "rg_tlayer_fwd", "rg_xlayer_fwd", "rg_frontier_set_window", "rg_layer_bwd_scratch_bytes", "rg_layer_bwd", "rg_tlayer_bwd_scratch_bytes", "rg_tlayer_bwd", "rg_xlayer_bwd", "rg_dense_fwd_supported", "rg_dense_scratch_bytes", "rg_dense_fwd", "rg_dense_fwd_dev", "rg_dense_train_fwd", "rg_dense_train_fwd_as", "rg_rows_addmm", "rg_dense_train_bwd", "rg_dense_train_bwd2", "rg_split3_roundtrip", "rg_split3_product_check", "rg_gram_tn_scratch_bytes", "rg_gram_tn", "rg_rank",
+    "rg_layer_fwd_scratch_bytes", "rg_layer_fwd", "rg_layer_fwd_plan", "rg_layer_fwd_wp_tickets", "rg_layer_fwd_single_source", "rg_tlayer_fwd", "rg_xlayer_fwd", "rg_frontier_set_window", "rg_layer_bwd_scratch_bytes", "rg_layer_bwd", "rg_tlayer_bwd_scratch_bytes", "rg_tlayer_bwd", "rg_xlayer_bwd", "rg_dense_fwd_supported", "rg_dense_scratch_bytes", "rg_dense_fwd", "rg_dense_fwd_dev", "rg_dense_train_fwd", "rg_dense_train_fwd_as", "rg_rows_addmm", "rg_dense_train_bwd", "rg_dense_train_bwd2", "rg_split3_roundtrip", "rg_split3_product_check", "rg_gram_tn_scratch_bytes", "rg_gram_tn", "rg_rank",
     "rg_frontier_expand_async", "rg_frontier_expand_nodes_async", "rg_frontier_set_edge_hint", "rg_frontier_count_ptr", "rg_frontier_level_counts", "rg_attn_tables",
     "rg_explain_scratch_bytes", "rg_explain_seed", "rg_explain_count", "rg_explain_emit", "rg_explain_gather",
     "rg_topk",
@@ -93,6 +93,7 @@ def lib():
     L.rg_layer_fwd_scratch_bytes.restype = sz
     L.rg_layer_fwd.argtypes = [vp, vp, i32, i64, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp, sz, i32, vp]
     L.rg_layer_fwd_plan.argtypes = [vp, vp, i32, i64, i64, i64, i32]
+    L.rg_layer_fwd_wp_tickets.argtypes = [vp, vp, i32, i32, C.POINTER(i64)]
     L.rg_layer_fwd_single_source.argtypes = [vp, vp, i32]
     L.rg_tlayer_fwd.argtypes = [vp, vp, i32, i64, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp, sz, vp]
     L.rg_xlayer_fwd.argtypes = [vp, vp, i32, i64, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp, sz, vp]

@@ -54,6 +54,23 @@ extern "C" int rg_layer_fwd_plan(const rg_frontier* f, const rg_graph* g, int32_
   return plan_general(f, g, level, n_old, n_new, n_edges, ld);
 }
 
+// items per queue ticket of the word-parallel walk `walk` (2 .. 7) on `level`, from the hop's edge count as the frontier holds it now
+// (n_edges after rg_frontier_expand, else the caller's edge_hint, else unknown); *n_items_out = the walk's work space.
+// A ticket is a returning atomic: about 200 edges' worth of items each (light items: hop 0; heavy ones are taken one by one)
+static int32_t wp_tickets(const rg_frontier* f, const rg_graph* g, int32_t level, int32_t walk, int64_t* n_items_out) {
+  const int64_t n_items = (int64_t)f->BW * (1 << (walk - 2)) * g->in_pk_packs.n;
+  if (n_items_out) *n_items_out = n_items;
+  const int64_t n_e = level == f->level ? (f->n_edges >= 0 ? f->n_edges : f->edge_hint) : -1;
+  const int64_t by_work = n_e < 0 ? 2 : 200 * n_items / std::max<int64_t>(n_e, 1);
+  return (int32_t)std::max<int64_t>(std::min<int64_t>(std::min<int64_t>(by_work, n_items / 8192), 32), 1);   // ... and never fewer tickets than waves
+}
+
+extern "C" int rg_layer_fwd_wp_tickets(const rg_frontier* f, const rg_graph* g, int32_t level, int32_t walk, int64_t* n_items_out) {
+  if (n_items_out) *n_items_out = 0;
+  if (!f || !g || walk < 2 || walk > 7 || g->in_pk_packs.n == 0) return 0;
+  return wp_tickets(f, g, level, walk, n_items_out);
+}
+
 extern "C" int rg_layer_fwd(const rg_frontier* f, const rg_graph* g, int32_t level, int64_t n_new, const float* hidden,
                             const float* rela, int32_t d, int32_t ld, const float* a_s, const float* a_r,
                             const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha, int32_t attn_dim,
@@ -98,17 +115,13 @@ extern "C" int rg_layer_fwd(const rg_frontier* f, const rg_graph* g, int32_t lev
     rgwp::WpArgs W;
     W.n_sub = 1 << (walk - 2);
     W.n_packs = g->in_pk_packs.n; W.BW = f->BW; W.W = f->W; W.n_slots = g->in_vr.n_slots;
-    W.n_items = (int64_t)f->BW * W.n_sub * W.n_packs;
+    W.ipt = wp_tickets(f, g, level, walk, &W.n_items);
     W.ent = g->in_pk_packs.ent; W.pack = g->in_pk_packs.pack; W.rows = g->in_pk_packs.rows;
     W.bits_old = f->bitsT[f->tcur ^ 1]; W.bits_new = f->bitsT[f->tcur];
     W.bm_old = A.bm_old; W.bm_new = A.bm_new;
     W.hidden = A.hidden; W.rela = A.rela; W.ld4 = A.ld4; W.a_s = A.a_s; W.a_r = A.a_r; W.a_q = A.a_q;
     W.w_alpha = w_alpha; W.b_alpha = b_alpha; W.attn_dim = attn_dim; W.n_rela_rows = g->n_rela_rows;
     W.agg = A.agg; W.partial = A.partial; W.queues = f->queues; W.queues_clean = A.walk.queues_clean;
-    // a ticket is a returning atomic: about 200 edges' worth of items each (light items: hop 0; heavy ones are taken one by one)
-    const int64_t n_e = level == f->level ? (f->n_edges >= 0 ? f->n_edges : f->edge_hint) : -1;
-    const int64_t by_work = n_e < 0 ? 2 : 200 * W.n_items / std::max<int64_t>(n_e, 1);
-    W.ipt = (int32_t)std::max<int64_t>(std::min<int64_t>(std::min<int64_t>(by_work, W.n_items / 8192), 32), 1);   // ... and never fewer tickets than waves
     const size_t n_part = (size_t)f->B * g->in_vr.n_slots;
     W.written = n_part ? (uint8_t*)scratch + rg::align_up(n_part * ld * sizeof(float), 256) : nullptr;
     if (n_part && rg::zero_async(W.written, rg::align_up(n_part, 256), s)) return 1;

@@ -1944,3 +1944,9 @@ def xrule_apply(graph, head, body, lag_lo, lag_hi, weight, subs, rels, days, row
         return _lib.lib().rg_xrule_apply(graph.handle, *a[:9], p(day_d), n_data, p(wl_d), p(wh_d), n_day, int(loop_window), *a[9:12],
                                          p(dp_d), p(do_d), p(ds_d), day_of.shape[0], *a[12:])
     return _apply_chunks("xrule_apply", "XRULE_APPLY_EVENTS", graph, (h, b, lo, hi), w, s[order], order, q_ptr, words, scratch_bytes, entry)
+
+
+def layer_fwd_wp_tickets(frontier, graph, level, walk):
+    """(items per queue ticket, work items) rg_layer_fwd would give the word-parallel walk ``walk`` on this hop now (rg_layer_fwd_wp_tickets)."""
+    n_items = C.c_int64()
+    return int(_lib.lib().rg_layer_fwd_wp_tickets(frontier.handle, graph.handle, level, walk, C.byref(n_items))), int(n_items.value)

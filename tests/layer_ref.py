@@ -477,6 +477,13 @@ CASES = {
     "b32_e1000": lambda: _case("b32_e1000", seed=28, B=32, n_ent=1000, m=3000),
     "b65_e97": lambda: _case("b65_e97", seed=29, B=65, n_ent=97, m=400),
     "b33_e1000": lambda: _case("b33_e1000", seed=30, B=33, n_ent=1000, m=3000),
+    # ---- tickets of more than one item in the word-parallel walk (layer_fwd.hip wp_tickets: items per ticket = min(200 n_items / E,
+    # n_items / 8192, 32), n_items = BW * n_sub * n_packs: every other case has n_items < 8192, i.e. 1): BW = 32 and >= 317 packs allow
+    # 1, 2, 4, 9, 19 (or more) on walks 2 .. 6 and reach the cap of 32 at walk 7 (>= 324 k items; layer_fwd_wp.hip resolve: the partial tail
+    # ticket, launch4: the grid).  B * W = 16384 frontier words > SMALL_MAX_WORDS (frontier.hip enqueue_expand: the general level build).
+    # One hop (n_new 65931, E 82760); the d 48 twin runs launch3's non-EXACT instance
+    "tickets": lambda: _case("tickets", seed=41, n_ent=500, n_rel=5, m=20000, B=1024, hops=1, d=64),
+    "tickets_d48": lambda: _case("tickets_d48", seed=41, n_ent=500, n_rel=5, m=20000, B=1024, hops=1, d=48),
     # ---- layer kind
     "temporal": lambda: _temporal_case("temporal", seed=32),
     "windowed": lambda: _windowed_case("windowed", seed=33),

@@ -22,7 +22,7 @@ pytestmark = pytest.mark.gpu
 # assertion uses C_BOUND)
 KERNEL_RATIOS = {"agg": 0.391, "grad_hidden": 0.193, "grad_rela": 0.23, "grad_time": 0.173, "grad_a_s": 0.0078, "grad_a_r": 0.0091,
                  "grad_a_q": 0.0078, "grad_w_alpha": 3.1e-4, "grad_b_alpha": 3.2e-4}
-# wall time of this file on an MI355X: 4.8 s (39 tests)
+# wall time of this file on an MI355X: 5.4 s (41 tests)
 
 KEYS = ("hidden", "rela", "time_tab", "a_s", "a_r", "a_q", "w_alpha", "b_alpha")
 

@@ -134,6 +134,17 @@ def test_table_covers_what_it_names():
         c = lr.CASES[name]()
         e = np.concatenate([h[2] for h in lr.hops(c)], 0)
         assert c.n_rela_rows in (4101, 4095) and (e[:, 2] == c.n_rela_rows - 1).any() and (e[:, 2] >= c.n_rel).any()
+    for name in ("tickets", "tickets_d48"):
+        c = lr.CASES[name]()
+        og = lr.oracle_graph(c)
+        (_, _, _, h), = lr.hops(c)
+        indeg = np.bincount(og.KG[:, 2], minlength=c.n_ent)
+        bw, packs = (c.B + 31) // 32, -(-len(og.KG) // 128)      # (at least: a pack holds whole rows or segments, 128 entries at most)
+        assert (len(og.KG), bw, h.n_new, h.E) == (40514, 32, 65931, 82760) and c.d == (64 if name == "tickets" else 48) == c.ld
+        assert sorted(indeg[indeg > 128].tolist()) == [2069, 2075]      # two cut rows: partial sums and their `written` bytes
+        # items per ticket the work space allows (layer_fwd.hip wp_tickets: n_items / 8192, at most 32), walks 2 .. 7
+        assert [min(bw * (1 << (w - 2)) * packs // 8192, 32) for w in range(2, 8)] == [1, 2, 4, 9, 19, 32]
+        assert c.B * ((c.n_ent + 31) // 32) == 16384 > 12288      # frontier.hip SMALL_MAX_WORDS
     s = lr.CASES["saturated"]()
     h = lr.hops(s)[1][3]
     x = lr.inputs(s, 1, h)
