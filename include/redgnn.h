@@ -483,7 +483,7 @@ int rg_digraph_tlayer_fwd(int32_t n_dst, int64_t n_edges, const int32_t* dst_ptr
                           const float* w_alpha, const float* b_alpha, int32_t attn_dim, float* agg_out, float* alpha_out, void* scratch,
                           size_t scratch_bytes, void* stream);
 
-/* ---- the adjoint of one rg_digraph_layer_fwd hop (static form only) with respect to a gate on every edge, the source states and
+/* ---- the adjoint of one rg_digraph_layer_fwd hop (static form; the timed forms follow) with respect to a gate on every edge, the source states and
  * their attention projection (csrc/digraph_bwd.hip; explain.RDigraph.saliency).  With a gate g_e on the message of edge e,
  * agg[o] = sum_e g_e alpha_e (hidden[s] + rela[r]), the call returns the gradients at g == 1 of a scalar whose gradient with respect
  * to agg is grad_agg [n_dst, ld].  rela, a_r, a_q, w_alpha and b_alpha are CONSTANTS here: there are no parameter gradients, and the
@@ -513,6 +513,30 @@ int rg_digraph_layer_bwd(int32_t n_src, int32_t n_dst, int64_t n_edges, const in
                          const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha,
                          int32_t attn_dim, const float* grad_agg, float* grad_gate, float* grad_hidden, float* grad_a_s, void* scratch,
                          size_t scratch_bytes, void* stream);
+
+/* ---- ... of one rg_digraph_tlayer_fwd hop: the timed forms (n_dir = 3, temporal interpolation; n_dir = 1, the extrapolation form).
+ * Everything rg_digraph_layer_bwd states holds - the same kernel with the time path compiled in, the same split rule and argument
+ * checks, plus the forward's (n_dir 1 or 3, n_time > 0, three rows per source and relation within int32) - with these differences.
+ * The message is m_e = hidden[hrow] + (rela[rrow] + time_tab[trow]), the rows formed exactly as rg_digraph_tlayer_fwd forms them
+ * from edge_time int32 [n_edges] (by position in the destination-ordered list) and q_time int32 [batch]: 64-bit differences, |dt|
+ * clamped to n_time - 1, the n_dir = 1 lag clamped to 0 .. n_time - 1; alpha_e reads the un-directed s and r (pass b_alpha = 0).
+ *   g_alpha = <G[o], m_e>
+ *   grad_gate[e]        = alpha_e * g_alpha
+ *   grad_hidden[hrow]  += alpha_e * G[o]                                       [n_dir * n_src, ld]
+ *   grad_a_s_dir[hrow] += g_alpha * alpha_e * (1 - alpha_e) * w * 1[pre > 0]   [n_dir * n_src, ap]: the caller adds a source's n_dir rows
+ * The work item is a DIRECTED source row u = n_dir * s + dir (dir = 0 for n_dir = 1), and the source view is segmented by it:
+ * src_ptr [n_dir * n_src + 1] (and src_ptr_host), edge_of the stable sort of the edges by u.  hidden has n_dir * n_src rows, rela
+ * n_dir * n_rela_rows, time_tab n_dir * n_time, a_s n_src and a_r n_rela_rows.  The kernel forms an edge's direction again from its
+ * times for rrow and trow, every index clamped into its table.  A directed row without edges is written as zeros; chunks are counted
+ * per directed row.  scratch: rg_digraph_layer_bwd_scratch_bytes(src_ptr_host, n_dir * n_src, ld, ap) - the function only reads the
+ * CSR it is handed, so it serves both forms with the number of rows of that CSR. */
+int rg_digraph_tlayer_bwd(int32_t n_src, int32_t n_dst, int64_t n_edges, const int32_t* src_ptr, const int32_t* src_ptr_host,
+                          const int32_t* edge_of, const int32_t* dst_of_edge, const int32_t* rel, const int32_t* edge_time,
+                          const int32_t* row_of_dst, const int32_t* q_time, int32_t n_rela_rows, int32_t batch, int32_t n_time,
+                          int32_t n_dir, const float* hidden, const float* rela, const float* time_tab, int32_t d, int32_t ld,
+                          const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha,
+                          int32_t attn_dim, const float* grad_agg, float* grad_gate, float* grad_hidden, float* grad_a_s_dir,
+                          void* scratch, size_t scratch_bytes, void* stream);
 
 /* ---- the per-hop index of an edited r-digraph: the arrays rg_digraph_(t)layer_fwd takes, built from the digraph's own edge list
  * under a keep mask (csrc/digraph_index.hip; explain.RDigraph.rescore of an extrapolation digraph).  edges int32 [n_edges, 5] =

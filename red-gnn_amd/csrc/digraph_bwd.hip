@@ -29,7 +29,18 @@
 // an r-digraph is the case: a row's only source is its subject, with every hop-1 edge.  No float atomics: the sums of a source are
 // formed in list order inside a chunk and in chunk order across chunks, so every output has the same bits on every run and does not
 // depend on what else the call carries.
+//
+// The timed form (rg_digraph_tlayer_bwd, template parameter TIMED; the static instantiation compiles to what it did without it), the
+// adjoint of rg_digraph_tlayer_fwd: the message is hidden[hrow] + (rela[rrow] + time_tab[trow]) with the rows digraph_fwd_kernel<...,
+// TIMED> forms (64-bit differences, |dt| clamped to n_time - 1, the n_dir = 1 lag clamped to 0 .. n_time - 1), alpha_e read from the
+// un-directed s and r.  The work item is a DIRECTED source row u - u = 3 s + dir for n_dir = 3, u = s for n_dir = 1 - and the
+// source-segmented view is sorted, stably, by u: src_ptr [n_dir * n_src + 1].  An item then loads one state row, hidden[u], and one
+// attention row, a_s[u / n_dir], and keeps one acc_h as the static kernel does; a source whose edges span three directions is three
+// items, and grad_a_s_dir [n_dir * n_src, ap] has a row per item (the caller adds a source's three).  The edge's direction is formed
+// again per edge for rrow and trow (it is not taken from u, so an inconsistent view reads other rows, never out of bounds); the time
+// table's gather is the only added traffic.  The split rule counts chunks per directed row.
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "attn.h"
@@ -66,10 +77,19 @@ struct DbArgs {
   float4* partial_as;          // [n_chunks, AP4]
 };
 
+// what the timed form (rg_digraph_tlayer_bwd) reads on top: kept apart so that the static kernel's arguments stay what they were.  There
+// n_src counts the DIRECTED source rows (the rows of hidden and of both state outputs).
+struct DbTimedArgs : DbArgs {
+  const int32_t* edge_time;    // [E], in the order of the destination-ordered list
+  const int32_t* q_time;       // [B]
+  const float4* time_tab;      // [n_dir * n_time, ld]
+  int n_time, n_dir;           // n_dir 3: interpolation (rows by direction), 1: extrapolation form (one table of lags)
+};
+
 __device__ __forceinline__ int clampi(int x, int hi) { return min(max(x, 0), hi); }
 
-template <int G, int AP4>
-__global__ __launch_bounds__(DB_BLOCK) void digraph_bwd_kernel(DbArgs A) {
+template <int G, int AP4, bool TIMED>
+__global__ __launch_bounds__(DB_BLOCK) void digraph_bwd_kernel(std::conditional_t<TIMED, DbTimedArgs, DbArgs> A) {
   constexpr int PER_WAVE = 64 / G;
   const int lane = threadIdx.x & 63;
   const int lane_g = lane & (G - 1), gbase = lane & ~(G - 1);
@@ -97,7 +117,9 @@ __global__ __launch_bounds__(DB_BLOCK) void digraph_bwd_kernel(DbArgs A) {
   }
   const float b_alpha = A.b_alpha[0];
   const float4 hv = A.hidden[(int64_t)s * A.ld4 + lane_c];
-  const float4* as_p = A.a_s + (int64_t)s * AP4;
+  const float4* as_p;
+  if constexpr (TIMED) as_p = A.a_s + (int64_t)(s / A.n_dir) * AP4;      // the attention reads the un-directed source
+  else as_p = A.a_s + (int64_t)s * AP4;
 
   float4 acc_h = rg::f4zero();
   float4 acc_as[AP4];
@@ -107,16 +129,18 @@ __global__ __launch_bounds__(DB_BLOCK) void digraph_bwd_kernel(DbArgs A) {
     // ---- one edge per lane: indices, the attention scalar and the sign bits of its pre-activation ---------------
     const int c = c0 + lane_g;
     const bool valid = c < end;
-    int e = 0, o = 0, r = 0;
+    int e = 0, o = 0, r = 0, trow = 0;
     unsigned pos = 0;                                    // bit 4k + u: component 4k + u of (a_s + a_r) + a_q is > 0
     float alpha = 0.f;
     if (valid) {
       e = clampi(A.edge_of[c], A.E - 1);
       o = clampi(A.dst_of_edge[e], A.n_dst - 1);
       r = clampi(A.rel[e], A.n_rela_rows - 1);
-      const float4* aq_p = A.a_q + (int64_t)clampi(A.row_of_dst[o], A.B - 1) * AP4;
+      const int b = clampi(A.row_of_dst[o], A.B - 1);
+      const float4* aq_p = A.a_q + (int64_t)b * AP4;
       float z = b_alpha;
-#pragma clang loop unroll_count(AP4 >= 8 ? 2 : AP4)
+      // (the timed form holds five more pointers and sizes in scalar registers: unrolled four times it would spill them at AP4 = 4)
+#pragma clang loop unroll_count(AP4 >= (TIMED ? 4 : 8) ? 2 : AP4)
       for (int k = 0; k < AP4; ++k) {
         const float4 as = as_p[k], ar = A.a_r[(int64_t)r * AP4 + k], aq = aq_p[k];
         rg::attn_acc_fwd(z, rg::attn_w4(A.w_alpha, A.attn_dim, k), as, ar, aq);
@@ -124,12 +148,25 @@ __global__ __launch_bounds__(DB_BLOCK) void digraph_bwd_kernel(DbArgs A) {
                (unsigned)(as.z + ar.z + aq.z > 0.f) << (4 * k + 2) | (unsigned)(as.w + ar.w + aq.w > 0.f) << (4 * k + 3);
       }
       alpha = rg::attn_alpha(z);
+      if constexpr (TIMED) {
+        // the rows of the message, as digraph_fwd_kernel forms them (the attention above read the un-directed r); 64-bit
+        // differences, so that no pair of times overflows, and the time row clamped into its table
+        const int64_t et = A.edge_time[e], qt = A.q_time[b];
+        if (A.n_dir == 3) {
+          const int64_t dt = et - qt;
+          const int dir = dt > 0 ? 2 : (dt == 0 ? 1 : 0);
+          r = dir * A.n_rela_rows + r;
+          trow = dir * A.n_time + (int)min(dt < 0 ? -dt : dt, (int64_t)(A.n_time - 1));
+        } else {
+          trow = (int)min(max(qt - et, (int64_t)0), (int64_t)(A.n_time - 1));
+        }
+      }
     }
     const int cnt = min(max(end - c0, 0), G);
     // ---- the round's edges in order, every lane its float4 of the rows; four edges' gathers in flight -----------
     float g_alpha = 0.f;
     for (int j = 0; __any(j < cnt); j += 4) {
-      int ou[4], ru[4];
+      int ou[4], ru[4], tu[4];
       float al[4];
       float4 gv[4], rv[4];
 #pragma unroll
@@ -138,11 +175,19 @@ __global__ __launch_bounds__(DB_BLOCK) void digraph_bwd_kernel(DbArgs A) {
         ou[u] = __shfl(o, from, 64);
         ru[u] = __shfl(r, from, 64);
         al[u] = __shfl(alpha, from, 64);
+        if constexpr (TIMED) tu[u] = __shfl(trow, from, 64);
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u) gv[u] = A.grad_agg[(int64_t)ou[u] * A.ld4 + lane_c];
 #pragma unroll
       for (int u = 0; u < 4; ++u) rv[u] = A.rela[(int64_t)ru[u] * A.ld4 + lane_c];
+      if constexpr (TIMED) {             // rela[rrow] + time_tab[trow] first, then hidden: the forward's association
+        float4 tv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) tv[u] = A.time_tab[(int64_t)tu[u] * A.ld4 + lane_c];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { rv[u].x += tv[u].x; rv[u].y += tv[u].y; rv[u].z += tv[u].z; rv[u].w += tv[u].w; }
+      }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         float p = gv[u].x * (hv.x + rv[u].x);
@@ -221,11 +266,111 @@ void count_cuts(const int32_t* ptr, int32_t n_src, int64_t* n_hubs, int64_t* n_c
 size_t list_bytes(int64_t n_hubs, int64_t n_chunks) { return rg::align_up((size_t)(n_hubs + n_chunks) * sizeof(int4), 256); }
 size_t rows_bytes(int64_t n_chunks, int32_t width) { return rg::align_up((size_t)n_chunks * width * sizeof(float), 256); }
 
-template <int G, int AP4>
-int launch(const DbArgs& A, hipStream_t s) {
+template <int G, int AP4, bool TIMED>
+int launch(const std::conditional_t<TIMED, DbTimedArgs, DbArgs>& A, hipStream_t s) {
   const int64_t waves = rg::ceil_div(A.n_items, 64 / G);
-  hipLaunchKernelGGL((digraph_bwd_kernel<G, AP4>), dim3((unsigned)rg::ceil_div(waves, DB_BLOCK / 64)), dim3(DB_BLOCK), 0, s, A);
+  hipLaunchKernelGGL((digraph_bwd_kernel<G, AP4, TIMED>), dim3((unsigned)rg::ceil_div(waves, DB_BLOCK / 64)), dim3(DB_BLOCK), 0, s, A);
   RG_LAUNCH_CHECK();
+  return 0;
+}
+
+// the time arguments of rg_digraph_tlayer_bwd; nullptr: the static entry point
+struct TimeIn {
+  const int32_t* edge_time;
+  const int32_t* q_time;
+  const float* time_tab;
+  int32_t n_time, n_dir;
+};
+
+// both entry points: every check, then the chunk list, the layer launch and the combine launch.  n_rows: the rows of the source view,
+// of hidden and of the state outputs - n_src, or n_dir * n_src directed rows in the timed form.
+int run(const char* who, const TimeIn* T, int32_t n_src, int32_t n_dst, int64_t n_edges, const int32_t* src_ptr, const int32_t* src_ptr_host,
+        const int32_t* edge_of, const int32_t* dst_of_edge, const int32_t* rel, const int32_t* row_of_dst, int32_t n_rela_rows,
+        int32_t batch, const float* hidden, const float* rela, int32_t d, int32_t ld, const float* a_s, const float* a_r, const float* a_q,
+        int32_t ap, const float* w_alpha, const float* b_alpha, int32_t attn_dim, const float* grad_agg, float* grad_gate,
+        float* grad_hidden, float* grad_a_s, void* scratch, size_t scratch_bytes, void* stream) {
+  RG_CHECK(n_src >= 0 && n_dst >= 0 && n_edges >= 0 && n_edges < ((int64_t)1 << 31),
+           "%s: n_src=%d n_dst=%d n_edges=%lld (need 0 <= n_src, 0 <= n_dst, 0 <= n_edges < 2^31)", who, n_src, n_dst, (long long)n_edges);
+  RG_CHECK(n_rela_rows >= 0 && batch >= 0, "%s: n_rela_rows=%d batch=%d (negative size)", who, n_rela_rows, batch);
+  RG_CHECK(d > 0 && ld >= d && ld % 4 == 0 && ld <= 256, "%s: d=%d ld=%d (need ld%%4==0, d<=ld<=256)", who, d, ld);
+  RG_CHECK(attn_dim > 0 && ap >= attn_dim && ap % 4 == 0, "%s: attn_dim=%d ap=%d", who, attn_dim, ap);
+  if (T) {
+    RG_CHECK(T->n_dir == 1 || T->n_dir == 3, "%s: n_dir=%d (need 1 or 3)", who, T->n_dir);
+    RG_CHECK(T->n_time > 0 && (int64_t)T->n_dir * T->n_time < ((int64_t)1 << 31), "%s: n_time=%d (need a positive table size)", who,
+             T->n_time);
+    RG_CHECK((int64_t)3 * n_src < ((int64_t)1 << 31) && (int64_t)3 * n_rela_rows < ((int64_t)1 << 31),
+             "%s: n_src=%d n_rela_rows=%d (three rows each overflow int32)", who, n_src, n_rela_rows);
+  }
+  RG_CHECK((grad_hidden == nullptr) == (grad_a_s == nullptr), "%s: grad_hidden and grad_a_s come together or not at all", who);
+  if (n_src == 0) {
+    RG_CHECK(n_edges == 0, "%s: %lld edges without a source", who, (long long)n_edges);
+    return 0;
+  }
+  const int32_t n_rows = T ? T->n_dir * n_src : n_src;
+  RG_CHECK(src_ptr_host, "%s: NULL argument (src_ptr_host)", who);
+  RG_CHECK(src_ptr_host[0] == 0, "%s: src_ptr starts at %d, not 0", who, src_ptr_host[0]);
+  for (int32_t s = 0; s < n_rows; ++s)
+    RG_CHECK(src_ptr_host[s + 1] >= src_ptr_host[s], "%s: src_ptr decreases at source %d", who, s);
+  RG_CHECK(src_ptr_host[n_rows] == n_edges, "%s: src_ptr ends at %d, not at the number of edges %lld", who, src_ptr_host[n_rows],
+           (long long)n_edges);
+  if (n_edges == 0) return 0;                            // nothing to sum and nothing launched: the caller owns the outputs
+  RG_CHECK(src_ptr && edge_of && dst_of_edge && rel && row_of_dst && hidden && rela && a_s && a_r && a_q && w_alpha && b_alpha &&
+           grad_agg && grad_gate, "%s: NULL argument", who);
+  RG_CHECK(!T || (T->edge_time && T->q_time && T->time_tab), "%s: NULL argument (edge_time, q_time or time_tab)", who);
+  RG_CHECK(n_dst > 0 && n_rela_rows > 0 && batch > 0, "%s: edges but n_dst=%d n_rela_rows=%d batch=%d", who, n_dst, n_rela_rows, batch);
+  RG_CHECK((((uintptr_t)hidden | (uintptr_t)rela | (uintptr_t)a_s | (uintptr_t)a_r | (uintptr_t)a_q | (uintptr_t)grad_agg |
+             (uintptr_t)grad_hidden | (uintptr_t)grad_a_s | (uintptr_t)scratch | (uintptr_t)(T ? T->time_tab : nullptr)) & 15) == 0,
+           "%s: float buffers must be 16-B aligned", who);
+  int64_t n_hubs, n_chunks;
+  count_cuts(src_ptr_host, n_rows, &n_hubs, &n_chunks);
+  RG_CHECK((int64_t)n_rows + n_chunks < ((int64_t)1 << 31), "%s: %lld items overflow int32", who, (long long)(n_rows + n_chunks));
+  const size_t need = n_hubs ? list_bytes(n_hubs, n_chunks) + rows_bytes(n_chunks, ld) + rows_bytes(n_chunks, ap) : 0;
+  RG_CHECK(need == 0 || (scratch && scratch_bytes >= need), "%s: scratch %zu B < required %zu B", who, scratch ? scratch_bytes : (size_t)0,
+           need);
+
+  DbTimedArgs A;
+  A.n_src = n_rows; A.n_items = (int)(n_rows + n_chunks); A.E = (int)n_edges; A.n_dst = n_dst; A.n_rela_rows = n_rela_rows; A.B = batch;
+  A.src_ptr = src_ptr; A.edge_of = edge_of; A.dst_of_edge = dst_of_edge; A.rel = rel; A.row_of_dst = row_of_dst;
+  A.hidden = (const float4*)hidden; A.rela = (const float4*)rela; A.grad_agg = (const float4*)grad_agg; A.ld4 = ld / 4;
+  A.a_s = (const float4*)a_s; A.a_r = (const float4*)a_r; A.a_q = (const float4*)a_q;
+  A.w_alpha = w_alpha; A.b_alpha = b_alpha; A.attn_dim = attn_dim;
+  A.grad_gate = grad_gate; A.grad_hidden = (float4*)grad_hidden; A.grad_a_s = (float4*)grad_a_s;
+  A.edge_time = T ? T->edge_time : nullptr; A.q_time = T ? T->q_time : nullptr; A.time_tab = T ? (const float4*)T->time_tab : nullptr;
+  A.n_time = T ? T->n_time : 0; A.n_dir = T ? T->n_dir : 0;
+  int4* hubs_dev = (int4*)scratch;
+  A.chunks = hubs_dev + n_hubs;
+  A.partial_h = n_hubs ? (float4*)((char*)scratch + list_bytes(n_hubs, n_chunks)) : nullptr;
+  A.partial_as = n_hubs ? (float4*)((char*)A.partial_h + rows_bytes(n_chunks, ld)) : nullptr;
+  // every argument error is out before anything is enqueued: the width dispatch is probed first
+  if (rg::with_ap4(ap / 4, who, [](auto) { return 0; })) return 1;
+  hipStream_t s = (hipStream_t)stream;
+  if (n_hubs) {
+    std::vector<int4> list((size_t)(n_hubs + n_chunks));
+    int64_t h = 0, slot = 0;
+    for (int32_t v = 0; v < n_rows; ++v) {
+      const int32_t lo = src_ptr_host[v], hi = src_ptr_host[v + 1];
+      if (hi - lo <= DIGRAPH_CHUNK) continue;
+      const int n_c = (int)rg::ceil_div(hi - lo, DIGRAPH_CHUNK);
+      list[h++] = make_int4(v, (int)slot, n_c, 0);
+      for (int k = 0; k < n_c; ++k, ++slot)
+        list[n_hubs + slot] = make_int4(v, lo + k * DIGRAPH_CHUNK, std::min(hi, lo + (k + 1) * DIGRAPH_CHUNK), (int)slot);
+    }
+    // (a copy from pageable memory: the runtime is done with the vector when the call returns)
+    RG_HIP(hipMemcpyAsync(hubs_dev, list.data(), list.size() * sizeof(int4), hipMemcpyHostToDevice, s));
+  }
+  const int rc = rg::with_g(A.ld4, [&](auto g) {
+    return rg::with_ap4(ap / 4, who, [&](auto a4) {
+      if (T) return launch<decltype(g)::value, decltype(a4)::value, true>(A, s);
+      return launch<decltype(g)::value, decltype(a4)::value, false>(A, s);
+    });
+  });
+  if (rc) return rc;
+  if (n_hubs && grad_hidden) {
+    const int64_t threads = n_hubs * (A.ld4 + ap / 4);
+    hipLaunchKernelGGL(digraph_bwd_combine_kernel, dim3((unsigned)rg::ceil_div(threads, 256)), dim3(256), 0, s, hubs_dev, (int)n_hubs,
+                       (const float4*)A.partial_h, (const float4*)A.partial_as, A.grad_hidden, A.grad_a_s, A.ld4, ap / 4);
+    RG_LAUNCH_CHECK();
+  }
   return 0;
 }
 
@@ -248,74 +393,20 @@ extern "C" int rg_digraph_layer_bwd(int32_t n_src, int32_t n_dst, int64_t n_edge
                                     const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha,
                                     const float* b_alpha, int32_t attn_dim, const float* grad_agg, float* grad_gate,
                                     float* grad_hidden, float* grad_a_s, void* scratch, size_t scratch_bytes, void* stream) {
-  using namespace rgdb;
-  const char* who = "rg_digraph_layer_bwd";
-  RG_CHECK(n_src >= 0 && n_dst >= 0 && n_edges >= 0 && n_edges < ((int64_t)1 << 31),
-           "%s: n_src=%d n_dst=%d n_edges=%lld (need 0 <= n_src, 0 <= n_dst, 0 <= n_edges < 2^31)", who, n_src, n_dst, (long long)n_edges);
-  RG_CHECK(n_rela_rows >= 0 && batch >= 0, "%s: n_rela_rows=%d batch=%d (negative size)", who, n_rela_rows, batch);
-  RG_CHECK(d > 0 && ld >= d && ld % 4 == 0 && ld <= 256, "%s: d=%d ld=%d (need ld%%4==0, d<=ld<=256)", who, d, ld);
-  RG_CHECK(attn_dim > 0 && ap >= attn_dim && ap % 4 == 0, "%s: attn_dim=%d ap=%d", who, attn_dim, ap);
-  RG_CHECK((grad_hidden == nullptr) == (grad_a_s == nullptr), "%s: grad_hidden and grad_a_s come together or not at all", who);
-  if (n_src == 0) {
-    RG_CHECK(n_edges == 0, "%s: %lld edges without a source", who, (long long)n_edges);
-    return 0;
-  }
-  RG_CHECK(src_ptr_host, "%s: NULL argument (src_ptr_host)", who);
-  RG_CHECK(src_ptr_host[0] == 0, "%s: src_ptr starts at %d, not 0", who, src_ptr_host[0]);
-  for (int32_t s = 0; s < n_src; ++s)
-    RG_CHECK(src_ptr_host[s + 1] >= src_ptr_host[s], "%s: src_ptr decreases at source %d", who, s);
-  RG_CHECK(src_ptr_host[n_src] == n_edges, "%s: src_ptr ends at %d, not at the number of edges %lld", who, src_ptr_host[n_src],
-           (long long)n_edges);
-  if (n_edges == 0) return 0;                            // nothing to sum and nothing launched: the caller owns the outputs
-  RG_CHECK(src_ptr && edge_of && dst_of_edge && rel && row_of_dst && hidden && rela && a_s && a_r && a_q && w_alpha && b_alpha &&
-           grad_agg && grad_gate, "%s: NULL argument", who);
-  RG_CHECK(n_dst > 0 && n_rela_rows > 0 && batch > 0, "%s: edges but n_dst=%d n_rela_rows=%d batch=%d", who, n_dst, n_rela_rows, batch);
-  RG_CHECK((((uintptr_t)hidden | (uintptr_t)rela | (uintptr_t)a_s | (uintptr_t)a_r | (uintptr_t)a_q | (uintptr_t)grad_agg |
-             (uintptr_t)grad_hidden | (uintptr_t)grad_a_s | (uintptr_t)scratch) & 15) == 0, "%s: float buffers must be 16-B aligned", who);
-  int64_t n_hubs, n_chunks;
-  count_cuts(src_ptr_host, n_src, &n_hubs, &n_chunks);
-  RG_CHECK((int64_t)n_src + n_chunks < ((int64_t)1 << 31), "%s: %lld items overflow int32", who, (long long)(n_src + n_chunks));
-  const size_t need = n_hubs ? list_bytes(n_hubs, n_chunks) + rows_bytes(n_chunks, ld) + rows_bytes(n_chunks, ap) : 0;
-  RG_CHECK(need == 0 || (scratch && scratch_bytes >= need), "%s: scratch %zu B < required %zu B", who, scratch ? scratch_bytes : (size_t)0,
-           need);
+  return rgdb::run("rg_digraph_layer_bwd", nullptr, n_src, n_dst, n_edges, src_ptr, src_ptr_host, edge_of, dst_of_edge, rel, row_of_dst,
+                   n_rela_rows, batch, hidden, rela, d, ld, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim, grad_agg, grad_gate, grad_hidden,
+                   grad_a_s, scratch, scratch_bytes, stream);
+}
 
-  DbArgs A;
-  A.n_src = n_src; A.n_items = (int)(n_src + n_chunks); A.E = (int)n_edges; A.n_dst = n_dst; A.n_rela_rows = n_rela_rows; A.B = batch;
-  A.src_ptr = src_ptr; A.edge_of = edge_of; A.dst_of_edge = dst_of_edge; A.rel = rel; A.row_of_dst = row_of_dst;
-  A.hidden = (const float4*)hidden; A.rela = (const float4*)rela; A.grad_agg = (const float4*)grad_agg; A.ld4 = ld / 4;
-  A.a_s = (const float4*)a_s; A.a_r = (const float4*)a_r; A.a_q = (const float4*)a_q;
-  A.w_alpha = w_alpha; A.b_alpha = b_alpha; A.attn_dim = attn_dim;
-  A.grad_gate = grad_gate; A.grad_hidden = (float4*)grad_hidden; A.grad_a_s = (float4*)grad_a_s;
-  int4* hubs_dev = (int4*)scratch;
-  A.chunks = hubs_dev + n_hubs;
-  A.partial_h = n_hubs ? (float4*)((char*)scratch + list_bytes(n_hubs, n_chunks)) : nullptr;
-  A.partial_as = n_hubs ? (float4*)((char*)A.partial_h + rows_bytes(n_chunks, ld)) : nullptr;
-  // every argument error is out before anything is enqueued: the width dispatch is probed first
-  if (rg::with_ap4(ap / 4, who, [](auto) { return 0; })) return 1;
-  hipStream_t s = (hipStream_t)stream;
-  if (n_hubs) {
-    std::vector<int4> list((size_t)(n_hubs + n_chunks));
-    int64_t h = 0, slot = 0;
-    for (int32_t v = 0; v < n_src; ++v) {
-      const int32_t lo = src_ptr_host[v], hi = src_ptr_host[v + 1];
-      if (hi - lo <= DIGRAPH_CHUNK) continue;
-      const int n_c = (int)rg::ceil_div(hi - lo, DIGRAPH_CHUNK);
-      list[h++] = make_int4(v, (int)slot, n_c, 0);
-      for (int k = 0; k < n_c; ++k, ++slot)
-        list[n_hubs + slot] = make_int4(v, lo + k * DIGRAPH_CHUNK, std::min(hi, lo + (k + 1) * DIGRAPH_CHUNK), (int)slot);
-    }
-    // (a copy from pageable memory: the runtime is done with the vector when the call returns)
-    RG_HIP(hipMemcpyAsync(hubs_dev, list.data(), list.size() * sizeof(int4), hipMemcpyHostToDevice, s));
-  }
-  const int rc = rg::with_g(A.ld4, [&](auto g) {
-    return rg::with_ap4(ap / 4, who, [&](auto a4) { return launch<decltype(g)::value, decltype(a4)::value>(A, s); });
-  });
-  if (rc) return rc;
-  if (n_hubs && grad_hidden) {
-    const int64_t threads = n_hubs * (A.ld4 + ap / 4);
-    hipLaunchKernelGGL(digraph_bwd_combine_kernel, dim3((unsigned)rg::ceil_div(threads, 256)), dim3(256), 0, s, hubs_dev, (int)n_hubs,
-                       (const float4*)A.partial_h, (const float4*)A.partial_as, A.grad_hidden, A.grad_a_s, A.ld4, ap / 4);
-    RG_LAUNCH_CHECK();
-  }
-  return 0;
+extern "C" int rg_digraph_tlayer_bwd(int32_t n_src, int32_t n_dst, int64_t n_edges, const int32_t* src_ptr, const int32_t* src_ptr_host,
+                                     const int32_t* edge_of, const int32_t* dst_of_edge, const int32_t* rel, const int32_t* edge_time,
+                                     const int32_t* row_of_dst, const int32_t* q_time, int32_t n_rela_rows, int32_t batch, int32_t n_time,
+                                     int32_t n_dir, const float* hidden, const float* rela, const float* time_tab, int32_t d, int32_t ld,
+                                     const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha,
+                                     const float* b_alpha, int32_t attn_dim, const float* grad_agg, float* grad_gate, float* grad_hidden,
+                                     float* grad_a_s_dir, void* scratch, size_t scratch_bytes, void* stream) {
+  const rgdb::TimeIn T{edge_time, q_time, time_tab, n_time, n_dir};
+  return rgdb::run("rg_digraph_tlayer_bwd", &T, n_src, n_dst, n_edges, src_ptr, src_ptr_host, edge_of, dst_of_edge, rel, row_of_dst,
+                   n_rela_rows, batch, hidden, rela, d, ld, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim, grad_agg, grad_gate, grad_hidden,
+                   grad_a_s_dir, scratch, scratch_bytes, stream);
 }

@@ -1219,20 +1219,35 @@ def _digraph_layer(who, dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s,
 DIGRAPH_BWD_EVENTS = None            # probes: a list that collects (start, end, n_src, n_edges) of every digraph_layer_bwd
 
 
-def digraph_source_view(dst_ptr, src_idx, n_src):
+def digraph_source_view(dst_ptr, src_idx, n_src, key=None):
     """The source-segmented view of a hop rg_digraph_layer_bwd sums over, from the destination-ordered lists digraph_layer_fwd takes:
     (src_ptr int32 [n_src + 1], src_ptr_host numpy, edge_of int32 [E], dst_of_edge int32 [E]).  ``edge_of`` is the stable sort of the
-    edges by source, so a source's edges keep their list order; ``dst_of_edge[e]`` is the destination whose CSR row holds e."""
-    E, dev = src_idx.numel(), src_idx.device
-    edge_of = torch.sort(src_idx, stable=True).indices.to(torch.int32)
+    edges by source, so a source's edges keep their list order; ``dst_of_edge[e]`` is the destination whose CSR row holds e.
+    ``key`` (an integer vector [E] with values in 0 .. n_src - 1): segment by it instead of by ``src_idx`` - the directed source row
+    of rg_digraph_tlayer_bwd, ``n_src`` then counting those rows (digraph_directed_rows)."""
+    key = src_idx if key is None else key
+    E, dev = key.numel(), key.device
+    edge_of = torch.sort(key, stable=True).indices.to(torch.int32)
     src_ptr = torch.zeros(n_src + 1, dtype=torch.int64, device=dev)
     if E:
-        src_ptr[1:] = torch.cumsum(torch.bincount(src_idx, minlength=n_src)[:n_src], 0)
+        src_ptr[1:] = torch.cumsum(torch.bincount(key, minlength=n_src)[:n_src], 0)
     src_ptr = src_ptr.to(torch.int32)
     n_dst = dst_ptr.numel() - 1
     dst_of_edge = torch.repeat_interleave(torch.arange(n_dst, dtype=torch.int32, device=dev), (dst_ptr[1:] - dst_ptr[:-1]).long(),
                                           output_size=E)
     return src_ptr, src_ptr.cpu().numpy(), edge_of.contiguous(), dst_of_edge.contiguous()
+
+
+def digraph_directed_rows(dst_ptr, src_idx, row_of_dst, edge_time, q_time, n_dir):
+    """int64 [E]: the directed source row u of every edge of a timed hop, the row of ``hidden`` rg_digraph_tlayer_fwd reads for it -
+    u = 3 s + dir with dir = 0 / 1 / 2 for edge time - query time < 0 / == 0 / > 0 (64-bit differences) for n_dir = 3, u = s for
+    n_dir = 1."""
+    if n_dir == 1:
+        return src_idx.long()
+    n_dst, E = dst_ptr.numel() - 1, src_idx.numel()
+    dst_of_edge = torch.repeat_interleave(torch.arange(n_dst, device=src_idx.device), (dst_ptr[1:] - dst_ptr[:-1]).long(), output_size=E)
+    dt = edge_time.long() - q_time.long()[row_of_dst.long()[dst_of_edge]]
+    return 3 * src_idx.long() + torch.sign(dt) + 1
 
 
 def digraph_layer_bwd(dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s, a_r, a_q, w_alpha, b_alpha, attn_dim, grad_agg,
@@ -1243,57 +1258,105 @@ def digraph_layer_bwd(dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s, a
     with ``want_state`` False (hop 1: the state is the constant 0), grad_gate's bits unchanged.  The source-segmented view of the hop
     is built here (digraph_source_view).  The same checks as digraph_layer_fwd (ValueError); no float atomics, the same bits on every
     run, and a source's rows and its edges' gate gradients do not depend on the rest of the call."""
-    who = "digraph_layer_bwd"
-    for name, t in (("dst_ptr", dst_ptr), ("src_idx", src_idx), ("rel", rel), ("row_of_dst", row_of_dst)):
+    return _digraph_layer_bwd("digraph_layer_bwd", dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s, a_r, a_q, w_alpha, b_alpha,
+                              attn_dim, grad_agg, want_state, None)
+
+
+def digraph_tlayer_bwd(dst_ptr, src_idx, rel, row_of_dst, hidden, rela, time_tab, d, a_s, a_r, a_q, w_alpha, b_alpha, attn_dim, grad_agg,
+                       edge_time, q_time, n_dir=3, want_state=True):
+    """The adjoint of digraph_tlayer_fwd on the same arguments with respect to a gate on every edge's message, ``hidden`` and ``a_s``
+    (rg_digraph_tlayer_bwd; the tables, ``a_r``, ``a_q``, ``w_alpha`` and ``b_alpha`` are constants): (grad_gate fp32 [E] in the order
+    of the edge list, grad_hidden fp32 [n_dir * n_src, ld] by directed row, grad_a_s fp32 [n_src, ap]) for ``grad_agg`` fp32 [n_dst,
+    ld]; the last two are None with ``want_state`` False (hop 1: the state is the constant 0), grad_gate's bits unchanged.  The kernel
+    works on directed source rows (digraph_directed_rows); the view segmented by them is built here, and a source's three attention
+    rows are added in the fixed order past, now, future.  digraph_tlayer_fwd's checks (ValueError); no float atomics, the same bits
+    on every run."""
+    return _digraph_layer_bwd("digraph_tlayer_bwd", dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s, a_r, a_q, w_alpha, b_alpha,
+                              attn_dim, grad_agg, want_state, (edge_time, q_time, time_tab, n_dir))
+
+
+def _digraph_layer_bwd(who, dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s, a_r, a_q, w_alpha, b_alpha, attn_dim, grad_agg,
+                       want_state, timed):
+    """Both wrappers: the host checks, the source view, the scratch, the launch.  ``timed``: None or (edge_time, q_time, time_tab,
+    n_dir)."""
+    ints = [("dst_ptr", dst_ptr), ("src_idx", src_idx), ("rel", rel), ("row_of_dst", row_of_dst)]
+    floats = [("hidden", hidden), ("rela", rela), ("a_s", a_s), ("a_r", a_r), ("a_q", a_q), ("grad_agg", grad_agg)]
+    n_dir = 1
+    if timed is not None:
+        edge_time, q_time, time_tab, n_dir = timed
+        if isinstance(n_dir, (bool, np.bool_)) or not isinstance(n_dir, (int, np.integer)) or n_dir not in (1, 3):
+            raise ValueError("%s: n_dir must be 1 or 3 (got %r)" % (who, n_dir))
+        n_dir = int(n_dir)
+        ints += [("edge_time", edge_time), ("q_time", q_time)]
+        floats.append(("time_tab", time_tab))
+    for name, t in ints:
         if not (torch.is_tensor(t) and t.dtype == torch.int32 and t.dim() == 1):
             raise ValueError("%s: %s must be an int32 vector" % (who, name))
-    floats = [("hidden", hidden), ("rela", rela), ("a_s", a_s), ("a_r", a_r), ("a_q", a_q), ("grad_agg", grad_agg)]
     for name, t in floats:
         if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.dim() == 2):
             raise ValueError("%s: %s must be a float32 matrix" % (who, name))
     n_dst, E = dst_ptr.numel() - 1, src_idx.numel()
-    n_src, ld, ap = hidden.shape[0], hidden.shape[1], a_s.shape[1]
+    n_src, ld, ap = a_s.shape[0], hidden.shape[1], a_s.shape[1]
+    n_rows = n_dir * n_src                                # the rows of hidden, of the source view and of the state outputs
     if n_dst < 0 or rel.numel() != E or row_of_dst.numel() != n_dst:
         raise ValueError("%s: dst_ptr [%d], src_idx [%d], rel [%d] and row_of_dst [%d] do not fit together"
                          % (who, dst_ptr.numel(), E, rel.numel(), row_of_dst.numel()))
-    if rela.shape[1] != ld or a_r.shape[1] != ap or a_q.shape[1] != ap or a_s.shape[0] != n_src or a_r.shape[0] != rela.shape[0] \
+    if rela.shape[1] != ld or a_r.shape[1] != ap or a_q.shape[1] != ap or hidden.shape[0] != n_rows or n_dir * a_r.shape[0] != rela.shape[0] \
             or tuple(grad_agg.shape) != (n_dst, ld):
         raise ValueError("%s: hidden %s, rela %s, a_s %s, a_r %s, a_q %s and grad_agg %s (%d destinations) do not fit together"
                          % (who, tuple(hidden.shape), tuple(rela.shape), tuple(a_s.shape), tuple(a_r.shape), tuple(a_q.shape),
                             tuple(grad_agg.shape), n_dst))
+    n_time = 0
+    if timed is not None:
+        n_time = time_tab.shape[0] // n_dir
+        if edge_time.numel() != E or q_time.numel() != a_q.shape[0] or time_tab.shape[1] != ld or n_time < 1 or n_time * n_dir != time_tab.shape[0]:
+            raise ValueError("%s: edge_time [%d] (%d edges), q_time [%d] (a_q %s) and time_tab %s (n_dir * n_time rows of %d) do not fit together"
+                             % (who, edge_time.numel(), E, q_time.numel(), tuple(a_q.shape), tuple(time_tab.shape), ld))
     _require_gpu(hidden.device)
-    tensors = (dst_ptr, src_idx, rel, row_of_dst, w_alpha, b_alpha) + tuple(t for _, t in floats)
+    tensors = tuple(t for _, t in ints + floats) + (w_alpha, b_alpha)
     if not all(t.is_cuda and t.is_contiguous() for t in tensors):
         raise ValueError("%s: every tensor must be contiguous and on the device" % who)
     dev = hidden.device
     grad_gate = torch.zeros(E, dtype=torch.float32, device=dev)
-    grad_hidden = torch.zeros((n_src, ld), dtype=torch.float32, device=dev) if want_state else None
-    grad_a_s = torch.zeros((n_src, ap), dtype=torch.float32, device=dev) if want_state else None
+    grad_hidden = torch.zeros((n_rows, ld), dtype=torch.float32, device=dev) if want_state else None
+    grad_a_s = torch.zeros((n_rows, ap), dtype=torch.float32, device=dev) if want_state else None
     ptr_h = dst_ptr.cpu().numpy()
     if ptr_h[0] != 0 or ptr_h[-1] != E or (np.diff(ptr_h) < 0).any():
         raise ValueError("%s: dst_ptr must start at 0, never decrease and end at the number of edges (%d)" % (who, E))
     if E:
         checked = [("src_idx", src_idx, n_src), ("rel", rel, a_r.shape[0]), ("row_of_dst", row_of_dst, a_q.shape[0])]
+        if timed is not None:                 # n_dir 3: a time id; n_dir 1: a day, any that is not negative
+            checked.append(("edge_time", edge_time, n_time if n_dir == 3 else 1 << 31))
         lo = torch.stack([t.min() for _, t, _ in checked]).tolist()
         hi = torch.stack([t.max() for _, t, _ in checked]).tolist()
         for (name, _, n), a, b in zip(checked, lo, hi):
             if a < 0 or b >= n:
                 raise ValueError("%s: %s out of range (%d..%d, %d rows)" % (who, name, a, b, n))
-    src_ptr, src_ptr_h, edge_of, dst_of_edge = digraph_source_view(dst_ptr, src_idx, n_src)
+    key = None if timed is None else digraph_directed_rows(dst_ptr, src_idx, row_of_dst, edge_time, q_time, n_dir)
+    src_ptr, src_ptr_h, edge_of, dst_of_edge = digraph_source_view(dst_ptr, src_idx, n_rows, key=key)
     L, p = _lib.lib(), _lib.ptr
-    nbytes = int(L.rg_digraph_layer_bwd_scratch_bytes(p(src_ptr_h), n_src, ld, ap)) if n_src > 0 else 0
+    nbytes = int(L.rg_digraph_layer_bwd_scratch_bytes(p(src_ptr_h), n_rows, ld, ap)) if n_rows > 0 else 0
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
     ev = None
     if DIGRAPH_BWD_EVENTS is not None:
         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         ev[0].record()
-    _lib.check(L.rg_digraph_layer_bwd(n_src, n_dst, E, p(src_ptr), p(src_ptr_h), p(edge_of), p(dst_of_edge), p(rel), p(row_of_dst),
-                                      a_r.shape[0], a_q.shape[0], p(hidden), p(rela), int(d), ld, p(a_s), p(a_r), p(a_q), ap, p(w_alpha),
-                                      p(b_alpha), int(attn_dim), p(grad_agg), p(grad_gate), p(grad_hidden), p(grad_a_s), p(scratch), nbytes,
-                                      _lib.stream_ptr()))
+    if timed is None:
+        _lib.check(L.rg_digraph_layer_bwd(n_src, n_dst, E, p(src_ptr), p(src_ptr_h), p(edge_of), p(dst_of_edge), p(rel), p(row_of_dst),
+                                          a_r.shape[0], a_q.shape[0], p(hidden), p(rela), int(d), ld, p(a_s), p(a_r), p(a_q), ap, p(w_alpha),
+                                          p(b_alpha), int(attn_dim), p(grad_agg), p(grad_gate), p(grad_hidden), p(grad_a_s), p(scratch), nbytes,
+                                          _lib.stream_ptr()))
+    else:
+        _lib.check(L.rg_digraph_tlayer_bwd(n_src, n_dst, E, p(src_ptr), p(src_ptr_h), p(edge_of), p(dst_of_edge), p(rel), p(edge_time),
+                                           p(row_of_dst), p(q_time), a_r.shape[0], a_q.shape[0], n_time, n_dir, p(hidden), p(rela),
+                                           p(time_tab), int(d), ld, p(a_s), p(a_r), p(a_q), ap, p(w_alpha), p(b_alpha), int(attn_dim),
+                                           p(grad_agg), p(grad_gate), p(grad_hidden), p(grad_a_s), p(scratch), nbytes, _lib.stream_ptr()))
     if ev is not None:
         ev[1].record()
-        DIGRAPH_BWD_EVENTS.append((ev[0], ev[1], n_src, E))
+        DIGRAPH_BWD_EVENTS.append((ev[0], ev[1], n_rows, E))
+    if want_state and n_dir == 3:             # a source's three rows: past, now, future, added in that order
+        g = grad_a_s.view(n_src, 3, ap)
+        grad_a_s = ((g[:, 0] + g[:, 1]) + g[:, 2]).contiguous()
     return grad_gate, grad_hidden, grad_a_s
 
 

@@ -18,7 +18,9 @@ one backward marking pass per hop reads only the marked tails' CSR rows.  This m
 Temporal interpolation (T_RED_GNN.explain, rg_texplain_*): ``rd = model.explain(batch, objs)`` with the batch dict of forward; every
 edge also carries its time id (``rd.time``), ``rd.q_time`` is the rows' query time and ``rd.direction()`` the forward's past / now /
 future of each edge.  ``rd.rescore(model, keep)`` re-scores the answers on the kept edges (rg_digraph_tlayer_fwd), ``rd.fact_mask``
-takes quadruples (h, r, t, time id) and ``model.fidelity(batch, objs, k, inverse_offset)`` is the static model's fidelity.  ``table = model.rules(batch, objs, k=2)`` counts the best paths as temporal rules, steps (relation, direction)
+takes quadruples (h, r, t, time id) and ``model.fidelity(batch, objs, k, inverse_offset)`` is the static model's fidelity;
+``rd.saliency(model)`` / ``model.saliency(batch, objs)`` is its edge saliency (rg_digraph_tlayer_bwd on directed source rows), facts
+being quadruples there.  ``table = model.rules(batch, objs, k=2)`` counts the best paths as temporal rules, steps (relation, direction)
 with identity steps written as direction 3 = any (TemporalRuleTable), and ``model.rule_quality(table)`` counts how they hold in the
 quadruple graph per anchor (entity, query time id) (TemporalRuleQuality; engine.trule_ground, csrc/trule_ground.hip).
 
@@ -32,7 +34,8 @@ windows (LagRuleQuality; engine.xrule_ground, csrc/xrule_ground.hip); ``model.ru
 the forecasts on the kept edges with the windows as they were - per hop the index of the live edges built in HIP from the hop's own
 edges (engine.digraph_hop_index, csrc/digraph_index.hip) and one rg_digraph_tlayer_fwd launch in its n_dir = 1 form -, ``rd.fact_mask``
 takes (s, p, o, day), ``rd.data_row_mask`` data rows, and ``model.fidelity(X, objs, k, inverse_offset)`` / ``fidelity_all`` are the static
-model's fidelity.
+model's fidelity; ``rd.saliency(model)`` / ``model.saliency(X, objs)`` is its edge saliency (rg_digraph_tlayer_bwd, n_dir = 1), with
+``Saliency.data_row_grad()`` per data row.
 """
 import types
 from dataclasses import dataclass, fields, replace
@@ -118,7 +121,15 @@ class RDigraph:
         the same ``score``, ``reached``, ``live`` and ``alpha`` bit for bit), then the hops backwards - the dense step's adjoint
         through tall_linear / gru_step with the parameters detached, the edge-list layer's in HIP (rg_digraph_layer_bwd,
         csrc/digraph_bwd.hip: no float atomics, the same bits on every run).  Dead edges and rows whose answer is not reached get
-        exactly 0.  Static and inductive models only: a temporal or extrapolation digraph is a ValueError."""
+        exactly 0.
+
+        The driver follows the model's class.  A static or inductive model walks a static digraph as above (a temporal or
+        extrapolation digraph is a ValueError there).  A temporal.T_RED_GNN walks the temporal interpolation digraph it explained
+        and an extrapolation.T_RED_GNN its extrapolation digraph: ``rescore``'s hop loop for that family, then per hop the
+        activation's adjoint, the timed edge-list layer's in HIP (rg_digraph_tlayer_bwd: a directed source row per work item) and
+        plain products with the direction linears and the attention projection - neither model has a GRU or a carry.  The message
+        gated there is the directed one, hidden_dir + (rela_dir + time row); ``mode`` must be "test".  A digraph of another
+        family than the model's is a ValueError."""
         return saliency(self, model, keep, mode)
 
     def fact_mask(self, facts, rows=None, inverse_offset=None):
@@ -1654,10 +1665,11 @@ def _check_keep(who, keep, E, device):
     return keep
 
 
-def rescore_temporal(rd, model, keep=None, mode="test"):
-    """RDigraph.rescore of a temporal interpolation digraph (see there): T_RED_GNN._run's layer over the kept edges, hop by hop."""
+def rescore_temporal(rd, model, keep=None, mode="test", who="rescore", tape=None):
+    """RDigraph.rescore of a temporal interpolation digraph (see there): T_RED_GNN._run's layer over the kept edges, hop by hop.
+    ``tape``: a list that receives, per hop walked, what the hop's adjoint needs (RDigraph.saliency): the hop, its index arrays, the
+    directed tables the kernel read and the sums it formed."""
     from .temporal import T_RED_GNN, eval_semantics
-    who = "rescore"
     if not isinstance(model, T_RED_GNN):
         raise ValueError("%s: a temporal r-digraph (time, q_time or data_row is set) is re-scored by the temporal.T_RED_GNN that "
                          "explained it (got %s)" % (who, type(model).__name__))
@@ -1724,6 +1736,11 @@ def rescore_temporal(rd, model, keep=None, mode="test"):
                                                 a_q, w2.reshape(-1).contiguous(), zero_b, a, edge_time=rd.time[at].contiguous(),
                                                 q_time=q_time, n_dir=3)
             alpha[at] = al
+            if tape is not None:
+                tape.append(dict(l=l, at=at, dst_ptr=dst_ptr, src=i32(src), rel=i32(rel[at]), row_of=i32(row_of), hidden=hidden_dir,
+                                 rela=rela_dir, time_tab=time_dir, a_s=a_s, a_r=a_r, a_q=a_q, w_alpha=w2.reshape(-1).contiguous(),
+                                 b_alpha=zero_b, edge_time=rd.time[at].contiguous(), q_time=q_time, agg=agg, w_dir=w_dir,
+                                 w_s=w1[:, :d]))
             hidden = model.act(agg[:, :d])                                    # no GRU, and eval semantics: no dropout
             keys_prev = keys
             if l == L:
@@ -1732,13 +1749,12 @@ def rescore_temporal(rd, model, keep=None, mode="test"):
     return Rescore(score=score, reached=reached, live=live, alpha=alpha)
 
 
-def rescore_extrapolation(rd, model, keep=None, mode="test"):
+def rescore_extrapolation(rd, model, keep=None, mode="test", who="rescore", tape=None):
     """RDigraph.rescore of an extrapolation digraph (see there): the inference branch of extrapolation.T_RED_GNN._run over the kept
-    edges, hop by hop, the per-hop index built in HIP (engine.digraph_hop_index)."""
+    edges, hop by hop, the per-hop index built in HIP (engine.digraph_hop_index).  ``tape``: as rescore_temporal's."""
     import math
     from .extrapolation import T_RED_GNN as XModel
     from .temporal import eval_semantics
-    who = "rescore"
     _check_temporal_fields(rd, who)
     if not isinstance(model, XModel):
         raise ValueError("%s: an extrapolation r-digraph (data_row is set, n_time is not) is re-scored by the extrapolation.T_RED_GNN "
@@ -1808,6 +1824,10 @@ def rescore_extrapolation(rd, model, keep=None, mode="test"):
                                                 w2.reshape(-1).contiguous(), zero_b, a, edge_time=tm, q_time=q_time, n_dir=1,
                                                 dst_ptr_host=dst_ptr.cpu().numpy())      # the hop's one copy: the kernel cuts hubs there
             alpha[at.long()] = al
+            if tape is not None:
+                tape.append(dict(l=l, at=at.long(), dst_ptr=dst_ptr, src=src, rel=rel, row_of=row_of, hidden=hidden_p, rela=rela_p,
+                                 time_tab=time_p, a_s=a_s, a_r=a_r, a_q=a_q, w_alpha=w2.reshape(-1).contiguous(), b_alpha=zero_b,
+                                 edge_time=tm, q_time=q_time, agg=agg, w_dir=w_past, w_s=w1[:, :d]))
             hidden = model.act(agg[:, :d])
             keys_prev = keys
             if l == L:
@@ -1968,8 +1988,16 @@ class Saliency:
         """(row int64 [F], fact int64 [F, 3] = (h, r, t) with r < n_rel, grad float32 [F]) ordered by (row, h, r, t): ``edge_grad``
         summed over all copies of a base fact in its row - the edge (h, r, t) and its twin (t, r + n_rel, h), at every hop; the
         identity relation 2 * n_rel is no fact.  RDigraph.fact_mask's grouping rule: to first order the score of the row changes by
-        -grad when the fact is deleted.  ``inverse_offset`` is fact_mask's: a static digraph knows its inverses and takes None."""
+        -grad when the fact is deleted.  ``inverse_offset`` is fact_mask's: a static digraph knows its inverses and takes None.
+
+        On a temporal digraph (interpolation or extrapolation) fact is int64 [F, 4] = (h, r, t, time id | day), ordered by (row, h, r,
+        t, time), grouped under fact_mask's temporal rule: every copy of a quadruple in its row at every hop; the identity relation
+        n_rel is no fact, and neither is an extrapolation self-loop (data_row < 0).  With ``inverse_offset`` = m an edge with
+        m <= r < 2 m counts as (t, r - m, h, time), so that for every returned fact with r < m (every fact when m is None) grad is
+        the sum of ``edge_grad`` over fact_mask([fact], rows=[row], inverse_offset=m)."""
         rd = self.digraph
+        if _has_times(rd):
+            return self._timed_fact_grad(inverse_offset)
         E, _ = _check_static_digraph(rd, "fact_grad")
         if inverse_offset is not None:
             raise ValueError("fact_grad: inverse_offset is for temporal r-digraphs; a static one knows its inverses (r + n_rel)")
@@ -1990,9 +2018,59 @@ class Saliency:
         r_, rest = rest % n_rel, rest // n_rel
         return rest // n_key, torch.stack([rest % n_key, r_, t_], 1), grad
 
+    def _timed_fact_grad(self, inverse_offset):
+        """fact_grad of a temporal interpolation or extrapolation digraph."""
+        who, rd = "fact_grad", self.digraph
+        xtr = _is_extrapolation(rd)
+        (_check_extrapolation_digraph if xtr else _check_temporal_digraph)(rd, who)
+        n_rel, dev, m = int(rd.n_rel), rd.edges.device, inverse_offset
+        if m is not None and (isinstance(m, (bool, np.bool_)) or not isinstance(m, (int, np.integer)) or m < 1 or 2 * m > n_rel):
+            raise ValueError("%s: inverse_offset must be an integer m with 1 <= m and 2 m <= n_rel = %d, relation r's inverse being r + m "
+                             "below m and r - m from there on (got %r)" % (who, n_rel, m))
+        e, tm = rd.edges.long(), rd.time.long().to(dev)
+        fact = e[:, 3] != n_rel                                           # the identity is no fact
+        if xtr:
+            fact = fact & (rd.data_row.to(dev) >= 0)                      # ... and a self-loop has no data row
+        e, tm = e[fact], tm[fact]
+        if e.shape[0] == 0:
+            return (torch.zeros(0, dtype=torch.int64, device=dev), torch.zeros((0, 4), dtype=torch.int64, device=dev),
+                    torch.zeros(0, dtype=torch.float32, device=dev))
+        h, r, t = e[:, 2], e[:, 3], e[:, 4]
+        if m is not None:
+            inv = (r >= int(m)) & (r < 2 * int(m))
+            h, r, t = torch.where(inv, e[:, 4], h), torch.where(inv, r - int(m), r), torch.where(inv, e[:, 2], t)
+        n_key, n_r, n_t = int(max(h.max(), t.max())) + 1, n_rel + 1, int(tm.max()) + 1
+        key = (((e[:, 0] * n_key + h) * n_r + r) * n_key + t) * n_t + tm
+        key, order = torch.sort(key, stable=True)                         # copies of a fact in edge order: a fixed order of the sum
+        keys, group = torch.unique_consecutive(key, return_inverse=True)
+        grad = _segment_sums(self.edge_grad[fact][order], group, keys.numel())
+        tm_, rest = keys % n_t, keys // n_t
+        t_, rest = rest % n_key, rest // n_key
+        r_, rest = rest % n_r, rest // n_r
+        return rest // n_key, torch.stack([rest % n_key, r_, t_, tm_], 1), grad
+
+    def data_row_grad(self):
+        """Extrapolation digraphs only: (row int64 [F], data_row int64 [F], grad float32 [F]) ordered by (row, data_row): ``edge_grad``
+        summed over the edges of a data row in its row, at every hop - RDigraph.data_row_mask's grouping, the exact identity of a
+        past fact; self-loops (data_row < 0) are left out."""
+        rd = self.digraph
+        _check_extrapolation_digraph(rd, "data_row_grad")
+        dev = rd.edges.device
+        dr = rd.data_row.to(dev).long()
+        fact = dr >= 0
+        row, dr = rd.edges[:, 0].long()[fact], dr[fact]
+        if dr.numel() == 0:
+            return (torch.zeros(0, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int64, device=dev),
+                    torch.zeros(0, dtype=torch.float32, device=dev))
+        n_key = int(dr.max()) + 1
+        key, order = torch.sort(row * n_key + dr, stable=True)
+        keys, group = torch.unique_consecutive(key, return_inverse=True)
+        return keys // n_key, keys % n_key, _segment_sums(self.edge_grad[fact][order], group, keys.numel())
+
     def top(self, k):
         """The k facts of every row with the largest |grad| (fact_grad), largest first, ties in (h, r, t) order: (fact int64 [B, k, 3],
-        grad float32 [B, k], count int64 [B]); -1 and 0 where the row has fewer than k facts."""
+        grad float32 [B, k], count int64 [B]); -1 and 0 where the row has fewer than k facts.  On a temporal digraph fact is
+        [B, k, 4] = (h, r, t, time id | day), ties in (h, r, t, time) order."""
         _check_count(k, "top", "k")
         k, B, dev = int(k), self.score.numel(), self.edge_grad.device
         row, fact, grad = self.fact_grad()
@@ -2002,7 +2080,7 @@ class Saliency:
         total = torch.bincount(row, minlength=B)
         rank = torch.arange(row.numel(), device=dev) - (torch.cumsum(total, 0) - total)[row]
         sel = rank < k
-        out_f = torch.full((B, k, 3), -1, dtype=torch.int64, device=dev)
+        out_f = torch.full((B, k, fact.shape[1]), -1, dtype=torch.int64, device=dev)
         out_g = torch.zeros((B, k), dtype=torch.float32, device=dev)
         out_f[row[sel], rank[sel]] = fact[sel]
         out_g[row[sel], rank[sel]] = grad[sel]
@@ -2022,19 +2100,73 @@ class Saliency:
 
     def format(self, id2rel=None, k=3):
         """One line per row: the score (``x``: o is not reached), then the row's ``k`` facts of largest |grad| as (h, relation, t)
-        with their gradient; ``id2rel`` names the relations."""
+        with their gradient - (h, relation, t, @time) on a temporal digraph; ``id2rel`` names the relations."""
         fact, grad, count = (t.cpu().tolist() for t in self.top(k))
         sc, ok = self.score.cpu().tolist(), self.reached.cpu().tolist()
         name = lambda r: str(id2rel[r]) if id2rel is not None else "r%d" % r
+        cell = lambda f: "(%d, %s, %d, @%d)" % (f[0], name(f[1]), f[2], f[3]) if len(f) == 4 else "(%d, %s, %d)" % (f[0], name(f[1]), f[2])
         return ["row %d: score %s  %s" % (b, "%.4f" % sc[b] if ok[b] else "x",
-                                         "  ".join("(%d, %s, %d) %+.4f" % (f[0], name(f[1]), f[2], g)
-                                                   for f, g in zip(fact[b][:count[b]], grad[b])))
+                                         "  ".join("%s %+.4f" % (cell(f), g) for f, g in zip(fact[b][:count[b]], grad[b])))
                 for b in range(len(sc))]
 
 
+def _digraph_family(rd):
+    return "an extrapolation" if _is_extrapolation(rd) else "a temporal interpolation" if _has_times(rd) else "a static"
+
+
+def _saliency_timed(rd, model, keep, mode, n_dir):
+    """RDigraph.saliency of a temporal interpolation (n_dir = 3) or extrapolation (n_dir = 1) digraph: the rescore with a tape, then
+    the hops backwards.  Neither model has a GRU, so a hop's new state is act(agg) and nothing else carries the old one."""
+    from .temporal import eval_semantics
+    tape = []
+    rs = (rescore_temporal if n_dir == 3 else rescore_extrapolation)(rd, model, keep, mode, "saliency", tape)
+    dev, L = rd.edges.device, int(rd.n_hops)
+    d, a = model.hidden_dim, model.attn_dim
+    edge_grad = torch.zeros(rd.edges.shape[0], dtype=torch.float32, device=dev)
+    out = lambda: Saliency(score=rs.score, reached=rs.reached, live=rs.live, alpha=rs.alpha, edge_grad=edge_grad, digraph=rd)
+    if len(tape) < L:                                                     # no row reaches its answer: nothing depends on any edge
+        return out()
+    g_state = None                                                        # d (sum of the scores) / d (the hop's new state) [n_dst, d]
+    for t in reversed(tape):
+        last, first = t["l"] == L, t["l"] == 1
+        if last:                                                          # every hop-L node is its row's answer: the classifier's row
+            g_state = model.linear_classifier.weight.detach().reshape(1, d).expand(t["agg"].shape[0], d)
+        # ---- through the activation, on the taped sums (eval semantics: no dropout; it has no parameters)
+        with torch.enable_grad(), eval_semantics(model):
+            agg = t["agg"].detach().requires_grad_(True)
+            g_agg, = torch.autograd.grad([model.act(agg[:, :d])], [agg], [g_state.contiguous()])
+        # ---- the edge-list layer's adjoint, in HIP
+        gate_grad, g_dir, g_a_s = engine.digraph_tlayer_bwd(
+            t["dst_ptr"], t["src"], t["rel"], t["row_of"], t["hidden"], t["rela"], t["time_tab"], d, t["a_s"], t["a_r"], t["a_q"],
+            t["w_alpha"].detach(), t["b_alpha"], a, g_agg.contiguous(), edge_time=t["edge_time"], q_time=t["q_time"], n_dir=n_dir,
+            want_state=not first)
+        edge_grad[t["at"]] = gate_grad
+        if not first:
+            # ---- back through the direction linears (row n_dir s + dir of the directed state is W_dir state[s]) and the attention
+            # projection: plain products with the detached weights
+            with torch.no_grad():
+                n_old = t["a_s"].shape[0]
+                g_state = g_dir[:, :d].reshape(n_old, n_dir * d) @ t["w_dir"].detach() + g_a_s[:, :a] @ t["w_s"].detach()
+    return out()
+
+
 def saliency(rd, model, keep=None, mode="test"):
-    """RDigraph.saliency (see there): _rescore_static with a tape, then the hops backwards."""
+    """RDigraph.saliency (see there).  The driver is chosen by the model's class: a temporal.T_RED_GNN walks a temporal interpolation
+    digraph, an extrapolation.T_RED_GNN an extrapolation one (_saliency_timed); every other model takes the static path -
+    _rescore_static with a tape, then the hops backwards."""
     from .models import gru_step, tall_linear
+    from .extrapolation import T_RED_GNN as XModel
+    from .temporal import T_RED_GNN as TModel
+    if isinstance(model, XModel):
+        if not _is_extrapolation(rd):
+            raise ValueError("saliency: an extrapolation.T_RED_GNN walks the extrapolation r-digraphs it explained (data_row is set, "
+                             "n_time is not); this is %s r-digraph" % _digraph_family(rd))
+        return _saliency_timed(rd, model, keep, mode, 1)
+    if isinstance(model, TModel):
+        if _is_extrapolation(rd) or not _has_times(rd):
+            raise ValueError("saliency: a temporal.T_RED_GNN walks the temporal interpolation r-digraphs it explained (time, q_time and "
+                             "n_time are set, data_row is not); this is %s r-digraph" % _digraph_family(rd))
+        return _saliency_timed(rd, model, keep, mode, 3)
     tape = []
     rs = _rescore_static(rd, model, keep, mode, "saliency", tape)
     dev, L = rd.edges.device, int(rd.n_hops)

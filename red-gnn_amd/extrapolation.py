@@ -390,6 +390,15 @@ class T_RED_GNN(nn.Module):
         from .explain import extrapolation_fidelity
         return extrapolation_fidelity(self, X, objs, k, inverse_offset)
 
+    def saliency(self, X, objs=None):
+        """How much a forecast depends on every past fact of its r-digraph, in one pass: ``explain`` followed by RDigraph.saliency -
+        the gradient of the score with respect to a gate on every edge's message, the windows as they were (the timed edge-list
+        layer's adjoint in HIP, rg_digraph_tlayer_bwd in its n_dir = 1 form).  Returns an explain.Saliency: ``edge_grad`` per edge of
+        ``.digraph``, ``fact_grad()`` / ``top(k)`` per fact (s, p, o, day), ``data_row_grad()`` per data row, ``deletion_estimate(mask)``
+        the first-order estimate of a rescore.  objs=None: the row's own top forecast, as explain.  Eval semantics; the parameters
+        get no gradient."""
+        return self.explain(X, objs).saliency(self)
+
     def fidelity_all(self, queries, k=4, batch_size=64, inverse_offset=None):
         """fidelity over ``queries`` int [n, 4] = (s, p, o, ts) (checked as evaluate's), each row a query with its object as the
         answer, in batches of ``batch_size``: the dict of BaseModel.fidelity - n, k, necessity_mean / _median, sufficiency_gap_mean /

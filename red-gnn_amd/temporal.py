@@ -151,6 +151,14 @@ class T_RED_GNN(nn.Module):
         from . import explain as _explain
         return _explain.temporal_fidelity(self, batch, objs, k, inverse_offset)
 
+    def saliency(self, batch, objs=None):
+        """How much the score of each answer depends on every quadruple of its r-digraph, in one pass: ``explain`` followed by
+        RDigraph.saliency - the gradient of the score with respect to a gate on every edge's message (the timed edge-list layer's
+        adjoint in HIP, rg_digraph_tlayer_bwd).  Returns an explain.Saliency: ``edge_grad`` per edge of ``.digraph``, ``fact_grad()`` /
+        ``top(k)`` per quadruple (h, r, t, time id), ``deletion_estimate(mask)`` the first-order estimate of a rescore.  objs=None: the
+        model's own top answer per row, as explain.  Eval semantics; the parameters get no gradient."""
+        return self.explain(batch, objs).saliency(self)
+
     def fidelity_all(self, quads, k=4, batch_size=64, inverse_offset=None):
         """fidelity over ``quads`` int [n, 4] = (head, rel, tail, time id), each row a query with its tail as the answer, walked in
         batches of ``batch_size`` rows: the dict BaseModel.fidelity returns (n, k, necessity_mean / _median, sufficiency_gap_mean /
