@@ -538,6 +538,49 @@ int rg_digraph_tlayer_bwd(int32_t n_src, int32_t n_dst, int64_t n_edges, const i
                           int32_t attn_dim, const float* grad_agg, float* grad_gate, float* grad_hidden, float* grad_a_s_dir,
                           void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- rg_digraph_layer_fwd with a gate on every edge's message, for n_rep >= 1 replicas of the hop in one launch (static form only;
+ * explain.RDigraph.integrated_gradients, and rescore / saliency with gate=).  Everything rg_digraph_layer_fwd states holds - the same
+ * kernel with the gate compiled in, the same split rule per replica and the same argument checks - plus: t float [n_rep] (device),
+ * gate_lo float [n_edges] or NULL (meaning 0) and gate_hi float [n_edges] or NULL (meaning 1), both by position in the
+ * destination-ordered list.  Replica k reads hidden rows k * n_src + s and a_s rows k * n_src + s (hidden [n_rep * n_src, ld], a_s
+ * [n_rep * n_src, ap]) and writes agg_out rows k * n_dst + o ([n_rep * n_dst, ld]) and alpha_out[k * n_edges + e] ([n_rep * n_edges] or
+ * NULL); rela, a_r, a_q, w_alpha, b_alpha and every index array are shared by the replicas.
+ *   g       = fmaf(t[k], gate_hi[e] - gate_lo[e], gate_lo[e])      lo == hi: that value exactly; lo = 0, hi = 1, t = 1: exactly 1
+ *   alpha_e   as rg_digraph_layer_fwd forms it from the replica's a_s row: the gate does not enter it
+ *   c       = g * alpha_e, rounded once;   acc = fmaf(c, hidden[s] + rela[r], acc) in list order
+ * At g == 1 every bit is rg_digraph_layer_fwd's.  A work item is a (replica, destination or chunk) pair, so a replica's outputs have
+ * the bits of an n_rep = 1 call with that replica's t, whatever else the call carries; no float atomics.  scratch:
+ * rg_digraph_layer_fwd_gated_scratch_bytes(dst_ptr_host, n_dst, ld, n_rep) bytes (the chunk list once, partial rows per replica).
+ * Errors, all before anything is enqueued: n_rep < 1 or > 65535; n_rep * max(n_src, n_dst), n_rep * n_edges or n_rep * (n_dst +
+ * chunks) beyond int32; a NULL t; and rg_digraph_layer_fwd's. */
+size_t rg_digraph_layer_fwd_gated_scratch_bytes(const int32_t* dst_ptr_host, int32_t n_dst, int32_t ld, int32_t n_rep);
+int rg_digraph_layer_fwd_gated(int32_t n_rep, const float* t, const float* gate_lo, const float* gate_hi, int32_t n_dst, int64_t n_edges,
+                               const int32_t* dst_ptr, const int32_t* dst_ptr_host, const int32_t* src_idx, const int32_t* rel,
+                               const int32_t* row_of_dst, int32_t n_src, int32_t n_rela_rows, int32_t batch, const float* hidden,
+                               const float* rela, int32_t d, int32_t ld, const float* a_s, const float* a_r, const float* a_q, int32_t ap,
+                               const float* w_alpha, const float* b_alpha, int32_t attn_dim, float* agg_out, float* alpha_out,
+                               void* scratch, size_t scratch_bytes, void* stream);
+
+/* ---- ... and its adjoint: rg_digraph_layer_bwd at the gates g above, for the same n_rep replicas (static form only).  Everything
+ * rg_digraph_layer_bwd states holds, plus t, gate_lo and gate_hi as in rg_digraph_layer_fwd_gated.  Replica k reads hidden rows
+ * k * n_src + s, a_s rows k * n_src + s and G = grad_agg rows k * n_dst + o ([n_rep * n_dst, ld]); the source view (src_ptr, edge_of,
+ * dst_of_edge), rel, row_of_dst and the constant tables are shared.  With c = g * alpha_e as the forward rounds it:
+ *   grad_gate[k * n_edges + e]  = alpha_e * <G[o], hidden[s] + rela[r]>                 [n_rep * n_edges]: the derivative with respect to
+ *                                                                                     g itself; the gate does not scale it
+ *   grad_hidden[k * n_src + s] += c * G[o]                                             [n_rep * n_src, ld]
+ *   grad_a_s[k * n_src + s]    += g * (g_alpha * alpha_e * (1 - alpha_e)) * w * 1[pre > 0]      [n_rep * n_src, ap]
+ * the products arranged so that g == 1 leaves rg_digraph_layer_bwd's bits.  A work item is a (replica, source or chunk) pair: a
+ * replica's outputs have the bits of an n_rep = 1 call with its t.  scratch: rg_digraph_layer_bwd_gated_scratch_bytes(src_ptr_host,
+ * n_src, ld, ap, n_rep) bytes.  The same errors as the gated forward's, before anything is enqueued. */
+size_t rg_digraph_layer_bwd_gated_scratch_bytes(const int32_t* src_ptr_host, int32_t n_src, int32_t ld, int32_t ap, int32_t n_rep);
+int rg_digraph_layer_bwd_gated(int32_t n_rep, const float* t, const float* gate_lo, const float* gate_hi, int32_t n_src, int32_t n_dst,
+                               int64_t n_edges, const int32_t* src_ptr, const int32_t* src_ptr_host, const int32_t* edge_of,
+                               const int32_t* dst_of_edge, const int32_t* rel, const int32_t* row_of_dst, int32_t n_rela_rows,
+                               int32_t batch, const float* hidden, const float* rela, int32_t d, int32_t ld, const float* a_s,
+                               const float* a_r, const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha,
+                               int32_t attn_dim, const float* grad_agg, float* grad_gate, float* grad_hidden, float* grad_a_s,
+                               void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- the per-hop index of an edited r-digraph: the arrays rg_digraph_(t)layer_fwd takes, built from the digraph's own edge list
  * under a keep mask (csrc/digraph_index.hip; explain.RDigraph.rescore of an extrapolation digraph).  edges int32 [n_edges, 5] =
  * (row, hop, head, rel, tail) ordered by (row, hop, tail) and offsets int64 [batch + 1] (start at 0, never decrease, end at n_edges:

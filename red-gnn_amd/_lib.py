@@ -28,6 +28,8 @@ SYMBOLS = [
     "rg_paths_scratch_bytes", "rg_paths_topk",
     "rg_digraph_layer_fwd_scratch_bytes", "rg_digraph_layer_fwd", "rg_digraph_tlayer_fwd",
     "rg_digraph_layer_bwd_scratch_bytes", "rg_digraph_layer_bwd", "rg_digraph_tlayer_bwd",
+    "rg_digraph_layer_fwd_gated_scratch_bytes", "rg_digraph_layer_fwd_gated",
+    "rg_digraph_layer_bwd_gated_scratch_bytes", "rg_digraph_layer_bwd_gated",
     "rg_digraph_hop_ranges", "rg_digraph_hop_index_scratch_bytes", "rg_digraph_hop_index",
     "rg_rule_ground_scratch_bytes", "rg_rule_ground",
     "rg_rule_apply_scratch_bytes", "rg_rule_apply",
@@ -160,6 +162,13 @@ def lib():
                                        vp, vp, vp, sz, vp]
     L.rg_digraph_tlayer_bwd.argtypes = [i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp,
                                         i32, vp, vp, i32, vp, vp, vp, vp, vp, sz, vp]
+    # the gated, replicated forms: (n_rep, t, gate_lo, gate_hi) in front of the ungated arguments
+    L.rg_digraph_layer_fwd_gated_scratch_bytes.argtypes = [vp, i32, i32, i32]
+    L.rg_digraph_layer_fwd_gated_scratch_bytes.restype = sz
+    L.rg_digraph_layer_fwd_gated.argtypes = [i32, vp, vp, vp] + L.rg_digraph_layer_fwd.argtypes
+    L.rg_digraph_layer_bwd_gated_scratch_bytes.argtypes = [vp, i32, i32, i32, i32]
+    L.rg_digraph_layer_bwd_gated_scratch_bytes.restype = sz
+    L.rg_digraph_layer_bwd_gated.argtypes = [i32, vp, vp, vp] + L.rg_digraph_layer_bwd.argtypes
     L.rg_digraph_hop_ranges.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp, vp, C.POINTER(i32), vp]
     L.rg_digraph_hop_index_scratch_bytes.argtypes = [i64]
     L.rg_digraph_hop_index_scratch_bytes.restype = sz

@@ -39,6 +39,17 @@
 // items, and grad_a_s_dir [n_dir * n_src, ap] has a row per item (the caller adds a source's three).  The edge's direction is formed
 // again per edge for rrow and trow (it is not taken from u, so an inconsistent view reads other rows, never out of bounds); the time
 // table's gather is the only added traffic.  The split rule counts chunks per directed row.
+//
+// The gated, replicated form (rg_digraph_layer_bwd_gated, template parameter GATED; static only, and the other instantiations compile
+// to what they did without it), the adjoint of rg_digraph_layer_fwd_gated at the gates g = fmaf(t[k], gate_hi[e] - gate_lo[e],
+// gate_lo[e]): n_rep replicas, replica k with its own hidden, a_s and grad_agg rows (k * n_src + s, k * n_dst + o) and its own outputs
+// (grad_gate[k * E + e], state rows k * n_src + s, partial rows k * n_chunks + slot); the source view, rel, row_of_dst, rela, a_r, a_q
+// and w are shared.  With c = g * alpha_e (rounded once, the forward's coefficient):
+//       grad_gate[e]     = alpha_e * g_alpha                   the derivative with respect to g itself: the gate does not scale it
+//       grad_hidden[s]  += c * G[o]
+//       grad_a_s[s]     += g * (g_alpha * alpha_e * (1 - alpha_e)) * w * 1[pre > 0]
+// so that g == 1 leaves the ungated kernel's bits.  An item is a (replica, source or chunk) pair, item k * n_items + i: a group works
+// exactly as it does in an n_rep = 1 call.  The combine launch has a grid row per replica.
 #include <algorithm>
 #include <type_traits>
 #include <vector>
@@ -86,15 +97,33 @@ struct DbTimedArgs : DbArgs {
   int n_time, n_dir;           // n_dir 3: interpolation (rows by direction), 1: extrapolation form (one table of lags)
 };
 
+// what the gated form (rg_digraph_layer_bwd_gated) reads on top
+struct DbGatedArgs : DbArgs {
+  int n_rep, n_chunks;         // replicas; chunks of ONE replica (replica k's partial rows start at k * n_chunks)
+  const float* t;              // [n_rep]
+  const float* gate_lo;        // [E] by position in the destination-ordered list, or nullptr: 0
+  const float* gate_hi;        // [E], or nullptr: 1
+};
+
+template <bool TIMED, bool GATED>
+using DbArgsOf = std::conditional_t<GATED, DbGatedArgs, std::conditional_t<TIMED, DbTimedArgs, DbArgs>>;
+
 __device__ __forceinline__ int clampi(int x, int hi) { return min(max(x, 0), hi); }
 
-template <int G, int AP4, bool TIMED>
-__global__ __launch_bounds__(DB_BLOCK) void digraph_bwd_kernel(std::conditional_t<TIMED, DbTimedArgs, DbArgs> A) {
+template <int G, int AP4, bool TIMED, bool GATED>
+__global__ __launch_bounds__(DB_BLOCK) void digraph_bwd_kernel(DbArgsOf<TIMED, GATED> A) {
+  static_assert(!(TIMED && GATED), "the gated form is static");
   constexpr int PER_WAVE = 64 / G;
   const int lane = threadIdx.x & 63;
   const int lane_g = lane & (G - 1), gbase = lane & ~(G - 1);
   const int wave = blockIdx.x * (DB_BLOCK / 64) + (threadIdx.x >> 6);
-  const int item = wave * PER_WAVE + lane / G;
+  int item = wave * PER_WAVE + lane / G;
+  int rep = 0;                                           // GATED: the item's replica, and the item inside it
+  if constexpr (GATED) {
+    rep = item / A.n_items;
+    item -= rep * A.n_items;
+    if (rep >= A.n_rep) { rep = 0; item = A.n_items; }   // past the last replica: no work
+  }
   const bool row_lane = lane_g < A.ld4;
   const int lane_c = row_lane ? lane_g : A.ld4 - 1;      // loads never branch: idle lanes re-read the last float4
 
@@ -108,18 +137,33 @@ __global__ __launch_bounds__(DB_BLOCK) void digraph_bwd_kernel(std::conditional_
     if (hi - lo <= DIGRAPH_CHUNK) {                      // (a cut source is written by the combine pass)
       beg = lo; end = max(hi, lo);
       if (A.grad_hidden) { out_h = A.grad_hidden + (int64_t)s * A.ld4; out_as = A.grad_a_s + (int64_t)s * AP4; }
+      if constexpr (GATED)
+        if (A.grad_hidden) { out_h += (int64_t)rep * A.n_src * A.ld4; out_as += (int64_t)rep * A.n_src * AP4; }
     }
   } else if (item < A.n_items) {
     const int4 c = A.chunks[item - A.n_src];
     s = clampi(c.x, A.n_src - 1);
     beg = clampi(c.y, A.E); end = min(max(clampi(c.z, A.E), beg), beg + DIGRAPH_CHUNK);
     if (A.grad_hidden) { out_h = A.partial_h + (int64_t)c.w * A.ld4; out_as = A.partial_as + (int64_t)c.w * AP4; }
+    if constexpr (GATED)
+      if (A.grad_hidden) { out_h += (int64_t)rep * A.n_chunks * A.ld4; out_as += (int64_t)rep * A.n_chunks * AP4; }
   }
   const float b_alpha = A.b_alpha[0];
-  const float4 hv = A.hidden[(int64_t)s * A.ld4 + lane_c];
+  // GATED: the replica's rows of hidden, a_s and grad_agg, its grad_gate and its t
+  int64_t srow = s;
+  const float4* grad_agg = A.grad_agg;
+  float* grad_gate = A.grad_gate;
+  float t_rep = 1.f;
+  if constexpr (GATED) {
+    srow += (int64_t)rep * A.n_src;
+    grad_agg += (int64_t)rep * A.n_dst * A.ld4;
+    grad_gate += (int64_t)rep * A.E;
+    t_rep = A.t[rep];
+  }
+  const float4 hv = A.hidden[srow * A.ld4 + lane_c];
   const float4* as_p;
   if constexpr (TIMED) as_p = A.a_s + (int64_t)(s / A.n_dir) * AP4;      // the attention reads the un-directed source
-  else as_p = A.a_s + (int64_t)s * AP4;
+  else as_p = A.a_s + srow * AP4;
 
   float4 acc_h = rg::f4zero();
   float4 acc_as[AP4];
@@ -131,7 +175,7 @@ __global__ __launch_bounds__(DB_BLOCK) void digraph_bwd_kernel(std::conditional_
     const bool valid = c < end;
     int e = 0, o = 0, r = 0, trow = 0;
     unsigned pos = 0;                                    // bit 4k + u: component 4k + u of (a_s + a_r) + a_q is > 0
-    float alpha = 0.f;
+    float alpha = 0.f, gate = 1.f, coef = 0.f;           // GATED: the edge's gate g and the message's coefficient c = g * alpha
     if (valid) {
       e = clampi(A.edge_of[c], A.E - 1);
       o = clampi(A.dst_of_edge[e], A.n_dst - 1);
@@ -148,6 +192,11 @@ __global__ __launch_bounds__(DB_BLOCK) void digraph_bwd_kernel(std::conditional_
                (unsigned)(as.z + ar.z + aq.z > 0.f) << (4 * k + 2) | (unsigned)(as.w + ar.w + aq.w > 0.f) << (4 * k + 3);
       }
       alpha = rg::attn_alpha(z);
+      if constexpr (GATED) {
+        const float lo = A.gate_lo ? A.gate_lo[e] : 0.f, hi = A.gate_hi ? A.gate_hi[e] : 1.f;
+        gate = fmaf(t_rep, hi - lo, lo);
+        coef = gate * alpha;
+      }
       if constexpr (TIMED) {
         // the rows of the message, as digraph_fwd_kernel forms them (the attention above read the un-directed r); 64-bit
         // differences, so that no pair of times overflows, and the time row clamped into its table
@@ -174,11 +223,11 @@ __global__ __launch_bounds__(DB_BLOCK) void digraph_bwd_kernel(std::conditional_
         const int from = gbase + ((j + u) & (G - 1));
         ou[u] = __shfl(o, from, 64);
         ru[u] = __shfl(r, from, 64);
-        al[u] = __shfl(alpha, from, 64);
+        al[u] = __shfl(GATED ? coef : alpha, from, 64);
         if constexpr (TIMED) tu[u] = __shfl(trow, from, 64);
       }
 #pragma unroll
-      for (int u = 0; u < 4; ++u) gv[u] = A.grad_agg[(int64_t)ou[u] * A.ld4 + lane_c];
+      for (int u = 0; u < 4; ++u) gv[u] = grad_agg[(int64_t)ou[u] * A.ld4 + lane_c];
 #pragma unroll
       for (int u = 0; u < 4; ++u) rv[u] = A.rela[(int64_t)ru[u] * A.ld4 + lane_c];
       if constexpr (TIMED) {             // rela[rrow] + time_tab[trow] first, then hidden: the forward's association
@@ -206,8 +255,9 @@ __global__ __launch_bounds__(DB_BLOCK) void digraph_bwd_kernel(std::conditional_
     }
     // ---- back on the edge's own lane: its gate gradient, and its share of the source's attention gradient ---------
     if (valid) {
-      A.grad_gate[e] = alpha * g_alpha;
-      const float g_p = g_alpha * alpha * (1.f - alpha);
+      grad_gate[e] = alpha * g_alpha;
+      float g_p = g_alpha * alpha * (1.f - alpha);
+      if constexpr (GATED) g_p = gate * g_p;
 #pragma unroll
       for (int k = 0; k < AP4; ++k) {      // (w is constant over the sum: it multiplies the total, below)
         acc_as[k].x += (pos >> (4 * k) & 1u) ? g_p : 0.f;
@@ -233,9 +283,14 @@ __global__ __launch_bounds__(DB_BLOCK) void digraph_bwd_kernel(std::conditional_
 
 // grad_hidden[s] and grad_a_s[s] of the cut sources: their chunks' partial rows added in chunk order, the first one initialising the
 // sum.  A thread per float4: the ld4 of the state row, then the ap4 of the attention row.
+// (gated form: grid row k is replica k, its partial rows n_chunks and its output rows n_src further on)
 __global__ void digraph_bwd_combine_kernel(const int4* __restrict__ hubs, int n_hubs, const float4* __restrict__ partial_h,
                                            const float4* __restrict__ partial_as, float4* __restrict__ grad_hidden,
-                                           float4* __restrict__ grad_a_s, int ld4, int ap4) {
+                                           float4* __restrict__ grad_a_s, int ld4, int ap4, int64_t n_chunks, int64_t n_src) {
+  partial_h += blockIdx.y * n_chunks * ld4;
+  partial_as += blockIdx.y * n_chunks * ap4;
+  grad_hidden += blockIdx.y * n_src * ld4;
+  grad_a_s += blockIdx.y * n_src * ap4;
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int w = ld4 + ap4;
   const int64_t h = tid / w;
@@ -266,10 +321,12 @@ void count_cuts(const int32_t* ptr, int32_t n_src, int64_t* n_hubs, int64_t* n_c
 size_t list_bytes(int64_t n_hubs, int64_t n_chunks) { return rg::align_up((size_t)(n_hubs + n_chunks) * sizeof(int4), 256); }
 size_t rows_bytes(int64_t n_chunks, int32_t width) { return rg::align_up((size_t)n_chunks * width * sizeof(float), 256); }
 
-template <int G, int AP4, bool TIMED>
-int launch(const std::conditional_t<TIMED, DbTimedArgs, DbArgs>& A, hipStream_t s) {
-  const int64_t waves = rg::ceil_div(A.n_items, 64 / G);
-  hipLaunchKernelGGL((digraph_bwd_kernel<G, AP4, TIMED>), dim3((unsigned)rg::ceil_div(waves, DB_BLOCK / 64)), dim3(DB_BLOCK), 0, s, A);
+template <int G, int AP4, bool TIMED, bool GATED = false>
+int launch(const DbArgsOf<TIMED, GATED>& A, hipStream_t s) {
+  int64_t items = A.n_items;
+  if constexpr (GATED) items *= A.n_rep;
+  const int64_t waves = rg::ceil_div(items, 64 / G);
+  hipLaunchKernelGGL((digraph_bwd_kernel<G, AP4, TIMED, GATED>), dim3((unsigned)rg::ceil_div(waves, DB_BLOCK / 64)), dim3(DB_BLOCK), 0, s, A);
   RG_LAUNCH_CHECK();
   return 0;
 }
@@ -282,9 +339,21 @@ struct TimeIn {
   int32_t n_time, n_dir;
 };
 
-// both entry points: every check, then the chunk list, the layer launch and the combine launch.  n_rows: the rows of the source view,
+// the gate arguments of rg_digraph_layer_bwd_gated; nullptr: the ungated entry points
+struct GateIn {
+  int32_t n_rep;
+  const float* t;
+  const float* gate_lo;
+  const float* gate_hi;
+};
+
+size_t scratch_need(int64_t n_hubs, int64_t n_chunks, int32_t ld, int32_t ap, int64_t n_rep) {
+  return n_hubs ? list_bytes(n_hubs, n_chunks) + rows_bytes(n_rep * n_chunks, ld) + rows_bytes(n_rep * n_chunks, ap) : 0;
+}
+
+// every entry point: every check, then the chunk list, the layer launch and the combine launch.  n_rows: the rows of the source view,
 // of hidden and of the state outputs - n_src, or n_dir * n_src directed rows in the timed form.
-int run(const char* who, const TimeIn* T, int32_t n_src, int32_t n_dst, int64_t n_edges, const int32_t* src_ptr, const int32_t* src_ptr_host,
+int run(const char* who, const TimeIn* T, const GateIn* Q, int32_t n_src, int32_t n_dst, int64_t n_edges, const int32_t* src_ptr, const int32_t* src_ptr_host,
         const int32_t* edge_of, const int32_t* dst_of_edge, const int32_t* rel, const int32_t* row_of_dst, int32_t n_rela_rows,
         int32_t batch, const float* hidden, const float* rela, int32_t d, int32_t ld, const float* a_s, const float* a_r, const float* a_q,
         int32_t ap, const float* w_alpha, const float* b_alpha, int32_t attn_dim, const float* grad_agg, float* grad_gate,
@@ -300,6 +369,16 @@ int run(const char* who, const TimeIn* T, int32_t n_src, int32_t n_dst, int64_t 
              T->n_time);
     RG_CHECK((int64_t)3 * n_src < ((int64_t)1 << 31) && (int64_t)3 * n_rela_rows < ((int64_t)1 << 31),
              "%s: n_src=%d n_rela_rows=%d (three rows each overflow int32)", who, n_src, n_rela_rows);
+  }
+  const int64_t n_rep = Q ? Q->n_rep : 1;
+  if (Q) {
+    RG_CHECK(!T, "%s: the gated form is static", who);
+    RG_CHECK(n_rep >= 1, "%s: n_rep=%lld (need at least one replica)", who, (long long)n_rep);
+    RG_CHECK(n_rep * std::max(n_src, n_dst) < ((int64_t)1 << 31) && n_rep * n_edges < ((int64_t)1 << 31),
+             "%s: n_rep=%lld times n_src=%d, n_dst=%d or n_edges=%lld overflows int32", who, (long long)n_rep, n_src, n_dst,
+             (long long)n_edges);
+    RG_CHECK(Q->t, "%s: NULL argument (t)", who);
+    RG_CHECK(n_rep <= 65535, "%s: n_rep=%lld (at most 65535: the combine launch has a grid row per replica)", who, (long long)n_rep);
   }
   RG_CHECK((grad_hidden == nullptr) == (grad_a_s == nullptr), "%s: grad_hidden and grad_a_s come together or not at all", who);
   if (n_src == 0) {
@@ -323,8 +402,9 @@ int run(const char* who, const TimeIn* T, int32_t n_src, int32_t n_dst, int64_t 
            "%s: float buffers must be 16-B aligned", who);
   int64_t n_hubs, n_chunks;
   count_cuts(src_ptr_host, n_rows, &n_hubs, &n_chunks);
-  RG_CHECK((int64_t)n_rows + n_chunks < ((int64_t)1 << 31), "%s: %lld items overflow int32", who, (long long)(n_rows + n_chunks));
-  const size_t need = n_hubs ? list_bytes(n_hubs, n_chunks) + rows_bytes(n_chunks, ld) + rows_bytes(n_chunks, ap) : 0;
+  RG_CHECK(n_rep * ((int64_t)n_rows + n_chunks) < ((int64_t)1 << 31) - 64, "%s: %lld items overflow int32", who,
+           (long long)(n_rep * (n_rows + n_chunks)));
+  const size_t need = scratch_need(n_hubs, n_chunks, ld, ap, n_rep);
   RG_CHECK(need == 0 || (scratch && scratch_bytes >= need), "%s: scratch %zu B < required %zu B", who, scratch ? scratch_bytes : (size_t)0,
            need);
 
@@ -340,7 +420,7 @@ int run(const char* who, const TimeIn* T, int32_t n_src, int32_t n_dst, int64_t 
   int4* hubs_dev = (int4*)scratch;
   A.chunks = hubs_dev + n_hubs;
   A.partial_h = n_hubs ? (float4*)((char*)scratch + list_bytes(n_hubs, n_chunks)) : nullptr;
-  A.partial_as = n_hubs ? (float4*)((char*)A.partial_h + rows_bytes(n_chunks, ld)) : nullptr;
+  A.partial_as = n_hubs ? (float4*)((char*)A.partial_h + rows_bytes(n_rep * n_chunks, ld)) : nullptr;
   // every argument error is out before anything is enqueued: the width dispatch is probed first
   if (rg::with_ap4(ap / 4, who, [](auto) { return 0; })) return 1;
   hipStream_t s = (hipStream_t)stream;
@@ -361,14 +441,21 @@ int run(const char* who, const TimeIn* T, int32_t n_src, int32_t n_dst, int64_t 
   const int rc = rg::with_g(A.ld4, [&](auto g) {
     return rg::with_ap4(ap / 4, who, [&](auto a4) {
       if (T) return launch<decltype(g)::value, decltype(a4)::value, true>(A, s);
+      if (Q) {
+        DbGatedArgs GA;
+        static_cast<DbArgs&>(GA) = A;
+        GA.n_rep = (int)n_rep; GA.n_chunks = (int)n_chunks; GA.t = Q->t; GA.gate_lo = Q->gate_lo; GA.gate_hi = Q->gate_hi;
+        return launch<decltype(g)::value, decltype(a4)::value, false, true>(GA, s);
+      }
       return launch<decltype(g)::value, decltype(a4)::value, false>(A, s);
     });
   });
   if (rc) return rc;
   if (n_hubs && grad_hidden) {
     const int64_t threads = n_hubs * (A.ld4 + ap / 4);
-    hipLaunchKernelGGL(digraph_bwd_combine_kernel, dim3((unsigned)rg::ceil_div(threads, 256)), dim3(256), 0, s, hubs_dev, (int)n_hubs,
-                       (const float4*)A.partial_h, (const float4*)A.partial_as, A.grad_hidden, A.grad_a_s, A.ld4, ap / 4);
+    hipLaunchKernelGGL(digraph_bwd_combine_kernel, dim3((unsigned)rg::ceil_div(threads, 256), (unsigned)n_rep), dim3(256), 0, s, hubs_dev,
+                       (int)n_hubs, (const float4*)A.partial_h, (const float4*)A.partial_as, A.grad_hidden, A.grad_a_s, A.ld4, ap / 4,
+                       n_chunks, (int64_t)n_rows);
     RG_LAUNCH_CHECK();
   }
   return 0;
@@ -384,7 +471,30 @@ extern "C" size_t rg_digraph_layer_bwd_scratch_bytes(const int32_t* src_ptr_host
   int64_t n_hubs, n_chunks;
   rgdb::count_cuts(src_ptr_host, n_src, &n_hubs, &n_chunks);
   if (n_hubs == 0) return 0;
-  return rgdb::list_bytes(n_hubs, n_chunks) + rgdb::rows_bytes(n_chunks, ld) + rgdb::rows_bytes(n_chunks, ap);
+  return rgdb::scratch_need(n_hubs, n_chunks, ld, ap, 1);
+}
+
+extern "C" size_t rg_digraph_layer_bwd_gated_scratch_bytes(const int32_t* src_ptr_host, int32_t n_src, int32_t ld, int32_t ap,
+                                                           int32_t n_rep) {
+  if (!src_ptr_host || n_src <= 0 || ld <= 0 || ap <= 0 || n_rep < 1) return 0;
+  for (int32_t s = 0; s < n_src; ++s)
+    if (src_ptr_host[s + 1] < src_ptr_host[s]) return 0;
+  int64_t n_hubs, n_chunks;
+  rgdb::count_cuts(src_ptr_host, n_src, &n_hubs, &n_chunks);
+  return rgdb::scratch_need(n_hubs, n_chunks, ld, ap, n_rep);
+}
+
+extern "C" int rg_digraph_layer_bwd_gated(int32_t n_rep, const float* t, const float* gate_lo, const float* gate_hi, int32_t n_src,
+                                          int32_t n_dst, int64_t n_edges, const int32_t* src_ptr, const int32_t* src_ptr_host,
+                                          const int32_t* edge_of, const int32_t* dst_of_edge, const int32_t* rel, const int32_t* row_of_dst,
+                                          int32_t n_rela_rows, int32_t batch, const float* hidden, const float* rela, int32_t d, int32_t ld,
+                                          const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha,
+                                          const float* b_alpha, int32_t attn_dim, const float* grad_agg, float* grad_gate,
+                                          float* grad_hidden, float* grad_a_s, void* scratch, size_t scratch_bytes, void* stream) {
+  const rgdb::GateIn Q{n_rep, t, gate_lo, gate_hi};
+  return rgdb::run("rg_digraph_layer_bwd_gated", nullptr, &Q, n_src, n_dst, n_edges, src_ptr, src_ptr_host, edge_of, dst_of_edge, rel,
+                   row_of_dst, n_rela_rows, batch, hidden, rela, d, ld, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim, grad_agg, grad_gate,
+                   grad_hidden, grad_a_s, scratch, scratch_bytes, stream);
 }
 
 extern "C" int rg_digraph_layer_bwd(int32_t n_src, int32_t n_dst, int64_t n_edges, const int32_t* src_ptr, const int32_t* src_ptr_host,
@@ -393,7 +503,7 @@ extern "C" int rg_digraph_layer_bwd(int32_t n_src, int32_t n_dst, int64_t n_edge
                                     const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha,
                                     const float* b_alpha, int32_t attn_dim, const float* grad_agg, float* grad_gate,
                                     float* grad_hidden, float* grad_a_s, void* scratch, size_t scratch_bytes, void* stream) {
-  return rgdb::run("rg_digraph_layer_bwd", nullptr, n_src, n_dst, n_edges, src_ptr, src_ptr_host, edge_of, dst_of_edge, rel, row_of_dst,
+  return rgdb::run("rg_digraph_layer_bwd", nullptr, nullptr, n_src, n_dst, n_edges, src_ptr, src_ptr_host, edge_of, dst_of_edge, rel, row_of_dst,
                    n_rela_rows, batch, hidden, rela, d, ld, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim, grad_agg, grad_gate, grad_hidden,
                    grad_a_s, scratch, scratch_bytes, stream);
 }
@@ -406,7 +516,7 @@ extern "C" int rg_digraph_tlayer_bwd(int32_t n_src, int32_t n_dst, int64_t n_edg
                                      const float* b_alpha, int32_t attn_dim, const float* grad_agg, float* grad_gate, float* grad_hidden,
                                      float* grad_a_s_dir, void* scratch, size_t scratch_bytes, void* stream) {
   const rgdb::TimeIn T{edge_time, q_time, time_tab, n_time, n_dir};
-  return rgdb::run("rg_digraph_tlayer_bwd", &T, n_src, n_dst, n_edges, src_ptr, src_ptr_host, edge_of, dst_of_edge, rel, row_of_dst,
+  return rgdb::run("rg_digraph_tlayer_bwd", &T, nullptr, n_src, n_dst, n_edges, src_ptr, src_ptr_host, edge_of, dst_of_edge, rel, row_of_dst,
                    n_rela_rows, batch, hidden, rela, d, ld, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim, grad_agg, grad_gate, grad_hidden,
                    grad_a_s_dir, scratch, scratch_bytes, stream);
 }

@@ -26,6 +26,15 @@
 //                    acc += alpha_e * (hidden[3 s + dir] + (rela[dir * n_rela_rows + r] + time_tab[dir * n_time + min(|dt|, n_time - 1)]))
 //       n_dir == 1   acc += alpha_e * (hidden[s] + (rela[r] + time_tab[clamp(q_time[b] - edge_time[e], 0, n_time - 1)]))   (rg_xlayer_fwd's)
 // alpha_e read from the un-directed s and r as above.  The group then exchanges four values per edge and has twelve gathers in flight.
+//
+// The gated, replicated form (rg_digraph_layer_fwd_gated, template parameter GATED; static only, and the other instantiations compile
+// to what they did without it): the call carries n_rep replicas of the hop, replica k with its own hidden and a_s rows (k * n_src + s)
+// and its own outputs (agg rows k * n_dst + o, alpha_out[k * E + e], partial rows k * n_chunks + slot), every index array, rela, a_r,
+// a_q and w shared.  An edge has a gate g = fmaf(t[k], gate_hi[e] - gate_lo[e], gate_lo[e]) that multiplies its message:
+//       c = g * alpha_e   (rounded once; exactly alpha_e at g == 1)        acc = fmaf(c, hidden[s] + rela[r], acc)
+// The gate does not enter alpha_e.  Mapping: an item is a (replica, destination or chunk) pair, item k * n_items + i, so a group works
+// exactly as it does in an n_rep = 1 call and a replica's bits do not depend on the others; the group exchanges c where the ungated
+// kernel exchanges alpha.  The combine launch has a grid row per replica.
 #include <algorithm>
 #include <type_traits>
 #include <vector>
@@ -68,15 +77,33 @@ struct DgTimedArgs : DgArgs {
   int n_time, n_dir;           // n_dir 3: interpolation (rows by direction), 1: extrapolation form (one table of lags)
 };
 
+// what the gated form (rg_digraph_layer_fwd_gated) reads on top
+struct DgGatedArgs : DgArgs {
+  int n_rep, n_chunks;         // replicas; chunks of ONE replica (replica k's partial rows start at k * n_chunks)
+  const float* t;              // [n_rep]
+  const float* gate_lo;        // [E] or nullptr: 0
+  const float* gate_hi;        // [E] or nullptr: 1
+};
+
+template <bool TIMED, bool GATED>
+using DgArgsOf = std::conditional_t<GATED, DgGatedArgs, std::conditional_t<TIMED, DgTimedArgs, DgArgs>>;
+
 __device__ __forceinline__ int clampi(int x, int hi) { return min(max(x, 0), hi); }
 
-template <int G, int AP4, bool TIMED>
-__global__ __launch_bounds__(DG_BLOCK) void digraph_fwd_kernel(std::conditional_t<TIMED, DgTimedArgs, DgArgs> A) {
+template <int G, int AP4, bool TIMED, bool GATED>
+__global__ __launch_bounds__(DG_BLOCK) void digraph_fwd_kernel(DgArgsOf<TIMED, GATED> A) {
+  static_assert(!(TIMED && GATED), "the gated form is static");
   constexpr int PER_WAVE = 64 / G;
   const int lane = threadIdx.x & 63;
   const int lane_g = lane & (G - 1), gbase = lane & ~(G - 1);
   const int wave = blockIdx.x * (DG_BLOCK / 64) + (threadIdx.x >> 6);
-  const int item = wave * PER_WAVE + lane / G;
+  int item = wave * PER_WAVE + lane / G;
+  int rep = 0;                                           // GATED: the item's replica, and the item inside it
+  if constexpr (GATED) {
+    rep = item / A.n_items;
+    item -= rep * A.n_items;
+    if (rep >= A.n_rep) { rep = 0; item = A.n_items; }   // past the last replica: no work
+  }
   const bool row_lane = lane_g < A.ld4;
   const int lane_c = row_lane ? lane_g : A.ld4 - 1;      // loads never branch: idle lanes re-read the last float4
 
@@ -89,18 +116,31 @@ __global__ __launch_bounds__(DG_BLOCK) void digraph_fwd_kernel(std::conditional_
     if (hi - lo <= DIGRAPH_CHUNK) {                      // (a cut destination is written by the combine pass)
       beg = lo; end = max(hi, lo);
       out = A.agg + (int64_t)o * A.ld4;
+      if constexpr (GATED) out += (int64_t)rep * A.n_dst * A.ld4;
     }
   } else if (item < A.n_items) {
     const int4 c = A.chunks[item - A.n_dst];
     o = clampi(c.x, A.n_dst - 1);
     beg = clampi(c.y, A.E); end = min(max(clampi(c.z, A.E), beg), beg + DIGRAPH_CHUNK);
     out = A.partial + (int64_t)c.w * A.ld4;
+    if constexpr (GATED) out += (int64_t)rep * A.n_chunks * A.ld4;
   }
   const int b = clampi(A.row_of_dst[o], A.B - 1);
   const float b_alpha = A.b_alpha[0];
   const float4* aq_p = A.a_q + (int64_t)b * AP4;
   int qt = 0;
   if constexpr (TIMED) qt = A.q_time[b];
+  // GATED: the replica's rows of hidden and a_s, its alpha_out and its t
+  const float4* hidden_p = A.hidden;
+  const float4* as_tab = A.a_s;
+  float* alpha_out = A.alpha_out;
+  float t_rep = 1.f;
+  if constexpr (GATED) {
+    hidden_p += (int64_t)rep * A.n_src * A.ld4;
+    as_tab += (int64_t)rep * A.n_src * AP4;
+    if (alpha_out) alpha_out += (int64_t)rep * A.E;
+    t_rep = A.t[rep];
+  }
 
   float4 acc = rg::f4zero();
   for (int c0 = beg; __any(c0 < end); c0 += G) {
@@ -115,9 +155,13 @@ __global__ __launch_bounds__(DG_BLOCK) void digraph_fwd_kernel(std::conditional_
       float z = b_alpha;
 #pragma clang loop unroll_count(AP4 >= 8 ? 2 : AP4)
       for (int k = 0; k < AP4; ++k)
-        rg::attn_acc_fwd(z, rg::attn_w4(A.w_alpha, A.attn_dim, k), A.a_s[(int64_t)s * AP4 + k], A.a_r[(int64_t)r * AP4 + k], aq_p[k]);
+        rg::attn_acc_fwd(z, rg::attn_w4(A.w_alpha, A.attn_dim, k), as_tab[(int64_t)s * AP4 + k], A.a_r[(int64_t)r * AP4 + k], aq_p[k]);
       alpha = rg::attn_alpha(z);
-      if (A.alpha_out) A.alpha_out[c] = alpha;
+      if (alpha_out) alpha_out[c] = alpha;
+      if constexpr (GATED) {                             // from here on alpha is the message's coefficient c = g * alpha_e
+        const float lo = A.gate_lo ? A.gate_lo[c] : 0.f, hi = A.gate_hi ? A.gate_hi[c] : 1.f;
+        alpha = fmaf(t_rep, hi - lo, lo) * alpha;
+      }
       if constexpr (TIMED) {
         // the rows of the message, as layer_fwd_kernel.h forms them (the attention above read the un-directed s and r); 64-bit
         // differences, so that no pair of times overflows, and the time row clamped into its table
@@ -148,7 +192,7 @@ __global__ __launch_bounds__(DG_BLOCK) void digraph_fwd_kernel(std::conditional_
         if constexpr (TIMED) tu[u] = __shfl(trow, from, 64);
       }
 #pragma unroll
-      for (int u = 0; u < 4; ++u) hv[u] = A.hidden[(int64_t)su[u] * A.ld4 + lane_c];
+      for (int u = 0; u < 4; ++u) hv[u] = hidden_p[(int64_t)su[u] * A.ld4 + lane_c];
 #pragma unroll
       for (int u = 0; u < 4; ++u) rv[u] = A.rela[(int64_t)ru[u] * A.ld4 + lane_c];
       if constexpr (TIMED) {             // rela[rrow] + time_tab[trow] first, then hidden: layer_fwd_kernel.h's association
@@ -173,8 +217,11 @@ __global__ __launch_bounds__(DG_BLOCK) void digraph_fwd_kernel(std::conditional_
 }
 
 // agg[o] of the cut destinations: their chunks' partial rows added in chunk order, the first one initialising the sum
+// (gated form: grid row k is replica k, its partial rows and its agg rows partial_rep / agg_rep float4 further on)
 __global__ void digraph_combine_kernel(const int4* __restrict__ hubs, int n_hubs, const float4* __restrict__ partial,
-                                       float4* __restrict__ agg, int ld4) {
+                                       float4* __restrict__ agg, int ld4, int64_t partial_rep, int64_t agg_rep) {
+  partial += blockIdx.y * partial_rep;
+  agg += blockIdx.y * agg_rep;
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t h = tid / ld4;
   const int c = (int)(tid - h * ld4);
@@ -200,10 +247,12 @@ void count_cuts(const int32_t* ptr, int32_t n_dst, int64_t* n_hubs, int64_t* n_c
 
 size_t list_bytes(int64_t n_hubs, int64_t n_chunks) { return rg::align_up((size_t)(n_hubs + n_chunks) * sizeof(int4), 256); }
 
-template <int G, int AP4, bool TIMED>
-int launch(const std::conditional_t<TIMED, DgTimedArgs, DgArgs>& A, hipStream_t s) {
-  const int64_t waves = rg::ceil_div(A.n_items, 64 / G);
-  hipLaunchKernelGGL((digraph_fwd_kernel<G, AP4, TIMED>), dim3((unsigned)rg::ceil_div(waves, DG_BLOCK / 64)), dim3(DG_BLOCK), 0, s, A);
+template <int G, int AP4, bool TIMED, bool GATED = false>
+int launch(const DgArgsOf<TIMED, GATED>& A, hipStream_t s) {
+  int64_t items = A.n_items;
+  if constexpr (GATED) items *= A.n_rep;
+  const int64_t waves = rg::ceil_div(items, 64 / G);
+  hipLaunchKernelGGL((digraph_fwd_kernel<G, AP4, TIMED, GATED>), dim3((unsigned)rg::ceil_div(waves, DG_BLOCK / 64)), dim3(DG_BLOCK), 0, s, A);
   RG_LAUNCH_CHECK();
   return 0;
 }
@@ -216,8 +265,20 @@ struct TimeIn {
   int32_t n_time, n_dir;
 };
 
-// both entry points: every check, then the chunk list, the layer launch and the combine launch
-int run(const char* who, const TimeIn* T, int32_t n_dst, int64_t n_edges, const int32_t* dst_ptr, const int32_t* dst_ptr_host,
+// the gate arguments of rg_digraph_layer_fwd_gated; nullptr: the ungated entry points
+struct GateIn {
+  int32_t n_rep;
+  const float* t;
+  const float* gate_lo;
+  const float* gate_hi;
+};
+
+size_t scratch_need(int64_t n_hubs, int64_t n_chunks, int32_t ld, int64_t n_rep) {
+  return n_hubs ? list_bytes(n_hubs, n_chunks) + rg::align_up((size_t)(n_rep * n_chunks) * ld * sizeof(float), 256) : 0;
+}
+
+// every entry point: every check, then the chunk list, the layer launch and the combine launch
+int run(const char* who, const TimeIn* T, const GateIn* Q, int32_t n_dst, int64_t n_edges, const int32_t* dst_ptr, const int32_t* dst_ptr_host,
         const int32_t* src_idx, const int32_t* rel, const int32_t* row_of_dst, int32_t n_src, int32_t n_rela_rows, int32_t batch,
         const float* hidden, const float* rela, int32_t d, int32_t ld, const float* a_s, const float* a_r, const float* a_q, int32_t ap,
         const float* w_alpha, const float* b_alpha, int32_t attn_dim, float* agg_out, float* alpha_out, void* scratch,
@@ -234,6 +295,16 @@ int run(const char* who, const TimeIn* T, int32_t n_dst, int64_t n_edges, const 
              T->n_time);
     RG_CHECK((int64_t)3 * n_src < ((int64_t)1 << 31) && (int64_t)3 * n_rela_rows < ((int64_t)1 << 31),
              "%s: n_src=%d n_rela_rows=%d (three rows each overflow int32)", who, n_src, n_rela_rows);
+  }
+  const int64_t n_rep = Q ? Q->n_rep : 1;
+  if (Q) {
+    RG_CHECK(!T, "%s: the gated form is static", who);
+    RG_CHECK(n_rep >= 1, "%s: n_rep=%lld (need at least one replica)", who, (long long)n_rep);
+    RG_CHECK(n_rep * std::max(n_src, n_dst) < ((int64_t)1 << 31) && n_rep * n_edges < ((int64_t)1 << 31),
+             "%s: n_rep=%lld times n_src=%d, n_dst=%d or n_edges=%lld overflows int32", who, (long long)n_rep, n_src, n_dst,
+             (long long)n_edges);
+    RG_CHECK(Q->t, "%s: NULL argument (t)", who);
+    RG_CHECK(n_rep <= 65535, "%s: n_rep=%lld (at most 65535: the combine launch has a grid row per replica)", who, (long long)n_rep);
   }
   if (n_dst == 0) {
     RG_CHECK(n_edges == 0, "%s: %lld edges without a destination", who, (long long)n_edges);
@@ -254,8 +325,9 @@ int run(const char* who, const TimeIn* T, int32_t n_dst, int64_t n_edges, const 
              (uintptr_t)scratch | (uintptr_t)(T ? T->time_tab : nullptr)) & 15) == 0, "%s: float buffers must be 16-B aligned", who);
   int64_t n_hubs, n_chunks;
   count_cuts(dst_ptr_host, n_dst, &n_hubs, &n_chunks);
-  RG_CHECK((int64_t)n_dst + n_chunks < ((int64_t)1 << 31), "%s: %lld items overflow int32", who, (long long)(n_dst + n_chunks));
-  const size_t need = n_hubs ? list_bytes(n_hubs, n_chunks) + rg::align_up((size_t)n_chunks * ld * sizeof(float), 256) : 0;
+  RG_CHECK(n_rep * ((int64_t)n_dst + n_chunks) < ((int64_t)1 << 31) - 64, "%s: %lld items overflow int32", who,
+           (long long)(n_rep * (n_dst + n_chunks)));
+  const size_t need = scratch_need(n_hubs, n_chunks, ld, n_rep);
   RG_CHECK(need == 0 || (scratch && scratch_bytes >= need), "%s: scratch %zu B < required %zu B", who, scratch ? scratch_bytes : (size_t)0,
            need);
 
@@ -291,14 +363,20 @@ int run(const char* who, const TimeIn* T, int32_t n_dst, int64_t n_edges, const 
   const int rc = rg::with_g(A.ld4, [&](auto g) {
     return rg::with_ap4(ap / 4, who, [&](auto a4) {
       if (T) return launch<decltype(g)::value, decltype(a4)::value, true>(A, s);
+      if (Q) {
+        DgGatedArgs GA;
+        static_cast<DgArgs&>(GA) = A;
+        GA.n_rep = (int)n_rep; GA.n_chunks = (int)n_chunks; GA.t = Q->t; GA.gate_lo = Q->gate_lo; GA.gate_hi = Q->gate_hi;
+        return launch<decltype(g)::value, decltype(a4)::value, false, true>(GA, s);
+      }
       return launch<decltype(g)::value, decltype(a4)::value, false>(A, s);
     });
   });
   if (rc) return rc;
   if (n_hubs) {
     const int64_t threads = n_hubs * A.ld4;
-    hipLaunchKernelGGL(digraph_combine_kernel, dim3((unsigned)rg::ceil_div(threads, 256)), dim3(256), 0, s, hubs_dev, (int)n_hubs,
-                       (const float4*)A.partial, A.agg, A.ld4);
+    hipLaunchKernelGGL(digraph_combine_kernel, dim3((unsigned)rg::ceil_div(threads, 256), (unsigned)n_rep), dim3(256), 0, s, hubs_dev,
+                       (int)n_hubs, (const float4*)A.partial, A.agg, A.ld4, n_chunks * A.ld4, (int64_t)n_dst * A.ld4);
     RG_LAUNCH_CHECK();
   }
   return 0;
@@ -314,7 +392,28 @@ extern "C" size_t rg_digraph_layer_fwd_scratch_bytes(const int32_t* dst_ptr_host
   int64_t n_hubs, n_chunks;
   rgdg::count_cuts(dst_ptr_host, n_dst, &n_hubs, &n_chunks);
   if (n_hubs == 0) return 0;
-  return rgdg::list_bytes(n_hubs, n_chunks) + rg::align_up((size_t)n_chunks * ld * sizeof(float), 256);
+  return rgdg::scratch_need(n_hubs, n_chunks, ld, 1);
+}
+
+extern "C" size_t rg_digraph_layer_fwd_gated_scratch_bytes(const int32_t* dst_ptr_host, int32_t n_dst, int32_t ld, int32_t n_rep) {
+  if (!dst_ptr_host || n_dst <= 0 || ld <= 0 || n_rep < 1) return 0;
+  for (int32_t o = 0; o < n_dst; ++o)
+    if (dst_ptr_host[o + 1] < dst_ptr_host[o]) return 0;
+  int64_t n_hubs, n_chunks;
+  rgdg::count_cuts(dst_ptr_host, n_dst, &n_hubs, &n_chunks);
+  return rgdg::scratch_need(n_hubs, n_chunks, ld, n_rep);
+}
+
+extern "C" int rg_digraph_layer_fwd_gated(int32_t n_rep, const float* t, const float* gate_lo, const float* gate_hi, int32_t n_dst,
+                                          int64_t n_edges, const int32_t* dst_ptr, const int32_t* dst_ptr_host, const int32_t* src_idx,
+                                          const int32_t* rel, const int32_t* row_of_dst, int32_t n_src, int32_t n_rela_rows, int32_t batch,
+                                          const float* hidden, const float* rela, int32_t d, int32_t ld, const float* a_s, const float* a_r,
+                                          const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha, int32_t attn_dim,
+                                          float* agg_out, float* alpha_out, void* scratch, size_t scratch_bytes, void* stream) {
+  const rgdg::GateIn Q{n_rep, t, gate_lo, gate_hi};
+  return rgdg::run("rg_digraph_layer_fwd_gated", nullptr, &Q, n_dst, n_edges, dst_ptr, dst_ptr_host, src_idx, rel, row_of_dst, n_src,
+                   n_rela_rows, batch, hidden, rela, d, ld, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim, agg_out, alpha_out, scratch,
+                   scratch_bytes, stream);
 }
 
 extern "C" int rg_digraph_layer_fwd(int32_t n_dst, int64_t n_edges, const int32_t* dst_ptr, const int32_t* dst_ptr_host,
@@ -323,7 +422,7 @@ extern "C" int rg_digraph_layer_fwd(int32_t n_dst, int64_t n_edges, const int32_
                                     const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha,
                                     const float* b_alpha, int32_t attn_dim, float* agg_out, float* alpha_out, void* scratch,
                                     size_t scratch_bytes, void* stream) {
-  return rgdg::run("rg_digraph_layer_fwd", nullptr, n_dst, n_edges, dst_ptr, dst_ptr_host, src_idx, rel, row_of_dst, n_src, n_rela_rows,
+  return rgdg::run("rg_digraph_layer_fwd", nullptr, nullptr, n_dst, n_edges, dst_ptr, dst_ptr_host, src_idx, rel, row_of_dst, n_src, n_rela_rows,
                    batch, hidden, rela, d, ld, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim, agg_out, alpha_out, scratch, scratch_bytes,
                    stream);
 }
@@ -336,7 +435,7 @@ extern "C" int rg_digraph_tlayer_fwd(int32_t n_dst, int64_t n_edges, const int32
                                      const float* b_alpha, int32_t attn_dim, float* agg_out, float* alpha_out, void* scratch,
                                      size_t scratch_bytes, void* stream) {
   const rgdg::TimeIn T{edge_time, q_time, time_tab, n_time, n_dir};
-  return rgdg::run("rg_digraph_tlayer_fwd", &T, n_dst, n_edges, dst_ptr, dst_ptr_host, src_idx, rel, row_of_dst, n_src, n_rela_rows,
+  return rgdg::run("rg_digraph_tlayer_fwd", &T, nullptr, n_dst, n_edges, dst_ptr, dst_ptr_host, src_idx, rel, row_of_dst, n_src, n_rela_rows,
                    batch, hidden, rela, d, ld, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim, agg_out, alpha_out, scratch, scratch_bytes,
                    stream);
 }

@@ -1142,9 +1142,37 @@ def digraph_tlayer_fwd(dst_ptr, src_idx, rel, row_of_dst, hidden, rela, time_tab
                           attn_dim, want_alpha, dst_ptr_host, (edge_time, q_time, time_tab, n_dir))
 
 
+def digraph_layer_fwd_gated(dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s, a_r, a_q, w_alpha, b_alpha, attn_dim, t, gate_lo=None,
+                            gate_hi=None, want_alpha=True, dst_ptr_host=None, check_index=True):
+    """digraph_layer_fwd with a gate on every edge's message, for ``t.numel()`` replicas of the hop in one launch
+    (rg_digraph_layer_fwd_gated): (agg fp32 [n_rep * n_dst, ld], alpha fp32 [n_rep * E] or None).  ``t`` fp32 [n_rep]; ``gate_lo`` /
+    ``gate_hi`` fp32 [E] in the order of the edge list, or None for 0 / 1; replica k's gate is fmaf(t[k], hi - lo, lo), it reads rows
+    k * n_src + s of ``hidden`` [n_rep * n_src, ld] and ``a_s`` [n_rep * n_src, ap] and writes rows k * n_dst + o of agg; the index arrays
+    and the other tables are shared.  The gate multiplies the message and does not enter alpha; at gate 1 the bits are
+    digraph_layer_fwd's, and a replica's are those of a one-replica call with its t.  digraph_layer_fwd's checks (ValueError);
+    ``check_index`` False skips the range check of the index arrays (a caller that hands over the same arrays again)."""
+    return _digraph_layer("digraph_layer_fwd_gated", dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s, a_r, a_q, w_alpha, b_alpha,
+                          attn_dim, want_alpha, dst_ptr_host, None, (t, gate_lo, gate_hi), check_index)
+
+
+def _check_gates(who, gated, E, n_rows):
+    """(n_rep, t, gate_lo, gate_hi) of a gated wrapper: ``t`` fp32 [n_rep] with n_rep >= 1 dividing the ``n_rows`` rows of the stacked
+    state, ``gate_lo`` / ``gate_hi`` fp32 [E] or None."""
+    t, lo, hi = gated
+    if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.dim() == 1 and t.numel() >= 1):
+        raise ValueError("%s: t must be a float32 vector with an entry per replica (at least one)" % who)
+    for name, g in (("gate_lo", lo), ("gate_hi", hi)):
+        if g is not None and not (torch.is_tensor(g) and g.dtype == torch.float32 and tuple(g.shape) == (E,)):
+            raise ValueError("%s: %s must be float32 [%d], one per edge, or None" % (who, name, E))
+    if n_rows % t.numel():
+        raise ValueError("%s: the %d rows of hidden and a_s are not a whole number of rows for each of the %d replicas" % (who, n_rows, t.numel()))
+    return t.numel(), t, lo, hi
+
+
 def _digraph_layer(who, dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s, a_r, a_q, w_alpha, b_alpha, attn_dim, want_alpha,
-                   dst_ptr_host, timed):
-    """Both wrappers: the host checks, the scratch, the launch.  ``timed``: None or (edge_time, q_time, time_tab, n_dir)."""
+                   dst_ptr_host, timed, gated=None, check_index=True):
+    """Every forward wrapper: the host checks, the scratch, the launch.  ``timed``: None or (edge_time, q_time, time_tab, n_dir);
+    ``gated``: None or (t, gate_lo, gate_hi), static only."""
     ints, floats = [("dst_ptr", dst_ptr), ("src_idx", src_idx), ("rel", rel), ("row_of_dst", row_of_dst)], \
         [("hidden", hidden), ("rela", rela), ("a_s", a_s), ("a_r", a_r), ("a_q", a_q)]
     n_dir = 1
@@ -1162,6 +1190,10 @@ def _digraph_layer(who, dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s,
             raise ValueError("%s: %s must be a float32 matrix" % (who, name))
     n_dst, E = dst_ptr.numel() - 1, src_idx.numel()
     ld, ap = hidden.shape[1], a_s.shape[1]
+    n_rep, gates = 1, ()
+    if gated is not None:
+        n_rep, *gates = _check_gates(who, gated, E, a_s.shape[0])
+    n_src = a_s.shape[0] // n_rep
     if n_dst < 0 or rel.numel() != E or row_of_dst.numel() != n_dst:
         raise ValueError("%s: dst_ptr [%d], src_idx [%d], rel [%d] and row_of_dst [%d] do not fit together"
                          % (who, dst_ptr.numel(), E, rel.numel(), row_of_dst.numel()))
@@ -1176,17 +1208,17 @@ def _digraph_layer(who, dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s,
             raise ValueError("%s: edge_time [%d] (%d edges), q_time [%d] (a_q %s) and time_tab %s (n_dir * n_time rows of %d) do not fit together"
                              % (who, edge_time.numel(), E, q_time.numel(), tuple(a_q.shape), tuple(time_tab.shape), ld))
     _require_gpu(hidden.device)
-    tensors = tuple(t for _, t in ints + floats) + (w_alpha, b_alpha)
+    tensors = tuple(t for _, t in ints + floats) + (w_alpha, b_alpha) + tuple(g for g in gates if g is not None)
     if not all(t.is_cuda and t.is_contiguous() for t in tensors):
         raise ValueError("%s: every tensor must be contiguous and on the device" % who)
     dev = hidden.device
-    agg = torch.zeros((max(n_dst, 0), ld), dtype=torch.float32, device=dev)
-    alpha = torch.zeros(E, dtype=torch.float32, device=dev) if want_alpha else None
+    agg = torch.zeros((n_rep * max(n_dst, 0), ld), dtype=torch.float32, device=dev)
+    alpha = torch.zeros(n_rep * E, dtype=torch.float32, device=dev) if want_alpha else None
     ptr_h = np.ascontiguousarray(dst_ptr.cpu().numpy() if dst_ptr_host is None else dst_ptr_host, dtype=np.int32)
     if ptr_h.shape != (n_dst + 1,) or ptr_h[0] != 0 or ptr_h[-1] != E or (np.diff(ptr_h) < 0).any():
         raise ValueError("%s: dst_ptr must start at 0, never decrease and end at the number of edges (%d)" % (who, E))
-    if E:
-        checked = [("src_idx", src_idx, a_s.shape[0]), ("rel", rel, a_r.shape[0]), ("row_of_dst", row_of_dst, a_q.shape[0])]
+    if E and check_index:
+        checked = [("src_idx", src_idx, n_src), ("rel", rel, a_r.shape[0]), ("row_of_dst", row_of_dst, a_q.shape[0])]
         if timed is not None:                 # n_dir 3: a time id; n_dir 1: a day, any that is not negative
             checked.append(("edge_time", edge_time, n_time if n_dir == 3 else 1 << 31))
         lo = torch.stack([t.min() for _, t, _ in checked]).tolist()
@@ -1195,13 +1227,23 @@ def _digraph_layer(who, dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s,
             if a < 0 or b >= n:
                 raise ValueError("%s: %s out of range (%d..%d, %d rows)" % (who, name, a, b, n))
     L, p = _lib.lib(), _lib.ptr
-    nbytes = int(L.rg_digraph_layer_fwd_scratch_bytes(p(ptr_h), n_dst, ld)) if n_dst > 0 else 0
+    if n_dst <= 0:
+        nbytes = 0
+    elif gated is not None:
+        nbytes = int(L.rg_digraph_layer_fwd_gated_scratch_bytes(p(ptr_h), n_dst, ld, n_rep))
+    else:
+        nbytes = int(L.rg_digraph_layer_fwd_scratch_bytes(p(ptr_h), n_dst, ld))
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
     ev = None
     if DIGRAPH_EVENTS is not None:
         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         ev[0].record()
-    if timed is None:
+    if gated is not None:
+        _lib.check(L.rg_digraph_layer_fwd_gated(n_rep, p(gates[0]), p(gates[1]), p(gates[2]), n_dst, E, p(dst_ptr), p(ptr_h), p(src_idx), p(rel),
+                                                p(row_of_dst), n_src, a_r.shape[0], a_q.shape[0], p(hidden), p(rela), int(d), ld, p(a_s), p(a_r),
+                                                p(a_q), ap, p(w_alpha), p(b_alpha), int(attn_dim), p(agg), p(alpha), p(scratch), nbytes,
+                                                _lib.stream_ptr()))
+    elif timed is None:
         _lib.check(L.rg_digraph_layer_fwd(n_dst, E, p(dst_ptr), p(ptr_h), p(src_idx), p(rel), p(row_of_dst), a_s.shape[0], a_r.shape[0],
                                           a_q.shape[0], p(hidden), p(rela), int(d), ld, p(a_s), p(a_r), p(a_q), ap, p(w_alpha), p(b_alpha),
                                           int(attn_dim), p(agg), p(alpha), p(scratch), nbytes, _lib.stream_ptr()))
@@ -1212,7 +1254,7 @@ def _digraph_layer(who, dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s,
                                            p(scratch), nbytes, _lib.stream_ptr()))
     if ev is not None:
         ev[1].record()
-        DIGRAPH_EVENTS.append((ev[0], ev[1], n_dst, E))
+        DIGRAPH_EVENTS.append((ev[0], ev[1], n_rep * n_dst, n_rep * E))
     return agg, alpha
 
 
@@ -1275,10 +1317,21 @@ def digraph_tlayer_bwd(dst_ptr, src_idx, rel, row_of_dst, hidden, rela, time_tab
                               attn_dim, grad_agg, want_state, (edge_time, q_time, time_tab, n_dir))
 
 
+def digraph_layer_bwd_gated(dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s, a_r, a_q, w_alpha, b_alpha, attn_dim, grad_agg, t,
+                            gate_lo=None, gate_hi=None, want_state=True, view=None, check_index=True):
+    """The adjoint of digraph_layer_fwd_gated on the same arguments (rg_digraph_layer_bwd_gated): (grad_gate fp32 [n_rep * E], replica k's
+    at k * E + the edge's list position, grad_hidden fp32 [n_rep * n_src, ld], grad_a_s fp32 [n_rep * n_src, ap]) for ``grad_agg`` fp32
+    [n_rep * n_dst, ld]; grad_gate is the derivative with respect to the gate itself at the gate fmaf(t[k], hi - lo, lo).  At gate 1 the
+    bits are digraph_layer_bwd's, and a replica's are those of a one-replica call with its t.  ``view``: the hop's
+    digraph_source_view, if at hand (it does not depend on the gates or the replicas); ``check_index`` as the forward's."""
+    return _digraph_layer_bwd("digraph_layer_bwd_gated", dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s, a_r, a_q, w_alpha,
+                              b_alpha, attn_dim, grad_agg, want_state, None, (t, gate_lo, gate_hi), view, check_index)
+
+
 def _digraph_layer_bwd(who, dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s, a_r, a_q, w_alpha, b_alpha, attn_dim, grad_agg,
-                       want_state, timed):
-    """Both wrappers: the host checks, the source view, the scratch, the launch.  ``timed``: None or (edge_time, q_time, time_tab,
-    n_dir)."""
+                       want_state, timed, gated=None, view=None, check_index=True):
+    """Every backward wrapper: the host checks, the source view, the scratch, the launch.  ``timed``: None or (edge_time, q_time,
+    time_tab, n_dir); ``gated``: None or (t, gate_lo, gate_hi), static only."""
     ints = [("dst_ptr", dst_ptr), ("src_idx", src_idx), ("rel", rel), ("row_of_dst", row_of_dst)]
     floats = [("hidden", hidden), ("rela", rela), ("a_s", a_s), ("a_r", a_r), ("a_q", a_q), ("grad_agg", grad_agg)]
     n_dir = 1
@@ -1296,13 +1349,17 @@ def _digraph_layer_bwd(who, dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, 
         if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.dim() == 2):
             raise ValueError("%s: %s must be a float32 matrix" % (who, name))
     n_dst, E = dst_ptr.numel() - 1, src_idx.numel()
-    n_src, ld, ap = a_s.shape[0], hidden.shape[1], a_s.shape[1]
-    n_rows = n_dir * n_src                                # the rows of hidden, of the source view and of the state outputs
+    ld, ap = hidden.shape[1], a_s.shape[1]
+    n_rep, gates = 1, ()
+    if gated is not None:
+        n_rep, *gates = _check_gates(who, gated, E, a_s.shape[0])
+    n_src = a_s.shape[0] // n_rep
+    n_rows = n_dir * n_src                                # the rows of hidden, of the source view and of the state outputs (per replica)
     if n_dst < 0 or rel.numel() != E or row_of_dst.numel() != n_dst:
         raise ValueError("%s: dst_ptr [%d], src_idx [%d], rel [%d] and row_of_dst [%d] do not fit together"
                          % (who, dst_ptr.numel(), E, rel.numel(), row_of_dst.numel()))
-    if rela.shape[1] != ld or a_r.shape[1] != ap or a_q.shape[1] != ap or hidden.shape[0] != n_rows or n_dir * a_r.shape[0] != rela.shape[0] \
-            or tuple(grad_agg.shape) != (n_dst, ld):
+    if rela.shape[1] != ld or a_r.shape[1] != ap or a_q.shape[1] != ap or hidden.shape[0] != n_rep * n_rows or n_dir * a_r.shape[0] != rela.shape[0] \
+            or tuple(grad_agg.shape) != (n_rep * n_dst, ld):
         raise ValueError("%s: hidden %s, rela %s, a_s %s, a_r %s, a_q %s and grad_agg %s (%d destinations) do not fit together"
                          % (who, tuple(hidden.shape), tuple(rela.shape), tuple(a_s.shape), tuple(a_r.shape), tuple(a_q.shape),
                             tuple(grad_agg.shape), n_dst))
@@ -1313,17 +1370,17 @@ def _digraph_layer_bwd(who, dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, 
             raise ValueError("%s: edge_time [%d] (%d edges), q_time [%d] (a_q %s) and time_tab %s (n_dir * n_time rows of %d) do not fit together"
                              % (who, edge_time.numel(), E, q_time.numel(), tuple(a_q.shape), tuple(time_tab.shape), ld))
     _require_gpu(hidden.device)
-    tensors = tuple(t for _, t in ints + floats) + (w_alpha, b_alpha)
+    tensors = tuple(t for _, t in ints + floats) + (w_alpha, b_alpha) + tuple(g for g in gates if g is not None)
     if not all(t.is_cuda and t.is_contiguous() for t in tensors):
         raise ValueError("%s: every tensor must be contiguous and on the device" % who)
     dev = hidden.device
-    grad_gate = torch.zeros(E, dtype=torch.float32, device=dev)
-    grad_hidden = torch.zeros((n_rows, ld), dtype=torch.float32, device=dev) if want_state else None
-    grad_a_s = torch.zeros((n_rows, ap), dtype=torch.float32, device=dev) if want_state else None
-    ptr_h = dst_ptr.cpu().numpy()
-    if ptr_h[0] != 0 or ptr_h[-1] != E or (np.diff(ptr_h) < 0).any():
+    grad_gate = torch.zeros(n_rep * E, dtype=torch.float32, device=dev)
+    grad_hidden = torch.zeros((n_rep * n_rows, ld), dtype=torch.float32, device=dev) if want_state else None
+    grad_a_s = torch.zeros((n_rep * n_rows, ap), dtype=torch.float32, device=dev) if want_state else None
+    ptr_h = dst_ptr.cpu().numpy() if check_index else None
+    if check_index and (ptr_h[0] != 0 or ptr_h[-1] != E or (np.diff(ptr_h) < 0).any()):
         raise ValueError("%s: dst_ptr must start at 0, never decrease and end at the number of edges (%d)" % (who, E))
-    if E:
+    if E and check_index:
         checked = [("src_idx", src_idx, n_src), ("rel", rel, a_r.shape[0]), ("row_of_dst", row_of_dst, a_q.shape[0])]
         if timed is not None:                 # n_dir 3: a time id; n_dir 1: a day, any that is not negative
             checked.append(("edge_time", edge_time, n_time if n_dir == 3 else 1 << 31))
@@ -1333,15 +1390,28 @@ def _digraph_layer_bwd(who, dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, 
             if a < 0 or b >= n:
                 raise ValueError("%s: %s out of range (%d..%d, %d rows)" % (who, name, a, b, n))
     key = None if timed is None else digraph_directed_rows(dst_ptr, src_idx, row_of_dst, edge_time, q_time, n_dir)
-    src_ptr, src_ptr_h, edge_of, dst_of_edge = digraph_source_view(dst_ptr, src_idx, n_rows, key=key)
+    src_ptr, src_ptr_h, edge_of, dst_of_edge = digraph_source_view(dst_ptr, src_idx, n_rows, key=key) if view is None else view
+    if src_ptr.numel() != n_rows + 1 or edge_of.numel() != E or dst_of_edge.numel() != E:
+        raise ValueError("%s: view is not the source view of this hop (%d sources, %d edges)" % (who, n_rows, E))
     L, p = _lib.lib(), _lib.ptr
-    nbytes = int(L.rg_digraph_layer_bwd_scratch_bytes(p(src_ptr_h), n_rows, ld, ap)) if n_rows > 0 else 0
+    if n_rows <= 0:
+        nbytes = 0
+    elif gated is not None:
+        nbytes = int(L.rg_digraph_layer_bwd_gated_scratch_bytes(p(src_ptr_h), n_rows, ld, ap, n_rep))
+    else:
+        nbytes = int(L.rg_digraph_layer_bwd_scratch_bytes(p(src_ptr_h), n_rows, ld, ap))
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
     ev = None
     if DIGRAPH_BWD_EVENTS is not None:
         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         ev[0].record()
-    if timed is None:
+    if gated is not None:
+        _lib.check(L.rg_digraph_layer_bwd_gated(n_rep, p(gates[0]), p(gates[1]), p(gates[2]), n_src, n_dst, E, p(src_ptr), p(src_ptr_h),
+                                                p(edge_of), p(dst_of_edge), p(rel), p(row_of_dst), a_r.shape[0], a_q.shape[0], p(hidden),
+                                                p(rela), int(d), ld, p(a_s), p(a_r), p(a_q), ap, p(w_alpha), p(b_alpha), int(attn_dim),
+                                                p(grad_agg), p(grad_gate), p(grad_hidden), p(grad_a_s), p(scratch), nbytes,
+                                                _lib.stream_ptr()))
+    elif timed is None:
         _lib.check(L.rg_digraph_layer_bwd(n_src, n_dst, E, p(src_ptr), p(src_ptr_h), p(edge_of), p(dst_of_edge), p(rel), p(row_of_dst),
                                           a_r.shape[0], a_q.shape[0], p(hidden), p(rela), int(d), ld, p(a_s), p(a_r), p(a_q), ap, p(w_alpha),
                                           p(b_alpha), int(attn_dim), p(grad_agg), p(grad_gate), p(grad_hidden), p(grad_a_s), p(scratch), nbytes,
@@ -1353,7 +1423,7 @@ def _digraph_layer_bwd(who, dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, 
                                            p(grad_agg), p(grad_gate), p(grad_hidden), p(grad_a_s), p(scratch), nbytes, _lib.stream_ptr()))
     if ev is not None:
         ev[1].record()
-        DIGRAPH_BWD_EVENTS.append((ev[0], ev[1], n_rows, E))
+        DIGRAPH_BWD_EVENTS.append((ev[0], ev[1], n_rep * n_rows, n_rep * E))
     if want_state and n_dir == 3:             # a source's three rows: past, now, future, added in that order
         g = grad_a_s.view(n_src, 3, ap)
         grad_a_s = ((g[:, 0] + g[:, 1]) + g[:, 2]).contiguous()

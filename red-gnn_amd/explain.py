@@ -11,6 +11,7 @@ s -> o through the query's subgraph (identity self-loops count as steps); each e
     rs = rd.rescore(model, keep=~paths.fact_mask(1))  # o re-scored with the best path's facts deleted (HIP: csrc/digraph_fwd.hip)
     fid = model.fidelity(subs, rels, objs, k=4)      # necessity and sufficiency of the best 1..k paths: an explain.Fidelity
     sal = rd.saliency(model)                         # d score / d (a gate on every edge), one pass (HIP: csrc/digraph_bwd.hip): an explain.Saliency
+    att = rd.integrated_gradients(model, steps=16)   # attributions that add up to the score (gated, replicated edge-list kernels): an explain.Attribution
 
 The extraction runs in HIP (csrc/explain.hip): a forward keeps all L + 1 frontier levels and each layer's attention projection, then
 one backward marking pass per hop reads only the marked tails' CSR rows.  This module holds the result type and the host drivers.
@@ -89,7 +90,7 @@ class RDigraph:
     n_rel: int = None
     n_time: int = None
 
-    def rescore(self, model, keep=None, mode="test"):
+    def rescore(self, model, keep=None, mode="test", gate=None):
         """The model's score of o on the digraph with only the edges ``keep`` (bool or uint8 [E] over ``edges``; None: all of them):
         an explain.Rescore.  RED-GNN's score of o depends on the r-digraph's edges alone, so this is the model's score on the knowledge
         graph with the facts behind the dropped edges deleted - a forward over the compact edge list, one HIP message-passing launch
@@ -110,10 +111,16 @@ class RDigraph:
         WERE".  The reference's time_offset_list makes a window start at the last row of day begin - 1 and end before the last row
         of day cur_t - 1, with offset 0 for days without rows, so deleting rows from the data itself moves window boundaries when a
         deleted row is the last of its day or a day loses all its rows; the rescore equals the forward of a model rebuilt from the
-        reduced data only for deletions that do neither."""
-        return rescore(self, model, keep, mode)
+        reduced data only for deletions that do neither.
 
-    def saliency(self, model, keep=None, mode="test"):
+        ``gate`` float32 [E] (a tensor or a numpy array, every entry finite; None: the ungated path, unchanged): the soft-gated rescore of
+        a static digraph - gate[e] multiplies the message of the kept edge e, agg[o] = sum_e gate_e alpha_e (hidden[s] + rela[r]), in
+        rg_digraph_layer_fwd_gated.  ``live`` and ``reached`` stay structural: they follow ``keep`` alone, and a gate of 0 disconnects
+        nothing.  A gate of ones gives the ungated call's bits.  The timed forms of the gated kernels are not built: a temporal or
+        extrapolation digraph or model with a gate is a ValueError."""
+        return rescore(self, model, keep, mode, gate)
+
+    def saliency(self, model, keep=None, mode="test", gate=None):
         """How much the score of o depends on every edge: an explain.Saliency.  Give every edge e a gate g_e that multiplies its
         message, agg[o] = sum_e g_e alpha_e (hidden[s] + rela[r]) in the forward ``rescore`` states; ``edge_grad[e]`` is d score / d g_e
         at g == 1 with the parameters fixed.  The gate does not enter alpha_e directly; it does enter the attention of later hops
@@ -129,8 +136,28 @@ class RDigraph:
         activation's adjoint, the timed edge-list layer's in HIP (rg_digraph_tlayer_bwd: a directed source row per work item) and
         plain products with the direction linears and the attention projection - neither model has a GRU or a carry.  The message
         gated there is the directed one, hidden_dir + (rela_dir + time row); ``mode`` must be "test".  A digraph of another
-        family than the model's is a ValueError."""
-        return saliency(self, model, keep, mode)
+        family than the model's is a ValueError.
+
+        ``gate`` float32 [E] (as ``rescore``'s; static digraphs only): ``edge_grad`` is the gradient at that gate instead of at 1, the
+        score, alpha and the states being those of ``rescore(gate=gate)`` (rg_digraph_layer_fwd_gated / rg_digraph_layer_bwd_gated).  A
+        gate of ones gives the ungated call's bits."""
+        return saliency(self, model, keep, mode, gate)
+
+    def integrated_gradients(self, model, steps=16, keep=None, baseline=None, target=None, rep_chunk=None, mode="test"):
+        """An attribution that adds up: integrated gradients of the score of o along the straight path of gates from ``baseline`` to
+        ``target``, an explain.Attribution.  edge_attr[e] = (target_e - baseline_e) * the mean over the path of d score / d g_e, so by
+        the fundamental theorem of calculus a row's edge_attr sum to score(target) - score(baseline); the quadrature is the midpoint
+        rule, t_k = (k + 1/2) / steps with weights 1 / steps, and ``residual`` is what it leaves.  ``baseline`` None: the identity edges
+        (relation 2 * n_rel) at 1 and every other edge at 0 - self-loops are part of the model, not facts; ``target`` None: 1
+        everywhere; both can be given as float32 [E].  ``keep`` as in ``rescore``.
+
+        The per-hop index and the source views are built once; the steps then run as REPLICAS of the hop in one launch per hop
+        (rg_digraph_layer_fwd_gated, rg_digraph_layer_bwd_gated), their rows stacked for the dense step and its autograd adjoint, in
+        groups of ``rep_chunk`` steps.  ``rep_chunk`` None: as many as keep replicas * edges at or under explain.IG_REP_EDGES = 2^20,
+        which bounds the stacked states at 2^20 rows per hop.  The sums run over k ascending, so the result does not depend on the run;
+        it depends on ``rep_chunk`` in the last bits only (the dense products see other row counts).  Static and inductive models; a
+        temporal or extrapolation digraph or model is a ValueError: the timed forms of the gated kernels are not built."""
+        return integrated_gradients(self, model, steps, keep, baseline, target, rep_chunk, mode)
 
     def fact_mask(self, facts, rows=None, inverse_offset=None):
         """bool [E]: the edges that stand for one of the facts ``facts`` int [F, 3] = (h, r, t), at any hop: an edge is marked if its
@@ -1856,9 +1883,11 @@ def extrapolation_fidelity_all(model, queries, k=4, batch_size=64, inverse_offse
     return _fidelity_summary(parts, k)
 
 
-def rescore(rd, model, keep=None, mode="test"):
+def rescore(rd, model, keep=None, mode="test", gate=None):
     """RDigraph.rescore (see there)."""
     who = "rescore"
+    if gate is not None:
+        return _gated_call(rd, model, keep, mode, gate, who, False)
     if _is_extrapolation(rd):
         return rescore_extrapolation(rd, model, keep, mode)
     if _has_times(rd):
@@ -1866,9 +1895,9 @@ def rescore(rd, model, keep=None, mode="test"):
     return _rescore_static(rd, model, keep, mode, who)
 
 
-def _rescore_static(rd, model, keep, mode, who, tape=None):
-    """RDigraph.rescore of a static r-digraph for ``who`` (rescore, saliency).  ``tape``: a list that receives, per hop walked, what the
-    hop's adjoint needs (RDigraph.saliency): the hop, its index arrays, the state and projection it read and the sums it formed."""
+def _static_setup(rd, model, keep, mode, who):
+    """The checks every walk of a static r-digraph starts with (ValueError), and what they establish: a namespace of the sizes, the
+    edge columns as int64, the kept edges and the padded widths."""
     E, B = _check_static_digraph(rd, who)
     for name in ("q_sub", "q_rel"):
         t = getattr(rd, name)
@@ -1900,12 +1929,22 @@ def _rescore_static(rd, model, keep, mode, who, tape=None):
     d, a = model.hidden_dim, model.attn_dim
     ld, ap = max(16, _pad4(d)), pad_attn(a)
     fused = model.fused_dense and engine.dense_supported(d, a)
+    kept = torch.ones(E, dtype=torch.bool, device=dev) if keep is None else keep.bool()
+    return types.SimpleNamespace(E=E, B=B, L=L, dev=dev, n_ent=n_ent, row=row, hop=hop, head=head, rel=rel, tail=tail, d=d, a=a, ld=ld,
+                                 ap=ap, fused=fused, kept=kept)
+
+
+def _rescore_static(rd, model, keep, mode, who, tape=None):
+    """RDigraph.rescore of a static r-digraph for ``who`` (rescore, saliency).  ``tape``: a list that receives, per hop walked, what the
+    hop's adjoint needs (RDigraph.saliency): the hop, its index arrays, the state and projection it read and the sums it formed."""
+    S = _static_setup(rd, model, keep, mode, who)
+    E, B, L, dev, n_ent, d, a, ld, ap, fused, kept = S.E, S.B, S.L, S.dev, S.n_ent, S.d, S.a, S.ld, S.ap, S.fused, S.kept
+    row, hop, head, rel, tail = S.row, S.hop, S.head, S.rel, S.tail
     i32 = lambda t: t.to(torch.int32).contiguous()
     live = torch.zeros(E, dtype=torch.bool, device=dev)
     alpha = torch.zeros(E, dtype=torch.float32, device=dev)
     score = torch.zeros(B, dtype=torch.float32, device=dev)
     reached = torch.zeros(B, dtype=torch.bool, device=dev)
-    kept = torch.ones(E, dtype=torch.bool, device=dev) if keep is None else keep.bool()
     with torch.no_grad():
         from .models import gru_step, tall_linear
         tables = model.inference_tables(rd.q_rel.contiguous(), ld, ap)
@@ -1964,43 +2003,19 @@ def _segment_sums(values, group, n_groups):
     return m.sum(1)
 
 
-@dataclass
-class Saliency:
-    """The gradient of an answer's score with respect to a gate on every edge of its r-digraph (RDigraph.saliency).  Tensors on the
-    digraph's device.
+class _FactSums:
+    """Per-edge values of an r-digraph summed per fact: the grouping Saliency (``edge_grad``) and Attribution (``edge_attr``) share.  A
+    subclass names its per-edge field in ``_VALUES`` and has ``digraph``, ``score`` and ``reached``."""
+    _VALUES = None
 
-    score      float32 [B]  the model's score of o on the kept digraph, exactly 0 where o is not reached     (as Rescore's)
-    reached    bool [B]     o has a length-L walk from s through kept edges
-    live       bool [E]     the edge is kept and its head is visited at hop - 1; only live edges carry messages
-    alpha      float32 [E]  the attention on the kept digraph, 0 for dead edges
-    edge_grad  float32 [E]  d score(o of the edge's row) / d g_e at g == 1, g_e multiplying the edge's message; exactly 0 for dead
-                            edges and for the rows that are not reached
-    digraph    RDigraph     the digraph the edges are those of
-    """
-    score: torch.Tensor
-    reached: torch.Tensor
-    live: torch.Tensor
-    alpha: torch.Tensor
-    edge_grad: torch.Tensor
-    digraph: RDigraph
-
-    def fact_grad(self, inverse_offset=None):
-        """(row int64 [F], fact int64 [F, 3] = (h, r, t) with r < n_rel, grad float32 [F]) ordered by (row, h, r, t): ``edge_grad``
-        summed over all copies of a base fact in its row - the edge (h, r, t) and its twin (t, r + n_rel, h), at every hop; the
-        identity relation 2 * n_rel is no fact.  RDigraph.fact_mask's grouping rule: to first order the score of the row changes by
-        -grad when the fact is deleted.  ``inverse_offset`` is fact_mask's: a static digraph knows its inverses and takes None.
-
-        On a temporal digraph (interpolation or extrapolation) fact is int64 [F, 4] = (h, r, t, time id | day), ordered by (row, h, r,
-        t, time), grouped under fact_mask's temporal rule: every copy of a quadruple in its row at every hop; the identity relation
-        n_rel is no fact, and neither is an extrapolation self-loop (data_row < 0).  With ``inverse_offset`` = m an edge with
-        m <= r < 2 m counts as (t, r - m, h, time), so that for every returned fact with r < m (every fact when m is None) grad is
-        the sum of ``edge_grad`` over fact_mask([fact], rows=[row], inverse_offset=m)."""
-        rd = self.digraph
+    def _fact_sums(self, inverse_offset=None, who="fact_grad"):
+        """(row, fact, sum) of the per-edge values under RDigraph.fact_mask's grouping rule: Saliency.fact_grad states it."""
+        rd, values = self.digraph, getattr(self, self._VALUES)
         if _has_times(rd):
-            return self._timed_fact_grad(inverse_offset)
-        E, _ = _check_static_digraph(rd, "fact_grad")
+            return self._timed_fact_sums(inverse_offset, who)
+        E, _ = _check_static_digraph(rd, who)
         if inverse_offset is not None:
-            raise ValueError("fact_grad: inverse_offset is for temporal r-digraphs; a static one knows its inverses (r + n_rel)")
+            raise ValueError("%s: inverse_offset is for temporal r-digraphs; a static one knows its inverses (r + n_rel)" % who)
         n_rel, dev = int(rd.n_rel), rd.edges.device
         e = rd.edges.long()
         e = e[e[:, 3] != 2 * n_rel]
@@ -2013,14 +2028,14 @@ class Saliency:
         key = ((e[:, 0] * n_key + h) * n_rel + r) * n_key + t
         key, order = torch.sort(key, stable=True)                         # copies of a fact in edge order: a fixed order of the sum
         keys, group = torch.unique_consecutive(key, return_inverse=True)
-        grad = _segment_sums(self.edge_grad[rd.edges[:, 3].long() != 2 * n_rel][order], group, keys.numel())
+        grad = _segment_sums(values[rd.edges[:, 3].long() != 2 * n_rel][order], group, keys.numel())
         t_, rest = keys % n_key, keys // n_key
         r_, rest = rest % n_rel, rest // n_rel
         return rest // n_key, torch.stack([rest % n_key, r_, t_], 1), grad
 
-    def _timed_fact_grad(self, inverse_offset):
-        """fact_grad of a temporal interpolation or extrapolation digraph."""
-        who, rd = "fact_grad", self.digraph
+    def _timed_fact_sums(self, inverse_offset, who):
+        """_fact_sums of a temporal interpolation or extrapolation digraph."""
+        rd, values = self.digraph, getattr(self, self._VALUES)
         xtr = _is_extrapolation(rd)
         (_check_extrapolation_digraph if xtr else _check_temporal_digraph)(rd, who)
         n_rel, dev, m = int(rd.n_rel), rd.edges.device, inverse_offset
@@ -2043,11 +2058,77 @@ class Saliency:
         key = (((e[:, 0] * n_key + h) * n_r + r) * n_key + t) * n_t + tm
         key, order = torch.sort(key, stable=True)                         # copies of a fact in edge order: a fixed order of the sum
         keys, group = torch.unique_consecutive(key, return_inverse=True)
-        grad = _segment_sums(self.edge_grad[fact][order], group, keys.numel())
+        grad = _segment_sums(values[fact][order], group, keys.numel())
         tm_, rest = keys % n_t, keys // n_t
         t_, rest = rest % n_key, rest // n_key
         r_, rest = rest % n_r, rest // n_r
         return rest // n_key, torch.stack([rest % n_key, r_, t_, tm_], 1), grad
+
+    def top(self, k):
+        """The k facts of every row with the largest |value| (fact_grad / fact_attr), largest first, ties in (h, r, t) order: (fact int64 [B, k, 3],
+        grad float32 [B, k], count int64 [B]); -1 and 0 where the row has fewer than k facts.  On a temporal digraph fact is
+        [B, k, 4] = (h, r, t, time id | day), ties in (h, r, t, time) order."""
+        _check_count(k, "top", "k")
+        k, B, dev = int(k), self.score.numel(), self.score.device
+        row, fact, grad = self._fact_sums()
+        order = torch.sort(-grad.abs(), stable=True).indices
+        order = order[torch.sort(row[order], stable=True).indices]        # by row, inside a row by |grad| descending
+        row, fact, grad = row[order], fact[order], grad[order]
+        total = torch.bincount(row, minlength=B)
+        rank = torch.arange(row.numel(), device=dev) - (torch.cumsum(total, 0) - total)[row]
+        sel = rank < k
+        out_f = torch.full((B, k, fact.shape[1]), -1, dtype=torch.int64, device=dev)
+        out_g = torch.zeros((B, k), dtype=torch.float32, device=dev)
+        out_f[row[sel], rank[sel]] = fact[sel]
+        out_g[row[sel], rank[sel]] = grad[sel]
+        return out_f, out_g, total.clamp(max=k)
+
+    def format(self, id2rel=None, k=3):
+        """One line per row: the score (``x``: o is not reached), then the row's ``k`` facts of largest |value| as (h, relation, t)
+        with their gradient (Saliency) or attribution (Attribution) - (h, relation, t, @time) on a temporal digraph; ``id2rel`` names
+        the relations."""
+        fact, grad, count = (t.cpu().tolist() for t in self.top(k))
+        sc, ok = self.score.cpu().tolist(), self.reached.cpu().tolist()
+        name = lambda r: str(id2rel[r]) if id2rel is not None else "r%d" % r
+        cell = lambda f: "(%d, %s, %d, @%d)" % (f[0], name(f[1]), f[2], f[3]) if len(f) == 4 else "(%d, %s, %d)" % (f[0], name(f[1]), f[2])
+        return ["row %d: score %s  %s" % (b, "%.4f" % sc[b] if ok[b] else "x",
+                                         "  ".join("%s %+.4f" % (cell(f), g) for f, g in zip(fact[b][:count[b]], grad[b])))
+                for b in range(len(sc))]
+
+
+@dataclass
+class Saliency(_FactSums):
+    """The gradient of an answer's score with respect to a gate on every edge of its r-digraph (RDigraph.saliency).  Tensors on the
+    digraph's device.
+
+    score      float32 [B]  the model's score of o on the kept digraph, exactly 0 where o is not reached     (as Rescore's)
+    reached    bool [B]     o has a length-L walk from s through kept edges
+    live       bool [E]     the edge is kept and its head is visited at hop - 1; only live edges carry messages
+    alpha      float32 [E]  the attention on the kept digraph, 0 for dead edges
+    edge_grad  float32 [E]  d score(o of the edge's row) / d g_e at g == 1, g_e multiplying the edge's message; exactly 0 for dead
+                            edges and for the rows that are not reached
+    digraph    RDigraph     the digraph the edges are those of
+    """
+    score: torch.Tensor
+    reached: torch.Tensor
+    live: torch.Tensor
+    alpha: torch.Tensor
+    edge_grad: torch.Tensor
+    digraph: RDigraph
+    _VALUES = "edge_grad"
+
+    def fact_grad(self, inverse_offset=None):
+        """(row int64 [F], fact int64 [F, 3] = (h, r, t) with r < n_rel, grad float32 [F]) ordered by (row, h, r, t): ``edge_grad``
+        summed over all copies of a base fact in its row - the edge (h, r, t) and its twin (t, r + n_rel, h), at every hop; the
+        identity relation 2 * n_rel is no fact.  RDigraph.fact_mask's grouping rule: to first order the score of the row changes by
+        -grad when the fact is deleted.  ``inverse_offset`` is fact_mask's: a static digraph knows its inverses and takes None.
+
+        On a temporal digraph (interpolation or extrapolation) fact is int64 [F, 4] = (h, r, t, time id | day), ordered by (row, h, r,
+        t, time), grouped under fact_mask's temporal rule: every copy of a quadruple in its row at every hop; the identity relation
+        n_rel is no fact, and neither is an extrapolation self-loop (data_row < 0).  With ``inverse_offset`` = m an edge with
+        m <= r < 2 m counts as (t, r - m, h, time), so that for every returned fact with r < m (every fact when m is None) grad is
+        the sum of ``edge_grad`` over fact_mask([fact], rows=[row], inverse_offset=m)."""
+        return self._fact_sums(inverse_offset, "fact_grad")
 
     def data_row_grad(self):
         """Extrapolation digraphs only: (row int64 [F], data_row int64 [F], grad float32 [F]) ordered by (row, data_row): ``edge_grad``
@@ -2067,25 +2148,6 @@ class Saliency:
         keys, group = torch.unique_consecutive(key, return_inverse=True)
         return keys // n_key, keys % n_key, _segment_sums(self.edge_grad[fact][order], group, keys.numel())
 
-    def top(self, k):
-        """The k facts of every row with the largest |grad| (fact_grad), largest first, ties in (h, r, t) order: (fact int64 [B, k, 3],
-        grad float32 [B, k], count int64 [B]); -1 and 0 where the row has fewer than k facts.  On a temporal digraph fact is
-        [B, k, 4] = (h, r, t, time id | day), ties in (h, r, t, time) order."""
-        _check_count(k, "top", "k")
-        k, B, dev = int(k), self.score.numel(), self.edge_grad.device
-        row, fact, grad = self.fact_grad()
-        order = torch.sort(-grad.abs(), stable=True).indices
-        order = order[torch.sort(row[order], stable=True).indices]        # by row, inside a row by |grad| descending
-        row, fact, grad = row[order], fact[order], grad[order]
-        total = torch.bincount(row, minlength=B)
-        rank = torch.arange(row.numel(), device=dev) - (torch.cumsum(total, 0) - total)[row]
-        sel = rank < k
-        out_f = torch.full((B, k, fact.shape[1]), -1, dtype=torch.int64, device=dev)
-        out_g = torch.zeros((B, k), dtype=torch.float32, device=dev)
-        out_f[row[sel], rank[sel]] = fact[sel]
-        out_g[row[sel], rank[sel]] = grad[sel]
-        return out_f, out_g, total.clamp(max=k)
-
     def deletion_estimate(self, mask):
         """float32 [B]: score - the sum of ``edge_grad`` over the live edges of ``mask`` (bool or uint8 [E]) per row, the first-order
         estimate of ``rescore(keep=~mask).score``: every gate of the mask taken from 1 to 0 along the tangent."""
@@ -2098,16 +2160,39 @@ class Saliency:
         return self.score - _segment_sums(torch.where(gone, self.edge_grad, torch.zeros_like(self.edge_grad)), rd.edges[:, 0].long(),
                                           self.score.numel())
 
-    def format(self, id2rel=None, k=3):
-        """One line per row: the score (``x``: o is not reached), then the row's ``k`` facts of largest |grad| as (h, relation, t)
-        with their gradient - (h, relation, t, @time) on a temporal digraph; ``id2rel`` names the relations."""
-        fact, grad, count = (t.cpu().tolist() for t in self.top(k))
-        sc, ok = self.score.cpu().tolist(), self.reached.cpu().tolist()
-        name = lambda r: str(id2rel[r]) if id2rel is not None else "r%d" % r
-        cell = lambda f: "(%d, %s, %d, @%d)" % (f[0], name(f[1]), f[2], f[3]) if len(f) == 4 else "(%d, %s, %d)" % (f[0], name(f[1]), f[2])
-        return ["row %d: score %s  %s" % (b, "%.4f" % sc[b] if ok[b] else "x",
-                                         "  ".join("%s %+.4f" % (cell(f), g) for f, g in zip(fact[b][:count[b]], grad[b])))
-                for b in range(len(sc))]
+
+@dataclass
+class Attribution(_FactSums):
+    """Integrated gradients of an answer's score along the straight path of gates from a baseline to a target
+    (RDigraph.integrated_gradients): per-edge attributions that add up to score - baseline_score per row, up to the quadrature error
+    ``residual``.  Tensors on the digraph's device.
+
+    score           float32 [B]  the model's score of o at the target gates, exactly 0 where o is not reached
+    baseline_score  float32 [B]  ... at the baseline gates
+    edge_attr       float32 [E]  (target - baseline) * the midpoint-rule mean of d score / d g_e along the path; exactly 0 for dead
+                                 edges, for the rows that are not reached and where target == baseline
+    residual        float32 [B]  score - baseline_score - the sum of the row's edge_attr (added in a fixed order): what ``steps``
+                                 midpoints leave of the path integral
+    reached         bool [B]     o has a length-L walk from s through kept edges: structural, whatever the gates
+    live            bool [E]     the edge is kept and its head is visited at hop - 1: structural as well, a gate of 0 disconnects nothing
+    steps           int          the quadrature steps
+    digraph         RDigraph     the digraph the edges are those of
+    """
+    score: torch.Tensor
+    baseline_score: torch.Tensor
+    edge_attr: torch.Tensor
+    residual: torch.Tensor
+    reached: torch.Tensor
+    live: torch.Tensor
+    steps: int
+    digraph: RDigraph
+    _VALUES = "edge_attr"
+
+    def fact_attr(self, inverse_offset=None):
+        """(row int64 [F], fact int64 [F, 3] = (h, r, t) with r < n_rel, attr float32 [F]) ordered by (row, h, r, t): ``edge_attr``
+        summed over all copies of a base fact in its row, Saliency.fact_grad's grouping (the identity relation is no fact, so with the
+        default baseline a row's fact_attr add up to the row's edge_attr).  ``top(k)`` and ``format(id2rel)`` rank by it."""
+        return self._fact_sums(inverse_offset, "fact_attr")
 
 
 def _digraph_family(rd):
@@ -2150,11 +2235,13 @@ def _saliency_timed(rd, model, keep, mode, n_dir):
     return out()
 
 
-def saliency(rd, model, keep=None, mode="test"):
+def saliency(rd, model, keep=None, mode="test", gate=None):
     """RDigraph.saliency (see there).  The driver is chosen by the model's class: a temporal.T_RED_GNN walks a temporal interpolation
     digraph, an extrapolation.T_RED_GNN an extrapolation one (_saliency_timed); every other model takes the static path -
-    _rescore_static with a tape, then the hops backwards."""
+    _rescore_static with a tape, then the hops backwards.  With ``gate`` the gated walk (_gated_call) takes over."""
     from .models import gru_step, tall_linear
+    if gate is not None:
+        return _gated_call(rd, model, keep, mode, gate, "saliency", True)
     from .extrapolation import T_RED_GNN as XModel
     from .temporal import T_RED_GNN as TModel
     if isinstance(model, XModel):
@@ -2205,6 +2292,200 @@ def saliency(rd, model, keep=None, mode="test"):
         if not first:
             g_hidden = g_hidden + grads[1]                                # the carry: the state also enters the next GRU step as h0
     return Saliency(score=rs.score, reached=rs.reached, live=rs.live, alpha=rs.alpha, edge_grad=edge_grad, digraph=rd)
+
+
+# ---- gated walks of a static r-digraph: rescore / saliency at any gate, and integrated gradients ------------------------------------
+IG_REP_EDGES = 1 << 20               # default rep_chunk: as many replicas as keep replicas * edges at or under this
+
+
+def _refuse_timed(rd, model, who):
+    """The gated edge-list kernels are static: a temporal or extrapolation digraph or model is a ValueError, before any HIP call."""
+    from .extrapolation import T_RED_GNN as XModel
+    from .temporal import T_RED_GNN as TModel
+    if _has_times(rd) or isinstance(model, (XModel, TModel)):
+        raise ValueError("%s: gates need the gated edge-list kernels, and their timed forms are not built; static and inductive models "
+                         "and their r-digraphs only (this is %s r-digraph and a %s)" % (who, _digraph_family(rd), type(model).__name__))
+
+
+def _check_gate(who, name, g, E, device):
+    """``g`` as a float32 [E] tensor on ``device``: a tensor or a numpy array of that shape and dtype, every entry finite (ValueError)."""
+    if not torch.is_tensor(g):
+        g = np.asarray(g)
+        if g.dtype != np.float32:
+            raise ValueError("%s: %s must be float32 [%d], one per edge (got %s)" % (who, name, E, g.dtype))
+        g = torch.as_tensor(g)
+    if g.dtype != torch.float32 or tuple(g.shape) != (E,):
+        raise ValueError("%s: %s must be float32 [%d], one per edge (got %s %s)" % (who, name, E, g.dtype, tuple(g.shape)))
+    if not bool(torch.isfinite(g).all()):
+        raise ValueError("%s: %s holds a value that is not finite" % (who, name))
+    return g.to(device).contiguous()
+
+
+def _static_hops(S, who):
+    """The index of every hop of a static walk, which depends on the kept edges alone - not on the states, the gates or the replicas:
+    ([per hop a dict of _hop_index's arrays as the kernels take them], live bool [E], reached bool [B]).  The list ends where no edge
+    is live; the source view of a hop (``view``) is added by the first adjoint that needs it."""
+    i32 = lambda t: t.to(torch.int32).contiguous()
+    live = torch.zeros(S.E, dtype=torch.bool, device=S.dev)
+    reached = torch.zeros(S.B, dtype=torch.bool, device=S.dev)
+    keys_prev = torch.arange(S.B, device=S.dev) * S.n_ent + S.q_sub           # hop 0: the node (row, s) of every row, sorted
+    hops = []
+    for l in range(1, S.L + 1):
+        at = torch.nonzero((S.hop == l) & S.kept).reshape(-1)
+        index = _hop_index(who, l, S.L, at, S.row, S.head, S.tail, keys_prev, S.n_ent, live)
+        if index is None:
+            break
+        at, src, keys, dst_ptr, row_of, prev_idx, had = index
+        hops.append(dict(l=l, at=at, src=i32(src), rel=i32(S.rel[at]), dst_ptr=dst_ptr, dst_ptr_host=dst_ptr.cpu().numpy(), row_of=row_of,
+                         prev_idx=prev_idx, had=had, n_prev=keys_prev.numel(), n_dst=keys.numel(), view=None))
+        if l == S.L:
+            reached[row_of] = True
+        keys_prev = keys
+    return hops, live, reached
+
+
+def _gated_group(S, rd, model, hops, t, lo, hi, want_grad, check_index=True):
+    """One group of n = t.numel() replicas of the static walk, replica k at the gates fmaf(t[k], hi - lo, lo) (``lo`` / ``hi`` float32
+    [E] or None for 0 / 1): _rescore_static's hop loop with the replicas' rows stacked, replica k's node j of a hop at row
+    k * n_nodes + j - one rg_digraph_layer_fwd_gated launch and one dense step per hop for all of them - and, with ``want_grad``,
+    saliency's backward loop on the same stacked rows (rg_digraph_layer_bwd_gated).  Returns (score [n, B], alpha [n, E], grad [n, E]
+    or None): the gradient of replica k's scores with respect to its gates.  With n == 1 and gates of 1 every tensor has the bits of
+    the ungated walk."""
+    from .models import gru_step, tall_linear
+    n, dev, B, E, L, d, a, ld, ap = t.numel(), S.dev, S.B, S.E, S.L, S.d, S.a, S.ld, S.ap
+    score = torch.zeros(n * B, dtype=torch.float32, device=dev)
+    alpha = torch.zeros((n, E), dtype=torch.float32, device=dev)
+    grad = torch.zeros((n, E), dtype=torch.float32, device=dev) if want_grad else None
+    rep = torch.arange(n, device=dev)[:, None]
+    w_b = lambda layer: (layer.w_alpha.weight.detach().reshape(-1).contiguous(), layer.w_alpha.bias.detach().contiguous())
+    tape = []
+    with torch.no_grad():
+        tables = model.inference_tables(rd.q_rel.contiguous(), ld, ap)
+        hidden = torch.zeros((n * B, ld), device=dev)
+        a_s = torch.zeros((n * B, ap), device=dev)                            # hidden == 0 at layer 0
+        for h in hops:
+            l, at = h["l"], h["at"]
+            layer, last = model.gnn_layers[l - 1], l == L
+            a_r, a_q, rela_p = (x.contiguous() for x in tables[l - 1])
+            g_lo, g_hi = (None if g is None else g[at].contiguous() for g in (lo, hi))
+            agg, al = engine.digraph_layer_fwd_gated(h["dst_ptr"], h["src"], h["rel"], h["row_of"].to(torch.int32).contiguous(), hidden,
+                                                     rela_p, d, a_s, a_r, a_q, *w_b(layer), a, t, g_lo, g_hi,
+                                                     dst_ptr_host=h["dst_ptr_host"], check_index=check_index)
+            alpha[:, at] = al.view(n, -1)
+            # the replicas' rows of the dense step: node j of replica k is row k * n_dst + j, its old state row k * n_prev + prev_idx[j]
+            had = h["had"].repeat(n)
+            prev_idx = torch.where(h["had"][None, :], h["prev_idx"][None, :] + (rep * h["n_prev"]).to(torch.int32),
+                                   h["prev_idx"][None, :]).reshape(-1).contiguous()
+            row_of = (h["row_of"][None, :] + rep * B).reshape(-1)
+            if want_grad:
+                tape.append(dict(h=h, hidden=hidden, a_s=a_s, agg=agg, prev_idx=prev_idx, had=had, a_r=a_r, a_q=a_q, rela=rela_p,
+                                 g_lo=g_lo, g_hi=g_hi))
+            if S.fused:                                                       # the dense step of _forward_inference
+                node_rows = torch.stack([row_of, torch.zeros_like(row_of)], 1).to(torch.int32).contiguous()
+                hidden, a_s = engine.dense_fwd(agg, hidden, prev_idx, d, layer.W_h.weight, model.act_name, model.gate,
+                                               Ws_next=None if last else model.gnn_layers[l].Ws_attn.weight, attn_dim=a, ap=ap,
+                                               W_final=model.W_final.weight if last else None, nodes=node_rows, n_ent=1,
+                                               scores_all=score, precision=model.dense_precision, want_hidden=not last)
+            else:                                                             # ... and of _run's ``kept`` branch
+                x = layer.act(tall_linear(agg[:, :d], layer.W_h.weight))
+                h0 = torch.zeros((agg.shape[0], d), device=dev)
+                h0[had] = hidden[:, :d][prev_idx[had].long()]
+                hid = gru_step(x, h0, model.gate)
+                if last:
+                    score[row_of] = tall_linear(hid, model.W_final.weight).squeeze(-1)
+                else:
+                    w_s = model.gnn_layers[l].Ws_attn.weight
+                    a_s = tall_linear(hid, F.pad(w_s, (0, 0, 0, ap - a)) if ap != a else w_s).contiguous()
+                    hidden = (F.pad(hid, (0, ld - d)) if ld != d else hid).contiguous()
+    score = score.view(n, B)
+    if not want_grad or len(hops) < L:                                        # no row reaches its answer: nothing depends on any edge
+        return score, alpha, grad
+    gate = types.SimpleNamespace(**{name: getattr(model.gate, name).detach()
+                                    for name in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")})
+    g_hidden = g_a_s = None                                                   # d (sum of the scores) / d (the hop's new state, its projection)
+    for tp in reversed(tape):
+        h = tp["h"]
+        l = h["l"]
+        layer, last, first = model.gnn_layers[l - 1], l == L, l == 1
+        # ---- the dense step's adjoint: saliency's, on the stacked rows
+        with torch.enable_grad():
+            agg = tp["agg"].detach().requires_grad_(True)
+            prev = tp["hidden"].detach().requires_grad_(not first)            # hop 1 reads the constant 0
+            x = layer.act(tall_linear(agg[:, :d], layer.W_h.weight.detach()))
+            h0 = torch.zeros((agg.shape[0], d), device=dev)
+            h0[tp["had"]] = prev[:, :d][tp["prev_idx"][tp["had"]].long()]
+            hid = gru_step(x, h0, gate)
+            if last:
+                outs, seeds = [tall_linear(hid, model.W_final.weight.detach()).squeeze(-1)], [torch.ones(agg.shape[0], device=dev)]
+            else:
+                w_s = model.gnn_layers[l].Ws_attn.weight.detach()
+                outs = [F.pad(hid, (0, ld - d)) if ld != d else hid, tall_linear(hid, F.pad(w_s, (0, 0, 0, ap - a)) if ap != a else w_s)]
+                seeds = [g_hidden, g_a_s]
+            grads = torch.autograd.grad(outs, [agg] if first else [agg, prev], seeds)
+        # ---- the edge-list layer's, in HIP, on the hop's source view (built once per hop, whatever the gates and the replicas)
+        if h["view"] is None:
+            h["view"] = engine.digraph_source_view(h["dst_ptr"], h["src"], h["n_prev"])
+        gate_grad, g_hidden, g_a_s = engine.digraph_layer_bwd_gated(
+            h["dst_ptr"], h["src"], h["rel"], h["row_of"].to(torch.int32).contiguous(), tp["hidden"], tp["rela"], d, tp["a_s"], tp["a_r"],
+            tp["a_q"], *w_b(layer), a, grads[0].contiguous(), t, tp["g_lo"], tp["g_hi"], want_state=not first, view=h["view"],
+            check_index=check_index)
+        grad[:, h["at"]] = gate_grad.view(n, -1)
+        if not first:
+            g_hidden = g_hidden + grads[1]                                    # the carry: the state also enters the next GRU step as h0
+    return score, alpha, grad
+
+
+def _gated_setup(rd, model, keep, mode, who, gates):
+    """The refusals and checks of a gated call, in the order that lets a host without a device reach them: the family, the digraph's
+    tensors, then ``gates`` - {name: float32 [E] or None} - and only then _static_setup, which needs the device.  Returns (S, gates on
+    the device)."""
+    _refuse_timed(rd, model, who)
+    E, _ = _check_static_digraph(rd, who)
+    gates = {name: None if g is None else _check_gate(who, name, g, E, rd.edges.device) for name, g in gates.items()}
+    S = _static_setup(rd, model, keep, mode, who)
+    S.q_sub = rd.q_sub
+    return S, gates
+
+
+def _gated_call(rd, model, keep, mode, gate, who, want_grad):
+    """RDigraph.rescore / saliency with ``gate``: one replica at lo == hi == gate, so the kernels' gate is that value exactly."""
+    S, g = _gated_setup(rd, model, keep, mode, who, dict(gate=gate))
+    hops, live, reached = _static_hops(S, who)
+    t = torch.ones(1, dtype=torch.float32, device=S.dev)
+    score, alpha, grad = _gated_group(S, rd, model, hops, t, g["gate"], g["gate"], want_grad)
+    if not want_grad:
+        return Rescore(score=score[0], reached=reached, live=live, alpha=alpha[0])
+    return Saliency(score=score[0], reached=reached, live=live, alpha=alpha[0], edge_grad=grad[0], digraph=rd)
+
+
+def integrated_gradients(rd, model, steps=16, keep=None, baseline=None, target=None, rep_chunk=None, mode="test"):
+    """RDigraph.integrated_gradients (see there)."""
+    who = "integrated_gradients"
+    _refuse_timed(rd, model, who)
+    _check_count(steps, who, "steps")
+    if rep_chunk is not None:
+        _check_count(rep_chunk, who, "rep_chunk")
+    S, g = _gated_setup(rd, model, keep, mode, who, dict(baseline=baseline, target=target))
+    steps, E, B, dev = int(steps), S.E, S.B, S.dev
+    lo = (S.rel == 2 * int(rd.n_rel)).to(torch.float32) if g["baseline"] is None else g["baseline"]     # self-loops are not facts
+    hi = torch.ones(E, dtype=torch.float32, device=dev) if g["target"] is None else g["target"]
+    hops, live, reached = _static_hops(S, who)                                # the index: once, whatever the gates
+    ends = torch.tensor([0.0, 1.0], dtype=torch.float32, device=dev)          # the two ends of the path in one call, no adjoint
+    score, _, _ = _gated_group(S, rd, model, hops, ends, lo, hi, False)
+    diff = hi - lo
+    weight = diff * (1.0 / steps)
+    edge_attr = torch.zeros(E, dtype=torch.float32, device=dev)
+    n_group = max(1, min(steps, IG_REP_EDGES // max(E, 1))) if rep_chunk is None else int(rep_chunk)
+    for k0 in range(0, steps, n_group):
+        k = torch.arange(k0, min(k0 + n_group, steps), dtype=torch.float64, device=dev)
+        t = ((k + 0.5) / steps).to(torch.float32)                             # the midpoint rule
+        _, _, grad = _gated_group(S, rd, model, hops, t, lo, hi, True, check_index=False)
+        for j in range(t.numel()):                                            # k ascending: a fixed order of the sum
+            edge_attr += weight * grad[j]
+    edge_attr = torch.where(diff != 0, edge_attr, torch.zeros_like(edge_attr))
+    residual = score[1] - score[0] - _segment_sums(edge_attr, S.row, B)
+    return Attribution(score=score[1], baseline_score=score[0], edge_attr=edge_attr, residual=residual, reached=reached, live=live,
+                       steps=steps, digraph=rd)
 
 
 def _fidelity_of(rd, model, k, loops, mode, inverse_offset=None):

@@ -581,6 +581,15 @@ class RED_GNN_trans(nn.Module):
         answer, as explain.  Eval semantics; the parameters get no gradient.  (Kept below _run: tests cite that function's lines.)"""
         return self.explain(subs, rels, objs, mode=mode).saliency(self, mode=mode)
 
+    def integrated_gradients(self, subs, rels, objs=None, steps=16, mode="test"):
+        """An attribution of the score of o to the facts of its r-digraph that adds up: ``explain`` followed by
+        RDigraph.integrated_gradients - the gate gradients at ``steps`` midpoints between the digraph with only its self-loops and
+        the full digraph, run as replicas of each hop in one HIP launch (rg_digraph_layer_fwd_gated / rg_digraph_layer_bwd_gated).
+        Returns an explain.Attribution (device tensors): ``edge_attr`` per edge of ``.digraph``, ``fact_attr()`` / ``top(k)`` per fact,
+        ``residual`` what the quadrature leaves of score - baseline_score.  ``objs=None``: each row's own top answer, as explain.
+        Eval semantics; the parameters get no gradient."""
+        return self.explain(subs, rels, objs, mode=mode).integrated_gradients(self, steps=steps, mode=mode)
+
     def _forward_graphed(self, graph, q_sub, q_rel, n, device):
         """Replay (or, on the third call with the same graph and batch size, capture) the forward as a HIP graph.
         Returns None when this call should run eagerly: the first two calls of a shape (the eager run also provides the
@@ -691,6 +700,9 @@ class RED_GNN_induc(RED_GNN_trans):
 
     def saliency(self, subs, rels, objs=None, mode="transductive"):
         return super().saliency(subs, rels, objs=objs, mode=mode)
+
+    def integrated_gradients(self, subs, rels, objs=None, steps=16, mode="transductive"):
+        return super().integrated_gradients(subs, rels, objs=objs, steps=steps, mode=mode)
 
     def rule_quality(self, table, mode="transductive", sources=None, scratch_bytes=engine.RULE_SCRATCH_BYTES):
         return super().rule_quality(table, mode=mode, sources=sources, scratch_bytes=scratch_bytes)
