@@ -581,6 +581,51 @@ int rg_digraph_layer_bwd_gated(int32_t n_rep, const float* t, const float* gate_
                                int32_t attn_dim, const float* grad_agg, float* grad_gate, float* grad_hidden, float* grad_a_s,
                                void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- ... and both with a gate per (replica, edge) instead of the path lo .. hi (learned edge masks, explain.RDigraph.learn_mask):
+ * gate float [n_rep * n_edges] (device), replica k's gate of the edge at list position e being gate[k * n_edges + e], taken as it is.
+ * Every other argument is the one of the same name of rg_digraph_layer_fwd_gated / rg_digraph_layer_bwd_gated and everything those two
+ * state holds: replica k reads hidden and a_s rows k * n_src + s, the outputs are stacked per replica, the gate does not enter
+ * alpha_e, c = g * alpha_e is rounded once, the split rule and the argument checks are the same.  They are the GATED instantiations
+ * with a replica stride on the gate pointer, so replica k's outputs (agg_out, alpha_out; grad_gate, grad_hidden, grad_a_s) have the
+ * bits of an n_rep = 1 call of the _gated entry point with gate_lo == gate_hi == gate + k * n_edges and t = 1, whatever else the call
+ * carries.  scratch: rg_digraph_layer_fwd_gated_scratch_bytes / rg_digraph_layer_bwd_gated_scratch_bytes serve these calls too.  Errors
+ * as the _gated calls', with a NULL gate in the place of a NULL t. */
+int rg_digraph_layer_fwd_gates(int32_t n_rep, const float* gate, int32_t n_dst, int64_t n_edges, const int32_t* dst_ptr,
+                               const int32_t* dst_ptr_host, const int32_t* src_idx, const int32_t* rel, const int32_t* row_of_dst,
+                               int32_t n_src, int32_t n_rela_rows, int32_t batch, const float* hidden, const float* rela, int32_t d,
+                               int32_t ld, const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha,
+                               const float* b_alpha, int32_t attn_dim, float* agg_out, float* alpha_out, void* scratch,
+                               size_t scratch_bytes, void* stream);
+int rg_digraph_layer_bwd_gates(int32_t n_rep, const float* gate, int32_t n_src, int32_t n_dst, int64_t n_edges, const int32_t* src_ptr,
+                               const int32_t* src_ptr_host, const int32_t* edge_of, const int32_t* dst_of_edge, const int32_t* rel,
+                               const int32_t* row_of_dst, int32_t n_rela_rows, int32_t batch, const float* hidden, const float* rela,
+                               int32_t d, int32_t ld, const float* a_s, const float* a_r, const float* a_q, int32_t ap,
+                               const float* w_alpha, const float* b_alpha, int32_t attn_dim, const float* grad_agg, float* grad_gate,
+                               float* grad_hidden, float* grad_a_s, void* scratch, size_t scratch_bytes, void* stream);
+
+/* ---- one step of learning an edge mask (csrc/mask_step.hip; explain.RDigraph.learn_mask): the objective's chain rule, the
+ * regularisers, Adam and the new gate for n_rep replicas of a digraph's n_edges edges, all arrays on the device.  The edges are
+ * ordered by row, offsets int64 [batch + 1] the digraph's own (clamped into 0 .. n_edges); free_edge uint8 [n_edges] marks the edges
+ * that are learned.  Per replica k and row b: score float [n_rep * batch] the current score, target / inv_scale / inv_n float [batch]
+ * (inv_n = 1 / the row's free edges, or 0), lambda_size / lambda_ent float [n_rep], grad float [n_rep * n_edges] = d score / d gate.
+ *   L[k, b] = ((score - target) inv_scale)^2 + lambda_size[k] inv_n[b] sum_e g_e + lambda_ent[k] sum_e H(g_e),  g = 1 / (1 + expf(-theta))
+ * For every free edge e of row b, t = step >= 1:
+ *   dL/dg = 2 (score[k, b] - target[b]) inv_scale[b]^2 grad[k, e] + lambda_size[k] inv_n[b] - lambda_ent[k] theta       (dH/dg = -theta)
+ *   gt = dL/dg g (1 - g);   m' = beta1 m + (1 - beta1) gt;   v' = beta2 v + (1 - beta2) gt^2
+ *   theta' = theta - lr (m' / (1 - beta1^t)) / (sqrtf(v' / (1 - beta2^t)) + eps);   gate_out[k, e] = 1 / (1 + expf(-theta'))
+ * theta, m, v float [n_rep * n_edges] are updated in place, gate_out float [n_rep * n_edges] is written; an edge that is not free
+ * keeps all four, bit for bit.  size_out float [n_rep * batch] = the sum of gate_out over the row's free edges, count_out int32
+ * [n_rep * batch] = how many of them are > 0.5.  No float atomics: a row is cut into chunks of RG_MASK_CHUNK edges counted from its
+ * own first edge, a chunk is summed in a fixed order and the chunks are added in chunk order, so every output has the same bits on
+ * every run and replica k's are those of an n_rep = 1 call on its slices.  No scratch.  Errors, all before anything is enqueued:
+ * n_rep < 1, step < 1, a negative size, beta1 or beta2 outside [0, 1), a NULL array, n_rep * n_edges or n_rep * batch beyond int32.
+ * n_edges == 0 or batch == 0 succeeds and launches nothing. */
+#define RG_MASK_CHUNK 512
+int rg_mask_step(int32_t n_rep, int32_t batch, int64_t n_edges, const int64_t* offsets, const uint8_t* free_edge, const float* score,
+                 const float* target, const float* inv_scale, const float* inv_n, const float* lambda_size, const float* lambda_ent,
+                 const float* grad, float lr, float beta1, float beta2, float eps, int32_t step, float* theta, float* m, float* v,
+                 float* gate_out, float* size_out, int32_t* count_out, void* stream);
+
 /* ---- the per-hop index of an edited r-digraph: the arrays rg_digraph_(t)layer_fwd takes, built from the digraph's own edge list
  * under a keep mask (csrc/digraph_index.hip; explain.RDigraph.rescore of an extrapolation digraph).  edges int32 [n_edges, 5] =
  * (row, hop, head, rel, tail) ordered by (row, hop, tail) and offsets int64 [batch + 1] (start at 0, never decrease, end at n_edges:

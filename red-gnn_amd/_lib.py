@@ -30,6 +30,7 @@ SYMBOLS = [
     "rg_digraph_layer_bwd_scratch_bytes", "rg_digraph_layer_bwd", "rg_digraph_tlayer_bwd",
     "rg_digraph_layer_fwd_gated_scratch_bytes", "rg_digraph_layer_fwd_gated",
     "rg_digraph_layer_bwd_gated_scratch_bytes", "rg_digraph_layer_bwd_gated",
+    "rg_digraph_layer_fwd_gates", "rg_digraph_layer_bwd_gates", "rg_mask_step",
     "rg_digraph_hop_ranges", "rg_digraph_hop_index_scratch_bytes", "rg_digraph_hop_index",
     "rg_rule_ground_scratch_bytes", "rg_rule_ground",
     "rg_rule_apply_scratch_bytes", "rg_rule_apply",
@@ -169,7 +170,12 @@ def lib():
     L.rg_digraph_layer_bwd_gated_scratch_bytes.argtypes = [vp, i32, i32, i32, i32]
     L.rg_digraph_layer_bwd_gated_scratch_bytes.restype = sz
     L.rg_digraph_layer_bwd_gated.argtypes = [i32, vp, vp, vp] + L.rg_digraph_layer_bwd.argtypes
-    L.rg_digraph_hop_ranges.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp, vp, C.POINTER(i32), vp]
+    # a gate per (replica, edge): (n_rep, gate) in front of the ungated arguments; the _gated scratch functions serve them
+    L.rg_digraph_layer_fwd_gates.argtypes = [i32, vp] + L.rg_digraph_layer_fwd.argtypes
+    L.rg_digraph_layer_bwd_gates.argtypes = [i32, vp] + L.rg_digraph_layer_bwd.argtypes
+    f32 = C.c_float
+    L.rg_mask_step.argtypes = [i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, f32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.rg_digraph_hop_ranges.argtypes =[vp, vp, i64, i32, i32, vp, vp, vp, vp, C.POINTER(i32), vp]
     L.rg_digraph_hop_index_scratch_bytes.argtypes = [i64]
     L.rg_digraph_hop_index_scratch_bytes.restype = sz
     L.rg_digraph_hop_index.argtypes = [vp, vp, vp, i64, i32, i32, i32, vp, vp, i64, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp,

@@ -50,6 +50,8 @@
 //       grad_a_s[s]     += g * (g_alpha * alpha_e * (1 - alpha_e)) * w * 1[pre > 0]
 // so that g == 1 leaves the ungated kernel's bits.  An item is a (replica, source or chunk) pair, item k * n_items + i: a group works
 // exactly as it does in an n_rep = 1 call.  The combine launch has a grid row per replica.
+//
+// A gate per (replica, edge) (rg_digraph_layer_bwd_gates): the replica stride on the gate pointers that digraph_fwd.hip describes.
 #include <algorithm>
 #include <type_traits>
 #include <vector>
@@ -100,9 +102,11 @@ struct DbTimedArgs : DbArgs {
 // what the gated form (rg_digraph_layer_bwd_gated) reads on top
 struct DbGatedArgs : DbArgs {
   int n_rep, n_chunks;         // replicas; chunks of ONE replica (replica k's partial rows start at k * n_chunks)
-  const float* t;              // [n_rep]
+  const float* t;              // [n_rep], or nullptr: 1 (the per-replica form)
   const float* gate_lo;        // [E] by position in the destination-ordered list, or nullptr: 0
   const float* gate_hi;        // [E], or nullptr: 1
+  int gate_rep;                // replica k's gates start k * gate_rep floats further on (n_rep * E fits int32): 0, the shared pair, or
+                               // E with gate_lo == gate_hi (rg_digraph_layer_bwd_gates)
 };
 
 template <bool TIMED, bool GATED>
@@ -158,8 +162,10 @@ __global__ __launch_bounds__(DB_BLOCK) void digraph_bwd_kernel(DbArgsOf<TIMED, G
     srow += (int64_t)rep * A.n_src;
     grad_agg += (int64_t)rep * A.n_dst * A.ld4;
     grad_gate += (int64_t)rep * A.E;
-    t_rep = A.t[rep];
+    if (A.t) t_rep = A.t[rep];
   }
+  int gate_at = 0;                                       // GATED: where the replica's gates start (n_rep * E fits int32)
+  if constexpr (GATED) gate_at = rep * A.gate_rep;
   const float4 hv = A.hidden[srow * A.ld4 + lane_c];
   const float4* as_p;
   if constexpr (TIMED) as_p = A.a_s + (int64_t)(s / A.n_dir) * AP4;      // the attention reads the un-directed source
@@ -193,7 +199,7 @@ __global__ __launch_bounds__(DB_BLOCK) void digraph_bwd_kernel(DbArgsOf<TIMED, G
       }
       alpha = rg::attn_alpha(z);
       if constexpr (GATED) {
-        const float lo = A.gate_lo ? A.gate_lo[e] : 0.f, hi = A.gate_hi ? A.gate_hi[e] : 1.f;
+        const float lo = A.gate_lo ? A.gate_lo[gate_at + e] : 0.f, hi = A.gate_hi ? A.gate_hi[gate_at + e] : 1.f;
         gate = fmaf(t_rep, hi - lo, lo);
         coef = gate * alpha;
       }
@@ -339,12 +345,14 @@ struct TimeIn {
   int32_t n_time, n_dir;
 };
 
-// the gate arguments of rg_digraph_layer_bwd_gated; nullptr: the ungated entry points
+// the gate arguments of rg_digraph_layer_bwd_gated / _gates; nullptr: the ungated entry points.  per_rep (rg_digraph_layer_bwd_gates):
+// gate_lo == gate_hi is the [n_rep, E] array and t is not read, as in digraph_fwd.hip
 struct GateIn {
   int32_t n_rep;
   const float* t;
   const float* gate_lo;
   const float* gate_hi;
+  bool per_rep;
 };
 
 size_t scratch_need(int64_t n_hubs, int64_t n_chunks, int32_t ld, int32_t ap, int64_t n_rep) {
@@ -377,7 +385,8 @@ int run(const char* who, const TimeIn* T, const GateIn* Q, int32_t n_src, int32_
     RG_CHECK(n_rep * std::max(n_src, n_dst) < ((int64_t)1 << 31) && n_rep * n_edges < ((int64_t)1 << 31),
              "%s: n_rep=%lld times n_src=%d, n_dst=%d or n_edges=%lld overflows int32", who, (long long)n_rep, n_src, n_dst,
              (long long)n_edges);
-    RG_CHECK(Q->t, "%s: NULL argument (t)", who);
+    if (Q->per_rep) RG_CHECK(Q->gate_lo, "%s: NULL argument (gate)", who);
+    else RG_CHECK(Q->t, "%s: NULL argument (t)", who);
     RG_CHECK(n_rep <= 65535, "%s: n_rep=%lld (at most 65535: the combine launch has a grid row per replica)", who, (long long)n_rep);
   }
   RG_CHECK((grad_hidden == nullptr) == (grad_a_s == nullptr), "%s: grad_hidden and grad_a_s come together or not at all", who);
@@ -445,6 +454,7 @@ int run(const char* who, const TimeIn* T, const GateIn* Q, int32_t n_src, int32_
         DbGatedArgs GA;
         static_cast<DbArgs&>(GA) = A;
         GA.n_rep = (int)n_rep; GA.n_chunks = (int)n_chunks; GA.t = Q->t; GA.gate_lo = Q->gate_lo; GA.gate_hi = Q->gate_hi;
+        GA.gate_rep = Q->per_rep ? (int)n_edges : 0;
         return launch<decltype(g)::value, decltype(a4)::value, false, true>(GA, s);
       }
       return launch<decltype(g)::value, decltype(a4)::value, false>(A, s);
@@ -491,8 +501,21 @@ extern "C" int rg_digraph_layer_bwd_gated(int32_t n_rep, const float* t, const f
                                           const float* a_s, const float* a_r, const float* a_q, int32_t ap, const float* w_alpha,
                                           const float* b_alpha, int32_t attn_dim, const float* grad_agg, float* grad_gate,
                                           float* grad_hidden, float* grad_a_s, void* scratch, size_t scratch_bytes, void* stream) {
-  const rgdb::GateIn Q{n_rep, t, gate_lo, gate_hi};
+  const rgdb::GateIn Q{n_rep, t, gate_lo, gate_hi, false};
   return rgdb::run("rg_digraph_layer_bwd_gated", nullptr, &Q, n_src, n_dst, n_edges, src_ptr, src_ptr_host, edge_of, dst_of_edge, rel,
+                   row_of_dst, n_rela_rows, batch, hidden, rela, d, ld, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim, grad_agg, grad_gate,
+                   grad_hidden, grad_a_s, scratch, scratch_bytes, stream);
+}
+
+extern "C" int rg_digraph_layer_bwd_gates(int32_t n_rep, const float* gate, int32_t n_src, int32_t n_dst, int64_t n_edges,
+                                          const int32_t* src_ptr, const int32_t* src_ptr_host, const int32_t* edge_of,
+                                          const int32_t* dst_of_edge, const int32_t* rel, const int32_t* row_of_dst, int32_t n_rela_rows,
+                                          int32_t batch, const float* hidden, const float* rela, int32_t d, int32_t ld, const float* a_s,
+                                          const float* a_r, const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha,
+                                          int32_t attn_dim, const float* grad_agg, float* grad_gate, float* grad_hidden, float* grad_a_s,
+                                          void* scratch, size_t scratch_bytes, void* stream) {
+  const rgdb::GateIn Q{n_rep, nullptr, gate, gate, true};
+  return rgdb::run("rg_digraph_layer_bwd_gates", nullptr, &Q, n_src, n_dst, n_edges, src_ptr, src_ptr_host, edge_of, dst_of_edge, rel,
                    row_of_dst, n_rela_rows, batch, hidden, rela, d, ld, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim, grad_agg, grad_gate,
                    grad_hidden, grad_a_s, scratch, scratch_bytes, stream);
 }

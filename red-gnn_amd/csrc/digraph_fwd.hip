@@ -35,6 +35,10 @@
 // The gate does not enter alpha_e.  Mapping: an item is a (replica, destination or chunk) pair, item k * n_items + i, so a group works
 // exactly as it does in an n_rep = 1 call and a replica's bits do not depend on the others; the group exchanges c where the ungated
 // kernel exchanges alpha.  The combine launch has a grid row per replica.
+//
+// A gate per (replica, edge) (rg_digraph_layer_fwd_gates; learned edge masks): the same instantiation with a replica stride on the
+// gate pointers, gate_lo == gate_hi == gate + k * E and t read as 1, so that g = fmaf(1, 0, gate[k * E + e]) is that value and replica
+// k has the bits of a one-replica gated call at lo == hi == gate[k].
 #include <algorithm>
 #include <type_traits>
 #include <vector>
@@ -80,9 +84,11 @@ struct DgTimedArgs : DgArgs {
 // what the gated form (rg_digraph_layer_fwd_gated) reads on top
 struct DgGatedArgs : DgArgs {
   int n_rep, n_chunks;         // replicas; chunks of ONE replica (replica k's partial rows start at k * n_chunks)
-  const float* t;              // [n_rep]
+  const float* t;              // [n_rep], or nullptr: 1 (the per-replica form)
   const float* gate_lo;        // [E] or nullptr: 0
   const float* gate_hi;        // [E] or nullptr: 1
+  int gate_rep;                // replica k's gates start k * gate_rep floats further on (n_rep * E fits int32): 0, the shared pair, or
+                               // E with gate_lo == gate_hi (rg_digraph_layer_fwd_gates)
 };
 
 template <bool TIMED, bool GATED>
@@ -139,8 +145,10 @@ __global__ __launch_bounds__(DG_BLOCK) void digraph_fwd_kernel(DgArgsOf<TIMED, G
     hidden_p += (int64_t)rep * A.n_src * A.ld4;
     as_tab += (int64_t)rep * A.n_src * AP4;
     if (alpha_out) alpha_out += (int64_t)rep * A.E;
-    t_rep = A.t[rep];
+    if (A.t) t_rep = A.t[rep];
   }
+  int gate_at = 0;                                       // GATED: where the replica's gates start (n_rep * E fits int32)
+  if constexpr (GATED) gate_at = rep * A.gate_rep;
 
   float4 acc = rg::f4zero();
   for (int c0 = beg; __any(c0 < end); c0 += G) {
@@ -159,7 +167,7 @@ __global__ __launch_bounds__(DG_BLOCK) void digraph_fwd_kernel(DgArgsOf<TIMED, G
       alpha = rg::attn_alpha(z);
       if (alpha_out) alpha_out[c] = alpha;
       if constexpr (GATED) {                             // from here on alpha is the message's coefficient c = g * alpha_e
-        const float lo = A.gate_lo ? A.gate_lo[c] : 0.f, hi = A.gate_hi ? A.gate_hi[c] : 1.f;
+        const float lo = A.gate_lo ? A.gate_lo[gate_at + c] : 0.f, hi = A.gate_hi ? A.gate_hi[gate_at + c] : 1.f;
         alpha = fmaf(t_rep, hi - lo, lo) * alpha;
       }
       if constexpr (TIMED) {
@@ -265,12 +273,14 @@ struct TimeIn {
   int32_t n_time, n_dir;
 };
 
-// the gate arguments of rg_digraph_layer_fwd_gated; nullptr: the ungated entry points
+// the gate arguments of rg_digraph_layer_fwd_gated / _gates; nullptr: the ungated entry points.  per_rep (rg_digraph_layer_fwd_gates):
+// gate_lo == gate_hi is the [n_rep, E] array and t is not read, so that the kernel's fmaf(1, 0, lo) is the array's value
 struct GateIn {
   int32_t n_rep;
   const float* t;
   const float* gate_lo;
   const float* gate_hi;
+  bool per_rep;
 };
 
 size_t scratch_need(int64_t n_hubs, int64_t n_chunks, int32_t ld, int64_t n_rep) {
@@ -303,7 +313,8 @@ int run(const char* who, const TimeIn* T, const GateIn* Q, int32_t n_dst, int64_
     RG_CHECK(n_rep * std::max(n_src, n_dst) < ((int64_t)1 << 31) && n_rep * n_edges < ((int64_t)1 << 31),
              "%s: n_rep=%lld times n_src=%d, n_dst=%d or n_edges=%lld overflows int32", who, (long long)n_rep, n_src, n_dst,
              (long long)n_edges);
-    RG_CHECK(Q->t, "%s: NULL argument (t)", who);
+    if (Q->per_rep) RG_CHECK(Q->gate_lo, "%s: NULL argument (gate)", who);
+    else RG_CHECK(Q->t, "%s: NULL argument (t)", who);
     RG_CHECK(n_rep <= 65535, "%s: n_rep=%lld (at most 65535: the combine launch has a grid row per replica)", who, (long long)n_rep);
   }
   if (n_dst == 0) {
@@ -367,6 +378,7 @@ int run(const char* who, const TimeIn* T, const GateIn* Q, int32_t n_dst, int64_
         DgGatedArgs GA;
         static_cast<DgArgs&>(GA) = A;
         GA.n_rep = (int)n_rep; GA.n_chunks = (int)n_chunks; GA.t = Q->t; GA.gate_lo = Q->gate_lo; GA.gate_hi = Q->gate_hi;
+        GA.gate_rep = Q->per_rep ? (int)n_edges : 0;
         return launch<decltype(g)::value, decltype(a4)::value, false, true>(GA, s);
       }
       return launch<decltype(g)::value, decltype(a4)::value, false>(A, s);
@@ -410,8 +422,20 @@ extern "C" int rg_digraph_layer_fwd_gated(int32_t n_rep, const float* t, const f
                                           const float* hidden, const float* rela, int32_t d, int32_t ld, const float* a_s, const float* a_r,
                                           const float* a_q, int32_t ap, const float* w_alpha, const float* b_alpha, int32_t attn_dim,
                                           float* agg_out, float* alpha_out, void* scratch, size_t scratch_bytes, void* stream) {
-  const rgdg::GateIn Q{n_rep, t, gate_lo, gate_hi};
+  const rgdg::GateIn Q{n_rep, t, gate_lo, gate_hi, false};
   return rgdg::run("rg_digraph_layer_fwd_gated", nullptr, &Q, n_dst, n_edges, dst_ptr, dst_ptr_host, src_idx, rel, row_of_dst, n_src,
+                   n_rela_rows, batch, hidden, rela, d, ld, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim, agg_out, alpha_out, scratch,
+                   scratch_bytes, stream);
+}
+
+extern "C" int rg_digraph_layer_fwd_gates(int32_t n_rep, const float* gate, int32_t n_dst, int64_t n_edges, const int32_t* dst_ptr,
+                                          const int32_t* dst_ptr_host, const int32_t* src_idx, const int32_t* rel, const int32_t* row_of_dst,
+                                          int32_t n_src, int32_t n_rela_rows, int32_t batch, const float* hidden, const float* rela,
+                                          int32_t d, int32_t ld, const float* a_s, const float* a_r, const float* a_q, int32_t ap,
+                                          const float* w_alpha, const float* b_alpha, int32_t attn_dim, float* agg_out, float* alpha_out,
+                                          void* scratch, size_t scratch_bytes, void* stream) {
+  const rgdg::GateIn Q{n_rep, nullptr, gate, gate, true};
+  return rgdg::run("rg_digraph_layer_fwd_gates", nullptr, &Q, n_dst, n_edges, dst_ptr, dst_ptr_host, src_idx, rel, row_of_dst, n_src,
                    n_rela_rows, batch, hidden, rela, d, ld, a_s, a_r, a_q, ap, w_alpha, b_alpha, attn_dim, agg_out, alpha_out, scratch,
                    scratch_bytes, stream);
 }

@@ -1155,9 +1155,27 @@ def digraph_layer_fwd_gated(dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, 
                           attn_dim, want_alpha, dst_ptr_host, None, (t, gate_lo, gate_hi), check_index)
 
 
+def digraph_layer_fwd_gates(dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s, a_r, a_q, w_alpha, b_alpha, attn_dim, gate,
+                            want_alpha=True, dst_ptr_host=None, check_index=True):
+    """digraph_layer_fwd_gated with a gate per (replica, edge) (rg_digraph_layer_fwd_gates): ``gate`` fp32 [n_rep, E] in the order of
+    the edge list, replica k's gates its row k, taken as they are.  The stacked arguments and results of digraph_layer_fwd_gated;
+    replica k's bits are those of a one-replica digraph_layer_fwd_gated call with gate_lo = gate_hi = gate[k] and t = 1."""
+    return _digraph_layer("digraph_layer_fwd_gates", dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s, a_r, a_q, w_alpha, b_alpha,
+                          attn_dim, want_alpha, dst_ptr_host, None, (gate,), check_index)
+
+
 def _check_gates(who, gated, E, n_rows):
     """(n_rep, t, gate_lo, gate_hi) of a gated wrapper: ``t`` fp32 [n_rep] with n_rep >= 1 dividing the ``n_rows`` rows of the stacked
-    state, ``gate_lo`` / ``gate_hi`` fp32 [E] or None."""
+    state, ``gate_lo`` / ``gate_hi`` fp32 [E] or None.  ``gated`` of one entry is the per-replica form, (n_rep, gate): ``gate`` fp32
+    [n_rep, E] with n_rep >= 1 dividing ``n_rows``."""
+    if len(gated) == 1:
+        gate, = gated
+        if not (torch.is_tensor(gate) and gate.dtype == torch.float32 and gate.dim() == 2 and gate.shape[0] >= 1 and gate.shape[1] == E):
+            raise ValueError("%s: gate must be float32 [n_rep, %d], a row per replica (at least one) and an entry per edge" % (who, E))
+        if n_rows % gate.shape[0]:
+            raise ValueError("%s: the %d rows of hidden and a_s are not a whole number of rows for each of the %d replicas"
+                             % (who, n_rows, gate.shape[0]))
+        return gate.shape[0], gate
     t, lo, hi = gated
     if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.dim() == 1 and t.numel() >= 1):
         raise ValueError("%s: t must be a float32 vector with an entry per replica (at least one)" % who)
@@ -1172,7 +1190,7 @@ def _check_gates(who, gated, E, n_rows):
 def _digraph_layer(who, dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s, a_r, a_q, w_alpha, b_alpha, attn_dim, want_alpha,
                    dst_ptr_host, timed, gated=None, check_index=True):
     """Every forward wrapper: the host checks, the scratch, the launch.  ``timed``: None or (edge_time, q_time, time_tab, n_dir);
-    ``gated``: None or (t, gate_lo, gate_hi), static only."""
+    ``gated``: None, (t, gate_lo, gate_hi) or (gate [n_rep, E],), static only."""
     ints, floats = [("dst_ptr", dst_ptr), ("src_idx", src_idx), ("rel", rel), ("row_of_dst", row_of_dst)], \
         [("hidden", hidden), ("rela", rela), ("a_s", a_s), ("a_r", a_r), ("a_q", a_q)]
     n_dir = 1
@@ -1238,7 +1256,12 @@ def _digraph_layer(who, dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s,
     if DIGRAPH_EVENTS is not None:
         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         ev[0].record()
-    if gated is not None:
+    if gated is not None and len(gates) == 1:
+        _lib.check(L.rg_digraph_layer_fwd_gates(n_rep, p(gates[0]), n_dst, E, p(dst_ptr), p(ptr_h), p(src_idx), p(rel), p(row_of_dst), n_src,
+                                                a_r.shape[0], a_q.shape[0], p(hidden), p(rela), int(d), ld, p(a_s), p(a_r), p(a_q), ap,
+                                                p(w_alpha), p(b_alpha), int(attn_dim), p(agg), p(alpha), p(scratch), nbytes,
+                                                _lib.stream_ptr()))
+    elif gated is not None:
         _lib.check(L.rg_digraph_layer_fwd_gated(n_rep, p(gates[0]), p(gates[1]), p(gates[2]), n_dst, E, p(dst_ptr), p(ptr_h), p(src_idx), p(rel),
                                                 p(row_of_dst), n_src, a_r.shape[0], a_q.shape[0], p(hidden), p(rela), int(d), ld, p(a_s), p(a_r),
                                                 p(a_q), ap, p(w_alpha), p(b_alpha), int(attn_dim), p(agg), p(alpha), p(scratch), nbytes,
@@ -1328,10 +1351,65 @@ def digraph_layer_bwd_gated(dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, 
                               b_alpha, attn_dim, grad_agg, want_state, None, (t, gate_lo, gate_hi), view, check_index)
 
 
+def digraph_layer_bwd_gates(dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s, a_r, a_q, w_alpha, b_alpha, attn_dim, grad_agg, gate,
+                            want_state=True, view=None, check_index=True):
+    """The adjoint of digraph_layer_fwd_gates on the same arguments (rg_digraph_layer_bwd_gates): digraph_layer_bwd_gated's stacked
+    results at the gates ``gate`` fp32 [n_rep, E]; replica k's bits are those of a one-replica digraph_layer_bwd_gated call with
+    gate_lo = gate_hi = gate[k] and t = 1."""
+    return _digraph_layer_bwd("digraph_layer_bwd_gates", dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s, a_r, a_q, w_alpha,
+                              b_alpha, attn_dim, grad_agg, want_state, None, (gate,), view, check_index)
+
+
+MASK_CHUNK = 512                     # include/redgnn.h: RG_MASK_CHUNK
+
+
+def mask_step(offsets, free, score, target, inv_scale, inv_n, lambda_size, lambda_ent, grad, theta, m, v, step, lr=0.05, beta1=0.9,
+              beta2=0.999, eps=1e-8, gate_out=None):
+    """One step of learning an edge mask for R replicas of a digraph's E edges (rg_mask_step; see include/redgnn.h for the
+    arithmetic): ``theta``, ``m``, ``v`` fp32 [R, E] are updated IN PLACE on the free edges (``free`` uint8 or bool [E]) and
+    (gate_out fp32 [R, E], size fp32 [R, B], count int32 [R, B]) is returned - the new gates (``gate_out``, if given, is written on
+    the free edges and otherwise left as it is; None: a new array of zeros), their sum over a row's free edges and how many of them
+    are above 0.5.  ``offsets`` int64 [B + 1] the digraph's, ``score`` fp32 [R, B], ``target`` / ``inv_scale`` / ``inv_n`` fp32 [B],
+    ``lambda_size`` / ``lambda_ent`` fp32 [R], ``grad`` fp32 [R, E] = d score / d gate, ``step`` >= 1 Adam's step count.  Shapes and
+    dtypes are checked here (ValueError).  No float atomics: the same bits on every run, and a replica's do not depend on the
+    others."""
+    who = "mask_step"
+    if isinstance(step, (bool, np.bool_)) or not isinstance(step, (int, np.integer)) or step < 1:
+        raise ValueError("%s: step must be a count from 1 (got %r)" % (who, step))
+    if not (torch.is_tensor(theta) and theta.dtype == torch.float32 and theta.dim() == 2 and theta.shape[0] >= 1):
+        raise ValueError("%s: theta must be float32 [R, E] with at least one replica" % who)
+    R, E = theta.shape
+    if not (torch.is_tensor(offsets) and offsets.dtype == torch.int64 and offsets.dim() == 1 and offsets.numel() >= 1):
+        raise ValueError("%s: offsets must be int64 [B + 1]" % who)
+    B = offsets.numel() - 1
+    if torch.is_tensor(free) and free.dtype == torch.bool:
+        free = free.view(torch.uint8)
+    if not (torch.is_tensor(free) and free.dtype == torch.uint8 and tuple(free.shape) == (E,)):
+        raise ValueError("%s: free must be uint8 or bool [%d], one per edge" % (who, E))
+    if gate_out is None:
+        gate_out = torch.zeros((R, E), dtype=torch.float32, device=theta.device)
+    for name, x, shape in (("m", m, (R, E)), ("v", v, (R, E)), ("grad", grad, (R, E)), ("gate_out", gate_out, (R, E)), ("score", score, (R, B)),
+                           ("target", target, (B,)), ("inv_scale", inv_scale, (B,)), ("inv_n", inv_n, (B,)),
+                           ("lambda_size", lambda_size, (R,)), ("lambda_ent", lambda_ent, (R,))):
+        if not (torch.is_tensor(x) and x.dtype == torch.float32 and tuple(x.shape) == shape):
+            raise ValueError("%s: %s must be float32 %s" % (who, name, list(shape)))
+    _require_gpu(theta.device)
+    tensors = (offsets, free, score, target, inv_scale, inv_n, lambda_size, lambda_ent, grad, theta, m, v, gate_out)
+    if not all(x.is_cuda and x.is_contiguous() for x in tensors):
+        raise ValueError("%s: every tensor must be contiguous and on the device" % who)
+    size = torch.zeros((R, B), dtype=torch.float32, device=theta.device)
+    count = torch.zeros((R, B), dtype=torch.int32, device=theta.device)
+    p = _lib.ptr
+    _lib.check(_lib.lib().rg_mask_step(R, B, E, p(offsets), p(free), p(score), p(target), p(inv_scale), p(inv_n), p(lambda_size),
+                                       p(lambda_ent), p(grad), float(lr), float(beta1), float(beta2), float(eps), int(step), p(theta), p(m),
+                                       p(v), p(gate_out), p(size), p(count), _lib.stream_ptr()))
+    return gate_out, size, count
+
+
 def _digraph_layer_bwd(who, dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s, a_r, a_q, w_alpha, b_alpha, attn_dim, grad_agg,
                        want_state, timed, gated=None, view=None, check_index=True):
     """Every backward wrapper: the host checks, the source view, the scratch, the launch.  ``timed``: None or (edge_time, q_time,
-    time_tab, n_dir); ``gated``: None or (t, gate_lo, gate_hi), static only."""
+    time_tab, n_dir); ``gated``: None, (t, gate_lo, gate_hi) or (gate [n_rep, E],), static only."""
     ints = [("dst_ptr", dst_ptr), ("src_idx", src_idx), ("rel", rel), ("row_of_dst", row_of_dst)]
     floats = [("hidden", hidden), ("rela", rela), ("a_s", a_s), ("a_r", a_r), ("a_q", a_q), ("grad_agg", grad_agg)]
     n_dir = 1
@@ -1405,7 +1483,12 @@ def _digraph_layer_bwd(who, dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, 
     if DIGRAPH_BWD_EVENTS is not None:
         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         ev[0].record()
-    if gated is not None:
+    if gated is not None and len(gates) == 1:
+        _lib.check(L.rg_digraph_layer_bwd_gates(n_rep, p(gates[0]), n_src, n_dst, E, p(src_ptr), p(src_ptr_h), p(edge_of), p(dst_of_edge),
+                                                p(rel), p(row_of_dst), a_r.shape[0], a_q.shape[0], p(hidden), p(rela), int(d), ld, p(a_s),
+                                                p(a_r), p(a_q), ap, p(w_alpha), p(b_alpha), int(attn_dim), p(grad_agg), p(grad_gate),
+                                                p(grad_hidden), p(grad_a_s), p(scratch), nbytes, _lib.stream_ptr()))
+    elif gated is not None:
         _lib.check(L.rg_digraph_layer_bwd_gated(n_rep, p(gates[0]), p(gates[1]), p(gates[2]), n_src, n_dst, E, p(src_ptr), p(src_ptr_h),
                                                 p(edge_of), p(dst_of_edge), p(rel), p(row_of_dst), a_r.shape[0], a_q.shape[0], p(hidden),
                                                 p(rela), int(d), ld, p(a_s), p(a_r), p(a_q), ap, p(w_alpha), p(b_alpha), int(attn_dim),

@@ -12,6 +12,7 @@ s -> o through the query's subgraph (identity self-loops count as steps); each e
     fid = model.fidelity(subs, rels, objs, k=4)      # necessity and sufficiency of the best 1..k paths: an explain.Fidelity
     sal = rd.saliency(model)                         # d score / d (a gate on every edge), one pass (HIP: csrc/digraph_bwd.hip): an explain.Saliency
     att = rd.integrated_gradients(model, steps=16)   # attributions that add up to the score (gated, replicated edge-list kernels): an explain.Attribution
+    mask = rd.learn_mask(model)                      # the small set of facts that reproduces the score (a gate per replica and edge, csrc/mask_step.hip): an explain.EdgeMask
 
 The extraction runs in HIP (csrc/explain.hip): a forward keeps all L + 1 frontier levels and each layer's attention projection, then
 one backward marking pass per hop reads only the marked tails' CSR rows.  This module holds the result type and the host drivers.
@@ -158,6 +159,35 @@ class RDigraph:
         it depends on ``rep_chunk`` in the last bits only (the dense products see other row counts).  Static and inductive models; a
         temporal or extrapolation digraph or model is a ValueError: the timed forms of the gated kernels are not built."""
         return integrated_gradients(self, model, steps, keep, baseline, target, rep_chunk, mode)
+
+    def learn_mask(self, model, lambdas=(0.01, 0.03, 0.1, 0.3, 1.0), entropy=0.0, iterations=100, lr=0.05, theta0=2.0, tol=0.05, keep=None,
+                   mode="test"):
+        """Which small set of facts reproduces this answer's score?  A learned edge mask (the GNNExplainer question asked of an
+        r-digraph): an explain.EdgeMask.  Every FREE edge - kept and no self-loop; the self-loops (relation 2 * n_rel) are part of the
+        model and stay at gate 1, edges not kept are outside the walk - gets a logit theta, starting at ``theta0``, and the gate
+        g = sigmoid(theta) that multiplies its message as in ``rescore(gate=)``.  With target the row's score at gate 1, baseline_score
+        its score with the free edges at 0 and scale = |target - baseline_score|, Adam (``lr``; beta 0.9 / 0.999, eps 1e-8) minimises
+        per row
+
+            ((score(g) - target) / scale)^2  +  lambda * mean of the row's free gates  +  entropy * sum of their binary entropies
+
+        for every lambda of ``lambdas`` at once: the lambdas are REPLICAS of the walk with a gate per (replica, edge), one launch per
+        hop for all of them (rg_digraph_layer_fwd_gates, rg_digraph_layer_bwd_gates), and the whole update - chain rule,
+        regularisers, Adam, the new gates and their per-row sums - is one more launch per iteration (rg_mask_step,
+        csrc/mask_step.hip).  The per-hop index and the source views are built once.  The dense step's autograd adjoint runs per
+        replica (explain.MASK_SPLIT_DENSE), so that R replicas in one call give, bit for bit, the gates of R one-replica calls: the
+        library GEMMs behind it round by row count, the HIP kernels do not.  A row with scale == 0 or whose answer is not
+        reached has no score term (its 1 / scale is taken as 0): its mask only decays under lambda and entropy.
+
+        After ``iterations`` steps (0: the initial gates) every replica's gates are rounded at 0.5 and scored in one stacked gated
+        forward (``hard_score``: the other edges at gate 0, which is not deletion - the attention of the edges that stay is what it was);
+        a row takes the replica with the fewest gates above 0.5 among those with |hard_score - target| <= ``tol`` * scale, or, if there
+        is none, the replica of the smallest deviation, ties to the lower replica.  ``keep`` / ``gate`` of the result are assembled from
+        the rows' replicas and ``kept_score`` is one exact ``rescore(keep=)`` of that mask: the facts really deleted.  ``keep`` (the
+        argument) as in ``rescore``.  The defaults are a starting point, not a tuned setting.  No float atomics anywhere: the same bits
+        on every run.  Static and inductive models; a temporal or extrapolation digraph or model is a ValueError: the timed forms of
+        the gated kernels are not built."""
+        return learn_mask(self, model, lambdas, entropy, iterations, lr, theta0, tol, keep, mode)
 
     def fact_mask(self, facts, rows=None, inverse_offset=None):
         """bool [E]: the edges that stand for one of the facts ``facts`` int [F, 3] = (h, r, t), at any hop: an edge is marked if its
@@ -1990,6 +2020,12 @@ def _rescore_static(rd, model, keep, mode, who, tape=None):
     return Rescore(score=score, reached=reached, live=live, alpha=alpha)
 
 
+def _segment_max(values, group, n_groups):
+    """float32 [n_groups]: the largest of ``values`` per ``group`` (int64); 0 for a group without values."""
+    out = torch.zeros(n_groups, dtype=torch.float32, device=values.device)
+    return out.scatter_reduce(0, group, values, "amax", include_self=False) if values.numel() else out
+
+
 def _segment_sums(values, group, n_groups):
     """float32 [n_groups]: the sum of ``values`` per ``group`` (int64, never decreasing), each group's values added in a fixed order -
     laid out as one matrix row per group and summed along it, no atomics: the same bits on every run."""
@@ -2007,6 +2043,8 @@ class _FactSums:
     """Per-edge values of an r-digraph summed per fact: the grouping Saliency (``edge_grad``) and Attribution (``edge_attr``) share.  A
     subclass names its per-edge field in ``_VALUES`` and has ``digraph``, ``score`` and ``reached``."""
     _VALUES = None
+
+    _REDUCE = staticmethod(_segment_sums)                                 # what is made of a fact's edges (EdgeMask: their maximum)
 
     def _fact_sums(self, inverse_offset=None, who="fact_grad"):
         """(row, fact, sum) of the per-edge values under RDigraph.fact_mask's grouping rule: Saliency.fact_grad states it."""
@@ -2028,7 +2066,7 @@ class _FactSums:
         key = ((e[:, 0] * n_key + h) * n_rel + r) * n_key + t
         key, order = torch.sort(key, stable=True)                         # copies of a fact in edge order: a fixed order of the sum
         keys, group = torch.unique_consecutive(key, return_inverse=True)
-        grad = _segment_sums(values[rd.edges[:, 3].long() != 2 * n_rel][order], group, keys.numel())
+        grad = self._REDUCE(values[rd.edges[:, 3].long() != 2 * n_rel][order], group, keys.numel())
         t_, rest = keys % n_key, keys // n_key
         r_, rest = rest % n_rel, rest // n_rel
         return rest // n_key, torch.stack([rest % n_key, r_, t_], 1), grad
@@ -2195,6 +2233,64 @@ class Attribution(_FactSums):
         return self._fact_sums(inverse_offset, "fact_attr")
 
 
+@dataclass
+class EdgeMask(_FactSums):
+    """A learned edge mask of an r-digraph (RDigraph.learn_mask): per row the gates of the replica (the lambda) the selection rule
+    took.  Tensors on the digraph's device; R = len(lambdas).
+
+    gate            float32 [E]     the soft gates of the row's replica: 1 at kept self-loops, 0 at edges that are not kept
+    keep            bool [E]        the mask: gate > 0.5 on the free edges, the kept self-loops, nothing else
+    score           float32 [B]     the score at ``gate`` (the soft score of the row's replica)
+    hard_score      float32 [B]     ... at the gates rounded to 0 / 1 (the other edges gated off, their attention left as it was)
+    kept_score      float32 [B]     ... of ``rescore(keep=keep)``: the other facts deleted
+    target          float32 [B]     the score at gate 1, exactly 0 where o is not reached
+    baseline_score  float32 [B]     the score with every free edge at gate 0
+    size            int64 [B]       free edges of the row with gate > 0.5
+    n_free          int64 [B]       free edges of the row
+    replica         int64 [B]       the replica the row took
+    lambdas         float32 [R]     the size weights, one per replica
+    history         namespace       per iteration i and replica: ``deviation`` float32 [iterations, R, B] = (score - target) / scale
+                                    at the gates iteration i starts from, ``size`` float32 and ``count`` int32 [iterations, R, B] = the
+                                    sum of the free gates it ends with and how many are above 0.5
+    reached         bool [B]        o has a length-L walk from s through kept edges: structural, whatever the gates
+    live            bool [E]        the edge is kept and its head is visited at hop - 1: structural as well
+    digraph         RDigraph        the digraph the edges are those of
+    replica_gate, replica_score, replica_hard_score, replica_size   float32 [R, E], float32 [R, B], float32 [R, B], int64 [R, B]: what
+                                    the selection saw of every replica
+    """
+    gate: torch.Tensor
+    keep: torch.Tensor
+    score: torch.Tensor
+    hard_score: torch.Tensor
+    kept_score: torch.Tensor
+    target: torch.Tensor
+    baseline_score: torch.Tensor
+    size: torch.Tensor
+    n_free: torch.Tensor
+    replica: torch.Tensor
+    lambdas: torch.Tensor
+    history: types.SimpleNamespace
+    reached: torch.Tensor
+    live: torch.Tensor
+    digraph: RDigraph
+    replica_gate: torch.Tensor = None
+    replica_score: torch.Tensor = None
+    replica_hard_score: torch.Tensor = None
+    replica_size: torch.Tensor = None
+    _VALUES = "gate"
+    _REDUCE = staticmethod(_segment_max)
+
+    def fact_gate(self):
+        """(row int64 [F], fact int64 [F, 3] = (h, r, t) with r < n_rel, gate float32 [F]) ordered by (row, h, r, t): the largest
+        ``gate`` over all copies of a base fact in its row, Saliency.fact_grad's grouping (the identity relation is no fact): a fact
+        is in the mask as soon as one of its edges is.  ``top(k)`` and ``format(id2rel)`` rank by it."""
+        return self._fact_sums(None, "fact_gate")
+
+    def sufficiency_gap(self):
+        """float32 [B]: target - kept_score, what the mask's facts alone fail to reproduce (0: they are sufficient)."""
+        return self.target - self.kept_score
+
+
 def _digraph_family(rd):
     return "an extrapolation" if _is_extrapolation(rd) else "a temporal interpolation" if _has_times(rd) else "a static"
 
@@ -2344,15 +2440,19 @@ def _static_hops(S, who):
     return hops, live, reached
 
 
-def _gated_group(S, rd, model, hops, t, lo, hi, want_grad, check_index=True):
+def _gated_group(S, rd, model, hops, t, lo, hi, want_grad, check_index=True, gate=None, split_dense=False):
     """One group of n = t.numel() replicas of the static walk, replica k at the gates fmaf(t[k], hi - lo, lo) (``lo`` / ``hi`` float32
     [E] or None for 0 / 1): _rescore_static's hop loop with the replicas' rows stacked, replica k's node j of a hop at row
     k * n_nodes + j - one rg_digraph_layer_fwd_gated launch and one dense step per hop for all of them - and, with ``want_grad``,
     saliency's backward loop on the same stacked rows (rg_digraph_layer_bwd_gated).  Returns (score [n, B], alpha [n, E], grad [n, E]
     or None): the gradient of replica k's scores with respect to its gates.  With n == 1 and gates of 1 every tensor has the bits of
-    the ungated walk."""
+    the ungated walk.  The other gate form, ``gate`` float32 [n, E] (then ``t``, ``lo`` and ``hi`` are None): replica k at the gates
+    gate[k], taken as they are (rg_digraph_layer_fwd_gates / rg_digraph_layer_bwd_gates); the walk is the same.  ``split_dense``: the
+    dense step's autograd adjoint runs on one replica's rows at a time instead of on the stacked rows.  The HIP launches stay stacked
+    and have a replica's bits whatever else they carry; the library GEMMs behind the adjoint do not (their rounding can follow the
+    row count), so only with it is replica k's gradient, bit for bit, that of a one-replica call - which learn_mask promises."""
     from .models import gru_step, tall_linear
-    n, dev, B, E, L, d, a, ld, ap = t.numel(), S.dev, S.B, S.E, S.L, S.d, S.a, S.ld, S.ap
+    n, dev, B, E, L, d, a, ld, ap = (t.numel() if gate is None else gate.shape[0]), S.dev, S.B, S.E, S.L, S.d, S.a, S.ld, S.ap
     score = torch.zeros(n * B, dtype=torch.float32, device=dev)
     alpha = torch.zeros((n, E), dtype=torch.float32, device=dev)
     grad = torch.zeros((n, E), dtype=torch.float32, device=dev) if want_grad else None
@@ -2367,10 +2467,14 @@ def _gated_group(S, rd, model, hops, t, lo, hi, want_grad, check_index=True):
             l, at = h["l"], h["at"]
             layer, last = model.gnn_layers[l - 1], l == L
             a_r, a_q, rela_p = (x.contiguous() for x in tables[l - 1])
-            g_lo, g_hi = (None if g is None else g[at].contiguous() for g in (lo, hi))
-            agg, al = engine.digraph_layer_fwd_gated(h["dst_ptr"], h["src"], h["rel"], h["row_of"].to(torch.int32).contiguous(), hidden,
-                                                     rela_p, d, a_s, a_r, a_q, *w_b(layer), a, t, g_lo, g_hi,
-                                                     dst_ptr_host=h["dst_ptr_host"], check_index=check_index)
+            # the hop's gates in either form: what follows attn_dim in the forward's and grad_agg in the adjoint's arguments
+            if gate is None:
+                fwd, bwd = engine.digraph_layer_fwd_gated, engine.digraph_layer_bwd_gated
+                g_hop = (t,) + tuple(None if g is None else g[at].contiguous() for g in (lo, hi))
+            else:
+                fwd, bwd, g_hop = engine.digraph_layer_fwd_gates, engine.digraph_layer_bwd_gates, (gate[:, at].contiguous(),)
+            agg, al = fwd(h["dst_ptr"], h["src"], h["rel"], h["row_of"].to(torch.int32).contiguous(), hidden, rela_p, d, a_s, a_r, a_q,
+                          *w_b(layer), a, *g_hop, dst_ptr_host=h["dst_ptr_host"], check_index=check_index)
             alpha[:, at] = al.view(n, -1)
             # the replicas' rows of the dense step: node j of replica k is row k * n_dst + j, its old state row k * n_prev + prev_idx[j]
             had = h["had"].repeat(n)
@@ -2379,7 +2483,7 @@ def _gated_group(S, rd, model, hops, t, lo, hi, want_grad, check_index=True):
             row_of = (h["row_of"][None, :] + rep * B).reshape(-1)
             if want_grad:
                 tape.append(dict(h=h, hidden=hidden, a_s=a_s, agg=agg, prev_idx=prev_idx, had=had, a_r=a_r, a_q=a_q, rela=rela_p,
-                                 g_lo=g_lo, g_hi=g_hi))
+                                 bwd=bwd, g_hop=g_hop))
             if S.fused:                                                       # the dense step of _forward_inference
                 node_rows = torch.stack([row_of, torch.zeros_like(row_of)], 1).to(torch.int32).contiguous()
                 hidden, a_s = engine.dense_fwd(agg, hidden, prev_idx, d, layer.W_h.weight, model.act_name, model.gate,
@@ -2400,34 +2504,42 @@ def _gated_group(S, rd, model, hops, t, lo, hi, want_grad, check_index=True):
     score = score.view(n, B)
     if not want_grad or len(hops) < L:                                        # no row reaches its answer: nothing depends on any edge
         return score, alpha, grad
-    gate = types.SimpleNamespace(**{name: getattr(model.gate, name).detach()
-                                    for name in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")})
+    gru = types.SimpleNamespace(**{name: getattr(model.gate, name).detach()
+                                   for name in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")})
     g_hidden = g_a_s = None                                                   # d (sum of the scores) / d (the hop's new state, its projection)
     for tp in reversed(tape):
         h = tp["h"]
         l = h["l"]
         layer, last, first = model.gnn_layers[l - 1], l == L, l == 1
-        # ---- the dense step's adjoint: saliency's, on the stacked rows
-        with torch.enable_grad():
-            agg = tp["agg"].detach().requires_grad_(True)
-            prev = tp["hidden"].detach().requires_grad_(not first)            # hop 1 reads the constant 0
-            x = layer.act(tall_linear(agg[:, :d], layer.W_h.weight.detach()))
-            h0 = torch.zeros((agg.shape[0], d), device=dev)
-            h0[tp["had"]] = prev[:, :d][tp["prev_idx"][tp["had"]].long()]
-            hid = gru_step(x, h0, gate)
-            if last:
-                outs, seeds = [tall_linear(hid, model.W_final.weight.detach()).squeeze(-1)], [torch.ones(agg.shape[0], device=dev)]
-            else:
-                w_s = model.gnn_layers[l].Ws_attn.weight.detach()
-                outs = [F.pad(hid, (0, ld - d)) if ld != d else hid, tall_linear(hid, F.pad(w_s, (0, 0, 0, ap - a)) if ap != a else w_s)]
-                seeds = [g_hidden, g_a_s]
-            grads = torch.autograd.grad(outs, [agg] if first else [agg, prev], seeds)
+        # ---- the dense step's adjoint: saliency's, on the stacked rows - or, with ``split_dense``, on one replica's rows at a time
+        def dense_adjoint(agg, prev, had, prev_idx, seeds):
+            with torch.enable_grad():
+                agg = agg.detach().requires_grad_(True)
+                prev = prev.detach().requires_grad_(not first)                # hop 1 reads the constant 0
+                x = layer.act(tall_linear(agg[:, :d], layer.W_h.weight.detach()))
+                h0 = torch.zeros((agg.shape[0], d), device=dev)
+                h0[had] = prev[:, :d][prev_idx[had].long()]
+                hid = gru_step(x, h0, gru)
+                if last:
+                    outs, seeds = [tall_linear(hid, model.W_final.weight.detach()).squeeze(-1)], [torch.ones(agg.shape[0], device=dev)]
+                else:
+                    w_s = model.gnn_layers[l].Ws_attn.weight.detach()
+                    outs = [F.pad(hid, (0, ld - d)) if ld != d else hid, tall_linear(hid, F.pad(w_s, (0, 0, 0, ap - a)) if ap != a else w_s)]
+                return torch.autograd.grad(outs, [agg] if first else [agg, prev], seeds)
+
+        if split_dense and n > 1:
+            n_d, n_p = h["n_dst"], h["n_prev"]
+            parts = [dense_adjoint(tp["agg"][k * n_d:(k + 1) * n_d], tp["hidden"][k * n_p:(k + 1) * n_p], h["had"], h["prev_idx"],
+                                   None if last else [g_hidden[k * n_d:(k + 1) * n_d], g_a_s[k * n_d:(k + 1) * n_d]]) for k in range(n)]
+            grads = [torch.cat([p[i] for p in parts], 0) for i in range(len(parts[0]))]
+        else:
+            grads = dense_adjoint(tp["agg"], tp["hidden"], tp["had"], tp["prev_idx"], None if last else [g_hidden, g_a_s])
         # ---- the edge-list layer's, in HIP, on the hop's source view (built once per hop, whatever the gates and the replicas)
         if h["view"] is None:
             h["view"] = engine.digraph_source_view(h["dst_ptr"], h["src"], h["n_prev"])
-        gate_grad, g_hidden, g_a_s = engine.digraph_layer_bwd_gated(
+        gate_grad, g_hidden, g_a_s = tp["bwd"](
             h["dst_ptr"], h["src"], h["rel"], h["row_of"].to(torch.int32).contiguous(), tp["hidden"], tp["rela"], d, tp["a_s"], tp["a_r"],
-            tp["a_q"], *w_b(layer), a, grads[0].contiguous(), t, tp["g_lo"], tp["g_hi"], want_state=not first, view=h["view"],
+            tp["a_q"], *w_b(layer), a, grads[0].contiguous(), *tp["g_hop"], want_state=not first, view=h["view"],
             check_index=check_index)
         grad[:, h["at"]] = gate_grad.view(n, -1)
         if not first:
@@ -2486,6 +2598,94 @@ def integrated_gradients(rd, model, steps=16, keep=None, baseline=None, target=N
     residual = score[1] - score[0] - _segment_sums(edge_attr, S.row, B)
     return Attribution(score=score[1], baseline_score=score[0], edge_attr=edge_attr, residual=residual, reached=reached, live=live,
                        steps=steps, digraph=rd)
+
+
+MASK_SPLIT_DENSE = True              # learn_mask: the dense step's autograd adjoint per replica (a replica's gates are then, bit for bit,
+#                                      those of a one-replica call); False: on the stacked rows, as integrated gradients runs it - about
+#                                      3.6 x faster per iteration at DESIGN 5's sizes, the gradients equal up to the last bits
+
+
+def _check_mask_args(who, lambdas, entropy, iterations, lr, theta0, tol):
+    """The host checks of learn_mask's own arguments (ValueError naming the argument); returns the lambdas as a float32 array."""
+    try:
+        lam = np.asarray(list(lambdas), dtype=np.float64)
+    except (TypeError, ValueError):
+        lam = None
+    if lam is None or lam.ndim != 1 or lam.size < 1 or not np.isfinite(lam).all() or (lam < 0).any():
+        raise ValueError("%s: lambdas must be a non-empty sequence of finite values >= 0 (got %r)" % (who, lambdas))
+    real = lambda x: isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, (bool, np.bool_)) and np.isfinite(x)
+    if not real(entropy) or entropy < 0:
+        raise ValueError("%s: entropy must be a finite value >= 0 (got %r)" % (who, entropy))
+    if isinstance(iterations, (bool, np.bool_)) or not isinstance(iterations, (int, np.integer)) or iterations < 0:
+        raise ValueError("%s: iterations must be a count >= 0 (got %r)" % (who, iterations))
+    if not real(lr) or lr <= 0:
+        raise ValueError("%s: lr must be a finite value > 0 (got %r)" % (who, lr))
+    if not real(tol) or tol < 0:
+        raise ValueError("%s: tol must be a finite value >= 0 (got %r)" % (who, tol))
+    if not real(theta0):
+        raise ValueError("%s: theta0 must be finite (got %r)" % (who, theta0))
+    return lam.astype(np.float32)
+
+
+def mask_selection(hard_score, size, target, scale, tol):
+    """learn_mask's selection rule: int64 [B], per row the replica with the fewest gates above 0.5 (``size`` int64 [R, B]) among those
+    with |hard_score - target| <= tol * scale (``hard_score`` float32 [R, B]), or, where there is none, the one of the smallest
+    deviation; ties to the lower replica."""
+    R = hard_score.shape[0]
+    k = torch.arange(R, device=hard_score.device)[:, None]
+    dev_h = (hard_score - target[None, :]).abs()
+    ok = dev_h <= tol * scale[None, :]
+    by_size = torch.where(ok, size * R + k, torch.full_like(size, torch.iinfo(torch.int64).max)).min(0).values % R
+    by_dev = torch.where(dev_h == dev_h.min(0, keepdim=True).values, k, R).min(0).values
+    return torch.where(ok.any(0), by_size, by_dev)
+
+
+def learn_mask(rd, model, lambdas=(0.01, 0.03, 0.1, 0.3, 1.0), entropy=0.0, iterations=100, lr=0.05, theta0=2.0, tol=0.05, keep=None,
+               mode="test"):
+    """RDigraph.learn_mask (see there)."""
+    who = "learn_mask"
+    lam = _check_mask_args(who, lambdas, entropy, iterations, lr, theta0, tol)
+    S, _ = _gated_setup(rd, model, keep, mode, who, {})
+    R, E, B, dev, iterations = lam.size, S.E, S.B, S.dev, int(iterations)
+    f32 = dict(dtype=torch.float32, device=dev)
+    hops, live, reached = _static_hops(S, who)                                # the index: once, whatever the gates
+    fixed = S.kept & (S.rel == 2 * int(rd.n_rel))                             # self-loops are not facts: gate 1 throughout
+    free = S.kept & ~fixed
+    # ---- the two ends in one two-replica walk, as integrated gradients takes them: the free edges at 0, and every gate at 1
+    ends, _, _ = _gated_group(S, rd, model, hops, torch.tensor([0.0, 1.0], **f32), fixed.to(torch.float32), torch.ones(E, **f32), False)
+    baseline, target = ends[0], ends[1]
+    scale = (target - baseline).abs()
+    inv_scale = torch.where((scale > 0) & reached, 1.0 / scale, torch.zeros_like(scale))
+    n_free = torch.bincount(S.row[free], minlength=B)[:B]
+    inv_n = torch.where(n_free > 0, 1.0 / n_free.to(torch.float32), torch.zeros(B, **f32))
+    lam_size, lam_ent = torch.as_tensor(lam).to(dev), torch.full((R,), float(entropy), **f32)
+    # ---- the state: a logit and Adam's moments per (replica, edge); the gates the kernels read
+    theta, m, v = torch.full((R, E), float(theta0), **f32), torch.zeros((R, E), **f32), torch.zeros((R, E), **f32)
+    gate = torch.zeros((R, E), **f32)
+    gate[:, free] = float(np.float32(1.0 / (1.0 + np.exp(-np.float64(theta0)))))
+    gate[:, fixed] = 1.0
+    free_u8 = free.to(torch.uint8).contiguous()
+    hist = types.SimpleNamespace(deviation=torch.zeros((iterations, R, B), **f32), size=torch.zeros((iterations, R, B), **f32),
+                                 count=torch.zeros((iterations, R, B), dtype=torch.int32, device=dev))
+    for it in range(iterations):
+        score, _, grad = _gated_group(S, rd, model, hops, None, None, None, True, check_index=False, gate=gate, split_dense=MASK_SPLIT_DENSE)
+        hist.deviation[it] = (score - target[None, :]) * inv_scale[None, :]
+        _, hist.size[it], hist.count[it] = engine.mask_step(rd.offsets, free_u8, score.contiguous(), target, inv_scale, inv_n, lam_size,
+                                                            lam_ent, grad, theta, m, v, it + 1, lr=lr, gate_out=gate)
+    # ---- selection: the soft gates and the gates rounded at 0.5 of every replica in one stacked walk
+    hard = torch.where(free[None, :], (gate > 0.5).to(torch.float32), gate)
+    both, _, _ = _gated_group(S, rd, model, hops, None, None, None, False, check_index=False, gate=torch.cat([gate, hard], 0))
+    soft_score, hard_score = both[:R], both[R:]
+    size = torch.zeros((R, B), dtype=torch.int64, device=dev).index_add_(1, S.row[free], (gate[:, free] > 0.5).long())
+    replica = mask_selection(hard_score, size, target, scale, float(tol))
+    rows = torch.arange(B, device=dev)
+    gate_sel = gate[replica[S.row], torch.arange(E, device=dev)]
+    keep_sel = torch.where(free, gate_sel > 0.5, fixed)
+    kept = rescore(rd, model, keep=keep_sel, mode=mode)
+    return EdgeMask(gate=gate_sel, keep=keep_sel, score=soft_score[replica, rows], hard_score=hard_score[replica, rows],
+                    kept_score=kept.score, target=target, baseline_score=baseline, size=size[replica, rows], n_free=n_free, replica=replica,
+                    lambdas=lam_size, history=hist, reached=reached, live=live, digraph=rd, replica_gate=gate, replica_score=soft_score,
+                    replica_hard_score=hard_score, replica_size=size)
 
 
 def _fidelity_of(rd, model, k, loops, mode, inverse_offset=None):

@@ -590,6 +590,16 @@ class RED_GNN_trans(nn.Module):
         Eval semantics; the parameters get no gradient."""
         return self.explain(subs, rels, objs, mode=mode).integrated_gradients(self, steps=steps, mode=mode)
 
+    def learn_mask(self, subs, rels, objs=None, lambdas=(0.01, 0.03, 0.1, 0.3, 1.0), entropy=0.0, iterations=100, lr=0.05, theta0=2.0,
+                   tol=0.05, mode="test"):
+        """The small set of facts that reproduces the score of o: ``explain`` followed by RDigraph.learn_mask - a gate per edge of
+        the r-digraph learned by Adam under a size penalty, every lambda of ``lambdas`` a replica of each hop in one HIP launch
+        (rg_digraph_layer_fwd_gates / rg_digraph_layer_bwd_gates) and the update one more (rg_mask_step).  Returns an explain.EdgeMask
+        (device tensors): ``keep`` / ``gate`` per edge of ``.digraph``, ``fact_gate()`` / ``top(k)`` per fact, ``kept_score`` the exact
+        rescore of the mask.  ``objs=None``: each row's own top answer, as explain.  Eval semantics; the parameters get no gradient."""
+        return self.explain(subs, rels, objs, mode=mode).learn_mask(self, lambdas=lambdas, entropy=entropy, iterations=iterations, lr=lr,
+                                                                    theta0=theta0, tol=tol, mode=mode)
+
     def _forward_graphed(self, graph, q_sub, q_rel, n, device):
         """Replay (or, on the third call with the same graph and batch size, capture) the forward as a HIP graph.
         Returns None when this call should run eagerly: the first two calls of a shape (the eager run also provides the
@@ -703,6 +713,9 @@ class RED_GNN_induc(RED_GNN_trans):
 
     def integrated_gradients(self, subs, rels, objs=None, steps=16, mode="transductive"):
         return super().integrated_gradients(subs, rels, objs=objs, steps=steps, mode=mode)
+
+    def learn_mask(self, subs, rels, objs=None, mode="transductive", **kw):
+        return super().learn_mask(subs, rels, objs=objs, mode=mode, **kw)
 
     def rule_quality(self, table, mode="transductive", sources=None, scratch_bytes=engine.RULE_SCRATCH_BYTES):
         return super().rule_quality(table, mode=mode, sources=sources, scratch_bytes=scratch_bytes)
