@@ -626,6 +626,39 @@ int rg_mask_step(int32_t n_rep, int32_t batch, int64_t n_edges, const int64_t* o
                  const float* grad, float lr, float beta1, float beta2, float eps, int32_t step, float* theta, float* m, float* v,
                  float* gate_out, float* size_out, int32_t* count_out, void* stream);
 
+/* ---- tied edge masks (csrc/mask_tie.hip; explain.RDigraph.learn_tied_mask, explain.learn_mask(tie=)): one learned gate per GROUP of
+ * edges - a fact with all its copies, a (hop, relation) pair, any label - every member edge reading its group's gate.  rg_mask_step
+ * runs unchanged on the group arrays ([n_rep * n_groups], offsets = the rows' group ranges, free_edge all ones); these two calls are
+ * the chain rule through the tie and the way back.  All arrays on the device except grp_ptr_host.
+ *
+ * rg_mask_tie_grad:  grp_grad[k * n_groups + g] = sum over p in grp_ptr[g] .. grp_ptr[g + 1] of grad[k * n_edges + member[p]]
+ * grp_ptr int32 [n_groups + 1] (device) and grp_ptr_host, the same array on the host, for the checks and the chunk list; member int32
+ * [n_member] the edges' list positions, a group's members contiguous, each clamped into 0 .. n_edges - 1; grad float
+ * [n_rep * n_edges]; grp_grad float [n_rep * n_groups].  The sum is defined, in float:
+ *   a group of n members is cut into chunks of RG_MASK_TIE_CHUNK members counted from its own first member;
+ *   chunk sum = ((x0 + x1) + x2) + ..., x_i the chunk's values in member order, starting FROM x0 (one member: that value's bits);
+ *   group sum = ((c0 + c1) + c2) + ..., the chunk sums in chunk order, starting from c0;   an empty group gives +0.
+ * No float atomics: a group of one chunk is summed by one lane, a cut group's chunks by a lane each into partial sums a second launch
+ * adds in chunk order, so every output has the same bits on every run, whatever the other groups and replicas are, and replica k's are
+ * those of an n_rep = 1 call on its slices.  scratch: rg_mask_tie_grad_scratch_bytes(grp_ptr_host, n_groups, n_rep) bytes, 16-B aligned;
+ * 0 (scratch may be NULL) when no group has more than RG_MASK_TIE_CHUNK members.  Errors, all before anything is enqueued: n_rep < 1,
+ * a negative size, n_rep * n_edges, n_rep * n_groups, n_rep * (the chunks of all groups) or n_member beyond int32, a NULL array,
+ * grp_ptr_host not starting at 0, decreasing or not ending at n_member, members without an edge (n_edges == 0), scratch too small.
+ * n_groups == 0 succeeds and launches nothing.
+ *
+ * rg_mask_tie_gates:  gate_out[k * n_edges + e] = grp_gate[k * n_groups + min(group_of[e], n_groups - 1)]  where group_of[e] >= 0
+ * group_of int32 [n_edges], -1 (any negative value): the edge is not tied and its gate_out cell is left as it is - nothing is stored
+ * there; grp_gate float [n_rep * n_groups]; gate_out float [n_rep * n_edges].  A copy: the bits are the group's.  Errors: n_rep < 1, a
+ * negative size, n_rep * n_edges or n_rep * n_groups beyond int32, a NULL array.  n_edges == 0 or n_groups == 0 succeeds and launches
+ * nothing. */
+#define RG_MASK_TIE_CHUNK 32
+size_t rg_mask_tie_grad_scratch_bytes(const int32_t* grp_ptr_host, int32_t n_groups, int32_t n_rep);
+int rg_mask_tie_grad(int32_t n_rep, int64_t n_edges, int32_t n_groups, int64_t n_member, const int32_t* grp_ptr,
+                     const int32_t* grp_ptr_host, const int32_t* member, const float* grad, float* grp_grad, void* scratch,
+                     size_t scratch_bytes, void* stream);
+int rg_mask_tie_gates(int32_t n_rep, int64_t n_edges, int32_t n_groups, const int32_t* group_of, const float* grp_gate, float* gate_out,
+                      void* stream);
+
 /* ---- the per-hop index of an edited r-digraph: the arrays rg_digraph_(t)layer_fwd takes, built from the digraph's own edge list
  * under a keep mask (csrc/digraph_index.hip; explain.RDigraph.rescore of an extrapolation digraph).  edges int32 [n_edges, 5] =
  * (row, hop, head, rel, tail) ordered by (row, hop, tail) and offsets int64 [batch + 1] (start at 0, never decrease, end at n_edges:

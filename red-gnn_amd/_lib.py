@@ -31,6 +31,7 @@ SYMBOLS = [
     "rg_digraph_layer_fwd_gated_scratch_bytes", "rg_digraph_layer_fwd_gated",
     "rg_digraph_layer_bwd_gated_scratch_bytes", "rg_digraph_layer_bwd_gated",
     "rg_digraph_layer_fwd_gates", "rg_digraph_layer_bwd_gates", "rg_mask_step",
+    "rg_mask_tie_grad_scratch_bytes", "rg_mask_tie_grad", "rg_mask_tie_gates",
     "rg_digraph_hop_ranges", "rg_digraph_hop_index_scratch_bytes", "rg_digraph_hop_index",
     "rg_rule_ground_scratch_bytes", "rg_rule_ground",
     "rg_rule_apply_scratch_bytes", "rg_rule_apply",
@@ -175,6 +176,10 @@ def lib():
     L.rg_digraph_layer_bwd_gates.argtypes = [i32, vp] + L.rg_digraph_layer_bwd.argtypes
     f32 = C.c_float
     L.rg_mask_step.argtypes = [i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, f32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.rg_mask_tie_grad_scratch_bytes.argtypes = [vp, i32, i32]
+    L.rg_mask_tie_grad_scratch_bytes.restype = sz
+    L.rg_mask_tie_grad.argtypes = [i32, i64, i32, i64, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.rg_mask_tie_gates.argtypes = [i32, i64, i32, vp, vp, vp, vp]
     L.rg_digraph_hop_ranges.argtypes =[vp, vp, i64, i32, i32, vp, vp, vp, vp, C.POINTER(i32), vp]
     L.rg_digraph_hop_index_scratch_bytes.argtypes = [i64]
     L.rg_digraph_hop_index_scratch_bytes.restype = sz

@@ -1406,6 +1406,69 @@ def mask_step(offsets, free, score, target, inv_scale, inv_n, lambda_size, lambd
     return gate_out, size, count
 
 
+MASK_TIE_CHUNK = 32                  # include/redgnn.h: RG_MASK_TIE_CHUNK
+
+
+def mask_tie_grad(grp_ptr, member, grad, n_groups, grp_ptr_host=None):
+    """The chain rule through tied gates (rg_mask_tie_grad; see include/redgnn.h for the sum's definition): grp_grad fp32 [R, n_groups],
+    entry (k, g) the sum of ``grad`` fp32 [R, E] over the edges member[grp_ptr[g] : grp_ptr[g + 1]] of group g, added in member order
+    in chunks of MASK_TIE_CHUNK, the chunk sums in chunk order; +0 for an empty group.  ``grp_ptr`` int32 [n_groups + 1] (starting at
+    0, never decreasing, ending at member.numel(); ``grp_ptr_host``: the same array as numpy, if at hand), ``member`` int32 [M] edge
+    positions (clamped into 0 .. E - 1).  Shapes and dtypes are checked here (ValueError).  No float atomics: the same bits on every
+    run, and a (replica, group) sum does not depend on the others."""
+    who = "mask_tie_grad"
+    if isinstance(n_groups, (bool, np.bool_)) or not isinstance(n_groups, (int, np.integer)) or n_groups < 0:
+        raise ValueError("%s: n_groups must be a count >= 0 (got %r)" % (who, n_groups))
+    n_groups = int(n_groups)
+    if not (torch.is_tensor(grad) and grad.dtype == torch.float32 and grad.dim() == 2 and grad.shape[0] >= 1):
+        raise ValueError("%s: grad must be float32 [R, E] with at least one replica" % who)
+    R, E = grad.shape
+    if not (torch.is_tensor(grp_ptr) and grp_ptr.dtype == torch.int32 and tuple(grp_ptr.shape) == (n_groups + 1,)):
+        raise ValueError("%s: grp_ptr must be int32 [%d], n_groups + 1" % (who, n_groups + 1))
+    if not (torch.is_tensor(member) and member.dtype == torch.int32 and member.dim() == 1):
+        raise ValueError("%s: member must be int32 [M]" % who)
+    M = member.numel()
+    ptr_h = np.ascontiguousarray(grp_ptr.cpu().numpy() if grp_ptr_host is None else grp_ptr_host, dtype=np.int32)
+    if ptr_h.shape != (n_groups + 1,) or ptr_h[0] != 0 or ptr_h[-1] != M:     # (that it never decreases: the entry point's one pass)
+        raise ValueError("%s: grp_ptr must start at 0, never decrease and end at the number of members (%d)" % (who, M))
+    if M and not E:
+        raise ValueError("%s: %d members but grad has no edges" % (who, M))
+    _require_gpu(grad.device)
+    if not all(x.is_cuda and x.is_contiguous() for x in (grp_ptr, member, grad)):
+        raise ValueError("%s: every tensor must be contiguous and on the device" % who)
+    if n_groups == 0 or M == 0:                                               # no sum to form: every group is empty
+        return torch.zeros((R, n_groups), dtype=torch.float32, device=grad.device)
+    grp_grad = torch.empty((R, n_groups), dtype=torch.float32, device=grad.device)    # every cell is written: an empty group's with +0
+    L, p = _lib.lib(), _lib.ptr
+    nbytes = int(L.rg_mask_tie_grad_scratch_bytes(p(ptr_h), n_groups, R))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=grad.device) if nbytes else None
+    _lib.check(L.rg_mask_tie_grad(R, E, n_groups, M, p(grp_ptr), p(ptr_h), p(member), p(grad), p(grp_grad), p(scratch), nbytes,
+                                  _lib.stream_ptr()))
+    return grp_grad
+
+
+def mask_tie_gates(group_of, grp_gate, gate_out):
+    """Tied gates written back to the edges (rg_mask_tie_gates): gate_out[k, e] = grp_gate[k, group_of[e]] where group_of[e] >= 0, IN
+    PLACE; every other cell of ``gate_out`` fp32 [R, E] is left as it is.  ``group_of`` int32 [E] (-1: not tied; clamped to
+    n_groups - 1), ``grp_gate`` fp32 [R, n_groups].  Returns ``gate_out``.  Shapes and dtypes are checked here (ValueError)."""
+    who = "mask_tie_gates"
+    if not (torch.is_tensor(gate_out) and gate_out.dtype == torch.float32 and gate_out.dim() == 2 and gate_out.shape[0] >= 1):
+        raise ValueError("%s: gate_out must be float32 [R, E] with at least one replica" % who)
+    R, E = gate_out.shape
+    if not (torch.is_tensor(group_of) and group_of.dtype == torch.int32 and tuple(group_of.shape) == (E,)):
+        raise ValueError("%s: group_of must be int32 [%d], one per edge" % (who, E))
+    if not (torch.is_tensor(grp_gate) and grp_gate.dtype == torch.float32 and grp_gate.dim() == 2 and grp_gate.shape[0] == R):
+        raise ValueError("%s: grp_gate must be float32 [%d, n_groups]" % (who, R))
+    _require_gpu(gate_out.device)
+    if not all(x.is_cuda and x.is_contiguous() for x in (group_of, grp_gate, gate_out)):
+        raise ValueError("%s: every tensor must be contiguous and on the device" % who)
+    if E == 0 or grp_gate.shape[1] == 0:                                      # no gate to hand on
+        return gate_out
+    p = _lib.ptr
+    _lib.check(_lib.lib().rg_mask_tie_gates(R, E, grp_gate.shape[1], p(group_of), p(grp_gate), p(gate_out), _lib.stream_ptr()))
+    return gate_out
+
+
 def _digraph_layer_bwd(who, dst_ptr, src_idx, rel, row_of_dst, hidden, rela, d, a_s, a_r, a_q, w_alpha, b_alpha, attn_dim, grad_agg,
                        want_state, timed, gated=None, view=None, check_index=True):
     """Every backward wrapper: the host checks, the source view, the scratch, the launch.  ``timed``: None or (edge_time, q_time,

@@ -13,6 +13,7 @@ s -> o through the query's subgraph (identity self-loops count as steps); each e
     sal = rd.saliency(model)                         # d score / d (a gate on every edge), one pass (HIP: csrc/digraph_bwd.hip): an explain.Saliency
     att = rd.integrated_gradients(model, steps=16)   # attributions that add up to the score (gated, replicated edge-list kernels): an explain.Attribution
     mask = rd.learn_mask(model)                      # the small set of facts that reproduces the score (a gate per replica and edge, csrc/mask_step.hip): an explain.EdgeMask
+    mask = rd.learn_tied_mask(model, tie="fact")     # ... with one gate per fact, per (hop, relation) or per caller label (csrc/mask_tie.hip)
 
 The extraction runs in HIP (csrc/explain.hip): a forward keeps all L + 1 frontier levels and each layer's attention projection, then
 one backward marking pass per hop reads only the marked tails' CSR rows.  This module holds the result type and the host drivers.
@@ -186,8 +187,32 @@ class RDigraph:
         the rows' replicas and ``kept_score`` is one exact ``rescore(keep=)`` of that mask: the facts really deleted.  ``keep`` (the
         argument) as in ``rescore``.  The defaults are a starting point, not a tuned setting.  No float atomics anywhere: the same bits
         on every run.  Static and inductive models; a temporal or extrapolation digraph or model is a ValueError: the timed forms of
-        the gated kernels are not built."""
+        the gated kernels are not built.  A gate per FACT, per (hop, relation) or per label instead of per edge: ``learn_tied_mask``."""
         return learn_mask(self, model, lambdas, entropy, iterations, lr, theta0, tol, keep, mode)
+
+    def learn_tied_mask(self, model, tie="fact", **kw):
+        """``learn_mask`` with TIED gates: one logit per group of free edges, every member edge reading the group's gate - an
+        explain.EdgeMask whose ``group*`` fields are set.  ``learn_mask`` learns a gate per edge, and a fact usually has several edges
+        in a row's digraph (the same fact at two hops, and its inverse): untied, the copies get different gates, ``keep`` can hold one
+        copy and drop another - a state the graph can never be in - and ``size`` counts edges.  ``tie`` (explain.mask_groups):
+
+            "fact"      a group per base fact (h, r, t) of a row, inverses folded back - ``fact_mask``'s rule.  The mask is a set of
+                        facts: ``keep`` is a ``fact_mask`` of the selected facts (and the kept self-loops), ``size`` counts facts
+            "relation"  a group per (hop, relation) of a row: a soft rule body, "which relations, at which hop, carry this answer"
+                        (``EdgeMask.format_groups``), next to model.rules
+            int64 [E]   any labels >= 0 on the free edges (entity, relation alone, ...): a group per (row, label)
+
+        ``**kw``: ``learn_mask``'s arguments, with the same meaning; the size penalty is lambda * the mean of the row's GROUP gates and
+        the entropy term runs over groups.  The state is [R, G]; an iteration is ``learn_mask``'s stacked walk at the [R, E] gates,
+        then the chain rule through the tie - d score / d gate_group = the sum over the group's edges of d score / d gate_edge, in
+        chunks of 32 members in a fixed order (rg_mask_tie_grad, csrc/mask_tie.hip) -, rg_mask_step on the group arrays and the group
+        gates copied to the edges (rg_mask_tie_gates).  No float atomics: the same bits on every run, and a replica's are those of a
+        one-replica call.  Where every group is one edge the group gradients are the edges', bit for bit; the gates are
+        ``learn_mask``'s up to rg_mask_step's own rounding, which follows a cell's position in its row.  ``size``, ``replica_size`` and
+        ``history.size`` / ``history.count`` count groups; ``n_free`` still counts edges.  ``tie`` is checked with ``learn_mask``'s
+        own arguments (ValueError "learn_mask: tie ..."), a label tensor's dtype and shape after the digraph's tensors.
+        explain.learn_mask(rd, model, ..., tie=) is the same call."""
+        return learn_mask(self, model, tie=tie, **kw)
 
     def fact_mask(self, facts, rows=None, inverse_offset=None):
         """bool [E]: the edges that stand for one of the facts ``facts`` int [F, 3] = (h, r, t), at any hop: an edge is marked if its
@@ -2257,6 +2282,16 @@ class EdgeMask(_FactSums):
     digraph         RDigraph        the digraph the edges are those of
     replica_gate, replica_score, replica_hard_score, replica_size   float32 [R, E], float32 [R, B], float32 [R, B], int64 [R, B]: what
                                     the selection saw of every replica
+
+    A TIED mask (RDigraph.learn_tied_mask; None otherwise) also carries
+    tie             "fact", "relation" or the label tensor
+    group           int64 [E]       the group whose gate the edge reads, -1 where it is not tied (not free)
+    group_row       int64 [G]       the row of every group; groups are ordered by (row, key)
+    group_key       int64 [G, c]    "fact": (h, r, t) with r < n_rel; "relation": (hop, rel); labels: (label,)
+    group_gate      float32 [G]     the group's gate in its row's replica: ``gate`` at every member edge, bit for bit
+    n_groups        int64 [B]       groups of the row
+    and there ``size``, ``replica_size`` and ``history.size`` / ``history.count`` count GROUPS (facts under "fact"), while ``n_free``
+    keeps its meaning: the row's free edges.
     """
     gate: torch.Tensor
     keep: torch.Tensor
@@ -2277,8 +2312,42 @@ class EdgeMask(_FactSums):
     replica_score: torch.Tensor = None
     replica_hard_score: torch.Tensor = None
     replica_size: torch.Tensor = None
+    tie: object = None
+    group: torch.Tensor = None
+    group_row: torch.Tensor = None
+    group_key: torch.Tensor = None
+    group_gate: torch.Tensor = None
+    n_groups: torch.Tensor = None
     _VALUES = "gate"
     _REDUCE = staticmethod(_segment_max)
+
+    def groups(self):
+        """(row int64 [G], key int64 [G, c], gate float32 [G]) of a tied mask, ordered by (row, key): every group with the gate its row's
+        replica gave it.  Under tie="fact" this is ``fact_gate()`` with no maximum to take: all copies of a fact hold one gate."""
+        if self.group_gate is None:
+            raise ValueError("groups: the mask is not tied (learn_tied_mask / learn_mask(tie=) make tied ones)")
+        return self.group_row, self.group_key, self.group_gate
+
+    def format_groups(self, id2rel=None, k=3):
+        """One line per row: its ``k`` groups of the largest gate, largest first, ties in key order - ``hop1 r3 0.98`` under
+        tie="relation" (a soft rule body: which relations, at which hop, carry the answer), ``(h, r3, t) 0.98`` under "fact", the
+        label otherwise; ``id2rel`` names the relations."""
+        _check_count(k, "format_groups", "k")
+        row, key, gate = (t.cpu() for t in self.groups())
+        name = lambda r: str(id2rel[r]) if id2rel is not None else "r%d" % r
+        if isinstance(self.tie, str) and self.tie == "relation":
+            cell = lambda q: "hop%d %s" % (q[0], name(q[1]))
+        elif isinstance(self.tie, str) and self.tie == "fact":
+            cell = lambda q: "(%d, %s, %d)" % (q[0], name(q[1]), q[2])
+        else:
+            cell = lambda q: " ".join("%d" % x for x in q)
+        order = torch.sort(-gate, stable=True).indices
+        order = order[torch.sort(row[order], stable=True).indices]            # by row, inside a row by gate descending
+        lines = [[] for _ in range(self.score.numel())]
+        for b, q, g in zip(row[order].tolist(), key[order].tolist(), gate[order].tolist()):
+            if len(lines[b]) < int(k):
+                lines[b].append("%s %.2f" % (cell(q), g))
+        return ["row %d: %s" % (b, "  ".join(cells)) for b, cells in enumerate(lines)]
 
     def fact_gate(self):
         """(row int64 [F], fact int64 [F, 3] = (h, r, t) with r < n_rel, gate float32 [F]) ordered by (row, h, r, t): the largest
@@ -2476,6 +2545,10 @@ def _gated_group(S, rd, model, hops, t, lo, hi, want_grad, check_index=True, gat
             agg, al = fwd(h["dst_ptr"], h["src"], h["rel"], h["row_of"].to(torch.int32).contiguous(), hidden, rela_p, d, a_s, a_r, a_q,
                           *w_b(layer), a, *g_hop, dst_ptr_host=h["dst_ptr_host"], check_index=check_index)
             alpha[:, at] = al.view(n, -1)
+            # the GEMM library of the dense step and of its adjoint, chosen here as the model's forward chooses it per layer: torch's
+            # choice is one switch per process, and left as the last forward set it the adjoint's last bits followed what had run before.
+            # The count is ONE replica's rows, never the stacked ones: a replica of a stacked call must get the library of its own call
+            engine.prefer_blas(h["n_dst"])
             # the replicas' rows of the dense step: node j of replica k is row k * n_dst + j, its old state row k * n_prev + prev_idx[j]
             had = h["had"].repeat(n)
             prev_idx = torch.where(h["had"][None, :], h["prev_idx"][None, :] + (rep * h["n_prev"]).to(torch.int32),
@@ -2511,6 +2584,7 @@ def _gated_group(S, rd, model, hops, t, lo, hi, want_grad, check_index=True, gat
         h = tp["h"]
         l = h["l"]
         layer, last, first = model.gnn_layers[l - 1], l == L, l == 1
+        engine.prefer_blas(h["n_dst"])                                        # (the hop's own choice again, per replica: a later hop may have moved it)
         # ---- the dense step's adjoint: saliency's, on the stacked rows - or, with ``split_dense``, on one replica's rows at a time
         def dense_adjoint(agg, prev, had, prev_idx, seeds):
             with torch.enable_grad():
@@ -2547,13 +2621,14 @@ def _gated_group(S, rd, model, hops, t, lo, hi, want_grad, check_index=True, gat
     return score, alpha, grad
 
 
-def _gated_setup(rd, model, keep, mode, who, gates):
+def _gated_setup(rd, model, keep, mode, who, gates, tie=None):
     """The refusals and checks of a gated call, in the order that lets a host without a device reach them: the family, the digraph's
-    tensors, then ``gates`` - {name: float32 [E] or None} - and only then _static_setup, which needs the device.  Returns (S, gates on
-    the device)."""
+    tensors, then ``gates`` - {name: float32 [E] or None} - and the labels of a tensor ``tie`` (learn_mask), which need E, and only
+    then _static_setup, which needs the device.  Returns (S, gates on the device)."""
     _refuse_timed(rd, model, who)
     E, _ = _check_static_digraph(rd, who)
     gates = {name: None if g is None else _check_gate(who, name, g, E, rd.edges.device) for name, g in gates.items()}
+    _check_tie_labels(who, tie, E)
     S = _static_setup(rd, model, keep, mode, who)
     S.q_sub = rd.q_sub
     return S, gates
@@ -2640,11 +2715,89 @@ def mask_selection(hard_score, size, target, scale, tol):
     return torch.where(ok.any(0), by_size, by_dev)
 
 
+MASK_TIES = ("fact", "relation")
+
+
+def _check_tie(who, tie):
+    """The kind of ``tie``, checked with learn_mask's own arguments: None, one of MASK_TIES, or a tensor / numpy array of labels
+    (whose dtype and shape need E: _check_tie_labels)."""
+    if tie is None or torch.is_tensor(tie) or isinstance(tie, np.ndarray) or (isinstance(tie, str) and tie in MASK_TIES):
+        return
+    raise ValueError('%s: tie must be None, "fact", "relation" or an int64 tensor or array [E] of labels, one per edge (got %r)' % (who, tie))
+
+
+def _check_tie_labels(who, tie, E):
+    """A tensor ``tie``: int64 [E] (ValueError); the named ties and None pass."""
+    if tie is None or isinstance(tie, str):
+        return
+    dtype = tie.dtype
+    if dtype not in (torch.int64, np.dtype(np.int64)) or tuple(tie.shape) != (E,):
+        raise ValueError("%s: tie must be int64 [%d], one label per edge (got %s %s)" % (who, E, dtype, tuple(tie.shape)))
+
+
+def mask_groups(rd, tie, free):
+    """The groups of tied edges of learn_mask(tie=): which of the edges ``free`` (bool [E]) share one gate.  Pure torch on the digraph's
+    device, CPU included.  ``tie``:
+
+        "fact"      the key is (h, r, t) with an inverse edge (t, r + n_rel, h) folded back on its fact: RDigraph.fact_mask's rule and
+                    Saliency.fact_grad's grouping; a self-loop (relation 2 * n_rel) is no fact and is never tied
+        "relation"  the key is (hop, rel), rel as the edge carries it (an inverse is a relation of its own): a soft rule body per row
+        int64 [E]   a tensor or numpy array of labels >= 0 on the free edges: the key is (label,)
+
+    Groups never span rows; they are ordered by (row, key ascending) and a group's members by ascending edge position.  Returns a
+    namespace: ``group_of`` int32 [E] (-1: not tied), ``grp_ptr`` int32 [G + 1] with its host copy ``grp_ptr_host`` (numpy) and
+    ``member`` int32 [M] as engine.mask_tie_grad takes them, ``row_ptr`` int64 [B + 1] the rows' group ranges, ``group_row`` int64 [G],
+    ``group_key`` int64 [G, c] and ``n_groups`` = G.  A tie of another kind, labels of a wrong dtype or shape or a negative label on
+    a free edge: ValueError("learn_mask: tie ...")."""
+    who = "learn_mask"
+    _check_tie(who, tie)
+    if tie is None:
+        raise ValueError("%s: tie None ties nothing: there are no groups" % who)
+    E, B = _check_static_digraph(rd, who)
+    _check_tie_labels(who, tie, E)
+    dev = rd.edges.device
+    free = (free if torch.is_tensor(free) else torch.as_tensor(np.asarray(free))).to(dev)
+    if free.dtype not in (torch.bool, torch.uint8) or tuple(free.shape) != (E,):
+        raise ValueError("%s: free must be bool [%d], one per edge (got %s %s)" % (who, E, free.dtype, tuple(free.shape)))
+    free, e, n_rel = free.bool(), rd.edges.long(), int(rd.n_rel)
+    if isinstance(tie, str) and tie == "fact":
+        free = free & (e[:, 3] != 2 * n_rel)
+        inv = e[:, 3] >= n_rel
+        cols = [torch.where(inv, e[:, 4], e[:, 2]), torch.where(inv, e[:, 3] - n_rel, e[:, 3]), torch.where(inv, e[:, 2], e[:, 4])]
+    elif isinstance(tie, str):
+        cols = [e[:, 1], e[:, 3]]
+    else:
+        label = (tie.detach() if torch.is_tensor(tie) else torch.as_tensor(tie)).to(dev)
+        if bool((label[free] < 0).any()):
+            raise ValueError("%s: tie holds a negative label on a free edge" % who)
+        cols = [label]
+    at = torch.nonzero(free).reshape(-1)
+    keys = torch.stack([e[:, 0]] + cols, 1)[at]
+    if at.numel():
+        keys, inverse = torch.unique(keys, dim=0, return_inverse=True)        # sorted by (row, key)
+    else:
+        inverse = at
+    G = keys.shape[0]
+    member = at[torch.sort(inverse, stable=True).indices].to(torch.int32)     # a group's members in edge order
+    grp_ptr = torch.zeros(G + 1, dtype=torch.int64, device=dev)
+    grp_ptr[1:] = torch.cumsum(torch.bincount(inverse, minlength=G), 0)
+    grp_ptr = grp_ptr.to(torch.int32)
+    group_of = torch.full((E,), -1, dtype=torch.int32, device=dev)
+    group_of[at] = inverse.to(torch.int32)
+    row_ptr = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+    row_ptr[1:] = torch.cumsum(torch.bincount(keys[:, 0], minlength=B)[:B], 0)
+    return types.SimpleNamespace(group_of=group_of, grp_ptr=grp_ptr, grp_ptr_host=grp_ptr.cpu().numpy(), member=member.contiguous(),
+                                 row_ptr=row_ptr, group_row=keys[:, 0].contiguous(), group_key=keys[:, 1:].contiguous(), n_groups=G)
+
+
 def learn_mask(rd, model, lambdas=(0.01, 0.03, 0.1, 0.3, 1.0), entropy=0.0, iterations=100, lr=0.05, theta0=2.0, tol=0.05, keep=None,
-               mode="test"):
-    """RDigraph.learn_mask (see there)."""
+               mode="test", tie=None):
+    """RDigraph.learn_mask, and with ``tie`` RDigraph.learn_tied_mask (see there)."""
     who = "learn_mask"
     lam = _check_mask_args(who, lambdas, entropy, iterations, lr, theta0, tol)
+    _check_tie(who, tie)
+    if tie is not None:
+        return _learn_tied_mask(who, rd, model, lam, entropy, iterations, lr, theta0, tol, keep, mode, tie)
     S, _ = _gated_setup(rd, model, keep, mode, who, {})
     R, E, B, dev, iterations = lam.size, S.E, S.B, S.dev, int(iterations)
     f32 = dict(dtype=torch.float32, device=dev)
@@ -2686,6 +2839,60 @@ def learn_mask(rd, model, lambdas=(0.01, 0.03, 0.1, 0.3, 1.0), entropy=0.0, iter
                     kept_score=kept.score, target=target, baseline_score=baseline, size=size[replica, rows], n_free=n_free, replica=replica,
                     lambdas=lam_size, history=hist, reached=reached, live=live, digraph=rd, replica_gate=gate, replica_score=soft_score,
                     replica_hard_score=hard_score, replica_size=size)
+
+
+def _learn_tied_mask(who, rd, model, lam, entropy, iterations, lr, theta0, tol, keep, mode, tie):
+    """learn_mask with a tie: the untied driver with the state per (replica, group).  An iteration is the same stacked walk at the
+    [R, E] gates, then the chain rule through the tie (rg_mask_tie_grad), rg_mask_step on the group arrays - the rows' group ranges
+    for offsets, every group free - and the group gates written back to the edges (rg_mask_tie_gates)."""
+    S, _ = _gated_setup(rd, model, keep, mode, who, {}, tie)
+    R, E, B, dev, iterations = lam.size, S.E, S.B, S.dev, int(iterations)
+    f32 = dict(dtype=torch.float32, device=dev)
+    hops, live, reached = _static_hops(S, who)
+    fixed = S.kept & (S.rel == 2 * int(rd.n_rel))
+    free = S.kept & ~fixed
+    T = mask_groups(rd, tie, free)
+    G = T.n_groups
+    ends, _, _ = _gated_group(S, rd, model, hops, torch.tensor([0.0, 1.0], **f32), fixed.to(torch.float32), torch.ones(E, **f32), False)
+    baseline, target = ends[0], ends[1]
+    scale = (target - baseline).abs()
+    inv_scale = torch.where((scale > 0) & reached, 1.0 / scale, torch.zeros_like(scale))
+    n_free = torch.bincount(S.row[free], minlength=B)[:B]
+    n_groups = T.row_ptr[1:] - T.row_ptr[:-1]
+    inv_n = torch.where(n_groups > 0, 1.0 / n_groups.to(torch.float32), torch.zeros(B, **f32))
+    lam_size, lam_ent = torch.as_tensor(lam).to(dev), torch.full((R,), float(entropy), **f32)
+    # ---- the state: a logit and Adam's moments per (replica, group), the groups' gates, and the edges' gates the kernels read
+    g0 = float(np.float32(1.0 / (1.0 + np.exp(-np.float64(theta0)))))
+    theta, m, v = torch.full((R, G), float(theta0), **f32), torch.zeros((R, G), **f32), torch.zeros((R, G), **f32)
+    grp_gate = torch.full((R, G), g0, **f32)
+    gate = torch.zeros((R, E), **f32)
+    gate[:, free] = g0
+    gate[:, fixed] = 1.0
+    all_free = torch.ones(G, dtype=torch.uint8, device=dev)
+    hist = types.SimpleNamespace(deviation=torch.zeros((iterations, R, B), **f32), size=torch.zeros((iterations, R, B), **f32),
+                                 count=torch.zeros((iterations, R, B), dtype=torch.int32, device=dev))
+    for it in range(iterations):
+        score, _, grad = _gated_group(S, rd, model, hops, None, None, None, True, check_index=False, gate=gate, split_dense=MASK_SPLIT_DENSE)
+        hist.deviation[it] = (score - target[None, :]) * inv_scale[None, :]
+        grp_grad = engine.mask_tie_grad(T.grp_ptr, T.member, grad, G, grp_ptr_host=T.grp_ptr_host)
+        _, hist.size[it], hist.count[it] = engine.mask_step(T.row_ptr, all_free, score.contiguous(), target, inv_scale, inv_n, lam_size,
+                                                            lam_ent, grp_grad, theta, m, v, it + 1, lr=lr, gate_out=grp_gate)
+        engine.mask_tie_gates(T.group_of, grp_gate, gate)
+    # ---- selection: as the untied driver's, the size of a replica's mask counted in groups
+    hard = torch.where(free[None, :], (gate > 0.5).to(torch.float32), gate)
+    both, _, _ = _gated_group(S, rd, model, hops, None, None, None, False, check_index=False, gate=torch.cat([gate, hard], 0))
+    soft_score, hard_score = both[:R], both[R:]
+    size = torch.zeros((R, B), dtype=torch.int64, device=dev).index_add_(1, T.group_row, (grp_gate > 0.5).long())
+    replica = mask_selection(hard_score, size, target, scale, float(tol))
+    rows = torch.arange(B, device=dev)
+    gate_sel = gate[replica[S.row], torch.arange(E, device=dev)]
+    keep_sel = torch.where(free, gate_sel > 0.5, fixed)
+    kept = rescore(rd, model, keep=keep_sel, mode=mode)
+    return EdgeMask(gate=gate_sel, keep=keep_sel, score=soft_score[replica, rows], hard_score=hard_score[replica, rows],
+                    kept_score=kept.score, target=target, baseline_score=baseline, size=size[replica, rows], n_free=n_free, replica=replica,
+                    lambdas=lam_size, history=hist, reached=reached, live=live, digraph=rd, replica_gate=gate, replica_score=soft_score,
+                    replica_hard_score=hard_score, replica_size=size, tie=tie, group=T.group_of.long(), group_row=T.group_row,
+                    group_key=T.group_key, group_gate=grp_gate[replica[T.group_row], torch.arange(G, device=dev)], n_groups=n_groups)
 
 
 def _fidelity_of(rd, model, k, loops, mode, inverse_offset=None):

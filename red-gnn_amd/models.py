@@ -591,14 +591,17 @@ class RED_GNN_trans(nn.Module):
         return self.explain(subs, rels, objs, mode=mode).integrated_gradients(self, steps=steps, mode=mode)
 
     def learn_mask(self, subs, rels, objs=None, lambdas=(0.01, 0.03, 0.1, 0.3, 1.0), entropy=0.0, iterations=100, lr=0.05, theta0=2.0,
-                   tol=0.05, mode="test"):
+                   tol=0.05, mode="test", tie=None):
         """The small set of facts that reproduces the score of o: ``explain`` followed by RDigraph.learn_mask - a gate per edge of
         the r-digraph learned by Adam under a size penalty, every lambda of ``lambdas`` a replica of each hop in one HIP launch
         (rg_digraph_layer_fwd_gates / rg_digraph_layer_bwd_gates) and the update one more (rg_mask_step).  Returns an explain.EdgeMask
         (device tensors): ``keep`` / ``gate`` per edge of ``.digraph``, ``fact_gate()`` / ``top(k)`` per fact, ``kept_score`` the exact
-        rescore of the mask.  ``objs=None``: each row's own top answer, as explain.  Eval semantics; the parameters get no gradient."""
-        return self.explain(subs, rels, objs, mode=mode).learn_mask(self, lambdas=lambdas, entropy=entropy, iterations=iterations, lr=lr,
-                                                                    theta0=theta0, tol=tol, mode=mode)
+        rescore of the mask.  ``objs=None``: each row's own top answer, as explain.  Eval semantics; the parameters get no gradient.
+        ``tie`` ("fact", "relation" or int64 labels per edge; None: a gate per edge): RDigraph.learn_tied_mask instead, one gate per
+        group of edges (rg_mask_tie_grad / rg_mask_tie_gates); labels need the digraph's edge order, so they suit a second call."""
+        from .explain import learn_mask
+        return learn_mask(self.explain(subs, rels, objs, mode=mode), self, lambdas=lambdas, entropy=entropy, iterations=iterations, lr=lr,
+                          theta0=theta0, tol=tol, mode=mode, tie=tie)
 
     def _forward_graphed(self, graph, q_sub, q_rel, n, device):
         """Replay (or, on the third call with the same graph and batch size, capture) the forward as a HIP graph.
