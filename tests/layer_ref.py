@@ -140,6 +140,9 @@ def _kappa(hop, a_s, a_r, a_q, w_alpha, b_alpha, alpha):
     return alpha + alpha * (1 - alpha) * Z
 
 
+kappa = _kappa      # (public: tests/hop_ref.py bounds a single alpha with it)
+
+
 def _message(hop, hidden, rela, time_tab, absolute=False):
     f = np.abs if absolute else (lambda x: x)
     m = f(hidden[hop.hrow]) + f(rela[hop.rrow])
